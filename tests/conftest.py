@@ -24,18 +24,6 @@ def oracle():
 
 
 @pytest.fixture(scope="session")
-def oracle_ref():
-    """oracle/_ref (the reference's own complex class); only where it was built."""
-    from oracle import oracle as orc
-    if os.path.isdir("/root/reference/DeviceArray/include"):
-        orc.build(ref=True)
-    try:
-        return orc.Oracle(ref=True)
-    except (FileNotFoundError, OSError):
-        pytest.skip("oracle/_ref not built (needs /root/reference)")
-
-
-@pytest.fixture(scope="session")
 def synth():
     return importlib.import_module("x-slam_amd.synth")
 

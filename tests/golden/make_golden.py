@@ -11,6 +11,9 @@ scalar_tables.npz      seeded operand tables + outputs of the REFERENCE's own
                        (/root/reference/DeviceArray/include/cuda_complex.hpp, compiled by
                        g++ from where it lies into oracle/_ref/liboracle_ref.so), and of the
                        dual-complex restatement instantiated over that class.
+scalar_live_ref.npz    the operands tests/test_oracle_scalar.py::test_live_against_reference_header
+                       draws (seed 7) and the reference complex<float>'s results on them (oracle/_ref),
+                       so that the test holds where oracle/_ref cannot be built.
 test_csfd_known_answers.json
                        the values the reference's test_CSFD demo prints
                        (Experiments/test_CSFD/main.cpp:113-219), recorded from a run of the
@@ -97,6 +100,24 @@ def scalar_tables(ref):
         out[f"c_csfdx_{op}"] = ref.cop(op, a)
         out[f"c_spec_{op}"] = ref.cop(op, spec)
     np.savez_compressed(os.path.join(OUT, "scalar_tables.npz"), **out)
+
+
+def live_operands():
+    """The operands of test_oracle_scalar.py::test_live_against_reference_header (drawn there the same way)."""
+    rng = np.random.default_rng(7)
+    a = np.stack([rng.uniform(0.01, 5, 4096), rng.uniform(-1e-6, 1e-6, 4096)], -1).astype(np.float32)
+    b = np.stack([rng.uniform(-5, 5, 4096), rng.uniform(-1e-6, 1e-6, 4096)], -1).astype(np.float32)
+    return a, b
+
+
+def live_reference_results(ref):
+    a, b = live_operands()
+    out = dict(a=a, b=b)
+    for op in ("add", "sub", "mul", "div", "div_scalar", "scalar_div", "mul_scalar", "scalar_sub"):
+        out[op] = ref.cop(op, a, b)
+    for op in ("sqrt", "abs", "exp", "sin", "cos", "sinh", "cosh", "sin_new", "sinh_new", "norm", "arg", "conj", "log"):
+        out[op] = ref.cop(op, a)
+    np.savez_compressed(os.path.join(OUT, "scalar_live_ref.npz"), **out)
 
 
 def known_answers():
@@ -193,6 +214,7 @@ if __name__ == "__main__":
     orc.build(ref=True)
     ref = orc.Oracle(ref=True)
     scalar_tables(ref)
+    live_reference_results(ref)
     known_answers()
     pipeline(ref, 64, [0, 1, 4], "pipeline_s1_n64.npz")
     pipeline(ref, 96, [0, 1, 4], "pipeline_s1_n96.npz")

@@ -211,7 +211,8 @@ def _worker(rank, world, port, n, nframes, threads=2):
         assert kf.process_frame(d) == 1
     assert np.allclose(whole.record[-1], kf.world2camera(), rtol=0, atol=5e-7)
     assert whole.U == kf.last_U() or not np.array_equal(whole.record[-1], kf.world2camera())
-    dist.barrier()
+    # gloo's own barrier: dist.barrier() picks a device through the accelerator probe, which opens the GPU in every rank where there is one
+    dist.monitored_barrier()
     dist.destroy_process_group()
 
 
@@ -291,7 +292,7 @@ def _hess_worker(rank, world, port):
     sh.reduce_tensor(dist, sh.OP_SUM_F64, t)
     want = gd["hess_a"]
     assert t[3].item() == want[3] and np.allclose(t.numpy(), want, rtol=1e-10)
-    dist.barrier()
+    dist.monitored_barrier()       # (not dist.barrier(): see _worker)
     dist.destroy_process_group()
 
 
