@@ -383,6 +383,41 @@ int xs_extract_points(const float *value, size_t vol_step, const int *res, float
 int xs_extract_normals(const float *value, size_t vol_step, const int *res, float voxel_size, int zs0, int zs1, const float *points_dev,
                        size_t n, float *normals_dev, void *stream);
 
+/* ---- surface mesh (export; marching cubes with complex-step vertex derivatives) -------------------------------------------------------
+ * No working counterpart in the reference (its extractMesh, ExtractPointCloud.cu:364-715, is never called).
+ * Cube (x, y, z), x < X-1, y < Y-1, z in [z0, z1), is live when all 8 corners have weight >= min_weight and value < 0.99 and its corners
+ * are neither all negative nor all non-negative (negative: value < 0).  One vertex per sign-changing edge of a live cube:
+ *   vertices_dev   xyz, the point export's expression (every vertex is, bit for bit, a point xs_extract_points reports)
+ *   vertex_im_dev  Im of the same expression on the (value, grad) pairs (raw: divide by the CSFD step); written only if grad != NULL
+ *   normals_dev    unit central difference of the trilinear TSDF (k_extract_normals' sampling; 0 where the point export's border rule
+ *                  gives 0), pointing toward increasing TSDF; written only if want_normals
+ *   keys_dev       ((z * Y + y) * X + x) * 3 + axis of the edge's lower endpoint in global coordinates, axis 0/1/2 = +x/+y/+z
+ * in ascending key order, and int32 index triples into them in triangles_dev, in ascending cube index ((z * Y + y) * X + x) then case
+ * table order, counter-clockwise seen from the non-negative side.  The output is a function of the volume alone: bit-identical across
+ * runs and with or without a sign map.  *vertex_count_host / *triangle_count_host always receive the counts found; if either exceeds its
+ * capacity the call returns XS_MESH_OVER_CAPACITY and writes no output array (count-then-fill: a call with capacities 0 and NULL arrays
+ * counts).  workspace: xs_mesh_workspace_bytes(res, opts).  Synchronises the stream. */
+#define XS_MESH_OVER_CAPACITY (-2)
+typedef struct xs_mesh_opts {
+    unsigned struct_bytes;           /* sizeof(xs_mesh_opts) */
+    int zs0, zs1;                    /* the arrays hold stored planes [zs0, zs1) and point at plane zs0 (whole volume: 0, 0 = res[2]) */
+    int z0, z1;                      /* the cubes of planes [z0, z1) are meshed, zs0 <= z0 <= z1 <= res[2] - 1, z1 < zs1 (plane z1 is read) */
+    int min_weight;                  /* corner weight gate; values below 1 mean 1 */
+    int want_normals;
+    const void *signmap;             /* a sign map that is a superset of the volume's negative voxels (xs_signmap_*), or NULL: bricks whose
+                                        dil byte is clear are skipped without reading the volume */
+    int signmap_shift;               /* its brick shift (2..6) */
+} xs_mesh_opts;
+size_t xs_mesh_workspace_bytes(const int *res, const xs_mesh_opts *opts);   /* opts NULL: enough for any plane range */
+int xs_extract_mesh(const float *value, const int *weight, const float *grad, size_t vol_step, const int *res, float voxel_size,
+                    const xs_mesh_opts *opts, float *vertices_dev, float *vertex_im_dev, float *normals_dev, unsigned long long *keys_dev,
+                    size_t vertex_capacity, int *triangles_dev, size_t triangle_capacity, void *workspace, size_t *vertex_count_host,
+                    size_t *triangle_count_host, void *stream);
+/* host only: the edges of a case's triangles, three per triangle, -1 after the last (at most 5).  Corner c sits at (c & 1, c >> 1 & 1,
+ * c >> 2 & 1) and is bit c of the case; edge e runs along axis e / 4 from the corner whose other two coordinates (x, y, z order) are the
+ * bits of e % 4.  On every face the crossings are paired by that face's signs alone (an ambiguous face cuts off its negative corners). */
+int xs_mesh_case_table(int cube_case, signed char out16[16]);
+
 /* ---- ICP normal equations ----------------------------------------------------------------- */
 size_t xs_icp_workspace_bytes(void);
 /* zero the workspace's arrival ticket once after allocation; every launch leaves it zero */

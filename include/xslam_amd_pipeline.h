@@ -84,6 +84,17 @@ int xs_kf_relocalize(void *kf, const uint16_t *depth_dev, size_t step_bytes, flo
  * ascii format (x y z nx ny nz) and returns the number of points, -1 if the file cannot be opened. */
 long long xs_kf_export_point_cloud(void *kf, int max_buffer, float *points_host, float *normals_host);
 long long xs_kf_export_ply(void *kf, int max_buffer, const char *filename);
+/* ExportMesh (no working counterpart in the reference; xs_extract_mesh in xslam_amd.h): the marching-cubes mesh of the TSDF with
+ * corner weight gate min_weight (1 = every observed voxel).  Returns the vertex count and sets *triangle_count and *has_im (1 while a
+ * CSFD seed is active: vertex_im then holds Im of every vertex, raw — divide by csfd_seed_h).  The arrays (any may be NULL: vertices,
+ * normals, vertex_im xyz triples; edge_keys; triangles index triples) are filled only if both counts fit the capacities: count with
+ * capacities 0, allocate, call again.  A sharded rank meshes the cubes of the planes it owns.  export_mesh_ply writes binary little-endian
+ * PLY (vertex x y z nx ny nz [dx dy dz: vertex_im, raw], face list uchar int vertex_indices); returns the vertex count, -1 if the file
+ * cannot be written. */
+long long xs_kf_export_mesh(void *kf, int min_weight, long long vertex_capacity, long long triangle_capacity, float *vertices_host,
+                            float *normals_host, float *vertex_im_host, unsigned long long *edge_keys_host, int *triangles_host,
+                            long long *triangle_count, int *has_im);
+long long xs_kf_export_mesh_ply(void *kf, const char *filename);
 void xs_kf_synchronize(void *kf);
 
 int xs_kf_frame_id(void *kf);

@@ -48,6 +48,12 @@ class RaycastOpts(C.Structure):
                 ("pyr_step2", C.c_size_t), ("completion_event", C.c_void_p), ("steps_dev", C.c_void_p), ("pyramid_built", C.c_int)]
 
 
+class MeshOpts(C.Structure):
+    """xs_mesh_opts (include/xslam_amd.h)."""
+    _fields_ = [("struct_bytes", C.c_uint), ("zs0", C.c_int), ("zs1", C.c_int), ("z0", C.c_int), ("z1", C.c_int), ("min_weight", C.c_int),
+                ("want_normals", C.c_int), ("signmap", C.c_void_p), ("signmap_shift", C.c_int)]
+
+
 _SIGS = {
     "xs_integrate_scaled_ex2": (C.c_int, [_vp, _sz, C.c_int, C.c_int, _f32p, C.c_int, _i32p, C.c_float, _f32p, _f32p, C.c_float, _vp, _vp, _vp,
                                          _sz, C.c_float, C.c_int, C.c_int, _vp, _vp, _vp, C.POINTER(IntegrateOpts), _vp]),
@@ -115,6 +121,10 @@ _SIGS = {
     "xs_extract_workspace_bytes": (_sz, [_i32p]),
     "xs_extract_points": (C.c_int, [_vp, _sz, _i32p, C.c_float, C.c_int, C.c_int, C.c_int, _vp, _sz, _vp, C.POINTER(_sz), C.POINTER(_sz), _vp]),
     "xs_extract_normals": (C.c_int, [_vp, _sz, _i32p, C.c_float, C.c_int, C.c_int, _vp, _sz, _vp, _vp]),
+    "xs_mesh_workspace_bytes": (_sz, [_i32p, C.POINTER(MeshOpts)]),
+    "xs_extract_mesh": (C.c_int, [_vp, _vp, _vp, _sz, _i32p, C.c_float, C.POINTER(MeshOpts), _vp, _vp, _vp, _vp, _sz, _vp, _sz, _vp,
+                                  C.POINTER(_sz), C.POINTER(_sz), _vp]),
+    "xs_mesh_case_table": (C.c_int, [C.c_int, C.c_void_p]),
     "xs_icp_wait_pairs": (C.c_int, [_vp, C.c_ulonglong, _vp, C.c_longlong]),
     "xs_icp_workspace_bytes": (_sz, []),
     "xs_icp_workspace_init": (C.c_int, [_vp, _vp]),
@@ -505,6 +515,65 @@ def extract_normals(value, vol_step, res, voxel_size, points, n, normals, zs0=0,
     zs1 = int(r[2]) if zs1 is None else zs1
     check(_lib.xs_extract_normals(_ptr(value), vol_step, r.ctypes.data_as(_i32p), voxel_size, zs0, zs1, _ptr(points), n, _ptr(normals),
                                   _stream(stream)))
+
+
+MESH_OVER_CAPACITY = -2   # XS_MESH_OVER_CAPACITY
+
+
+def mesh_opts(z0=0, z1=None, res=None, zs0=0, zs1=0, min_weight=1, want_normals=True, signmap=None, signmap_shift=3):
+    o = MeshOpts()
+    o.struct_bytes = C.sizeof(MeshOpts)
+    o.zs0, o.zs1, o.z0 = zs0, zs1, z0
+    o.z1 = int(res[2]) - 1 if z1 is None else z1
+    o.min_weight, o.want_normals = min_weight, int(bool(want_normals))
+    o.signmap, o.signmap_shift = _ptr(signmap), signmap_shift if signmap is not None else 0
+    return o
+
+
+def mesh_workspace_bytes(res, opts=None):
+    r = _ia(res, 3)
+    return _lib.xs_mesh_workspace_bytes(r.ctypes.data_as(_i32p), C.byref(opts) if opts is not None else None)
+
+
+def mesh_case_table(cube_case):
+    """xs_mesh_case_table (host only): the case's triangles as a list of edge triples."""
+    out = (C.c_byte * 16)()
+    check(_lib.xs_mesh_case_table(int(cube_case), out))
+    e = [v for v in out if v >= 0]
+    return [tuple(e[i:i + 3]) for i in range(0, len(e), 3)]
+
+
+def extract_mesh_raw(value, weight, grad, vol_step, res, voxel_size, opts, vertices, vertex_im, normals, keys, vcap, triangles, tcap,
+                     workspace, stream=None):
+    """xs_extract_mesh on caller-provided buffers: returns (status, vertices found, triangles found) — status 0 or MESH_OVER_CAPACITY."""
+    r = _ia(res, 3)
+    nv, nt = _sz(0), _sz(0)
+    rc = _lib.xs_extract_mesh(_ptr(value), _ptr(weight), _ptr(grad), vol_step, r.ctypes.data_as(_i32p), voxel_size, C.byref(opts),
+                              _ptr(vertices), _ptr(vertex_im), _ptr(normals), _ptr(keys), vcap, _ptr(triangles), tcap, _ptr(workspace),
+                              C.byref(nv), C.byref(nt), _stream(stream))
+    if rc != MESH_OVER_CAPACITY:
+        check(rc)
+    return rc, int(nv.value), int(nt.value)
+
+
+def extract_mesh(value, weight, grad, vol_step, res, voxel_size, z0=0, z1=None, zs0=0, zs1=0, min_weight=1, want_normals=True,
+                 signmap=None, signmap_shift=3, stream=None):
+    """Marching-cubes mesh of the TSDF (xs_extract_mesh, count then fill): a dict of CUDA tensors vertices [V, 3] f32, vertex_im [V, 3]
+    f32 (None without grad), normals [V, 3] f32 (None unless want_normals), triangles [T, 3] i32, edge_keys [V] u64.  Synchronises."""
+    import torch
+    dev = value.device
+    opts = mesh_opts(z0, z1, res, zs0, zs1, min_weight, want_normals, signmap, signmap_shift)
+    ws = torch.empty(max(1, mesh_workspace_bytes(res, opts)), dtype=torch.uint8, device=dev)
+    args = (value, weight, grad, vol_step, res, voxel_size, opts)
+    rc, nv, nt = extract_mesh_raw(*args, None, None, None, None, 0, None, 0, ws, stream)
+    f = lambda n: torch.empty((n, 3), dtype=torch.float32, device=dev)
+    out = {"vertices": f(nv), "vertex_im": f(nv) if grad is not None else None, "normals": f(nv) if want_normals else None,
+           "triangles": torch.empty((nt, 3), dtype=torch.int32, device=dev), "edge_keys": torch.empty(nv, dtype=torch.uint64, device=dev)}
+    if rc == MESH_OVER_CAPACITY:
+        rc, nv2, nt2 = extract_mesh_raw(*args, out["vertices"], out["vertex_im"], out["normals"], out["edge_keys"], nv, out["triangles"], nt,
+                                        ws, stream)
+        assert rc == 0 and (nv2, nt2) == (nv, nt), (rc, nv2, nt2, nv, nt)
+    return out
 
 
 def resize_pyramid(vmap0, nmap0, in_step, rows0, cols0, vmap1, nmap1, mid_step, vmap2, nmap2, out_step, stream=None):

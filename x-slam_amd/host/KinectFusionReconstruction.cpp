@@ -1467,6 +1467,71 @@ bool KinectFusionReconstruction::CPointCloud::exportPly(const std::string &filen
     return true;
 }
 
+KinectFusionReconstruction::CMesh KinectFusionReconstruction::ExportMesh(int min_weight) {
+    CMesh m;
+    if (!tsdf_volume_d_ptr) return m;
+    if (sign_map_stale_) { RebuildSignMap(); sign_map_stale_ = false; }   // (the map must be a superset of the negative voxels)
+    const int res[3] = {volume_resolution.x(), volume_resolution.y(), volume_resolution.z()};
+    const bool seeded = csfd_seed_row >= 0 && csfd_seed_row < 4 && csfd_seed_col >= 0 && csfd_seed_col < 4;
+    m.has_im = seeded;   // (also for an empty mesh: a rank without surface still says whether its vertices would carry derivatives)
+    DeviceArray2D<float> value = tsdf_volume_d_ptr->value(), grad = tsdf_volume_d_ptr->grad();
+    DeviceArray2D<int> weight = tsdf_volume_d_ptr->weight();
+    // (TsdfVolume allocates the three arrays alike: one pitch)
+    xs_mesh_opts o{};
+    o.struct_bytes = sizeof(o);
+    o.zs0 = zs0; o.zs1 = zs1;
+    o.z0 = zo0; o.z1 = std::max(std::min(zo1, res[2] - 1), zo0);   // (as ExportPointCloud)
+    o.min_weight = min_weight; o.want_normals = 1;
+    o.signmap = sign_map_ptr(); o.signmap_shift = raycast_sign_map_shift;
+    DeviceArray<unsigned char> ws;
+    ws.create(xs_mesh_workspace_bytes(res, &o));
+    const float *g = seeded ? grad.ptr(0) : nullptr;
+    size_t nv = 0, nt = 0;
+    int rc = xs_extract_mesh(value.ptr(0), weight.ptr(0), g, value.step(), res, voxel_size, &o, nullptr, nullptr, nullptr, nullptr, 0, nullptr, 0,
+                             ws.ptr(), &nv, &nt, current_stream());
+    if (rc == 0) return m;   // (nothing fits in no room only when there is nothing)
+    if (rc != XS_MESH_OVER_CAPACITY) check_rc(rc, "mesh count");
+    DeviceArray<float> verts, vim, normals;
+    DeviceArray<unsigned long long> keys;
+    DeviceArray<int> tris;
+    verts.create(3 * nv); normals.create(3 * nv); keys.create(nv); tris.create(3 * std::max<size_t>(nt, 1));
+    if (seeded) vim.create(3 * nv);
+    size_t nv2 = 0, nt2 = 0;
+    check_rc(xs_extract_mesh(value.ptr(0), weight.ptr(0), g, value.step(), res, voxel_size, &o, verts.ptr(), seeded ? vim.ptr() : nullptr,
+                             normals.ptr(), keys.ptr(), nv, tris.ptr(), nt, ws.ptr(), &nv2, &nt2, current_stream()), "mesh");
+    m.positions.resize(3 * nv); m.normals.resize(3 * nv); m.edge_keys.resize(nv); m.triangles.resize(3 * nt);
+    hipSafeCall(hipMemcpy(m.positions.data(), verts.ptr(), 3 * nv * sizeof(float), hipMemcpyDeviceToHost));
+    hipSafeCall(hipMemcpy(m.normals.data(), normals.ptr(), 3 * nv * sizeof(float), hipMemcpyDeviceToHost));
+    hipSafeCall(hipMemcpy(m.edge_keys.data(), keys.ptr(), nv * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+    if (nt) hipSafeCall(hipMemcpy(m.triangles.data(), tris.ptr(), 3 * nt * sizeof(int), hipMemcpyDeviceToHost));
+    if (seeded) {
+        m.vertex_im.resize(3 * nv);
+        hipSafeCall(hipMemcpy(m.vertex_im.data(), vim.ptr(), 3 * nv * sizeof(float), hipMemcpyDeviceToHost));
+    }
+    return m;
+}
+bool KinectFusionReconstruction::CMesh::exportPly(const std::string &filename) const {
+    std::ofstream f(filename, std::ios::binary);
+    if (!f.is_open()) return false;
+    const bool d = has_im;
+    f << "ply\nformat binary_little_endian 1.0\nelement vertex " << vertices() << "\n";
+    f << "property float x\nproperty float y\nproperty float z\nproperty float nx\nproperty float ny\nproperty float nz\n";
+    if (d) f << "property float dx\nproperty float dy\nproperty float dz\n";
+    f << "element face " << faces() << "\nproperty list uchar int vertex_indices\nend_header\n";
+    std::vector<float> row(d ? 9 : 6);   // (x86 / the hosts this builds for are little-endian: the floats go out as they are)
+    for (size_t i = 0; i < vertices(); ++i) {
+        for (int k = 0; k < 3; ++k) { row[k] = positions[3 * i + k]; row[3 + k] = normals[3 * i + k]; if (d) row[6 + k] = vertex_im[3 * i + k]; }
+        f.write(reinterpret_cast<const char *>(row.data()), (std::streamsize)(row.size() * sizeof(float)));
+    }
+    char face[13];
+    face[0] = 3;
+    for (size_t t = 0; t < faces(); ++t) {
+        std::memcpy(face + 1, &triangles[3 * t], 12);
+        f.write(face, 13);
+    }
+    return (bool)f;
+}
+
 void KinectFusionReconstruction::synchronize() { hipSafeCall(hipStreamSynchronize(current_stream())); }
 
 long long KinectFusionReconstruction::lastUpdatedVoxels() { return last_frame_counter(0); }

@@ -233,6 +233,21 @@ public:
         bool exportPly(const std::string &filename) const;  // CPointCloud.cpp:42-67: ascii, x y z nx ny nz
     };
     CPointCloud ExportPointCloud(int max_buffer);
+    // ExportMesh (no working counterpart in the reference; xs_extract_mesh in include/xslam_amd.h): the marching-cubes mesh of the
+    // TSDF, vertices in ascending edge key, triangles in cube order.  vertex_im (Im of every vertex, raw: divide by csfd_seed_h) only
+    // while a CSFD seed is active, else empty.  The orchestrator's sign map lets the kernel skip bricks without a negative voxel.  A
+    // sharded rank meshes the cubes of its owned planes [zo0, min(zo1, Z - 1)), reading plane zo1 from its halo: vertices on a shared
+    // plane appear in both neighbours' meshes with the same bits and key.
+    struct CMesh {
+        std::vector<float> positions, normals, vertex_im;   // xyz triples
+        std::vector<unsigned long long> edge_keys;
+        std::vector<int> triangles;                          // index triples
+        bool has_im = false;                                 // a CSFD seed was active: vertex_im holds every vertex's Im
+        size_t vertices() const { return edge_keys.size(); }
+        size_t faces() const { return triangles.size() / 3; }
+        bool exportPly(const std::string &filename) const;   // binary little-endian: x y z nx ny nz [dx dy dz]; list uchar int vertex_indices
+    };
+    CMesh ExportMesh(int min_weight = 1);
 
     // volume checkpoint: raw float32 value (+ grad, + int32 weight), X*Y*Z each, dense
     // (the reference's saveTSDFVolume writes value only and res[0]*res[2]*res[2] floats,

@@ -178,6 +178,25 @@ long long xs_kf_export_ply(void *kf, int max_buffer, const char *filename) {
     const auto pc = ((KF *)kf)->ExportPointCloud(max_buffer);
     return pc.exportPly(filename) ? (long long)pc.size() : -1;
 }
+long long xs_kf_export_mesh(void *kf, int min_weight, long long vertex_capacity, long long triangle_capacity, float *vertices_host,
+                            float *normals_host, float *vertex_im_host, unsigned long long *edge_keys_host, int *triangles_host,
+                            long long *triangle_count, int *has_im) {
+    const auto m = ((KF *)kf)->ExportMesh(min_weight);
+    const long long nv = (long long)m.vertices(), nt = (long long)m.faces();
+    if (triangle_count) *triangle_count = nt;
+    if (has_im) *has_im = m.has_im ? 1 : 0;
+    if (nv > vertex_capacity || nt > triangle_capacity) return nv;   // counts only: the caller allocates and calls again
+    if (vertices_host && nv) std::memcpy(vertices_host, m.positions.data(), m.positions.size() * sizeof(float));
+    if (normals_host && nv) std::memcpy(normals_host, m.normals.data(), m.normals.size() * sizeof(float));
+    if (vertex_im_host && m.has_im && nv) std::memcpy(vertex_im_host, m.vertex_im.data(), m.vertex_im.size() * sizeof(float));
+    if (edge_keys_host && nv) std::memcpy(edge_keys_host, m.edge_keys.data(), m.edge_keys.size() * sizeof(unsigned long long));
+    if (triangles_host && nt) std::memcpy(triangles_host, m.triangles.data(), m.triangles.size() * sizeof(int));
+    return nv;
+}
+long long xs_kf_export_mesh_ply(void *kf, const char *filename) {
+    const auto m = ((KF *)kf)->ExportMesh(1);
+    return m.exportPly(filename) ? (long long)m.vertices() : -1;
+}
 void xs_kf_synchronize(void *kf) { ((KF *)kf)->synchronize(); }
 
 int xs_kf_frame_id(void *kf) { return ((KF *)kf)->frame_id; }

@@ -3,6 +3,7 @@ libxslam_host.so built from x-slam_amd/host/).  The orchestrator itself is C++
 (KinectFusionReconstruction, mirroring the reference class); this module only lets Python
 callers — bench.py and the parity tests — drive it.  No CPU fallback: a missing library is an
 ImportError."""
+import collections
 import ctypes as C
 import os
 
@@ -37,6 +38,9 @@ _SIGS = {
     "xs_kf_relocalize": (C.c_int, [_vp, _vp, _sz, _f32p, C.c_int, C.c_float, _f64p]),
     "xs_kf_export_point_cloud": (C.c_longlong, [_vp, C.c_int, _f32p, _f32p]),
     "xs_kf_export_ply": (C.c_longlong, [_vp, C.c_int, C.c_char_p]),
+    "xs_kf_export_mesh": (C.c_longlong, [_vp, C.c_int, C.c_longlong, C.c_longlong, _f32p, _f32p, _f32p, C.POINTER(C.c_uint64), _i32p,
+                                         C.POINTER(C.c_longlong), _i32p]),
+    "xs_kf_export_mesh_ply": (C.c_longlong, [_vp, C.c_char_p]),
     "xs_kf_synchronize": (None, [_vp]),
     "xs_kf_frame_id": (C.c_int, [_vp]),
     "xs_kf_num_poses": (C.c_int, [_vp]),
@@ -136,6 +140,10 @@ def set_stream(stream):
     _lib.xs_kf_set_stream(None if stream is None else (stream.cuda_stream if hasattr(stream, "cuda_stream") else int(stream)))
 
 
+class Mesh(collections.namedtuple("Mesh", "vertices vertex_im normals triangles edge_keys")):
+    """A triangle mesh of the TSDF (KinectFusion.export_mesh): numpy arrays, vertices in ascending edge key."""
+
+
 class KinectFusion:
     """Handle to a C++ KinectFusionReconstruction."""
 
@@ -216,6 +224,25 @@ class KinectFusion:
 
     def export_ply(self, filename, max_buffer=1000000):
         return _lib.xs_kf_export_ply(self.h, max_buffer, str(filename).encode())
+
+    def export_mesh(self, min_weight=1):
+        """ExportMesh: the marching-cubes mesh on the host, a Mesh of vertices [V, 3] f32, vertex_im [V, 3] f32 (raw Im, divide by
+        csfd_seed_h; None without a CSFD seed), normals [V, 3] f32, triangles [T, 3] i32 and edge_keys [V] u64."""
+        nt, has_im = C.c_longlong(0), C.c_int(0)
+        nv = _lib.xs_kf_export_mesh(self.h, min_weight, 0, 0, None, None, None, None, None, C.byref(nt), C.byref(has_im))
+        while True:   # (the volume does not change between the calls: one retry)
+            cap_v, cap_t = nv, nt.value
+            v, n, im = (np.zeros((cap_v, 3), np.float32) for _ in range(3))
+            k = np.zeros(cap_v, np.uint64)
+            t = np.zeros((cap_t, 3), np.int32)
+            nv = _lib.xs_kf_export_mesh(self.h, min_weight, cap_v, cap_t, v.ctypes.data_as(_f32p), n.ctypes.data_as(_f32p), im.ctypes.data_as(_f32p),
+                                        k.ctypes.data_as(C.POINTER(C.c_uint64)), t.ctypes.data_as(_i32p), C.byref(nt), C.byref(has_im))
+            if nv <= cap_v and nt.value <= cap_t:
+                return Mesh(v[:nv], im[:nv] if has_im.value else None, n[:nv], t[:nt.value], k[:nv])
+
+    def export_mesh_ply(self, filename):
+        """Binary little-endian PLY of export_mesh (with dx dy dz = vertex_im while a CSFD seed is active); the vertex count, -1 on failure."""
+        return _lib.xs_kf_export_mesh_ply(self.h, str(filename).encode())
 
     def synchronize(self):
         _lib.xs_kf_synchronize(self.h)

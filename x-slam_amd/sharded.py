@@ -236,6 +236,18 @@ class ShardedKinectFusion(pl.KinectFusion):
         return v[a:b], w[a:b], g[a:b]
 
 
+def weld_meshes(meshes):
+    """One mesh from the ranks' export_mesh results, in rank order: the vertices merged by edge key (a vertex on a plane two ranks share
+    carries the same bits in both), the triangles concatenated (each rank meshes the cubes of its own planes) and re-indexed.  Works
+    for any list of pl.Mesh whose cube planes are disjoint and ascending."""
+    keys = np.concatenate([m.edge_keys for m in meshes])
+    uniq, first = np.unique(keys, return_index=True)
+    pick = lambda f: None if any(getattr(m, f) is None for m in meshes) else np.concatenate([getattr(m, f) for m in meshes])[first]
+    tris = [np.searchsorted(uniq, m.edge_keys[m.triangles]).astype(np.int32) if len(m.triangles) else np.zeros((0, 3), np.int32)
+            for m in meshes]
+    return pl.Mesh(pick("vertices"), pick("vertex_im"), pick("normals"), np.concatenate(tris).reshape(-1, 3), uniq)
+
+
 def tsdf_hessian_sharded(dist, rank, world, depth_scaled, scaled_step, rows, cols, intr, res, voxel_size, Rv2c, tv2c, tranc_dist, gt_slab,
                          workspace, out4, stream=None):
     """BASELINE config 4: the dual-complex Hessian kernel on this rank's z-slab of the ground-truth
