@@ -362,6 +362,43 @@ void xs_gn_post_poses(void *mailbox_host, const float *Rv2c108, const float *tv2
 /* shard mode: the n <= 32 sums as they stand in device memory behind the stream's all-reduce, published like the kernel's own (word [32] = seq) */
 int xs_gn_publish_sums(const double *sums_dev, int n, double *publish_host, unsigned long long seq, void *stream);
 
+/* ---- band index of a fixed map: batched Gauss-Newton passes for relocalisation (xs_band.hip) ------------------
+ * xs_tsdf_gauss_newton_terms scans the whole slab on every pass to find its band voxels (gt != 0, |gt| <= 0.95).  The band depends on gt
+ * alone, so for a map that does not change it can be found once: xs_tsdf_band_build records the band voxels of the slab [z0, z1) of gt in
+ * the order the Gauss-Newton kernel's walk deals them to its lanes — per wave segment (workgroup b, wave w), entry 64 k + lane for the
+ * lane's k-th take — and xs_tsdf_gauss_newton_terms_band replays that order for up to XS_BAND_MAX_FRAMES query frames per launch.  Frame
+ * f's 29 sums are bit-identical to those of xs_tsdf_gauss_newton_terms for the same depth, poses and gt (same tiling: the build reads gt at
+ * the address the dense pass would be given, whose 16-byte alignment picks the walk), whatever the other frames of the launch are. */
+#define XS_BAND_MAX_FRAMES 32
+#define XS_BAND_OVER_CAPACITY (-3)
+typedef struct xs_band_index {
+    /* the caller's buffers */
+    unsigned long long *keys;       /* capacity entries: x | y << 21 | z << 42 (global voxel coordinates) */
+    float *values;                  /* capacity entries: gt at the key, bit for bit */
+    long long capacity;
+    long long *segs;                /* device, xs_tsdf_band_segs_bytes(res, z0, z1): [0, 4 nblocks) offsets, [4 nblocks, 8 nblocks) lengths of the
+                                       wave segments (segment 4 b + w: workgroup b, wave w of the dense pass) */
+    /* filled by the build */
+    long long count;                /* band voxels */
+    int nblocks;                    /* workgroups of the dense pass over this slab */
+    int res[3], z0, z1;
+} xs_band_index;
+size_t xs_tsdf_band_segs_bytes(const int *res, int z0, int z1);
+/* Two walks over the slab: lengths, then (their exclusive scan on the host) keys and values.  index->count and the other filled fields are
+ * always set; if count > capacity the call returns XS_BAND_OVER_CAPACITY and writes neither keys nor values (count-then-fill: capacity 0 and
+ * NULL arrays count; segs is written either way).  Synchronises the stream. */
+int xs_tsdf_band_build(const float *gt, const int *res, int z0, int z1, xs_band_index *index, void *stream);
+/* workspace of xs_tsdf_gauss_newton_terms_band for up to `frames` frames: per-frame arrival tickets in its first 256 bytes, the poses, the
+ * records.  Zero the first 256 bytes ONCE after allocation (xs_tsdf_reduce_workspace_init does it): every launch leaves each frame's ticket at
+ * zero again.  One launch at a time per workspace; after a launch that did not complete (a device fault), zero them again. */
+size_t xs_tsdf_band_workspace_bytes(int frames);
+/* The six-pose Gauss-Newton terms of `frames` (1 .. XS_BAND_MAX_FRAMES) query frames over a built index: frame f's depth is
+ * depth_scaled[f] (host array of device pointers; all frames rows x cols with one step), its six seeded poses Rv2c108xF + 108 f /
+ * tv2c36xF + 36 f (the layout of xs_tsdf_gauss_newton_terms), its 29 sums out29xF_dev + 29 f.  No synchronisation. */
+int xs_tsdf_gauss_newton_terms_band(int frames, const float *const *depth_scaled, size_t scaled_step, int rows, int cols, const float *intr4,
+                                    float voxel_size, const float *Rv2c108xF, const float *tv2c36xF, float tranc_dist, const xs_band_index *index,
+                                    void *workspace, double *out29xF_dev, void *stream);
+
 /* ---- surface extraction (export; real-valued) ------------------------------------------------ */
 size_t xs_extract_workspace_bytes(const int *res);
 /* size_t extractPoints(value_volume, weight_volume, grad_volume, volume_resolution, voxel_size,

@@ -78,6 +78,16 @@ void xs_kf_get_camera2volume(void *kf, float *out32);
  * the end.  Both return 1, or 0 when there is nothing to align to. */
 int xs_kf_gauss_newton_terms(void *kf, const uint16_t *depth_dev, size_t step_bytes, const float *c2v32, double *out29);
 int xs_kf_relocalize(void *kf, const uint16_t *depth_dev, size_t step_bytes, float *c2v32, int iterations, float damping, double *loss_out);
+/* Batched relocalisation against the current map: xs_kf_relocalize for each of `frames` depth images (device pointers depth_dev[f], one
+ * step_bytes) from c2v32xF + 32 f (refined in place), all frames of a pass in one band-index launch (chunks of XS_BAND_MAX_FRAMES; DESIGN.md
+ * section 4.15).  The band index of the owned planes is built on first use and rebuilt after anything wrote the volume (integrate,
+ * loadCheckpoint, xs_kf_volume_ptr(kf, 0, .), xs_kf_rebuild_sign_map).  Frame f's ok_out[f], pose and losses (loss_out + f (iterations + 1);
+ * NULL: no final loss pass, as xs_kf_relocalize) are bit-identical to what xs_kf_relocalize returns for that frame alone.  Returns the
+ * number of frames that succeeded (-1: bad arguments). */
+int xs_kf_relocalize_batch(void *kf, int frames, const uint16_t *const *depth_dev, size_t step_bytes, float *c2v32xF, int iterations, float damping,
+                           double *loss_out, int *ok_out);
+/* band voxels in the relocalisation index as last built (0 before the first batch) */
+long long xs_kf_relocalization_index_voxels(void *kf);
 /* ExportPointCloud(max_buffer)  .cpp:334-372 (+ CPointCloud::exportPly, main.cpp:78-80): zero-crossing points of
  * the TSDF with normals, at most max_buffer; xyz triples into the host arrays (either may be NULL); returns
  * the number of points.  A sharded rank exports the planes it owns.  export_ply writes the reference's

@@ -1,0 +1,281 @@
+"""GPU: the band index of a fixed map (xs_tsdf_band_build) and the batched Gauss-Newton pass over it
+(xs_tsdf_gauss_newton_terms_band): index contents against the map, every frame's 29 sums bit-identical to the dense
+pass (xs_tsdf_gauss_newton_terms) whatever the batch, the capacity protocol and the per-frame tickets."""
+import importlib
+
+import numpy as np
+import pytest
+
+from helpers import intr_of, s1_transforms, synth, tranc_dist
+from test_gauss_newton_gpu import seeded_poses, twist_matrix
+
+W, H = synth.WIDTH, synth.HEIGHT
+
+pytestmark = pytest.mark.gpu
+
+
+@pytest.fixture(scope="module")
+def dev():
+    import torch
+    assert torch.cuda.is_available()
+    return torch, importlib.import_module("x-slam_amd.capi")
+
+
+@pytest.fixture(scope="module")
+def oracle():
+    from oracle.oracle import Oracle
+    return Oracle()
+
+
+def oracle_map(oracle, prm, res, frames=(0, 1)):
+    v, w, g = oracle.new_volume(res)
+    for k in frames:
+        T = s1_transforms(k, prm)
+        oracle.integrate(oracle.scale_depth(synth.s1_frame(k)), v, w, g, res, tranc_dist(prm), 100, T["Rv2c"], T["tv2c"], intr_of(prm),
+                         prm["tsdf_voxel_size"])
+    return v
+
+
+def v2c_of(prm, k, rng=None, scale=1.0):
+    T = s1_transforms(k, prm)
+    v2c = np.eye(4); v2c[:3, :3] = np.asarray(T["Rv2c"])[..., 0]; v2c[:3, 3] = np.asarray(T["tv2c"])[..., 0]
+    if rng is not None:
+        v2c = np.linalg.inv(twist_matrix(rng.normal(size=6) * scale * np.array([0.01, 0.01, 0.01, 0.004, 0.004, 0.004])) @ np.linalg.inv(v2c))
+    return v2c
+
+
+def poses_of(v2c):
+    return seeded_poses(np.linalg.inv(v2c.astype(np.float32).astype(np.float64)))
+
+
+def check_index(torch, capi, gt_slab, res, z0, z1):
+    """gt_slab: the dense map from plane z0 on (a flat float32 device tensor); the index against the band of the map itself."""
+    X, Y, _ = res
+    idx = capi.tsdf_band_build(gt_slab, res, z0, z1)
+    n = int(idx.count)
+    slab = gt_slab[:(z1 - z0) * X * Y]
+    want = torch.nonzero((slab != 0) & (slab.abs() <= 0.95)).reshape(-1)
+    assert n == want.numel()
+    keys = idx.keys_t[:n]
+    lin = ((keys >> 42) * Y + ((keys >> 21) & 0x1FFFFF)) * X + (keys & 0x1FFFFF) - z0 * X * Y
+    assert torch.equal(torch.sort(lin).values, want)
+    assert torch.equal(idx.values_t[:n].view(torch.int32), slab[lin].view(torch.int32))
+    nb = idx.nblocks
+    segs = idx.segs_t[:8 * nb].cpu().numpy()
+    off, cnt = segs[:4 * nb], segs[4 * nb:]
+    assert cnt.sum() == n and np.array_equal(off, np.concatenate([[0], np.cumsum(cnt)[:-1]]))
+    assert (idx.z0, idx.z1, list(idx.res)) == (z0, z1, list(res))
+    return idx
+
+
+class Runner:
+    def __init__(self, torch, capi, prm):
+        self.torch, self.capi, self.prm = torch, capi, prm
+        self.ws = torch.zeros(capi.tsdf_reduce_workspace_bytes(), dtype=torch.uint8, device="cuda")
+        self.bws = torch.zeros(capi.tsdf_band_workspace_bytes(capi.BAND_MAX_FRAMES), dtype=torch.uint8, device="cuda")
+        self.out = torch.zeros(32, dtype=torch.float64, device="cuda")
+        self.outF = torch.zeros(29 * capi.BAND_MAX_FRAMES, dtype=torch.float64, device="cuda")
+        self.k4, self.vs, self.trunc = intr_of(prm), prm["tsdf_voxel_size"], tranc_dist(prm)
+
+    def dense(self, ds, res, Rs, ts, gt_slab, z0, z1):
+        self.out.fill_(-1.0)
+        self.capi.tsdf_gauss_newton_terms(ds, W * 4, H, W, self.k4, res, self.vs, Rs, ts, self.trunc, gt_slab, self.ws, self.out, z0=z0, z1=z1)
+        self.torch.cuda.synchronize()
+        return self.out.cpu().numpy()[:29].copy()
+
+    def band(self, dss, RsF, tsF, idx):
+        F = len(dss)
+        self.outF.fill_(-1.0)
+        self.capi.tsdf_gauss_newton_terms_band(dss, W * 4, H, W, self.k4, self.vs, np.stack(RsF), np.stack(tsF), self.trunc, idx, self.bws, self.outF)
+        self.torch.cuda.synchronize()
+        return self.outF.cpu().numpy()[:29 * F].reshape(F, 29).copy()
+
+
+def test_index_contents_shapes_and_slabs(dev, oracle):
+    """Wide interleaved walk (X % 4 == 0), the one-column walk (X % 4 != 0, and a map that is only 4-byte aligned), a non-cubic volume and
+    z-slabs inside it: the index holds exactly the band voxels, values bit for bit, the segment table adds up."""
+    torch, capi = dev
+    prm = synth.s1_params(96)
+    for X, Y, Z in ((96, 96, 96), (97, 64, 80), (100, 72, 90)):
+        res = [X, Y, Z]
+        v = oracle_map(oracle, prm, res)
+        store = torch.zeros(X * Y * Z + 5, dtype=torch.float32, device="cuda")
+        for shift in (4, 5):
+            gt = store[shift:shift + X * Y * Z]
+            gt.copy_(torch.from_numpy(v))
+            for z0, z1 in ((0, Z), (10, Z - 7), (33, 60)):
+                idx = check_index(torch, capi, gt[z0 * X * Y:], res, z0, z1)
+                if (z0, z1) == (0, Z):
+                    assert idx.count > 1000
+
+
+def test_band_pass_equals_dense_random_shapes_poses_and_slabs(dev, oracle):
+    """As test_residual_kernels_random_shapes_poses_and_slabs: random extents, perturbed poses and slabs, aligned and 4-byte aligned maps.
+    At F = 1 the band pass's 29 doubles are the dense pass's, byte for byte."""
+    torch, capi = dev
+    rng = np.random.default_rng(20261015)
+    prm = synth.s1_params(96)
+    r = Runner(torch, capi, prm)
+    ds = torch.from_numpy(oracle.scale_depth(synth.s1_frame(2))).cuda()
+    for trial in range(6):
+        X, Y, Z = int(rng.integers(90, 101)), int(rng.integers(60, 73)), int(rng.integers(70, 97))
+        X = 96 if trial == 0 else (97 if trial == 1 else X)
+        res = [X, Y, Z]
+        v = oracle_map(oracle, prm, res)
+        Rs, ts = poses_of(v2c_of(prm, 2, rng))
+        store = torch.zeros(X * Y * Z + 5, dtype=torch.float32, device="cuda")
+        cuts = sorted(int(c) for c in rng.choice(np.arange(8, Z - 8), size=2, replace=False))
+        for shift in (4, 5):
+            gt = store[shift:shift + X * Y * Z]
+            gt.copy_(torch.from_numpy(v))
+            for z0, z1 in ((0, Z), (0, cuts[0]), (cuts[0], cuts[1]), (cuts[1], Z)):
+                g = gt[z0 * X * Y:]
+                idx = capi.tsdf_band_build(g, res, z0, z1)
+                want = r.dense(ds, res, Rs, ts, g, z0, z1)
+                got = r.band([ds], [Rs], [ts], idx)[0]
+                assert got.tobytes() == want.tobytes(), (trial, res, shift, z0, z1, got[28], want[28])
+                if (z0, z1) == (0, Z):
+                    assert want[28] > 200
+
+
+def test_band_pass_equals_dense_scene_s3_256(dev):
+    """The box room (scene S3) fused at 256^3 by the pipeline: band pass = dense pass, bit for bit, for the next frames at perturbed poses."""
+    torch, capi = dev
+    pl = importlib.import_module("x-slam_amd.pipeline")
+    n = 256
+    prm = synth.s1_params(n)
+    kf = pl.KinectFusion(prm)
+    for k in range(4):
+        assert kf.process_frame(torch.from_numpy(synth.s3_frame(k).view(np.int16)).cuda()) == 1
+    c2v = kf.camera2volume()[..., 0].astype(np.float64)
+    gt = torch.from_numpy(kf.volume()[0]).cuda()
+    kf.close()
+    res = [n, n, n]
+    r = Runner(torch, capi, prm)
+    idx = check_index(torch, capi, gt, res, 0, n)
+    scaled = torch.empty((H, W), dtype=torch.float32, device="cuda")
+    rng = np.random.default_rng(3)
+    dss, RsF, tsF, wants = [], [], [], []
+    for k in (4, 5):
+        capi.scale_depth(torch.from_numpy(synth.s3_frame(k).view(np.int16)).cuda(), W * 2, H, W, scaled, W * 4)
+        ds = scaled.clone()
+        for _ in range(2):
+            Rs, ts = poses_of(np.linalg.inv(twist_matrix(rng.normal(size=6) * [0.01, 0.01, 0.01, 0.004, 0.004, 0.004]) @ c2v))
+            wants.append(r.dense(ds, res, Rs, ts, gt, 0, n))
+            dss.append(ds); RsF.append(Rs); tsF.append(ts)
+    got = r.band(dss, RsF, tsF, idx)
+    for f in range(len(dss)):
+        assert wants[f][28] > 1000 and got[f].tobytes() == wants[f].tobytes(), f
+
+
+def test_batch_independence(dev, oracle):
+    """F in {2, 3, 8, 32}: every frame's record equals its own F = 1 record; a permutation of the frames permutes the records; the same
+    frame in two slots gives two equal records; a frame whose view misses the map counts 0 and disturbs nothing."""
+    torch, capi = dev
+    prm = synth.s1_params(96)
+    res = [96, 96, 96]
+    v = oracle_map(oracle, prm, res, frames=(0, 1, 2))
+    gt = torch.from_numpy(v).cuda()
+    r = Runner(torch, capi, prm)
+    idx = capi.tsdf_band_build(gt, res)
+    rng = np.random.default_rng(11)
+    depths = [torch.from_numpy(oracle.scale_depth(synth.s1_frame(k))).cuda() for k in range(2, 6)]
+    away = np.eye(4); away[:3, 3] = [0, 0, -50.0]           # the camera 50 m behind the map, looking away from it
+    frames = []
+    for i in range(32):
+        d = i % len(depths)
+        v2c = v2c_of(prm, 2 + d, rng, 0.5) if i != 5 else away
+        Rs, ts = poses_of(v2c)
+        frames.append((depths[d], Rs, ts))
+    solo = [r.band([f[0]], [f[1]], [f[2]], idx)[0] for f in frames]
+    assert solo[5][28] == 0 and all(s[28] > 100 for i, s in enumerate(solo) if i != 5)
+    assert solo[0].tobytes() == r.dense(frames[0][0], res, frames[0][1], frames[0][2], gt, 0, 96).tobytes()
+    for F in (2, 3, 8, 32):
+        sel = list(range(F)) if F < 32 else list(range(32))
+        if F in (3, 8):
+            sel = [5] + list(range(F - 1))                  # the off-map frame in slot 0
+        got = r.band([frames[i][0] for i in sel], [frames[i][1] for i in sel], [frames[i][2] for i in sel], idx)
+        for slot, i in enumerate(sel):
+            assert got[slot].tobytes() == solo[i].tobytes(), (F, slot, i)
+    perm = rng.permutation(8)
+    got = r.band([frames[i][0] for i in perm], [frames[i][1] for i in perm], [frames[i][2] for i in perm], idx)
+    for slot, i in enumerate(perm):
+        assert got[slot].tobytes() == solo[i].tobytes()
+    got = r.band([frames[3][0], frames[7][0], frames[3][0]], [frames[3][1], frames[7][1], frames[3][1]], [frames[3][2], frames[7][2], frames[3][2]], idx)
+    assert got[0].tobytes() == got[2].tobytes() == solo[3].tobytes() and got[1].tobytes() == solo[7].tobytes()
+
+
+def test_capacity_protocol_and_tickets(dev, oracle):
+    """Too small a capacity: XS_BAND_OVER_CAPACITY with the exact count, keys and values untouched (sentinel fill).  A hundred band passes
+    back to back on one workspace all publish the same bits and leave every frame's ticket at zero; a dense pass on a zeroed reduce
+    workspace and another band pass are still correct after them."""
+    torch, capi = dev
+    prm = synth.s1_params(64)
+    res = [64, 64, 64]
+    gt = torch.from_numpy(oracle_map(oracle, prm, res)).cuda()
+    want = check_index(torch, capi, gt, res, 0, 64)
+    n = int(want.count)
+    segs = torch.zeros(capi.tsdf_band_segs_bytes(res) // 8, dtype=torch.int64, device="cuda")
+    keys = torch.full((n,), -7, dtype=torch.int64, device="cuda")
+    values = torch.full((n,), 12345.0, dtype=torch.float32, device="cuda")
+    rc, idx = capi.tsdf_band_build_raw(gt, res, 0, 64, keys, values, n - 1, segs)
+    torch.cuda.synchronize()
+    assert rc == capi.BAND_OVER_CAPACITY and idx.count == n
+    assert bool((keys == -7).all()) and bool((values == 12345.0).all())
+    rc, idx = capi.tsdf_band_build_raw(gt, res, 0, 64, keys, values, n, segs)
+    assert rc == 0 and torch.equal(torch.sort(keys).values, torch.sort(want.keys_t[:n]).values)
+    r = Runner(torch, capi, prm)
+    ds = torch.from_numpy(oracle.scale_depth(synth.s1_frame(2))).cuda()
+    Rs, ts = poses_of(v2c_of(prm, 2))
+    dense = r.dense(ds, res, Rs, ts, gt, 0, 64)
+    F = 4
+    outs = torch.zeros((100, 29 * F), dtype=torch.float64, device="cuda")
+    R4, t4 = np.stack([Rs] * F), np.stack([ts] * F)
+    for i in range(100):
+        capi.tsdf_gauss_newton_terms_band([ds] * F, W * 4, H, W, r.k4, r.vs, R4, t4, r.trunc, idx, r.bws, outs[i])
+    torch.cuda.synchronize()
+    o = outs.cpu().numpy().reshape(100, F, 29)
+    assert all(o[i, f].tobytes() == dense.tobytes() for i in range(100) for f in range(F))
+    assert bool((r.bws[:256] == 0).all())
+    r.ws.zero_()
+    assert r.dense(ds, res, Rs, ts, gt, 0, 64).tobytes() == dense.tobytes()
+    assert r.band([ds], [Rs], [ts], idx)[0].tobytes() == dense.tobytes()
+    with pytest.raises(capi.XsError):
+        capi.tsdf_gauss_newton_terms_band([ds] * 33, W * 4, H, W, r.k4, r.vs, np.stack([Rs] * 33), np.stack([ts] * 33), r.trunc, idx, r.bws, r.outF)
+
+
+def test_band_index_and_pass_at_1024(dev):
+    """1024^3 (two S1 frames fused on the GPU): the index holds exactly the band voxels of the whole volume and of a slab of it, and the band
+    pass of the next frame equals the dense pass bit for bit."""
+    torch, capi = dev
+    n = 1024
+    prm = synth.s1_params(n)
+    res = [n, n, n]
+    value = torch.zeros((n * n, n), dtype=torch.float32, device="cuda")
+    weight = torch.zeros((n * n, n), dtype=torch.int32, device="cuda")
+    grad = torch.zeros((n * n, n), dtype=torch.float32, device="cuda")
+    scaled = torch.empty((H, W), dtype=torch.float32, device="cuda")
+    dmax = torch.zeros(1, dtype=torch.float32, device="cuda")
+    iws = torch.zeros(capi.integrate_workspace_bytes(res), dtype=torch.uint8, device="cuda")
+    upd = torch.zeros(1, dtype=torch.int64, device="cuda")
+    for k in (0, 1):
+        T = s1_transforms(k, prm)
+        depth = torch.from_numpy(synth.s1_frame(k).view(np.int16)).cuda()
+        dmax.zero_()
+        capi.scale_depth_max(depth, W * 2, H, W, scaled, W * 4, dmax)
+        capi.integrate_scaled(scaled, W * 4, H, W, intr_of(prm), 100, res, prm["tsdf_voxel_size"], T["Rv2c"], T["tv2c"], tranc_dist(prm),
+                              value, weight, grad, n * 4, z0=0, z1=n, updated=upd, depth_max=dmax, workspace=iws)
+    torch.cuda.synchronize()
+    del weight, grad, iws
+    gt = value.reshape(-1)
+    r = Runner(torch, capi, prm)
+    depth = torch.from_numpy(synth.s1_frame(2).view(np.int16)).cuda()
+    capi.scale_depth_max(depth, W * 2, H, W, scaled, W * 4, dmax)
+    Rs, ts = poses_of(v2c_of(prm, 2))
+    for z0, z1 in ((0, n), (384, 512)):
+        idx = check_index(torch, capi, gt[z0 * n * n:], res, z0, z1)
+        want = r.dense(scaled, res, Rs, ts, gt[z0 * n * n:], z0, z1)
+        got = r.band([scaled], [Rs], [ts], idx)[0]
+        assert got.tobytes() == want.tobytes(), (z0, z1)
+        if z0 == 0:
+            assert idx.count > 500_000 and want[28] > 10_000

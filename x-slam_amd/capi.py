@@ -54,6 +54,12 @@ class MeshOpts(C.Structure):
                 ("want_normals", C.c_int), ("signmap", C.c_void_p), ("signmap_shift", C.c_int)]
 
 
+class BandIndex(C.Structure):
+    """xs_band_index (include/xslam_amd.h): the band voxels of a slab in the Gauss-Newton walk's order."""
+    _fields_ = [("keys", C.c_void_p), ("values", C.c_void_p), ("capacity", C.c_longlong), ("segs", C.c_void_p), ("count", C.c_longlong),
+                ("nblocks", C.c_int), ("res", C.c_int * 3), ("z0", C.c_int), ("z1", C.c_int)]
+
+
 _SIGS = {
     "xs_integrate_scaled_ex2": (C.c_int, [_vp, _sz, C.c_int, C.c_int, _f32p, C.c_int, _i32p, C.c_float, _f32p, _f32p, C.c_float, _vp, _vp, _vp,
                                          _sz, C.c_float, C.c_int, C.c_int, _vp, _vp, _vp, C.POINTER(IntegrateOpts), _vp]),
@@ -85,6 +91,11 @@ _SIGS = {
     "xs_depth_tiles": (C.c_int, [_vp, _sz, C.c_int, C.c_int, _vp, _vp]),
     "xs_depth_tiles_bytes": (_sz, [C.c_int, C.c_int]),
     "xs_tsdf_reduce_workspace_bytes": (_sz, []),
+    "xs_tsdf_band_segs_bytes": (_sz, [_i32p, C.c_int, C.c_int]),
+    "xs_tsdf_band_build": (C.c_int, [_vp, _i32p, C.c_int, C.c_int, C.POINTER(BandIndex), _vp]),
+    "xs_tsdf_band_workspace_bytes": (_sz, [C.c_int]),
+    "xs_tsdf_gauss_newton_terms_band": (C.c_int, [C.c_int, C.POINTER(_vp), _sz, C.c_int, C.c_int, _f32p, C.c_float, _f32p, _f32p, C.c_float,
+                                                  C.POINTER(BandIndex), _vp, _vp, _vp]),
     "xs_tsdf_reduce_workspace_init": (C.c_int, [_vp, _vp]),
     "xs_compute_local_tsdf_hessian": (C.c_int, [_vp, _sz, C.c_int, C.c_int, _f32p, _i32p, C.c_float, _f32p, _f32p, C.c_float, _vp,
                                                 _vp, _vp, _vp, _vp, C.c_int, C.c_int, _vp, _vp, _vp]),
@@ -454,6 +465,58 @@ def tsdf_gauss_newton_terms(depth_scaled, scaled_step, rows, cols, intr, res, vo
     check(_lib.xs_tsdf_gauss_newton_terms(_ptr(depth_scaled), scaled_step, rows, cols, k.ctypes.data_as(_f32p), r.ctypes.data_as(_i32p),
                                           voxel_size, R.ctypes.data_as(_f32p), t.ctypes.data_as(_f32p), tranc_dist, _ptr(gt), z0, z1,
                                           _ptr(workspace), _ptr(out29), _stream(stream)))
+
+
+BAND_OVER_CAPACITY = -3   # XS_BAND_OVER_CAPACITY
+BAND_MAX_FRAMES = 32      # XS_BAND_MAX_FRAMES
+
+
+def tsdf_band_segs_bytes(res, z0=0, z1=None):
+    r = _ia(res, 3)
+    return int(_lib.xs_tsdf_band_segs_bytes(r.ctypes.data_as(_i32p), z0, int(r[2]) if z1 is None else z1))
+
+
+def tsdf_band_build_raw(gt, res, z0, z1, keys, values, capacity, segs, stream=None):
+    """xs_tsdf_band_build on caller-provided buffers: (status 0 or BAND_OVER_CAPACITY, the BandIndex)."""
+    r = _ia(res, 3)
+    idx = BandIndex()
+    idx.keys, idx.values, idx.capacity, idx.segs = _ptr(keys), _ptr(values), int(capacity), _ptr(segs)
+    rc = _lib.xs_tsdf_band_build(_ptr(gt), r.ctypes.data_as(_i32p), z0, z1, C.byref(idx), _stream(stream))
+    if rc != BAND_OVER_CAPACITY:
+        check(rc)
+    return rc, idx
+
+
+def tsdf_band_build(gt, res, z0=0, z1=None, stream=None):
+    """The band index of the slab [z0, z1) of the dense map gt (pointing at plane z0): count, then fill.  Returns the BandIndex with its
+    device buffers attached (.keys_t int64, .values_t float32, .segs_t int64 torch tensors), which keep them alive."""
+    import torch
+    r = _ia(res, 3)
+    z1 = int(r[2]) if z1 is None else z1
+    segs = torch.empty(max(tsdf_band_segs_bytes(r, z0, z1) // 8, 1), dtype=torch.int64, device=gt.device)
+    rc, idx = tsdf_band_build_raw(gt, r, z0, z1, None, None, 0, segs, stream)
+    n = int(idx.count)
+    keys = torch.empty(max(n, 1), dtype=torch.int64, device=gt.device)
+    values = torch.empty(max(n, 1), dtype=torch.float32, device=gt.device)
+    rc, idx = tsdf_band_build_raw(gt, r, z0, z1, keys, values, n, segs, stream)
+    assert rc == 0 and idx.count == n
+    idx.keys_t, idx.values_t, idx.segs_t = keys, values, segs
+    return idx
+
+
+def tsdf_band_workspace_bytes(frames):
+    return int(_lib.xs_tsdf_band_workspace_bytes(int(frames)))
+
+
+def tsdf_gauss_newton_terms_band(depths_scaled, scaled_step, rows, cols, intr, voxel_size, Rv2c6xF, tv2c6xF, tranc_dist, index, workspace, out29xF,
+                                 stream=None):
+    """xs_tsdf_gauss_newton_terms_band: F = len(depths_scaled) frames over a built index; Rv2c6xF [F, 6, 3, 3, 2], tv2c6xF [F, 6, 3, 2];
+    frame f's 29 sums land at out29xF[29 f : 29 f + 29] (float64 device tensor)."""
+    F = len(depths_scaled)
+    k, R, t = _fa(intr, 4), _fa(Rv2c6xF, 108 * F), _fa(tv2c6xF, 36 * F)
+    P = (_vp * max(F, 1))(*[_ptr(d) for d in depths_scaled])
+    check(_lib.xs_tsdf_gauss_newton_terms_band(F, P, scaled_step, rows, cols, k.ctypes.data_as(_f32p), voxel_size, R.ctypes.data_as(_f32p),
+                                               t.ctypes.data_as(_f32p), tranc_dist, C.byref(index), _ptr(workspace), _ptr(out29xF), _stream(stream)))
 
 
 class GnOpts(C.Structure):

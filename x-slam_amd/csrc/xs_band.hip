@@ -1,0 +1,174 @@
+// xs_band.hip — the band index of a fixed map and the batched Gauss-Newton pass over it (relocalisation).
+//
+// The six-pose Gauss-Newton pass (k_tsdf_gauss_newton, xs_tsdf.hip) scans the whole dense slab to find its band voxels (gt != 0,
+// |gt| <= 0.95) and evaluates only those.  The band is a function of gt alone: for a map that does not change, every pass of every query
+// frame scans the same gigabytes to find the same voxels.  Here the scan runs once per map version and RECORDS what it deals out:
+//   k_band_count / k_band_write  walk the slab exactly as the Gauss-Newton kernel does (walk_band with hess_tiling(heavy_body = true): the
+//                                same grid, tiling, interleave, skew and per-wave LDS queue) and store each band voxel in segment
+//                                (workgroup b, wave w) at entry 64 k + lane for the lane's k-th take — the order the kernel dealt it in;
+//   k_band_gauss_newton          workgroup (b, f) replays segment b's four wave segments for frame f: lane l of wave w takes entries l,
+//                                l + 64, ... — the very voxels, in the very order, that lane l of wave w of workgroup b met in the dense
+//                                pass — and folds its 29 sums through block_fold_and_finish_of with one ticket per frame.
+// Every double addition therefore meets the same operands in the same order as in the dense pass: a frame's 29 sums are bit-identical to
+// xs_tsdf_gauss_newton_terms' for its depth and poses, whatever the other frames of the launch are.  The frames go into workgroups, not
+// registers (the kernel keeps the dense kernel's 29 accumulators); the index is read F times, from the Infinity Cache after the first.
+#include <hip/hip_runtime.h>
+#include <string.h>
+#include <vector>
+#include "xs_gn_band.h"
+#include "../../include/xslam_amd.h"
+
+#if defined(__HIP_DEVICE_COMPILE__) && !defined(__gfx942__) && !defined(__gfx950__)
+#error "write-through record publish (block_fold_and_finish_of): gfx942 / gfx950 only"
+#endif
+
+static_assert(XS_BAND_MAX_FRAMES == 32, "the header's bound");
+enum { BAND_RECORD_DOUBLES = 32, BAND_POSES_OFFSET = 256 };
+static size_t band_records_offset() { return BAND_POSES_OFFSET + (size_t)XS_BAND_MAX_FRAMES * sizeof(GnPoses); }
+
+__device__ __forceinline__ unsigned long long band_key(int x, int y, int z) {
+    return (unsigned long long)x | ((unsigned long long)y << 21) | ((unsigned long long)z << 42);   // BandQueue's packing
+}
+
+// segs: [0, nseg) offsets, [nseg, 2 nseg) lengths of the nseg = 4 nblocks wave segments (long long)
+template <bool WRITE>
+__global__ void __launch_bounds__(256) k_band_record(const HessArgs a, long long *segs, unsigned long long *keys, unsigned *values) {
+    const int lane = threadIdx.x, wave = threadIdx.y;
+    const unsigned nseg = gridDim.x * 4u, seg = blockIdx.x * 4u + (unsigned)wave;
+    const long long base = WRITE ? segs[seg] : 0;
+    // walk_band deals sixty-four voxels per take to lanes 0 .. 63 and the last, shorter take to lanes 0 .. n - 1: a lane's k-th call of the body
+    // is its wave's k-th take, entry 64 k + lane of the segment
+    long long k = 0;
+    walk_band(a, [&](int x, int y, int z, size_t, float gt) {
+        if (WRITE) {
+            const long long e = base + 64 * k + lane;
+            keys[e] = band_key(x, y, z);
+            values[e] = __float_as_uint(gt);
+        }
+        ++k;
+    });
+    if (!WRITE) {
+        const unsigned long long n = wave_sum_u64((unsigned long long)k);
+        if (lane == 0) segs[nseg + seg] = (long long)n;
+    }
+}
+
+struct BandGnArgs {
+    HessArgs a;                                  // the residual's fields (depth: frame 0's; each workgroup takes its frame's)
+    const float *depth[XS_BAND_MAX_FRAMES];
+    const unsigned long long *keys;
+    const float *values;
+    const long long *segs;
+    const GnPoses *poses;                        // [F], in the workspace
+    double *records;                             // [F][nblocks][32]
+    unsigned *tickets;                           // [F], zero between launches
+    double *out;                                 // [F][29]
+};
+__global__ void __launch_bounds__(256) k_band_gauss_newton(const BandGnArgs g) {
+    __shared__ GnPoses P;
+    const int f = blockIdx.y, lane = threadIdx.x, wave = threadIdx.y;
+    const unsigned nblocks = gridDim.x, nseg = 4u * nblocks, seg = blockIdx.x * 4u + (unsigned)wave;
+    {
+        const float *src = reinterpret_cast<const float *>(g.poses + f);
+        float *dst = reinterpret_cast<float *>(&P);
+        for (int i = threadIdx.y * 64 + threadIdx.x; i < (int)(sizeof(GnPoses) / sizeof(float)); i += 256) dst[i] = src[i];
+        __syncthreads();
+    }
+    HessArgs a = g.a;
+    a.depth = g.depth[f];
+    double acc[29];
+#pragma unroll
+    for (int k = 0; k < 29; ++k) acc[k] = 0.0;
+    const long long off = g.segs[seg], n = g.segs[nseg + seg];
+    for (long long e = lane; e < n; e += 64) {
+        const unsigned long long key = g.keys[off + e];
+        const int x = (int)(key & 0x1fffff), y = (int)((key >> 21) & 0x1fffff), z = (int)(key >> 42);
+        gn_terms_add(a, P, x, y, z, g.values[off + e], acc);
+    }
+    block_fold_and_finish_of<29>(acc, g.records + (size_t)f * nblocks * BAND_RECORD_DOUBLES, g.tickets + f, g.out + 29 * f, nullptr, 0, false,
+                                 nblocks, blockIdx.x);
+}
+
+// the larger of the two grids the slab's walk can take (16-byte aligned gt or not)
+extern "C" size_t xs_tsdf_band_segs_bytes(const int *res, int z0, int z1) {
+    if (!res || z0 < 0 || z1 > res[2] || z1 <= z0) return 0;
+    unsigned most = 0;
+    for (uintptr_t addr : {(uintptr_t)256, (uintptr_t)4}) {
+        HessArgs a; dim3 grid;
+        if (hess_tiling(a, res, reinterpret_cast<const float *>(addr), z0, z1, grid, true)) return 0;
+        most = grid.x > most ? grid.x : most;
+    }
+    return (size_t)most * 4 * 2 * sizeof(long long);
+}
+
+extern "C" int xs_tsdf_band_build(const float *gt, const int *res, int z0, int z1, xs_band_index *index, void *stream) {
+    if (!gt || !res || !index || !index->segs) return xs_set_error(hipErrorInvalidValue, "xs_tsdf_band_build: null pointer");
+    if (z0 < 0 || z1 > res[2] || z1 <= z0) return xs_set_error(hipErrorInvalidValue, "xs_tsdf_band_build: bad slab");
+    if (index->capacity > 0 && (!index->keys || !index->values)) return xs_set_error(hipErrorInvalidValue, "xs_tsdf_band_build: capacity without arrays");
+    if ((long long)res[0] > 0x1fffff || (long long)res[1] > 0x1fffff || (long long)res[2] > 0x3fffff)
+        return xs_set_error(hipErrorInvalidValue, "xs_tsdf_band_build: volume too large for the packed keys");
+    hipStream_t st = (hipStream_t)stream;
+    HessArgs a; dim3 grid;
+    memset(&a, 0, sizeof(a));
+    int rc = hess_tiling(a, res, gt, z0, z1, grid, true);
+    if (rc) return rc;
+    const unsigned nseg = grid.x * 4u;
+    index->count = 0; index->nblocks = 0;
+    hipLaunchKernelGGL(k_band_record<false>, grid, dim3(64, 4), 0, st, a, index->segs, nullptr, nullptr);
+    XS_CHECK(hipGetLastError());
+    std::vector<long long> segs(2 * (size_t)nseg);
+    XS_CHECK(hipMemcpyAsync(segs.data() + nseg, index->segs + nseg, nseg * sizeof(long long), hipMemcpyDeviceToHost, st));
+    XS_CHECK(hipStreamSynchronize(st));
+    long long total = 0;
+    for (unsigned s = 0; s < nseg; ++s) { segs[s] = total; total += segs[nseg + s]; }
+    index->count = total;
+    index->nblocks = (int)grid.x;
+    index->res[0] = res[0]; index->res[1] = res[1]; index->res[2] = res[2];
+    index->z0 = z0; index->z1 = z1;
+    if (total > index->capacity) return XS_BAND_OVER_CAPACITY;
+    XS_CHECK(hipMemcpyAsync(index->segs, segs.data(), nseg * sizeof(long long), hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(k_band_record<true>, grid, dim3(64, 4), 0, st, a, index->segs, index->keys, reinterpret_cast<unsigned *>(index->values));
+    XS_CHECK(hipGetLastError());
+    XS_CHECK(hipStreamSynchronize(st));   // (segs, the host's copy of the offsets, is gone when this returns)
+    return 0;
+}
+
+extern "C" size_t xs_tsdf_band_workspace_bytes(int frames) {
+    if (frames < 1 || frames > XS_BAND_MAX_FRAMES) return 0;
+    return band_records_offset() + (size_t)frames * XS_TSDF_REDUCE_MAX_BLOCKS_C * BAND_RECORD_DOUBLES * sizeof(double);
+}
+
+extern "C" int xs_tsdf_gauss_newton_terms_band(int frames, const float *const *depth_scaled, size_t scaled_step, int rows, int cols, const float *intr4,
+                                               float voxel_size, const float *Rv2c108xF, const float *tv2c36xF, float tranc_dist,
+                                               const xs_band_index *index, void *workspace, double *out29xF_dev, void *stream) {
+    if (frames < 1 || frames > XS_BAND_MAX_FRAMES) return xs_set_error(hipErrorInvalidValue, "xs_tsdf_gauss_newton_terms_band: frames outside 1 .. XS_BAND_MAX_FRAMES");
+    if (!depth_scaled || !intr4 || !Rv2c108xF || !tv2c36xF || !index || !workspace || !out29xF_dev)
+        return xs_set_error(hipErrorInvalidValue, "xs_tsdf_gauss_newton_terms_band: null pointer");
+    if (index->nblocks < 1 || index->nblocks > XS_TSDF_REDUCE_MAX_BLOCKS_C || !index->segs || (index->count > 0 && (!index->keys || !index->values)))
+        return xs_set_error(hipErrorInvalidValue, "xs_tsdf_gauss_newton_terms_band: the index was not built");
+    BandGnArgs g;
+    memset(&g, 0, sizeof(g));
+    for (int f = 0; f < frames; ++f) {
+        if (!depth_scaled[f]) return xs_set_error(hipErrorInvalidValue, "xs_tsdf_gauss_newton_terms_band: null depth");
+        g.depth[f] = depth_scaled[f];
+    }
+    HessArgs &a = g.a;   // as hess_common fills them for the dense pass
+    a.depth = depth_scaled[0]; a.dstep = scaled_step; a.drows = rows; a.dcols = cols;
+    a.voxel_size = voxel_size; a.tranc_dist = tranc_dist; a.tranc_dist_inv = 1.0f / tranc_dist;
+    a.intr = Intr{intr4[0], intr4[1], intr4[2], intr4[3]};
+    a.X = index->res[0]; a.Y = index->res[1]; a.Z = index->res[2]; a.z0 = index->z0; a.z1 = index->z1;
+    std::vector<GnPoses> P((size_t)frames);
+    memset(P.data(), 0, P.size() * sizeof(GnPoses));
+    for (int f = 0; f < frames; ++f)
+        for (int k = 0; k < 6; ++k) { load_mat(Rv2c108xF + 108 * f + 18 * k, P[f].R[k]); load_vec(tv2c36xF + 36 * f + 6 * k, P[f].t[k]); }
+    char *ws = static_cast<char *>(workspace);
+    g.tickets = reinterpret_cast<unsigned *>(ws);
+    g.poses = reinterpret_cast<const GnPoses *>(ws + BAND_POSES_OFFSET);
+    g.records = reinterpret_cast<double *>(ws + band_records_offset());
+    g.keys = index->keys; g.values = index->values; g.segs = index->segs; g.out = out29xF_dev;
+    hipStream_t st = (hipStream_t)stream;
+    XS_CHECK(hipMemcpyAsync(ws + BAND_POSES_OFFSET, P.data(), P.size() * sizeof(GnPoses), hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(k_band_gauss_newton, dim3((unsigned)index->nblocks, (unsigned)frames), dim3(64, 4), 0, st, g);
+    XS_CHECK(hipGetLastError());
+    return 0;
+}

@@ -108,6 +108,16 @@ __device__ __forceinline__ double wave_sum_f64(double v) {
     return v;
 }
 
+// host: a MatS33 / devComplex3 from (re, im) float pairs, row-major (the launchers' pose arguments)
+static inline void load_mat(const float *p, MatS33 &m) {
+    for (int r = 0; r < 3; ++r) {
+        m.data[r].x = cfloat(p[r * 6 + 0], p[r * 6 + 1]);
+        m.data[r].y = cfloat(p[r * 6 + 2], p[r * 6 + 3]);
+        m.data[r].z = cfloat(p[r * 6 + 4], p[r * 6 + 5]);
+    }
+}
+static inline void load_vec(const float *p, cfloat3 &v) { v.x = cfloat(p[0], p[1]); v.y = cfloat(p[2], p[3]); v.z = cfloat(p[4], p[5]); }
+
 }  // namespace xs
 
 // status plumbing for the C ABI: 0 = ok, otherwise the hipError_t value

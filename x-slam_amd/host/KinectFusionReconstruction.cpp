@@ -801,6 +801,7 @@ void KinectFusionReconstruction::DebugSetIcpSequence(unsigned long long v) {
 }
 
 int KinectFusionReconstruction::IntegrateFrame(const DeviceArray2D<ushort> &depth_frame_d) {
+    ++volume_generation;   // (the relocalisation index of this volume is stale from here on)
     if (use_gtPose) {
         Matrix4cf c2w = gt_poses[frame_id];
         world2camera = inverse(c2w);
@@ -1268,7 +1269,6 @@ static void gn_seeded_poses(const xs_host::Matrix4cf &camera2volume, float R[6][
 // kernel indexes (a pitched volume is packed first); the pinned record and the mailbox of the loop protocol.
 const float *KinectFusionReconstruction::GaussNewtonPrepare(const DeviceArray2D<ushort> &depth_frame_d) {
     hipStream_t st = current_stream();
-    DeviceArray2D<float> value = tsdf_volume_d_ptr->value();
     depthRawScaled_d.create(depth_frame_d.rows(), depth_frame_d.cols());
     check_rc(xs_scale_depth(depth_frame_d.ptr(), depth_frame_d.step(), depth_frame_d.rows(), depth_frame_d.cols(), depthRawScaled_d.ptr(),
                             depthRawScaled_d.step(), st), "scaleDepth");
@@ -1282,6 +1282,11 @@ const float *KinectFusionReconstruction::GaussNewtonPrepare(const DeviceArray2D<
         std::memset(gn_publish_, 0, xs_gn_publish_bytes());
     }
     if (!gn_mailbox_ && gn_post_pose) check_rc(xs_icp_mailbox_alloc(&gn_mailbox_, &gn_mailbox_in_device_), "Gauss-Newton mailbox");
+    return GaussNewtonDenseView();
+}
+const float *KinectFusionReconstruction::GaussNewtonDenseView() {
+    hipStream_t st = current_stream();
+    DeviceArray2D<float> value = tsdf_volume_d_ptr->value();
     const size_t row_bytes = (size_t)volume_resolution[0] * sizeof(float), plane_rows = (size_t)volume_resolution[1];
     const float *gt = reinterpret_cast<const float *>(reinterpret_cast<const char *>(value.ptr()) + (size_t)(zo0 - zs0) * plane_rows * value.step());
     if (value.step() != row_bytes) {
@@ -1324,6 +1329,31 @@ void KinectFusionReconstruction::GaussNewtonEnqueue(const DeviceArray2D<ushort> 
         }
     }
 }
+// the kernel's sums of the seeded imaginary parts -> derivative sums: divided by h^2 (J^T J) and h (J^T r)
+static void gn_scale_sums(const double *raw, double out29[29]) {
+    const double ih = 1.0 / (double)(float)H_;
+    for (int i = 0; i < 21; ++i) out29[i] = raw[i] * ih * ih;
+    for (int i = 21; i < 27; ++i) out29[i] = raw[i] * ih;
+    out29[27] = raw[27]; out29[28] = raw[28];
+}
+// One host step of the Gauss-Newton loop on pass p's sums: the loss goes into the history; then 1 = the loop is finished (p was the final loss
+// pass), -1 = it failed (nothing to align to, or the damped system is not positive definite), 0 = camera2volume took the step, go on.
+static int gn_loop_step(const double s[29], int p, int iterations, float damping, xs_host::Matrix4cf &camera2volume, std::vector<double> *loss_history) {
+    using namespace xs_host;
+    if (loss_history) loss_history->push_back(s[28] > 0 ? s[27] / s[28] : 0.0);
+    if (p == iterations) return 1;                        // the final loss pass
+    if (s[28] < 6) return -1;                             // nothing to align to
+    double A[36], b[6], x[6];
+    int q = 0;
+    for (int j = 0; j < 6; ++j)
+        for (int k = j; k < 6; ++k, ++q) { A[j * 6 + k] = s[q]; A[k * 6 + j] = s[q]; }
+    for (int k = 0; k < 6; ++k) { A[k * 6 + k] *= 1.0 + (double)damping; b[k] = -s[21 + k]; }
+    if (!solve_spd6(A, b, x)) return -1;
+    hostComplex xi[6];
+    for (int k = 0; k < 6; ++k) xi[k] = hostComplex((float)x[k], 0.f);
+    camera2volume = se3Exp(xi) * camera2volume;
+    return 0;
+}
 // spins on the record's sequence word; false if the launch reported that it left without summing (abandoned, or its poses never came)
 bool KinectFusionReconstruction::GaussNewtonWait(unsigned long long seq, double out29[29]) {
     volatile unsigned long long *flag = reinterpret_cast<volatile unsigned long long *>(gn_publish_) + 32;
@@ -1337,10 +1367,7 @@ bool KinectFusionReconstruction::GaussNewtonWait(unsigned long long seq, double 
 #endif
     }
     __atomic_thread_fence(__ATOMIC_ACQUIRE);
-    const double ih = 1.0 / (double)(float)H_;
-    for (int i = 0; i < 21; ++i) out29[i] = gn_publish_[i] * ih * ih;
-    for (int i = 21; i < 27; ++i) out29[i] = gn_publish_[i] * ih;
-    out29[27] = gn_publish_[27]; out29[28] = gn_publish_[28];
+    gn_scale_sums(gn_publish_, out29);
     return true;
 }
 void KinectFusionReconstruction::GaussNewtonCollectEvents() {
@@ -1404,18 +1431,9 @@ int KinectFusionReconstruction::RelocalizeGaussNewton(const DeviceArray2D<ushort
         if (!GaussNewtonWait(seq, s)) { leave(0); break; }
         ++done;
         if (p > 0 && ahead) { gn_poll_us += gn_publish_[30] * 0.01; ++gn_poll_passes; }   // (this pass was enqueued ahead: what its kernel waited for its poses, 100 MHz ticks)
-        if (loss_history) loss_history->push_back(s[28] > 0 ? s[27] / s[28] : 0.0);
-        if (p == iterations) break;                           // the final loss pass
-        if (s[28] < 6) { leave(0); break; }                   // nothing to align to
-        double A[36], b[6], x[6];
-        int q = 0;
-        for (int j = 0; j < 6; ++j)
-            for (int k = j; k < 6; ++k, ++q) { A[j * 6 + k] = s[q]; A[k * 6 + j] = s[q]; }
-        for (int k = 0; k < 6; ++k) { A[k * 6 + k] *= 1.0 + (double)damping; b[k] = -s[21 + k]; }
-        if (!solve_spd6(A, b, x)) { leave(0); break; }
-        hostComplex xi[6];
-        for (int k = 0; k < 6; ++k) xi[k] = hostComplex((float)x[k], 0.f);
-        camera2volume = se3Exp(xi) * camera2volume;
+        const int step = gn_loop_step(s, p, iterations, damping, camera2volume, loss_history);
+        if (step > 0) break;
+        if (step < 0) { leave(0); break; }
         if (p + 1 < passes) {
             gn_seeded_poses(camera2volume, R, t);
             if (next_seq) { xs_gn_post_poses(gn_mailbox_, &R[0][0], &t[0][0], next_mail, 0); seq = next_seq; }
@@ -1426,6 +1444,90 @@ int KinectFusionReconstruction::RelocalizeGaussNewton(const DeviceArray2D<ushort
     gn_passes += done;
     GaussNewtonCollectEvents();
     return rc;
+}
+
+// The band index of the owned planes, rebuilt when anything wrote the volume since it was built (volume_generation).  Count, then fill: the
+// arrays grow to the count when they are too small.
+void KinectFusionReconstruction::BandIndexPrepare() {
+    if (band_generation_ == volume_generation && band_.nblocks > 0) return;
+    hipStream_t st = current_stream();
+    const int res[3] = {volume_resolution[0], volume_resolution[1], volume_resolution[2]};
+    const float *gt = GaussNewtonDenseView();
+    const size_t segs_bytes = xs_tsdf_band_segs_bytes(res, zo0, zo1);
+    if (segs_bytes == 0) { std::cout << "error::KinectFusionReconstruction, relocalisation index: bad slab" << std::endl; exit(-1); }
+    if (band_segs_.size() < segs_bytes / sizeof(long long)) band_segs_.create(segs_bytes / sizeof(long long));
+    for (int attempt = 0;; ++attempt) {
+        band_.keys = band_keys_.ptr(); band_.values = band_values_.ptr(); band_.segs = band_segs_.ptr();
+        band_.capacity = (long long)std::min(band_keys_.size(), band_values_.size());
+        const int rc = xs_tsdf_band_build(gt, res, zo0, zo1, &band_, st);
+        if (rc == 0) break;
+        if (rc != XS_BAND_OVER_CAPACITY || attempt > 0) check_rc(rc, "relocalisation index");
+        band_keys_.create((size_t)band_.count);
+        band_values_.create((size_t)band_.count);
+    }
+    band_generation_ = volume_generation;
+}
+
+int KinectFusionReconstruction::RelocalizeGaussNewtonBatch(const std::vector<DeviceArray2D<ushort>> &depths, Matrix4cf *camera2volume, int iterations,
+                                                           float damping, int *ok, std::vector<double> *loss_history) {
+    const int F = (int)depths.size();
+    for (int f = 0; f < F; ++f) ok[f] = 0;
+    if (!tsdf_volume_d_ptr || F == 0) return 0;
+    const int passes = iterations + (loss_history ? 1 : 0);
+    if (passes <= 0) { for (int f = 0; f < F; ++f) ok[f] = 1; return F; }
+    hipStream_t st = current_stream();
+    BandIndexPrepare();
+    const size_t ws_bytes = xs_tsdf_band_workspace_bytes(XS_BAND_MAX_FRAMES);
+    if (band_ws_.size() < ws_bytes) {
+        band_ws_.create(ws_bytes);
+        check_rc(xs_tsdf_reduce_workspace_init(band_ws_.ptr(), st), "band workspace");   // (zeroes the tickets: once)
+    }
+    if (band_sums_.size() < (size_t)XS_BAND_MAX_FRAMES * 29) band_sums_.create((size_t)XS_BAND_MAX_FRAMES * 29);
+    if ((int)band_depth_.size() < F) band_depth_.resize((size_t)F);
+    const int rows = depths[0].rows(), cols = depths[0].cols();
+    for (int f = 0; f < F; ++f) {   // the depth is scaled once per frame, not per pass
+        band_depth_[(size_t)f].create(rows, cols);
+        check_rc(xs_scale_depth(depths[(size_t)f].ptr(), depths[(size_t)f].step(), rows, cols, band_depth_[(size_t)f].ptr(), band_depth_[(size_t)f].step(), st),
+                 "scaleDepth");
+    }
+    const size_t scaled_step = band_depth_[0].step();
+    for (int f = 1; f < F; ++f)
+        if (band_depth_[(size_t)f].step() != scaled_step) { std::cout << "error::KinectFusionReconstruction, batch: depth steps differ" << std::endl; exit(-1); }
+    const bool sharded = shard_count > 1 && collective;
+    std::vector<int> active(F);
+    for (int f = 0; f < F; ++f) active[(size_t)f] = f;
+    std::vector<float> R((size_t)XS_BAND_MAX_FRAMES * 108), t((size_t)XS_BAND_MAX_FRAMES * 36);
+    std::vector<const float *> dptr(XS_BAND_MAX_FRAMES);
+    std::vector<double> raw((size_t)XS_BAND_MAX_FRAMES * 29);
+    int succeeded = 0;
+    for (int p = 0; p < passes && !active.empty(); ++p) {
+        std::vector<int> next;
+        for (size_t c0 = 0; c0 < active.size(); c0 += XS_BAND_MAX_FRAMES) {   // one launch per chunk of the frames still active
+            const int n = (int)std::min(active.size() - c0, (size_t)XS_BAND_MAX_FRAMES);
+            for (int i = 0; i < n; ++i) {
+                const int f = active[c0 + (size_t)i];
+                gn_seeded_poses(camera2volume[f], reinterpret_cast<float (*)[18]>(&R[(size_t)i * 108]), reinterpret_cast<float (*)[6]>(&t[(size_t)i * 36]));
+                dptr[(size_t)i] = band_depth_[(size_t)f].ptr();
+            }
+            check_rc(xs_tsdf_gauss_newton_terms_band(n, dptr.data(), scaled_step, rows, cols, &kinect_intrinsic.fx, voxel_size, R.data(), t.data(),
+                                                     tsdf_volume_d_ptr->getTsdfTruncDist(), &band_, band_ws_.ptr(), band_sums_.ptr(), st), "GaussNewtonTermsBand");
+            if (sharded) collective(collective_user, 0, band_sums_.ptr(), (long)n * 29);   // the per-pass all-reduce of GaussNewtonEnqueue, F x 29 wide
+            hipSafeCall(hipMemcpyAsync(raw.data(), band_sums_.ptr(), (size_t)n * 29 * sizeof(double), hipMemcpyDeviceToHost, st));
+            hipSafeCall(hipStreamSynchronize(st));
+            for (int i = 0; i < n; ++i) {
+                const int f = active[c0 + (size_t)i];
+                double s[29];
+                gn_scale_sums(&raw[(size_t)i * 29], s);
+                const int step = gn_loop_step(s, p, iterations, damping, camera2volume[f], loss_history ? &loss_history[f] : nullptr);
+                if (step == 0 && p + 1 == passes) ok[f] = 1;   // (no loss pass: the last step ends the loop, as in RelocalizeGaussNewton)
+                if (step > 0) ok[f] = 1;
+                if (step == 0 && p + 1 < passes) next.push_back(f);
+            }
+        }
+        active.swap(next);
+    }
+    for (int f = 0; f < F; ++f) succeeded += ok[f];
+    return succeeded;
 }
 
 // reference :334-372
@@ -1596,6 +1698,7 @@ void KinectFusionReconstruction::saveCheckpoint(const std::string &filename) {
 // the exact file length.  Returns false (state unchanged) on any mismatch.
 // The sign map from the volume alone (allocation, checkpoint, anything that wrote the value array without the integrate kernels).
 void KinectFusionReconstruction::RebuildSignMap() {
+    ++volume_generation;   // the documented "the volume was written" call: the relocalisation index is rebuilt too
     if (!sign_map_on() || !sign_map_.ptr() || !tsdf_volume_d_ptr) return;
     const int res[3] = {volume_resolution.x(), volume_resolution.y(), volume_resolution.z()};
     DeviceArray2D<float> value = tsdf_volume_d_ptr->value();
@@ -1637,6 +1740,7 @@ bool KinectFusionReconstruction::loadCheckpoint(const std::string &filename) {
     restore_rows(dv, v, X, rows);
     restore_rows(dg, g, X, rows);
     restore_rows(dw, w, X, rows);
+    ++volume_generation;
     RebuildSignMap();    // the volume was written behind the integrate kernels' back
     world2camera_record.swap(poses);
     world2camera = world2camera_record.back();

@@ -224,6 +224,18 @@ public:
                             unsigned long long seq);
     bool GaussNewtonWait(unsigned long long seq, double out29[29]);
     void GaussNewtonCollectEvents();
+    // Batched relocalisation against a fixed map: the band voxels of the owned planes are compacted once per volume
+    // generation into an index in the six-pose kernel's own dealing order (xs_tsdf_band_build), and every pass evaluates the index for all frames
+    // still active, at most XS_BAND_MAX_FRAMES per launch (xs_tsdf_gauss_newton_terms_band).  Frame f's sums are bit-identical to the dense pass's,
+    // and the host step is RelocalizeGaussNewton's own (gn_loop_step): ok[f], camera2volume[f] and loss_history[f] are what RelocalizeGaussNewton
+    // returns for that frame alone.  A frame that fails or finishes drops out of the launches.  In shard mode the F x 29 sums are all-reduced.
+    // loss_history: null, or F vectors (each gets the losses RelocalizeGaussNewton would give it).  Returns the number of frames that succeeded.
+    int RelocalizeGaussNewtonBatch(const std::vector<DeviceArray2D<ushort>> &depths, Matrix4cf *camera2volume, int iterations, float damping,
+                                   int *ok, std::vector<double> *loss_history = nullptr);
+    long long RelocalizationIndexVoxels() const { return band_generation_ >= 0 ? band_.count : 0; }   // the index as last built, 0 before any
+    // bumped by everything that writes the volume: integrate calls, loadCheckpoint, xs_kf_volume_ptr(kf, 0, .), RebuildSignMap (the band index is rebuilt
+    // when its generation differs)
+    long long volume_generation = 0;
 
     // ExportPointCloud (reference :334-372, main.cpp:78-80): zero-crossing points of the TSDF with
     // normals, at most max_buffer of them; a sharded rank exports the planes it owns.
@@ -285,6 +297,16 @@ private:
     std::vector<std::pair<hipEvent_t, hipEvent_t>> gn_events_;
     DeviceArray<float> gn_dense_;              // packed copy of the owned planes when the volume is pitched
     DeviceArray<unsigned char> gn_ws_;         // reduce workspace of the Gauss-Newton / Hessian kernels
+    const float *GaussNewtonDenseView();       // the owned planes as the dense array the Gauss-Newton kernels index (packed into gn_dense_ when pitched)
+    void BandIndexPrepare();                   // (re)builds band_ when the volume changed since it was built
+    xs_band_index band_ = {};                  // band index of the owned planes (RelocalizeGaussNewtonBatch)
+    long long band_generation_ = -1;           // the volume_generation it was built at
+    DeviceArray<unsigned long long> band_keys_;
+    DeviceArray<float> band_values_;
+    DeviceArray<long long> band_segs_;
+    DeviceArray<unsigned char> band_ws_;       // xs_tsdf_band_workspace_bytes(XS_BAND_MAX_FRAMES), tickets zeroed once
+    DeviceArray<double> band_sums_;            // XS_BAND_MAX_FRAMES x 29
+    std::vector<DeviceArray2D<float>> band_depth_;   // the batch's scaled depths, one per frame
     DeviceArray2D<ushort> depth_ingest_d_;     // device copy of a host frame (ProcessFrameHost)
     ushort *ingest_pinned_[2] = {nullptr, nullptr};
     hipEvent_t ingest_done_[2] = {nullptr, nullptr};

@@ -168,6 +168,26 @@ int xs_kf_relocalize(void *kf, const uint16_t *depth_dev, size_t step_bytes, flo
     if (loss_out) for (size_t i = 0; i < hist.size() && i <= (size_t)iterations; ++i) loss_out[i] = hist[i];
     return rc;
 }
+int xs_kf_relocalize_batch(void *kf, int frames, const uint16_t *const *depth_dev, size_t step_bytes, float *c2v32xF, int iterations, float damping,
+                           double *loss_out, int *ok_out) {
+    KF *k = (KF *)kf;
+    if (frames < 0 || (frames > 0 && (!depth_dev || !c2v32xF || !ok_out))) return -1;
+    std::vector<DeviceArray2D<ushort>> depths;
+    std::vector<Matrix4cf> m((size_t)frames);
+    for (int f = 0; f < frames; ++f) {
+        depths.push_back(wrap_depth(k, depth_dev[f], step_bytes));
+        std::memcpy(static_cast<void *>(&m[(size_t)f]), c2v32xF + 32 * (size_t)f, 32 * sizeof(float));
+    }
+    std::vector<std::vector<double>> hist(loss_out ? (size_t)frames : 0);
+    const int n = k->RelocalizeGaussNewtonBatch(depths, m.data(), iterations, damping, ok_out, loss_out ? hist.data() : nullptr);
+    for (int f = 0; f < frames; ++f) {
+        std::memcpy(c2v32xF + 32 * (size_t)f, &m[(size_t)f], 32 * sizeof(float));
+        if (loss_out)
+            for (size_t i = 0; i < hist[(size_t)f].size() && i <= (size_t)iterations; ++i) loss_out[(size_t)f * (iterations + 1) + i] = hist[(size_t)f][i];
+    }
+    return n;
+}
+long long xs_kf_relocalization_index_voxels(void *kf) { return ((KF *)kf)->RelocalizationIndexVoxels(); }
 long long xs_kf_export_point_cloud(void *kf, int max_buffer, float *points_host, float *normals_host) {
     const auto pc = ((KF *)kf)->ExportPointCloud(max_buffer);
     if (points_host && pc.size()) std::memcpy(points_host, pc.positions.data(), pc.positions.size() * sizeof(float));
@@ -244,7 +264,8 @@ void *xs_kf_volume_ptr(void *kf, int which, size_t *step_bytes) {
     if (which == 1) { auto a = k->tsdf_volume_d_ptr->weight(); if (step_bytes) *step_bytes = a.step(); return a.ptr(); }
     auto a = which == 0 ? k->tsdf_volume_d_ptr->value() : k->tsdf_volume_d_ptr->grad();
     if (step_bytes) *step_bytes = a.step();
-    if (which == 0) k->MarkSignMapStale();   // a caller that writes values through this pointer need not know about the sign map
+    if (which == 0) { k->MarkSignMapStale(); ++k->volume_generation; }   // a caller that writes values through this pointer need not know about the sign map
+                                                                          // or the relocalisation index
     return a.ptr();
 }
 

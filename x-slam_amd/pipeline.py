@@ -36,6 +36,8 @@ _SIGS = {
     "xs_kf_get_camera2volume": (None, [_vp, _f32p]),
     "xs_kf_gauss_newton_terms": (C.c_int, [_vp, _vp, _sz, _f32p, _f64p]),
     "xs_kf_relocalize": (C.c_int, [_vp, _vp, _sz, _f32p, C.c_int, C.c_float, _f64p]),
+    "xs_kf_relocalize_batch": (C.c_int, [_vp, C.c_int, C.POINTER(_vp), _sz, _f32p, C.c_int, C.c_float, _f64p, _i32p]),
+    "xs_kf_relocalization_index_voxels": (C.c_longlong, [_vp]),
     "xs_kf_export_point_cloud": (C.c_longlong, [_vp, C.c_int, _f32p, _f32p]),
     "xs_kf_export_ply": (C.c_longlong, [_vp, C.c_int, C.c_char_p]),
     "xs_kf_export_mesh": (C.c_longlong, [_vp, C.c_int, C.c_longlong, C.c_longlong, _f32p, _f32p, _f32p, C.POINTER(C.c_uint64), _i32p,
@@ -214,6 +216,24 @@ class KinectFusion:
         ok = _lib.xs_kf_relocalize(self.h, depth_dev.data_ptr(), self.width * 2, m.ctypes.data_as(_f32p), iterations, damping,
                                    hist.ctypes.data_as(_f64p))
         return ok == 1, m.reshape(4, 4, 2), hist
+
+    def relocalize_batch(self, depths, c2vs, iterations=5, damping=1e-3):
+        """relocalize for F depth frames at once over the map's band index: (ok [F] bool, refined c2v [F, 4, 4, 2], loss histories
+        [F, iterations + 1]).  Frame f's results equal relocalize(depths[f], c2vs[f], ...) bit for bit."""
+        F = len(depths)
+        m = np.ascontiguousarray(c2vs, dtype=np.float32).reshape(F * 32).copy()
+        hist = np.zeros((F, iterations + 1), np.float64)
+        ok = np.zeros(F, np.int32)
+        P = (_vp * max(F, 1))(*[d if isinstance(d, int) else d.data_ptr() for d in depths])
+        n = _lib.xs_kf_relocalize_batch(self.h, F, P, self.width * 2, m.ctypes.data_as(_f32p), iterations, damping, hist.ctypes.data_as(_f64p),
+                                        ok.ctypes.data_as(_i32p))
+        if n < 0:
+            raise ValueError("xs_kf_relocalize_batch: bad arguments")
+        return ok == 1, m.reshape(F, 4, 4, 2), hist
+
+    def relocalization_index_voxels(self):
+        """Band voxels in the relocalisation index as last built by relocalize_batch (0 before the first)."""
+        return int(_lib.xs_kf_relocalization_index_voxels(self.h))
 
     def export_point_cloud(self, max_buffer=1000000):
         """ExportPointCloud: (points [n, 3], normals [n, 3]) float32 on the host."""
