@@ -207,13 +207,19 @@ int xs_tsdf_reduce_workspace_init(void *workspace, void *stream);
  * One fused pass: the reference's kernel + 4 thrust::reduce.  out4_dev = {loss, grad, hessian,
  * count} as doubles.  gt: dense unpitched TSDF of the slab [z0, z1).  The four per-voxel
  * volumes (indexed like gt) are optional: all four or none.  threshold / k are unused by the
- * reference kernel and absent here. */
+ * reference kernel and absent here.  workspace: xs_tsdf_reduce_workspace_bytes(), its first 256 bytes ZERO
+ * (xs_tsdf_reduce_workspace_init).  Otherwise no workgroup is elected last and nothing is published: out4_dev
+ * keeps its old contents and the call still returns 0.  A host wait on a published result (the orchestrator's,
+ * xs_estimate_combined's) reports such a launch as an error instead of spinning. */
 int xs_compute_local_tsdf_hessian(const float *depth_scaled, size_t scaled_step, int rows, int cols, const float *intr4,
                                   const int *res, float voxel_size, const float *Rv2c36, const float *tv2c12, float tranc_dist,
                                   const float *gt, float *real_out, float *grad_out, float *hess_out, int *count_out, int z0, int z1,
                                   void *workspace, double *out4_dev, void *stream);
 /* float2 ComputeLocalTsdf_loss(..., const Mat33& Rv2c, const float3& tv2c, ..., gt, real, count)
- *                                                  TsdfFusion.h:48-52, TsdfFusion.cu:335-447 */
+ *                                                  TsdfFusion.h:48-52, TsdfFusion.cu:335-447
+ * workspace: as xs_compute_local_tsdf_hessian — first 256 bytes ZERO (xs_tsdf_reduce_workspace_init), otherwise
+ * nothing is published (out2_dev keeps its old contents, the call still returns 0; a host wait on a published result
+ * reports such a launch as an error instead of spinning). */
 int xs_compute_local_tsdf_loss(const float *depth_scaled, size_t scaled_step, int rows, int cols, const float *intr4, const int *res,
                                float voxel_size, const float *Rv2c9, const float *tv2c3, float tranc_dist, const float *gt,
                                float *real_out, int *count_out, int z0, int z1, void *workspace, double *out2_dev, void *stream);
@@ -328,11 +334,16 @@ int xs_raycast_compose_scatter(const void *entries_dev, long n, float *vmap, flo
  * Rv2c108 / tv2c36: six MatS33 / devComplex3, pose k carrying i*h on degree of freedom k (equal real parts).
  * out29_dev: sum d_j d_k for j <= k (21, row-major upper triangle), sum d_k r (6), sum r^2, count, with
  * d_k = Im(error_k) = h * dr/dtheta_k and r = Re(error_0), over voxels with gt != 0, |gt| <= 0.95 that pass the
- * kernel's gates for all six poses.  Other arguments as xs_compute_local_tsdf_hessian.  No synchronisation. */
+ * kernel's gates for all six poses.  Other arguments as xs_compute_local_tsdf_hessian.  No synchronisation.
+ * workspace: first 256 bytes ZERO (xs_tsdf_reduce_workspace_init).  Otherwise no workgroup is elected last and nothing
+ * is published: out29_dev keeps its old contents and the call still returns 0 (the orchestrator's wait reports such a
+ * launch as an error instead of spinning). */
 int xs_tsdf_gauss_newton_terms(const float *depth_scaled, size_t scaled_step, int rows, int cols, const float *intr4, const int *res,
                                float voxel_size, const float *Rv2c108, const float *tv2c36, float tranc_dist, const float *gt, int z0, int z1,
                                void *workspace, double *out29_dev, void *stream);
-/* ... with the loop protocol the ICP iterations have (round 6): opts NULL = plain xs_tsdf_gauss_newton_terms.
+/* ... with the loop protocol the ICP iterations have (round 6): opts NULL = plain xs_tsdf_gauss_newton_terms.  The same workspace contract: first
+ * 256 bytes ZERO (xs_tsdf_reduce_workspace_init), otherwise nothing is published — neither out29_dev nor publish_host's word; the orchestrator's
+ * wait then sees the stream drain without the word and reports that as an error instead of spinning.
  *   publish_host / publish_seq   host-coherent pinned memory of xs_gn_publish_bytes() bytes (hipHostMalloc, coherent + mapped): the launch's last
  *                                workgroup stores the 29 sums there and then the 64-bit word [32] = publish_seq; the host spins on that word
  *                                instead of hipMemcpyAsync + hipStreamSynchronize.  Use a different number for every launch on a buffer.
@@ -457,7 +468,7 @@ int xs_mesh_case_table(int cube_case, signed char out16[16]);
 
 /* ---- ICP normal equations ----------------------------------------------------------------- */
 size_t xs_icp_workspace_bytes(void);
-/* zero the workspace's arrival ticket once after allocation; every launch leaves it zero */
+/* zero the workspace's arrival ticket (its first 256 bytes) once after allocation; every launch leaves it zero */
 int xs_icp_workspace_init(void *workspace, void *stream);
 /* Device half of estimateCombined (ICP.h:24-31, ICP.cu:166-281 + 120-164): sums_dev receives 55
  * doubles — the 27 complex<double> sums in the reference's mbuf order, then the inlier count.
@@ -468,7 +479,10 @@ int xs_icp_workspace_init(void *workspace, void *stream);
  * XS_ICP_PAIRS_BYTES taking 55 pairs {u64 done_seq, double sum} — every sum leaves as one 16-byte store that carries its own sequence
  * word, so no completion word has to be ordered behind the sums (on the device: no wait for the stores' acknowledgement, no barrier, no
  * release store).  The host spins until all 55 sequence words equal done_seq (xs_icp_wait_pairs does); a posted launch that gave up
- * writes done_seq | 1 << 63 into the first pair's word.  Use a different done_seq for every launch on a buffer. */
+ * writes done_seq | 1 << 63 into the first pair's word.  Use a different done_seq for every launch on a buffer.
+ * workspace (xs_icp_accumulate and every variant that takes one): its first 256 bytes must be ZERO (xs_icp_workspace_init).  Otherwise
+ * no workgroup is elected last and nothing is published — sums_dev, the pairs and done_flag are not written, and the call still returns 0;
+ * xs_estimate_combined and the orchestrator see the stream drain without the result and report an error instead of spinning. */
 #define XS_ICP_PUBLISH_PAIRS ((unsigned long long *)(size_t)1)
 #define XS_ICP_PAIRS_BYTES (55 * 16)
 /* host: spin until every pair of `pairs_host` carries `seq`, then copy the 55 sums out.  0 = done, 1 = the launch gave up (its poses never
@@ -486,8 +500,8 @@ int xs_icp_accumulate(const float *Rcurr18, const float *tcurr6, const float *vm
  * protocol).  seq: non-zero, below 2^63, different from the previous launch's on the same buffer.
  * xs_icp_records_count: records a launch over pixel rows [y0, y1) of a cols-wide level writes.
  * xs_icp_sum_records (host only): waits for record 0 .. count - 1 in turn and adds them in that order (deterministic); sums55 = 54
- * sums + inlier count.  Returns 0; 1 if the launch reports that it gave up waiting for a posted pose; -1 after max_spins polls of one
- * record (max_spins <= 0: wait for ever). */
+ * sums + inlier count.  Returns 0; 1 if the launch reports that it gave up waiting for a posted pose; -1 after max_spins polls
+ * (max_spins <= 0: wait for ever). */
 size_t xs_icp_records_bytes(void);
 int xs_icp_records_count(int cols, int y0, int y1);
 int xs_icp_accumulate_records(const float *Rcurr18, const float *tcurr6, const void *mailbox, unsigned mailbox_seq, const float *vmap_curr,
@@ -563,6 +577,8 @@ int xs_icp_iterate(const float *Rcurr18, const float *tcurr6, const float *vmap_
 /* estimateCombined(...) whole: accumulate, wait for the launch (the host spins on a pinned record the kernel's last workgroup writes: everything
  * before it on the stream has completed when the call returns — what the reference's device synchronisation gives, without the stream drain),
  * unpack into the symmetric A (36 complex<double>, A[i*6+j] = A[j*6+i]) and b (6).  sums_dev: optional device copy of the 55 doubles.
+ * A launch that fails returns its HIP error; one that completes without publishing (a workspace whose ticket is not zero, see
+ * xs_icp_workspace_init) returns hipErrorLaunchTimeOut about a millisecond after the stream drained.
  *                                                                              ICP.cu:365-429 */
 int xs_estimate_combined(const float *Rcurr18, const float *tcurr6, const float *vmap_curr, const float *nmap_curr,
                          const float *Rprev_inv18, const float *tprev6, const float *intr4, const float *vmap_g_prev,

@@ -373,6 +373,37 @@ def test_icp_normal_equations(dev, oracle, level):
     assert np.array_equal(A, A2) and np.array_equal(b, b2)
 
 
+def test_estimate_combined_reports_a_launch_that_published_nothing(dev, oracle):
+    """A workspace whose arrival ticket is not zero elects no last workgroup: the launch completes and publishes nothing.
+    xs_estimate_combined sees its stream drain without the sums and returns an error within seconds instead of spinning out its
+    budget; after xs_icp_workspace_init the same call gives the bits of a call on a clean workspace."""
+    import time
+    torch, capi = dev
+    prm, T0, pv, pn, cv, cn = icp_inputs(oracle)
+    rows, cols = cv.shape[0] // 3, cv.shape[1]
+    Rprev_inv = oracle.m3_inverse(T0["Rc2w"])
+    angle = float(np.sin(np.float32(15.0) / np.float32(180.0) * np.pi))
+    maps = [to_dev(torch, m) for m in (cv, cn, pv, pn)]
+    call = lambda ws, sums: capi.estimate_combined(T0["Rc2w"], T0["tc2w"], maps[0], maps[1], Rprev_inv, T0["tc2w"], intr_of(prm), maps[2],
+                                                   maps[3], cols * 8, rows, cols, 0.10, angle, ws, sums)
+    want_sums = torch.zeros(55, dtype=torch.float64, device="cuda")
+    want = call(torch.zeros(capi.icp_workspace_bytes(), dtype=torch.uint8, device="cuda"), want_sums)
+    ws = torch.zeros(capi.icp_workspace_bytes(), dtype=torch.uint8, device="cuda")
+    ws[:4].view(torch.int32).fill_(1 << 30)          # the ticket word, far above any grid size
+    sums = torch.zeros(55, dtype=torch.float64, device="cuda")
+    torch.cuda.synchronize()
+    t0 = time.time()
+    with pytest.raises(capi.XsError, match="published nothing"):
+        call(ws, sums)
+    assert time.time() - t0 < 5.0
+    capi.icp_workspace_init(ws)
+    A, b, inl = call(ws, sums)
+    torch.cuda.synchronize()
+    assert want[2] > 0.3 * rows * cols and inl == want[2]
+    assert np.array_equal(A.view(np.uint64), want[0].view(np.uint64)) and np.array_equal(b.view(np.uint64), want[1].view(np.uint64))
+    assert np.array_equal(sums.cpu().numpy().view(np.uint64), want_sums.cpu().numpy().view(np.uint64))
+
+
 def test_icp_normal_equations_randomized_poses(dev, oracle):
     """The fixed-pose tests above hold the reduction at the pose the maps were made for.  Round 6: 60 random current poses (20 per level) — the
     previous pose moved by up to 3 degrees about a random axis and 4 cm, random first-order imaginary parts on every entry — at the three pyramid

@@ -13,11 +13,14 @@
 // second launch.  The 55 sums go to device memory, or straight into host-coherent pinned memory with a completion word behind them
 // (done_flag), or — the orchestrator's form since round 6 — as 55 stores of {launch number, sum} that need no word behind them
 // (XS_ICP_PUBLISH_PAIRS).  How each phase was measured: profiles/tools/trace_icp.sh, profiles/r02_icp_phases.txt.
+#include <algorithm>
+#include <climits>
 #include <string.h>
 #include "xs_device.h"
 #include "xs_env.h"
 #include "xs_mailbox.h"
 #include "xs_icp_solve.h"
+#include "xs_host_wait.h"
 #include "../../include/xslam_amd.h"
 
 using namespace xs;
@@ -203,6 +206,7 @@ __device__ __forceinline__ bool search(const IcpArgs &a, const MatS33 &Rcurr, co
 }
 constexpr int NS = 54;      // 27 complex sums
 constexpr int NP = 56;      // partial record: 54 sums + count + pad
+static_assert(NP == XS_ICP_RECORD_DOUBLES && NS + 1 == XS_ICP_PAIRS, "the host's wire formats (xs_host_wait.h)");
 }  // namespace
 
 // host-visible completion word: push everything out, then publish the sequence number
@@ -944,29 +948,16 @@ extern "C" int xs_icp_accumulate_records(const float *Rcurr18, const float *tcur
                       angleThres, y0, y1, nullptr, nullptr, nullptr, 0, nullptr, nullptr, nullptr, stream, "xs_icp_accumulate_records: null pointer",
                       Rcurr18 ? nullptr : mailbox, mailbox_seq, records_host, seq);
 }
-/* Host half: waits (spinning) until record i carries `seq`, adds it, for i = 0 .. count - 1 — one fixed order, so the 55 results are
- * the same bits for the same records whatever order the workgroups finished in.  sums55: 54 sums + inlier count.  Returns 0; 1 if a
- * record reports that its launch gave up waiting for a posted pose; -1 after max_spins polls of one record (<= 0: no limit). */
+/* Host half: waits (spinning) until records 0 .. count - 1 carry `seq`, then adds them in that order — one fixed order, so the 55 results
+ * are the same bits for the same records whatever order the workgroups finished in.  sums55: 54 sums + inlier count.  Returns 0; 1 if a
+ * record reports that its launch gave up waiting for a posted pose; -1 after max_spins polls (<= 0: no limit). */
 extern "C" int xs_icp_sum_records(const double *records_host, int count, unsigned long long seq, double *sums55, long long max_spins) {
     if (!records_host || !sums55 || count < 1) return -1;
-    double acc[NP];
-    for (int k = 0; k < NP; ++k) acc[k] = 0.0;
-    for (int i = 0; i < count; ++i) {
-        const double *rec = records_host + (size_t)i * NP;
-        const volatile unsigned long long *flag = reinterpret_cast<const volatile unsigned long long *>(rec + (NP - 1));
-        long long spins = 0;
-        unsigned long long seen;
-        while ((seen = *flag) != seq) {
-            if (seen == (seq | kIcpTimeoutBit)) return 1;
-            if (max_spins > 0 && ++spins > max_spins) return -1;
-#if defined(__x86_64__)
-            __builtin_ia32_pause();
-#endif
-        }
-        __atomic_thread_fence(__ATOMIC_ACQUIRE);
-        for (int k = 0; k < NP - 1; ++k) acc[k] += rec[k];
-    }
-    for (int k = 0; k < NP - 1; ++k) sums55[k] = acc[k];
+    int next = 0;
+    const xs_wait_result w = xs_host_wait([&] { return xs_poll_records(records_host, count, seq, &next); }, max_spins <= 0 ? LLONG_MAX : max_spins);
+    if (w.status == xs_wait::left) return 1;
+    if (w.status != xs_wait::published) return -1;
+    xs_fold_records(records_host, count, sums55);
     return 0;
 }
 
@@ -983,22 +974,10 @@ extern "C" int xs_icp_accumulate_posted(const void *mailbox, unsigned mailbox_se
 }
 /* host half of XS_ICP_PUBLISH_PAIRS: every pair {sequence number, sum} arrives as one 16-byte write; done when all 55 carry `seq` */
 extern "C" int xs_icp_wait_pairs(const void *pairs_host, unsigned long long seq, double *sums55, long long max_spins) {
-    const volatile unsigned long long *p = static_cast<const volatile unsigned long long *>(pairs_host);
-    for (long long spins = 0;; ++spins) {
-        int have = 0;
-        for (int i = 0; i < NS + 1; ++i) have += p[2 * i] == seq;
-        if (have == NS + 1) break;
-        if (p[0] == (seq | kIcpTimeoutBit)) return 1;
-        if (spins >= max_spins) return 2;
-#if defined(__x86_64__)
-        __builtin_ia32_pause();
-#endif
-    }
-    __atomic_thread_fence(__ATOMIC_ACQUIRE);
-    for (int i = 0; i < NS + 1; ++i) {
-        const unsigned long long bits = p[2 * i + 1];
-        memcpy(&sums55[i], &bits, sizeof(double));
-    }
+    const xs_wait_result w = xs_host_wait([&] { return xs_poll_pairs(pairs_host, seq); }, std::max(max_spins, 1LL));
+    if (w.status == xs_wait::left) return 1;
+    if (w.status != xs_wait::published) return 2;
+    xs_read_pairs(pairs_host, sums55);
     return 0;
 }
 /* Host side of the mailbox (xs_mailbox.h has the layout and the reasons).  With MOVDIR64B each of the two 64-byte lines goes out as one write,
@@ -1085,19 +1064,33 @@ extern "C" int xs_estimate_combined(const float *Rcurr18, const float *tcurr6, c
     static thread_local double *host = nullptr;            // the 55 sums as doubles (what xs_icp_unpack and the optional copy read)
     static thread_local void *pairs = nullptr;             // XS_ICP_PUBLISH_PAIRS: 55 x {sequence number, sum} written by the launch
     static thread_local unsigned long long seq = 0;
-    if (!host) {
-        XS_CHECK(hipHostMalloc((void **)&host, 64 * sizeof(double), hipHostMallocCoherent | hipHostMallocMapped));
-        memset(host, 0, 64 * sizeof(double));
-        XS_CHECK(hipHostMalloc(&pairs, XS_ICP_PAIRS_BYTES, hipHostMallocCoherent | hipHostMallocMapped));
-        memset(pairs, 0, XS_ICP_PAIRS_BYTES);
+    if (!host) {   // both buffers or neither: a failed allocation is retried by the next call
+        double *h = nullptr;
+        void *p = nullptr;
+        hipError_t e = hipHostMalloc((void **)&h, 64 * sizeof(double), hipHostMallocCoherent | hipHostMallocMapped);
+        if (e == hipSuccess) e = hipHostMalloc(&p, XS_ICP_PAIRS_BYTES, hipHostMallocCoherent | hipHostMallocMapped);
+        if (e != hipSuccess) {
+            if (h) (void)hipHostFree(h);
+            return xs_set_error(e, "xs_estimate_combined: hipHostMalloc");
+        }
+        memset(h, 0, 64 * sizeof(double));
+        memset(p, 0, XS_ICP_PAIRS_BYTES);
+        host = h;
+        pairs = p;
     }
     ++seq;
     int rc = xs_icp_accumulate(Rcurr18, tcurr6, vmap_curr, nmap_curr, Rprev_inv18, tprev6, intr4, vmap_g_prev, nmap_g_prev, map_step,
                                rows, cols, distThres, angleThres, 0, rows, workspace, static_cast<double *>(pairs), XS_ICP_PUBLISH_PAIRS, seq, stream);
     if (rc) return rc;
     if (rows <= 0 || cols <= 0) { XS_CHECK(hipStreamSynchronize((hipStream_t)stream)); memset(host, 0, 55 * sizeof(double)); }   // (nothing was launched: nothing publishes)
-    else if (xs_icp_wait_pairs(pairs, seq, host, 4000000000LL) != 0)
-        return xs_set_error(hipErrorLaunchTimeOut, "xs_estimate_combined: the launch never published its sums");
+    else {
+        const xs_wait_result w = xs_host_wait([&] { return xs_poll_pairs(pairs, seq); }, 4000000000LL, (hipStream_t)stream);
+        if (w.status == xs_wait::failed) return xs_set_error(w.error, "xs_estimate_combined");
+        if (w.status != xs_wait::published)   // (drained: the workspace's ticket was not zero — xs_icp_workspace_init)
+            return xs_set_error(hipErrorLaunchTimeOut, w.status == xs_wait::drained ? "xs_estimate_combined: the stream drained and the launch published nothing"
+                                                                                     : "xs_estimate_combined: the launch published nothing within the poll budget");
+        xs_read_pairs(pairs, host);
+    }
     xs_icp_unpack(host, A72_host, b12_host);
     if (inliers) *inliers = (long long)host[54];
     if (sums_dev) XS_CHECK(hipMemcpyAsync(sums_dev, host, 55 * sizeof(double), hipMemcpyHostToDevice, (hipStream_t)stream));

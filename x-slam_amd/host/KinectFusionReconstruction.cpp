@@ -13,6 +13,18 @@
 
 using namespace xs_host;
 
+// The poll budget of every wait for a published result (xs_host_wait).  The wait also watches the stream, so the budget only ends a wait whose
+// stream is still busy after this many polls (tens of seconds).
+static constexpr long long kWaitPolls = 2000000000LL;
+// A wait that ended without its result where none can be spared: one line naming the site and what happened, then exit(-1) (the hipSafeCall /
+// check_rc convention).
+[[noreturn]] static void wait_fatal(const char *site, const xs_wait_result &w) {
+    std::cout << "error::KinectFusionReconstruction, " << site << ": " << xs_wait_str(w.status);
+    if (w.status == xs_wait::failed) std::cout << " (" << hipGetErrorString(w.error) << ")";
+    std::cout << std::endl;
+    exit(-1);
+}
+
 KinectFusionReconstruction::KinectFusionReconstruction() {
     depth_width = 0;
     depth_height = 0;
@@ -426,8 +438,7 @@ int KinectFusionReconstruction::PoseEstimate(Matrix3frm Rcurr, Vector3cf tcurr, 
                     last_mail_seq = mail_of[enqueued - 1];   // an abandon command with this number releases every launch in the queue
                     next_enqueued = true;
                 }
-                volatile unsigned long long *flag = reinterpret_cast<volatile unsigned long long *>(pinned_sums_ + 56);
-                auto launch_gave_up = [&]() {   // never expected: the launch gave up on its pose
+                auto launch_gave_up = [&](xs_wait status) {   // never expected: the launch gave up on its pose, or never published
                     if (next_enqueued) xs_icp_post_pose(mailbox, nullptr, nullptr, last_mail_seq, 1);
                     if (posted_pending_) {   // the integrate launch gated on this frame's pose leaves too — before the stream is drained, or the drain waits out its gate
                         xs_icp_post_pose(integrate_mailbox_, nullptr, nullptr, posted_seq_, 1);
@@ -437,27 +448,12 @@ int KinectFusionReconstruction::PoseEstimate(Matrix3frm Rcurr, Vector3cf tcurr, 
                     check_rc(xs_icp_workspace_init(icp_ws_.ptr(), current_stream()), "icp workspace");
                     stage_end(ST_ICP);
                     AbandonClassifiedList();
-                    std::cout << "error::KinectFusionReconstruction, ICP launch timed out waiting for its pose" << std::endl;
+                    std::cout << "error::KinectFusionReconstruction, ICP launch: " << xs_wait_str(status) << std::endl;
                     return 0;
                 };
-                if (icp_host_fold) {
-                    // the workgroups' records arrive in pinned memory; add them here, in index order
-                    const int level_cols = vmaps_curr_d[level_index].cols(), level_rows = vmaps_curr_d[level_index].rows() / 3;
-                    if (xs_icp_sum_records(pinned_records_, xs_icp_records_count(level_cols, 0, level_rows), seq, pinned_sums_, 2000000000LL) != 0)
-                        return launch_gave_up();
-                } else if (icp_publish_pairs) {
-                    if (xs_icp_wait_pairs(pinned_pairs_, seq, pinned_sums_, 2000000000LL) != 0) return launch_gave_up();
-                } else {
-                    long spins = 0;
-                    unsigned long long seen;
-                    while ((seen = *flag) != seq) {
-                        if (seen == (seq | (1ull << 63)) || ++spins > 2000000000L) return launch_gave_up();
-#if defined(__x86_64__)
-                        __builtin_ia32_pause();
-#endif
-                    }
-                    __atomic_thread_fence(__ATOMIC_ACQUIRE);
-                }
+                const xs_wait_result w = wait_icp_sums(icp_host_fold ? IcpSink::records : icp_publish_pairs ? IcpSink::pairs : IcpSink::word, seq, level_index);
+                if (w.status == xs_wait::failed) wait_fatal("ICP launch", w);
+                if (w.status != xs_wait::published) return launch_gave_up(w.status);
                 xs_icp_unpack(pinned_sums_, reinterpret_cast<double *>(A), reinterpret_cast<double *>(b));
                 inliers = (long long)pinned_sums_[54];
             } else
@@ -538,7 +534,6 @@ int KinectFusionReconstruction::PoseEstimateOnDevice(Matrix3frm Rcurr, Vector3cf
                                                      Matrix4cf c2w_curr, int total_iters) {
     struct PoseState { float R[18]; float t[6]; int status; int iters; double det; double pad[2]; };
     static_assert(sizeof(PoseState) == 128, "pose state layout (xs_icp_iterate)");
-    volatile unsigned long long *flag = reinterpret_cast<volatile unsigned long long *>(pinned_sums_ + 56);
     PoseState *pose_host = reinterpret_cast<PoseState *>(pinned_sums_ + 64);
     double *log_host = pinned_sums_ + 128;
     const unsigned long long seq = ++icp_seq_;
@@ -559,14 +554,8 @@ int KinectFusionReconstruction::PoseEstimateOnDevice(Matrix3frm Rcurr, Vector3cf
                      "xs_icp_iterate");
         }
     }
-    long spins = 0;
-    while (*flag != seq) {
-        if (++spins > 2000000000L) { hipSafeCall(hipStreamSynchronize(st)); break; }  // never expected: fall back to a real wait
-#if defined(__x86_64__)
-        __builtin_ia32_pause();
-#endif
-    }
-    __atomic_thread_fence(__ATOMIC_ACQUIRE);
+    const xs_wait_result w = xs_host_wait([&] { return xs_poll_word(pinned_sums_ + 56, seq); }, kWaitPolls, st);
+    if (w.status != xs_wait::published) wait_fatal("ICP loop on the device", w);
     stage_end(ST_ICP);
     const PoseState ps = *pose_host;
     for (int i = 0; i < ps.iters && i < total_iters; ++i)
@@ -586,6 +575,25 @@ int KinectFusionReconstruction::PoseEstimateOnDevice(Matrix3frm Rcurr, Vector3cf
     return 1;
 }
 
+// The 55 sums of ICP launch `seq` over all rows of `level`, from the sink the launch wrote (its records, added in index order; its 55 pairs; or
+// the sums behind the completion word), into pinned_sums_[0..54].  One wait on the current stream.
+xs_wait_result KinectFusionReconstruction::wait_icp_sums(IcpSink sink, unsigned long long seq, int level) {
+    const hipStream_t st = current_stream();
+    if (sink == IcpSink::records) {
+        const int count = xs_icp_records_count(vmaps_curr_d[level].cols(), 0, vmaps_curr_d[level].rows() / 3);
+        int next = 0;
+        const xs_wait_result w = xs_host_wait([&] { return xs_poll_records(pinned_records_, count, seq, &next); }, kWaitPolls, st);
+        if (w.status == xs_wait::published) xs_fold_records(pinned_records_, count, pinned_sums_);
+        return w;
+    }
+    if (sink == IcpSink::pairs) {
+        const xs_wait_result w = xs_host_wait([&] { return xs_poll_pairs(pinned_pairs_, seq); }, kWaitPolls, st);
+        if (w.status == xs_wait::published) xs_read_pairs(pinned_pairs_, pinned_sums_);
+        return w;
+    }
+    return xs_host_wait([&] { return xs_poll_word(pinned_sums_ + 56, seq); }, kWaitPolls, st);
+}
+
 // estimateCombined (ICP.cu:365-429) on this rank's pixel rows, summed over ranks, then unpacked
 void KinectFusionReconstruction::icp_normal_equations(const MatS33 &Rcurr, const devComplex3 &tcurr, const MatS33 &Rprev_inv,
                                                       const devComplex3 &tprev, int level, hostComplexICP *A, hostComplexICP *b,
@@ -600,30 +608,18 @@ void KinectFusionReconstruction::icp_normal_equations(const MatS33 &Rcurr, const
     if (icp_local && !profiling_icp_sync) {
         // single GPU: the kernel writes the sums straight into host-coherent pinned memory and then
         // publishes a sequence number; the host spins on it (no copy kernel, no stream synchronise)
-        volatile unsigned long long *flag = reinterpret_cast<volatile unsigned long long *>(pinned_sums_ + 56);
         const unsigned long long seq = ++icp_seq_;
-        if (icp_host_fold) {
+        if (icp_host_fold)
             check_rc(xs_icp_accumulate_records(&Rcurr.data[0].x.re, &tcurr.x.re, nullptr, 0, &vc.ptr()->re, &nc.ptr()->re, &Rprev_inv.data[0].x.re,
                                                &tprev.x.re, &k.fx, &vp.ptr()->re, &np_.ptr()->re, vc.step(), rows, cols, distThres, angleThres, y0, y1,
                                                pinned_records_, seq, st), "estimateCombined (records)");
-            if (xs_icp_sum_records(pinned_records_, xs_icp_records_count(cols, y0, y1), seq, pinned_sums_, 2000000000LL) != 0) {
-                printf("HIP error(estimateCombined): the ICP records never arrived\n");
-                exit(-1);
-            }
-        } else {
+        else
             check_rc(xs_icp_accumulate(&Rcurr.data[0].x.re, &tcurr.x.re, &vc.ptr()->re, &nc.ptr()->re, &Rprev_inv.data[0].x.re, &tprev.x.re,
                                        &k.fx, &vp.ptr()->re, &np_.ptr()->re, vc.step(), rows, cols, distThres, angleThres, y0, y1,
                                        icp_ws_.ptr(), pinned_sums_, reinterpret_cast<unsigned long long *>(pinned_sums_ + 56), seq, st),
                      "estimateCombined");
-            long spins = 0;
-            while (*flag != seq) {
-                if (++spins > 2000000000L) { hipSafeCall(hipStreamSynchronize(st)); break; }  // never expected: fall back to a real wait
-#if defined(__x86_64__)
-                __builtin_ia32_pause();
-#endif
-            }
-            __atomic_thread_fence(__ATOMIC_ACQUIRE);
-        }
+        const xs_wait_result w = wait_icp_sums(icp_host_fold ? IcpSink::records : IcpSink::word, seq, level);
+        if (w.status != xs_wait::published) wait_fatal("estimateCombined", w);
     } else {
         check_rc(xs_icp_accumulate(&Rcurr.data[0].x.re, &tcurr.x.re, &vc.ptr()->re, &nc.ptr()->re, &Rprev_inv.data[0].x.re, &tprev.x.re,
                                    &k.fx, &vp.ptr()->re, &np_.ptr()->re, vc.step(), rows, cols, distThres, angleThres, y0, y1,
@@ -1354,19 +1350,12 @@ static int gn_loop_step(const double s[29], int p, int iterations, float damping
     camera2volume = se3Exp(xi) * camera2volume;
     return 0;
 }
-// spins on the record's sequence word; false if the launch reported that it left without summing (abandoned, or its poses never came)
+// spins on the record's sequence word; false if the launch reported that it left without summing (abandoned, or its poses never came),
+// fatal if the stream failed or drained without publishing
 bool KinectFusionReconstruction::GaussNewtonWait(unsigned long long seq, double out29[29]) {
-    volatile unsigned long long *flag = reinterpret_cast<volatile unsigned long long *>(gn_publish_) + 32;
-    unsigned long long seen;
-    long spins = 0;
-    while ((seen = *flag) != seq) {
-        if (seen == (seq | (1ull << 63))) return false;
-        if (++spins > 4000000000L) { std::cout << "error::KinectFusionReconstruction, Gauss-Newton pass never published its sums" << std::endl; exit(-1); }
-#if defined(__x86_64__)
-        __builtin_ia32_pause();
-#endif
-    }
-    __atomic_thread_fence(__ATOMIC_ACQUIRE);
+    const xs_wait_result w = xs_host_wait([&] { return xs_poll_word(gn_publish_ + 32, seq); }, kWaitPolls, current_stream());
+    if (w.status == xs_wait::left) return false;
+    if (w.status != xs_wait::published) wait_fatal("Gauss-Newton pass", w);
     gn_scale_sums(gn_publish_, out29);
     return true;
 }

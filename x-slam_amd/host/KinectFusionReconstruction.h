@@ -12,6 +12,7 @@
 #pragma once
 #include "TsdfVolume.h"
 #include "flat_yaml.hpp"
+#include "../csrc/xs_host_wait.h"
 #include <chrono>
 #include <string>
 #include <vector>
@@ -396,6 +397,8 @@ private:
     bool profiling_icp_sync = false;           // true: copy + stream synchronise instead of the spin (debug aid)
     int PoseEstimateOnDevice(Matrix3frm Rcurr, Vector3cf tcurr, const Matrix3frm &Rprev_inv, const Vector3cf &tprev, Matrix4cf c2w_curr,
                              int total_iters);
+    enum class IcpSink { records, pairs, word };   // where an ICP launch wrote its sums (xs_icp_accumulate_records, XS_ICP_PUBLISH_PAIRS, done_flag)
+    xs_wait_result wait_icp_sums(IcpSink sink, unsigned long long seq, int level);
     void icp_normal_equations(const MatS33 &Rcurr, const devComplex3 &tcurr, const MatS33 &Rprev_inv, const devComplex3 &tprev, int level,
                               hostComplexICP *A, hostComplexICP *b, long long *inliers);
     // deferred profiling: one slot of events + one pinned counter record per frame, folded into
