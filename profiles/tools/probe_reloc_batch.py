@@ -24,7 +24,7 @@ def main(n):
     pl = importlib.import_module("x-slam_amd.pipeline")
     synth = importlib.import_module("x-slam_amd.synth")
     from helpers import intr_of, tranc_dist
-    from test_gauss_newton_gpu import seeded_poses
+    from independent_cases import seeded_poses
 
     nmap, F = 4, 16
     gtp = np.zeros((nmap, 4, 4, 2), np.float32)

@@ -237,18 +237,32 @@ def icp_normal_equations(d, h, Rcurr, tcurr, vmap_curr, nmap_curr, Rprev_inv, tp
 
 # ------------------------------------------------------------------------------------------------
 # Dual-complex local-TSDF residual — ComputeLocalTsdfHessianKernel, XKinectFusion/src/TsdfFusion.cu:204-283
-def tsdf_residual_loss(p, h, Rv2c, tv2c, gt_planes, depth_m, intr, voxel_size, trunc, z0=0, dec=None):
-    """sum over the voxels of gt_planes ([nz, Y, X]: planes z0 .. z0 + nz of the map, as the C ABI takes a slab) of error(p)^2,
-    error = (|Dp (xl, yl, 1)| - |v_c| - gt * trunc) / trunc, for the pose x(p) = re.re + p * re.im / h (Rv2c [3, 3, 4],
-    tv2c [3, 4] dual-complex groups).  Returns (loss, count, dec)."""
-    Rq, tq = np.asarray(Rv2c, np.float64).reshape(3, 3, 4), np.asarray(tv2c, np.float64).reshape(3, 4)
-    R = Rq[..., 0] + (p / h) * Rq[..., 1]
-    t = tq[..., 0] + (p / h) * tq[..., 1]
+def seeded_pose(p, h, Rv2c, tv2c):
+    """The real pose at seed offsets p = (p1, p2) of packed groups Rv2c [3, 3, k], tv2c [3, k]: k = 4 dual-complex (re.re, re.im, im.re,
+    im.im): x = re.re + p1 * re.im / h + p2 * im.re / h + p1 * p2 * im.im / h^2; k = 2 complex (re, im): x = re + p1 * im / h.  A scalar p
+    is (p, 0)."""
+    p1, p2 = (p, 0.0) if np.ndim(p) == 0 else p
+    out = []
+    for a, shape in ((Rv2c, (3, 3)), (tv2c, (3,))):
+        q = np.asarray(a, np.float64).reshape(*shape, -1)
+        x = q[..., 0] + (p1 / h) * q[..., 1]
+        if q.shape[-1] == 4:
+            x = x + (p2 / h) * q[..., 2] + (p1 * p2 / h / h) * q[..., 3]
+        else:
+            assert q.shape[-1] == 2 and p2 == 0.0
+        out.append(x)
+    return out
+
+
+def tsdf_residuals(p, h, Rv2c, tv2c, gt_planes, depth_m, intr, voxel_size, trunc, z0=0, dec=None):
+    """Per-voxel form of tsdf_residual_loss: (error [n], use [n], dec) over the band voxels dec['xyz'] [n, 3] of gt_planes; error is
+    meaningful where use holds (the voxels the kernel sums)."""
+    R, t = seeded_pose(p, h, Rv2c, tv2c)
     fx, fy, cx, cy = (float(F32(v)) for v in intr)
     vs, tr = float(F32(voxel_size)), float(F32(trunc))
     rows, cols = depth_m.shape
     if dec is None:
-        assert p == 0.0
+        assert np.all(np.asarray(p) == 0.0)
         g = np.asarray(gt_planes, np.float64)
         band = (g != 0) & ~(np.abs(g) > 0.95)                            # :221-223
         zz, yy, xx = np.nonzero(band)
@@ -278,8 +292,33 @@ def tsdf_residual_loss(p, h, Rv2c, tv2c, gt_planes, depth_m, intr, voxel_size, t
     err = (dist - g * tr) / tr                                           # :268-269
     if "use" not in dec:
         dec["use"] = dec["keep"] & ~((Dp > 5) | (Dp < 0.2)) & ~(np.abs(err) > 1)                # :260, :271
-    use = dec["use"]
+    return err, dec["use"], dec
+
+
+def tsdf_residual_loss(p, h, Rv2c, tv2c, gt_planes, depth_m, intr, voxel_size, trunc, z0=0, dec=None):
+    """sum over the voxels of gt_planes ([nz, Y, X]: planes z0 .. z0 + nz of the map, as the C ABI takes a slab) of error(p)^2,
+    error = (|Dp (xl, yl, 1)| - |v_c| - gt * trunc) / trunc, for the pose seeded_pose(p, h, Rv2c, tv2c) (Rv2c [3, 3, 4], tv2c [3, 4]
+    dual-complex groups; p a scalar or the two offsets (p1, p2)).  Returns (loss, count, dec)."""
+    err, use, dec = tsdf_residuals(p, h, Rv2c, tv2c, gt_planes, depth_m, intr, voxel_size, trunc, z0, dec)
     return float((err[use] ** 2).sum()), int(use.sum()), dec             # :274-280 + the four reductions :317-324
+
+
+def gn_terms(Rv2c6, tv2c6, gt_planes, depth_m, intr, voxel_size, trunc, z0=0, h=1e-7, fd=1e-6):
+    """The 29 Gauss-Newton sums of the same residual for six complex poses (Rv2c6 [6, 3, 3, 2], tv2c6 [6, 3, 2]) that share one real
+    part: d_k = h * (r_k(+fd) - r_k(-fd)) / 2 fd, the central difference of pose k's real residual along its imaginary part; out =
+    sum d_j d_k (j <= k, row-major: 21), sum d_k r (6), sum r^2, count, over the voxels that pass the gates at the shared real pose."""
+    Rs = np.asarray(Rv2c6, np.float32).reshape(6, 3, 3, 2)
+    ts = np.asarray(tv2c6, np.float32).reshape(6, 3, 2)
+    assert np.all(Rs[..., 0] == Rs[0, ..., 0]) and np.all(ts[..., 0] == ts[0, ..., 0])
+    args = (gt_planes, depth_m, intr, voxel_size, trunc, z0)
+    e0, use, dec = tsdf_residuals(0.0, h, Rs[0], ts[0], *args)
+    D = np.empty((6, int(use.sum())))
+    for k in range(6):
+        ep = tsdf_residuals(+fd, h, Rs[k], ts[k], *args, dec=dec)[0]
+        em = tsdf_residuals(-fd, h, Rs[k], ts[k], *args, dec=dec)[0]
+        D[k] = (h * (ep - em) / (2 * fd))[use]
+    r = e0[use]
+    return np.array([D[j] @ D[k] for j in range(6) for k in range(j, 6)] + [D[k] @ r for k in range(6)] + [r @ r, float(use.sum())])
 
 
 def central(f, step):

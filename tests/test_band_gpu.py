@@ -7,7 +7,8 @@ import numpy as np
 import pytest
 
 from helpers import intr_of, s1_transforms, synth, tranc_dist
-from test_gauss_newton_gpu import seeded_poses, twist_matrix
+from independent_cases import seeded_poses
+from test_gauss_newton_gpu import twist_matrix
 
 W, H = synth.WIDTH, synth.HEIGHT
 

@@ -7,11 +7,11 @@ import numpy as np
 import pytest
 
 from helpers import intr_of, s1_transforms, synth, tranc_dist
+from independent_cases import HSTEP, seeded_poses
 
 W, H = synth.WIDTH, synth.HEIGHT
 
 pytestmark = pytest.mark.gpu
-HSTEP = np.float32(1e-7)
 
 
 @pytest.fixture(scope="module")
@@ -39,23 +39,6 @@ def twist_matrix(xi):
         V = np.eye(3) + (1 - np.cos(th)) / th ** 2 * K + (th - np.sin(th)) / th ** 3 * K @ K
     T = np.eye(4); T[:3, :3] = R; T[:3, 3] = V @ v
     return T
-
-
-def seeded_poses(c2v_real):
-    """The six complex v2c poses the orchestrator builds: inverse(se3Exp(i h e_k) c2v), first order in h."""
-    Rs = np.zeros((6, 3, 3, 2), np.float32); ts = np.zeros((6, 3, 2), np.float32)
-    v2c = np.linalg.inv(c2v_real)
-    for k in range(6):
-        G = np.zeros((4, 4))
-        if k < 3:
-            G[k, 3] = 1
-        else:
-            w = np.zeros(3); w[k - 3] = 1
-            G[:3, :3] = np.array([[0, -w[2], w[1]], [w[2], 0, -w[0]], [-w[1], w[0], 0]])
-        d = -v2c @ G          # d/deps inverse(exp(eps G) c2v) at 0
-        Rs[k, :, :, 0] = v2c[:3, :3]; Rs[k, :, :, 1] = HSTEP * d[:3, :3]
-        ts[k, :, 0] = v2c[:3, 3]; ts[k, :, 1] = HSTEP * d[:3, 3]
-    return Rs, ts
 
 
 def test_gn_terms_equal_oracle(dev, oracle):

@@ -1,7 +1,8 @@
 """GPU: the HIP kernels, through the C ABI, against the independently written float64 model and its central differences
 (tests/independent_f64.py; no text shared with oracle/): kernel values to float32 rounding and — the point of the
 product — the imaginary parts / h against finite-difference derivatives of a real-valued model, per kernel: integrate
-voxel update, raycast vertex + normal, ICP rows + 27 sums, dual-complex residual (loss, gradient, second derivative).
+voxel update, raycast vertex + normal, ICP rows + 27 sums, dual-complex residual (loss, gradient, second derivative; the full 6 x 6
+Hessian from mixed seeds), six-pose Gauss-Newton sums (dense and band pass).
 Measured figures are written to gpurun_out/independent_f64.json when that directory exists."""
 import importlib
 import json
@@ -105,3 +106,73 @@ def test_survey_reference_kernel_figures_through_the_kernels(be, n):
     assert abs(U - fig["integrate_U"][str(n)]) <= max(2, 1e-4 * fig["integrate_U"][str(n)])
     assert abs(hits - fig["raycast_hits"][str(n)]) <= 2
     assert abs(inl - fig["icp_inliers_level0"][str(n)]) <= 0.003 * fig["icp_inliers_level0"][str(n)]
+
+
+# ---- the residual kernels with seeds along se(3) generators (tests/independent_cases.py: pair_pose, seeded_v2c) ----------------------
+@pytest.mark.parametrize("scene,perturb,cross", [("s3", 3.0, (1, 3)), ("s1", 0.0, (3, 5))])
+def test_full_hessian_from_21_launches(be, scene, perturb, cross):
+    """xs_compute_local_tsdf_hessian seeded with eps1 along generator a and eps2 along b, for every pair a <= b (plus one pair with the
+    eps1 eps2 input, which makes hessian / h^2 the exact entry of L(v2c exp(-theta_a G_a - theta_b G_b))): the 6 x 6 Hessian, each entry
+    against the float64 model's four-point stencil.  S3 three units off the optimum, where the eps1 eps2 input's part of H_ab is 2.6e-3 of the
+    scale; S1 at the frame's pose, where that part is below the tolerance (the entry is checked, the input is not exercised) — off the pose,
+    one voxel on the sphere's depth edge moves S1's H_ab by more than the tolerance under the kernel's own float32 rounding."""
+    r = ic.check_full_hessian(be, n=128, scene=scene, cross=(cross,), perturb=perturb)
+    LOG[f"full_hessian_{scene}_128"] = dict(worst=r["worst"], count_diff=r["count_diff"], count_spread=r["count_spread"],
+                                            entries={k: {f: e[f] for f in ("hess", "hess_model", "hess_err", "grad_err")} for k, e in r["entries"].items()})
+    assert r["count_spread"] == 0 and len(r["entries"]) == 22
+    for e in r["entries"].values():
+        ic.assert_hessian_pair(e)
+
+
+def _cropped_map(be, n, res):
+    _, states = ic.two_frames(be, n, "s3", (0, 3), 0.0)
+    return ic.crop(states[1][0], n, res)
+
+
+@pytest.mark.parametrize("form", ["rows_not_16B", "slab", "address_4B"])
+def test_hessian_pairs_on_the_other_scan_forms(be, form):
+    """Mixed-seed pairs where the kernel scans otherwise than on the 16-byte aligned n^3 maps above: a 90 x 72 x 84 map
+    (rows of 360 bytes: the one-column scan, a non-cubic volume), planes [40, 88) of the 128^3 map (z0 > 0, slab-relative addressing), and
+    the 128^3 map at an address that is only 4-byte aligned (the one-column scan).  The eps1 eps2 pairs — on t for (t_y, omega_x), on R for
+    (omega_x, omega_z) — are taken three units off the optimum (ic.perturbed_v2c), where that input's part of H_ab is 3.8e-4 .. 2.6e-3 and
+    3.6e-3 .. 6.1e-3 of the scale: a scan that drops or misplaces it fails."""
+    if form == "rows_not_16B":
+        res = (90, 72, 84)
+        kw = dict(n=96, gt=_cropped_map(be, 96, res), res=res)
+    elif form == "slab":
+        kw = dict(n=128, z0=40, z1=88)
+    else:
+        kw = dict(n=128, misalign=True)
+    out = {}
+    for a, b, cross in ((2, 4, False), (3, 5, False), (1, 3, True), (3, 5, True)):
+        r = ic.check_hessian_pair(be, a, b, scene="s3", cross=cross, perturb=3.0 if cross else 0.0, **kw)
+        out[f"{a}{b}{'x' if cross else ''}"] = r
+        ic.assert_hessian_pair(r)
+    LOG[f"hessian_pairs_{form}"] = out
+
+
+@pytest.mark.parametrize("scene,n,z0,z1", [("s3", 128, 0, None), ("s1", 128, 0, None), ("s3", 256, 0, None), ("s3", 128, 40, 88)])
+def test_gauss_newton_sums_against_the_model(be, scene, n, z0, z1):
+    """xs_tsdf_gauss_newton_terms: all 29 sums (21 J^T J, 6 J^T r, sum r^2, count) against central differences of the float64 model's
+    residual along each of the six seeded poses, over the whole map and over a slab."""
+    r = ic.check_gn_terms(be, n=n, scene=scene, z0=z0, z1=z1)
+    LOG[f"gn_terms_{scene}_{n}_{z0}_{n if z1 is None else z1}"] = r
+    ic.assert_gn(r)
+
+
+def test_band_pass_three_frames_against_the_model(be):
+    """xs_tsdf_gauss_newton_terms_band, F = 3 frames in one launch, each with its own depth frame and its own perturbed pose: every
+    frame's 29 sums against the model for that frame (a frame that read another frame's depth or poses fails)."""
+    rs = ic.check_gn_band(be, n=128, scene="s3", frames=(1, 2, 3))
+    LOG["gn_band_s3_128_F3"] = rs
+    for r in rs:
+        ic.assert_gn(r)
+
+
+@pytest.mark.parametrize("scene", ["s3", "s1"])
+def test_hessian_gradient_equals_gauss_newton_gradient(be, scene):
+    """The Hessian kernel seeded with eps1 = h (-v2c G_k), eps2 = 0 and the six-pose kernel at the same real pose: grad / h ==
+    2 sum d_k r / HSTEP for all six k, and the same voxel count."""
+    r = ic.check_hessian_gn_identity(be, n=128, scene=scene)
+    LOG[f"hessian_gn_identity_{scene}_128"] = r
+    ic.assert_identity(r)

@@ -1008,7 +1008,9 @@ def test_tsdf_hessian_full_size_512(dev, oracle):
     on t_x.  (1) eight z-slabs add up to the whole-volume pass — the sharded form, count exact; (2) the slab holding most
     of the band equals the CPU oracle on the same planes; (3) on those planes loss, d/dt_x and d2/dt_x^2 equal the
     independent float64 model's value and central differences (tests/independent_f64.py); (4) sanity of the sums: every
-    voxel contributes a square, and near the true pose the second derivative is positive."""
+    voxel contributes a square, and near the true pose the second derivative is positive; (5) on those planes, three
+    mixed-seed pairs against the model."""
+    import independent_cases as ic
     import independent_f64 as ind
     from independent_cases import dual_pose
     torch, capi = dev
@@ -1065,6 +1067,20 @@ def test_tsdf_hessian_full_size_512(dev, oracle):
     assert abs(got[0] - l0) <= 5e-4 * l0
     assert abs(got[1] / h2 - g_model) <= 5e-4 * max(abs(g_model), (l0 * abs(h_model)) ** 0.5)
     assert abs(got[2] / h2 / h2 - h_model) <= 5e-4 * abs(h_model)
+    # (5) mixed seeds on the same planes (independent_cases.pair_pose / pair_model): eps1 and eps2 along two se(3) generators —
+    # rotation x translation, rotation x rotation at the frame's pose, and (omega_y, omega_z) with the eps1 eps2 input (on R) half a unit
+    # off it (its own decisions; further off, the residual gate empties these planes), where that input's part of H_ab is 1.8e-3 of the
+    # scale — against the four-point stencil
+    for a, b, cross in ((4, 2, False), (3, 5, False), (4, 5, True)):
+        v2c = ic.perturbed_v2c(prm, 3, 0.5 if cross else 0.0)
+        Rp, tp = ic.pair_pose(v2c, a, b, cross=cross)
+        assert cross or (np.array_equal(Rp[..., 0], Rd[..., 0]) and np.array_equal(tp[:, 0], td[:, 0]))
+        out4 = torch.zeros(4, dtype=torch.float64, device="cuda")
+        capi.compute_local_tsdf_hessian(scaled, W * 4, H, W, intr_of(prm), res, prm["tsdf_voxel_size"], Rp, tp, tranc_dist(prm), gt_dev[z0 * n * n:], ws,
+                                        out4, z0=z0, z1=z1)
+        torch.cuda.synchronize()
+        m, _ = ic.pair_model(Rp, tp, args[2:], dec=None if cross else dec)
+        ic.assert_hessian_pair(ic.pair_errors(out4.cpu().numpy(), m))
 
 
 # ---- DeviceArray scalar math on the device ------------------------------------------------

@@ -144,7 +144,7 @@ def test_tsdf_residual_kernels_thousands_of_launches_512(dev):
     r = out.cpu().numpy()
     assert r[0, 3] > 100000 and len(np.unique(r.view(np.int64), axis=0)) == 1
     # the six-pose first-order kernel: real pose of frame 3 with the six unit seeds the orchestrator builds
-    from test_gauss_newton_gpu import seeded_poses
+    from independent_cases import seeded_poses
     T3 = s1_transforms(3, prm, seed=None)
     v2c = np.eye(4)
     v2c[:3, :3] = np.asarray(T3["Rv2c"], np.float64).reshape(3, 3, 2)[..., 0]
