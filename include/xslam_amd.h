@@ -96,7 +96,7 @@ int xs_integrate_scaled(const float *depth_scaled, size_t scaled_step, int rows,
 #define XS_INTEGRATE_HEADER_IS_CLEAR 1u
 #define XS_INTEGRATE_NO_FOLD 2u
 #define XS_INTEGRATE_ALWAYS_STORE 8u    /* store all three words of every updated voxel, also where their bits do not change (the default stores only words that change: same volume, fewer bytes) */
-#define XS_INTEGRATE_POSE_POSTED 16u     /* the kernel takes its pose from a mailbox (xs_integrate_opts.pose_mailbox; posted with xs_icp_post_pose): see below */
+/* (16u was the posted launch of ABI 2, whose kernel took its pose from a mailbox: a call that still sets it fails with hipErrorInvalidValue) */
 #define XS_INTEGRATE_NO_TILES 32u        /* every brick takes the exact per-voxel walk: no free-space / nothing-to-write classification from the depth tiles (A/B and tests; same volume either way) */
 #define XS_INTEGRATE_COUNT_CLASSES 64u   /* the kernel counts the wave-sized boxes it classified: 32-bit words 48 / 49 / 50 of the workspace = free / nothing to write / exact walk (cleared with the header; tests and bench figures) */
 #define XS_INTEGRATE_RECLASSIFY_BOXES 128u /* with XS_INTEGRATE_LIST_IS_READY: the brick list holds for this pose but the box classes xs_integrate_classify left do not (xs_integrate_list_covers returned 1, not 3): classify the boxes again, with this pose */
@@ -117,17 +117,9 @@ int xs_integrate_fold_counts(void *workspace, unsigned long long *updated_dev, v
  * still takes the exact tests with the final pose).
  * With a depth-tile table named (xs_integrate_opts.depth_tiles) xs_integrate_classify_ex also decides the boxes' classes (free space /
  * nothing to write / per-voxel walk), padded for every pose within the slack's allowances; xs_integrate_list_covers returns 0 (the
- * list does not hold), 1 (the list holds, the classes do not: add XS_INTEGRATE_RECLASSIFY_BOXES to the call's flags) or 3 (both hold). */
-/* The integrate kernel enqueued before its pose exists (flag XS_INTEGRATE_POSE_POSTED, with XS_INTEGRATE_LIST_IS_READY | XS_INTEGRATE_HEADER_IS_CLEAR):
- * xs_integrate_opts.pose_mailbox / mailbox_seq / mailbox_slack / pose_dev name — for an xs_integrate_scaled_ex2 call — the mailbox
- * (xs_icp_mailbox_alloc: one of its own, not the ICP loop's) that a one-wave gate kernel in front of the integrate kernel polls, the sequence number
- * it waits for, the factor the call widens the frustum planes by, and 128 bytes of device memory (pose_dev) through which the gate hands the pose on; that call is given the pose the brick list was classified with (xs_integrate_classify) and uses it for the planes only.
- * When the final pose is known: if xs_integrate_pose_covered(..., list pose, slack_scale, final pose) post it with
- * xs_icp_post_pose(mailbox, Rv2c18, tv2c6, seq, 0) — the kernel then integrates with exactly that pose, same volume as a plain call — else post
- * xs_icp_post_pose(mailbox, NULL, NULL, seq, 1): the launch leaves without touching the volume, and a plain call follows.  Every posted launch must
- * be answered by exactly one post (it gives up after ~1 s otherwise).  Sequence numbers: non-zero, increasing per mailbox. */
-int xs_integrate_pose_covered(int rows, int cols, const float *intr4, const int *res, float voxel_size, const float *Rv2c18_list,
-                              const float *tv2c6_list, float slack_scale, const float *Rv2c18, const float *tv2c6);
+ * list does not hold), 1 (the list holds, the classes do not: add XS_INTEGRATE_RECLASSIFY_BOXES to the call's flags) or 3 (both hold).
+ * The integrate call takes those classes only when it is an xs_integrate_scaled_ex2 call that names the same table and its own pose lies
+ * within their slack (it checks: see the options structs below); otherwise it decides the boxes again with its own pose. */
 int xs_integrate_classify(int rows, int cols, const float *intr4, const int *res, float voxel_size, const float *Rv2c18, const float *tv2c6,
                           float tranc_dist, int z0, int z1, const float *depth_max_dev, void *workspace, float slack_scale, unsigned flags,
                           void *stream);
@@ -139,7 +131,7 @@ int xs_integrate_list_covers(int rows, int cols, const float *intr4, const int *
 size_t xs_integrate_workspace_bytes(const int *res, int nz);
 
 /* ---- Options structs ---------------------------------------------------------------------------------------------------------------
- * Everything a call takes besides its arguments proper — depth-tile table, sign map, events, pose mailbox, pyramid outputs — travels in an
+ * Everything a call takes besides its arguments proper — depth-tile table, sign map, events, pyramid outputs — travels in an
  * options struct that is an argument of the call: xs_integrate_scaled_ex2 / xs_integrate_classify_ex / xs_raycast_ex / xs_raycast_slab_ex /
  * xs_resize_pyramid_ex.  The library keeps NO per-thread state (ABI version 2: the xs_*_set_* functions of version 1 are gone), so nothing
  * a previous call set, or an early return forgot to clear, can leak into a call.  The entry points without a struct (xs_integrate_scaled*,
@@ -159,10 +151,6 @@ typedef struct xs_integrate_opts {
     const void *depth_tiles;         /* this frame's xs_scale_depth_tiles table, or NULL (the call builds its own in its workspace) */
     void *signmap;                   /* the sign map the call marks, or NULL */
     void *start_event, *stop_event;  /* hipEvent_t riding on the integrate kernel's dispatch (classify: stop_event = its last dispatch); NULL = none */
-    const void *pose_mailbox;        /* XS_INTEGRATE_POSE_POSTED: the mailbox the gate polls ... */
-    unsigned mailbox_seq;            /* ... the sequence number it waits for ... */
-    float mailbox_slack;             /* ... the factor the call widens the list pose's frustum planes by ... */
-    void *pose_dev;                  /* ... and 128 bytes of device memory through which the gate hands the pose on */
 } xs_integrate_opts;
 int xs_integrate_scaled_ex2(const float *depth_scaled, size_t scaled_step, int rows, int cols, const float *intr4, int max_weight,
                             const int *res, float voxel_size, const float *Rv2c18, const float *tv2c6, float tranc_dist, float *value,

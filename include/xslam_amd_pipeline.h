@@ -170,9 +170,6 @@ void xs_kf_rebuild_sign_map(void *kf);
 /* shard mode: bytes this rank has received through the raycast composite's collectives since creation (a ring all-reduce of S bytes over N
  * ranks counted as 2 (N - 1) / N x S, the gather of the owned pixels as the other ranks' parts) */
 long long xs_kf_composite_bytes(void *kf);
-/* integrate_post_pose: how many posted integrate launches were given their pose, and how many were told to leave because the final pose was
- * not covered by the planes they had been given (those frames took the plain call) */
-void xs_kf_posted_integrate_counts(void *kf, long long *accepted, long long *refused);
 /* How often the brick list and box classes decided ahead of a frame's final pose (behind its last ICP launch) held for that pose: counts4[0]
  * neither (everything classified again), [1] the list only (the boxes decided again with the final pose), [3] both. */
 void xs_kf_list_cover_counts(void *kf, long long *counts4);

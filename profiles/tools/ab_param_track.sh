@@ -1,6 +1,6 @@
 #!/bin/bash
 # GPU box: bench.py's track (the headline pipeline) with an orchestrator parameter set two ways, alternating; usage:
-#   bash profiles/tools/ab_param_track.sh integrate_classify_beside_icp true false [rounds]
+#   bash profiles/tools/ab_param_track.sh integrate_classify_ahead true false [rounds]
 cd "$(dirname "$0")/../.." && mkdir -p gpurun_out
 V=$1; A=$2; B=$3; R=${4:-2}
 for rep in $(seq 1 $R); do for val in $A $B; do

@@ -30,12 +30,12 @@ def test_every_declared_symbol_is_exported(header, lib):
         assert hasattr(h, n), f"{n} declared in include/{header} but not exported by {lib}"
 
 
-def test_ctypes_tables_cover_the_headers():
+def test_ctypes_tables_cover_the_abi3_headers():
     capi = importlib.import_module("x-slam_amd.capi")
     pl = importlib.import_module("x-slam_amd.pipeline")
     assert set(declared("xslam_amd.h")) == set(capi._SIGS)
     assert set(declared("xslam_amd_pipeline.h")) == set(pl._SIGS)
-    assert capi.abi_version() == 2
+    assert capi.abi_version() == 3
     assert capi.icp_workspace_bytes() > 0 and capi.tsdf_reduce_workspace_bytes() > 0
     assert capi.integrate_workspace_bytes([512, 512, 512]) == 256 + 8192 * 4 + 8 * 128 * 256 * 4 + 8 * 128 * 256 * 4 * 4 + (1 << 20) + 8 * 128 * 256 * 4   # header + update counts (a word per workgroup) + brick list + box classes (a word per wave-sized box) + the call's own depth-tile table + the list in the order it is taken
     assert capi.depth_tiles_bytes(480, 640) == (60 * 80 + 15 * 10) * 8

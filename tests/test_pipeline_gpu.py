@@ -236,28 +236,14 @@ def test_pipeline_fewer_pyramid_levels_against_live_oracle(dev, oracle, levels):
     kf.close()
 
 
-def test_brick_list_classified_ahead_changes_nothing(dev):
+def test_brick_list_classified_behind_the_last_icp_launch_changes_nothing(dev):
     """integrate_classify_ahead (the integrate call's brick list built behind the last ICP launch, from the pose that launch
     starts from) against the plain order and against a list slack of 1 — with which no final pose is ever covered, so every frame
-    takes the fall-back (header cleared again, classification repeated); and integrate_post_pose (the integrate kernel itself
-    enqueued behind the classification and handed the final pose through its mailbox), covered and — slack 1 — never covered (the
-    posted launch told to leave every frame): the same poses, counts and volume, bit for bit.  Also the two scheduling switches that
-    were measured and left off: the classification on the auxiliary stream beside the ICP launch (integrate_classify_beside_icp: the
-    integrate launch waits for its completion event) and one / two ICP iterations early (integrate_classify_early: a pose that many
-    more updates old — some frames then classify again, some decide only the boxes again); and the classification at the frame's start
-    for a predicted pose (integrate_classify_predicted), at the usual slack and at a wide one."""
+    takes the fall-back (header cleared again, classification repeated): the same poses, counts and volume, bit for bit."""
     torch, pl = dev
     prm = synth.s1_params(128)
     runs = [pl.KinectFusion(dict(prm, integrate_classify_ahead=False)), pl.KinectFusion(dict(prm, integrate_classify_ahead=True)),
-            pl.KinectFusion(dict(prm, integrate_classify_ahead=True, integrate_classify_slack=1.0)),
-            pl.KinectFusion(dict(prm, integrate_classify_ahead=True, integrate_post_pose=True)),
-            pl.KinectFusion(dict(prm, integrate_classify_ahead=True, integrate_post_pose=True, integrate_classify_slack=1.0)),
-            pl.KinectFusion(dict(prm, integrate_classify_ahead=True, integrate_classify_beside_icp=True)),
-            pl.KinectFusion(dict(prm, integrate_classify_ahead=True, integrate_classify_beside_icp=True, integrate_classify_early=1)),
-            pl.KinectFusion(dict(prm, integrate_classify_ahead=True, integrate_classify_early=2)),
-            pl.KinectFusion(dict(prm, integrate_classify_ahead=True, integrate_classify_beside_icp=True, integrate_post_pose=True)),
-            pl.KinectFusion(dict(prm, integrate_classify_ahead=True, integrate_classify_predicted=True)),
-            pl.KinectFusion(dict(prm, integrate_classify_ahead=True, integrate_classify_predicted=True, integrate_classify_slack=6.0))]
+            pl.KinectFusion(dict(prm, integrate_classify_ahead=True, integrate_classify_slack=1.0))]
     blank = upload(torch, np.zeros_like(synth.s1_frame(0)))
     for k in list(range(6)) + ["blank", 6, 7]:
         d = blank if k == "blank" else upload(torch, synth.s1_frame(k))
@@ -272,6 +258,34 @@ def test_brick_list_classified_ahead_changes_nothing(dev):
         assert np.array_equal(w, w0) and np.array_equal(v, v0) and np.array_equal(g, g0)
     for r in runs:
         r.close()
+
+
+RETIRED_TAIL_KEYS = {"integrate_post_pose": (True, False), "integrate_post_early": (True, False), "integrate_classify_beside_icp": (True, False),
+                     "integrate_classify_predicted": (True, False), "integrate_classify_early": (1, 0)}   # key: (a value it refuses, its default)
+
+
+def test_retired_tail_schedules_are_refused(dev):
+    """The integrate-tail schedules removed in ABI 3: a configuration that asks for one is refused — it would
+    otherwise run the default under another name — while the key at its default value is accepted; and a raw integrate call that still
+    sets flag bit 16 (the posted launch) fails instead of integrating with the pose it was handed."""
+    torch, pl = dev
+    capi = importlib.import_module("x-slam_amd.capi")
+    n = 64
+    prm = synth.s1_params(n)
+    for key, (refused, default) in RETIRED_TAIL_KEYS.items():
+        with pytest.raises(ValueError):
+            pl.KinectFusion(dict(prm, **{key: refused}))
+        pl.KinectFusion(dict(prm, **{key: default})).close()
+    res = [n, n, n]
+    value = torch.zeros((n * n, n), dtype=torch.float32, device="cuda")
+    weight = torch.zeros((n * n, n), dtype=torch.int32, device="cuda")
+    grad = torch.zeros((n * n, n), dtype=torch.float32, device="cuda")
+    ws = torch.zeros(capi.integrate_workspace_bytes(res), dtype=torch.uint8, device="cuda")
+    scaled = torch.zeros((H, W), dtype=torch.float32, device="cuda")
+    T = synth.s1_transforms(0, prm)
+    with pytest.raises(capi.XsError, match="bit 16"):
+        capi.integrate_scaled_ex(scaled, W * 4, H, W, synth.intr_of(prm), 100, res, prm["tsdf_voxel_size"], T["Rv2c"], T["tv2c"], synth.tranc_dist(prm),
+                                 value, weight, grad, n * 4, 16 | 4 | 1, workspace=ws)
 
 
 @pytest.mark.parametrize("n,scene", [(128, "s1"), (512, "s1"), (256, "s3")])
@@ -500,14 +514,14 @@ def test_posted_pose_numbers_cross_the_2_to_32_wrap(dev):
     a.close(); b.close()
 
 
-def test_alignment_failure_after_the_bricks_were_classified_ahead(dev):
+def test_alignment_failure_after_the_classification_behind_the_last_icp_launch(dev):
     """The brick classification of the integrate call is enqueued behind the last ICP launch; if that last iteration then fails (forced
     here: the determinant gate of iteration 11), IntegrateFrame never runs and the list must not survive into the retried frame — whose
     map preparation clears the workspace header and rewrites the depth maximum on the auxiliary stream.  The retry and the following
     frames give the same poses, counts and volume as a run that never failed."""
     torch, pl = dev
     prm = synth.s1_params(128)
-    a = pl.KinectFusion(dict(prm, integrate_classify_ahead=True, integrate_post_pose=True))   # (the failure path of the posted launch too)
+    a = pl.KinectFusion(dict(prm, integrate_classify_ahead=True))
     b = pl.KinectFusion(dict(prm, integrate_classify_ahead=True))
     for k in range(3):
         d = upload(torch, synth.s1_frame(k))

@@ -37,8 +37,7 @@ _lib = _load()
 class IntegrateOpts(C.Structure):
     """xs_integrate_opts (include/xslam_amd.h): what an integrate / classify call takes besides its arguments proper."""
     _fields_ = [("struct_bytes", C.c_uint), ("flags", C.c_uint), ("depth_tiles", C.c_void_p), ("signmap", C.c_void_p),
-                ("start_event", C.c_void_p), ("stop_event", C.c_void_p), ("pose_mailbox", C.c_void_p), ("mailbox_seq", C.c_uint),
-                ("mailbox_slack", C.c_float), ("pose_dev", C.c_void_p)]
+                ("start_event", C.c_void_p), ("stop_event", C.c_void_p)]
 
 
 class RaycastOpts(C.Structure):
@@ -166,7 +165,6 @@ _SIGS = {
     "xs_csfd_array_op": (C.c_int, [C.c_int, C.c_int, _vp, _vp, _vp, C.c_long, _vp]),
     "xs_dcsfd_f1": (C.c_int, [_vp, _vp, _vp, C.c_long, _vp]),
     "xs_complex_table": (C.c_int, [C.c_int, C.c_int, _vp, _vp, _vp, C.c_long, _vp]),
-    "xs_integrate_pose_covered": (C.c_int, [C.c_int, C.c_int, _f32p, _i32p, C.c_float, _f32p, _f32p, C.c_float, _f32p, _f32p]),
     "xs_const_div_prepare": (C.c_uint, [C.c_float]),
     "xs_raycast_signmap_shift": (C.c_int, [_f32p, C.c_float, C.c_float]),
     "xs_signmap_bytes": (C.c_size_t, [_i32p, C.c_int]),
@@ -300,23 +298,21 @@ def integrate_scaled(depth_scaled, scaled_step, rows, cols, intr, max_weight, re
 
 def integrate_scaled_ex(depth_scaled, scaled_step, rows, cols, intr, max_weight, res, voxel_size, Rv2c, tv2c, tranc_dist, value, weight,
                         grad, vol_step, flags, threshold=0.0, z0=0, z1=None, updated=None, depth_max=None, workspace=None, stream=None, **opts):
-    """xs_integrate_scaled_ex2 with its options as keyword arguments (integrate_opts' fields: depth_tiles, signmap, start_event, stop_event,
-    pose_mailbox, mailbox_seq, mailbox_slack, pose_dev) and the flags positional, as the tests write it."""
+    """xs_integrate_scaled_ex2 with its options as keyword arguments (integrate_opts' fields: depth_tiles, signmap, start_event, stop_event)
+    and the flags positional, as the tests write it."""
     return integrate_scaled_ex2(depth_scaled, scaled_step, rows, cols, intr, max_weight, res, voxel_size, Rv2c, tv2c, tranc_dist, value, weight, grad, vol_step,
                                 integrate_opts(flags=flags, **opts), threshold=threshold, z0=z0, z1=z1, updated=updated, depth_max=depth_max,
                                 workspace=workspace, stream=stream)
 
 
-def integrate_opts(flags=0, depth_tiles=None, signmap=None, start_event=None, stop_event=None, pose_mailbox=None, mailbox_seq=0, mailbox_slack=2.0,
-                   pose_dev=None):
+def integrate_opts(flags=0, depth_tiles=None, signmap=None, start_event=None, stop_event=None):
     """An xs_integrate_opts for integrate_scaled_ex2 / integrate_classify_ex (tensors or raw addresses for the pointers)."""
     o = IntegrateOpts()
     o.struct_bytes = C.sizeof(IntegrateOpts)
     o.flags = flags
-    o.depth_tiles, o.signmap, o.pose_mailbox, o.pose_dev = _ptr(depth_tiles), _ptr(signmap), _ptr(pose_mailbox), _ptr(pose_dev)
+    o.depth_tiles, o.signmap = _ptr(depth_tiles), _ptr(signmap)
     o.start_event = start_event.value if hasattr(start_event, "value") else start_event
     o.stop_event = stop_event.value if hasattr(stop_event, "value") else stop_event
-    o.mailbox_seq, o.mailbox_slack = mailbox_seq, mailbox_slack
     return o
 
 
@@ -355,14 +351,6 @@ def integrate_list_covers(rows, cols, intr, res, voxel_size, Rv2c_list, tv2c_lis
     a, b, c, d = _fa(Rv2c_list, 18), _fa(tv2c_list, 6), _fa(Rv2c, 18), _fa(tv2c, 6)
     P = lambda x: x.ctypes.data_as(_f32p)
     return int(_lib.xs_integrate_list_covers(rows, cols, P(k), r.ctypes.data_as(_i32p), voxel_size, P(a), P(b), slack_scale, P(c), P(d)))
-
-
-def integrate_pose_covered(rows, cols, intr, res, voxel_size, Rv2c_list, tv2c_list, slack_scale, Rv2c, tv2c):
-    r = _ia(res, 3)
-    k = _fa(intr, 4)
-    a, b, c, d = _fa(Rv2c_list, 18), _fa(tv2c_list, 6), _fa(Rv2c, 18), _fa(tv2c, 6)
-    P = lambda x: x.ctypes.data_as(_f32p)
-    return bool(_lib.xs_integrate_pose_covered(rows, cols, P(k), r.ctypes.data_as(_i32p), voxel_size, P(a), P(b), slack_scale, P(c), P(d)))
 
 
 def integrate_workspace_clear(workspace, stream=None):

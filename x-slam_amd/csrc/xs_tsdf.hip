@@ -142,7 +142,7 @@ static void launch_scale_depth(const Src *src, size_t src_step, int rows, int co
 /* max_dev: optional device float that receives max(scaled) via atomicMax on its bits; the caller
  * zeroes it before the launch (used by integrate to stop walking behind the farthest surface).
  * tiles_dev: optional table of xs_depth_tiles_bytes(rows, cols) bytes that receives the per-tile depth range
- * (xs_integrate_set_depth_tiles hands it to the integrate calls). */
+ * (xs_integrate_opts.depth_tiles hands it to the integrate calls). */
 extern "C" size_t xs_depth_tiles_bytes(int rows, int cols) {
     if (rows <= 0 || cols <= 0) return 0;
     return depth_tiles_count(rows, cols) * sizeof(DepthTile);
@@ -222,8 +222,6 @@ struct IntegrateArgs {
     int bricks_x, bricks_y, bricks_z, brick_z;  // brick_z: planes per brick (runtime; BRICK_Z by default)
     unsigned kflags;              // KF_*
     float near_margin;            // pixels: how near a half-integer a streamed voxel's approximate image coordinate may come before the exact path decides (stream_margins)
-    const unsigned *mailbox; unsigned mailbox_seq;   // posted pose: what k_pose_gate polls ...
-    unsigned *pose_dev;                              // ... and where it leaves {cmd, 24 floats} for k_integrate_bricks<., true>
     unsigned char *signmap;       // xs_signmap.h buffer (whole-volume launches) or null: bricks that receive a negative value are marked
     DepthTiles dt;                // per-tile depth range of the frame (k_scale_depth), for k_classify_boxes
     unsigned *box_class;          // [list entry][BOXES_PER_BRICK] box_word (k_classify_boxes) or null: every box takes the exact walk
@@ -288,7 +286,7 @@ __device__ __forceinline__ bool box_may_pass(const Frustum &f, int x0, int x1, i
 // The reference's per-voxel body (TsdfFusion.cu:110-168) for one voxel whose current state
 // (value, grad, weight) has already been loaded.  Returns true and the new state if the voxel is
 // written.
-struct PoseRT { MatS33 R; cfloat3 t; };   // volume-to-camera pose: the kernel argument's, or the one a posted launch took from its mailbox
+struct PoseRT { MatS33 R; cfloat3 t; };   // volume-to-camera pose (the kernel argument's)
 struct VoxelCtx {
     cfloat base[3];
     float fx, fy, cx, cy, ulo, uhi, vlo, vhi;
@@ -1113,23 +1111,6 @@ __global__ void __launch_bounds__(256) k_classify_boxes(const IntegrateArgs a, c
     }
 }
 
-// One wave waits at the mailbox for the pose of a posted integrate launch and leaves it in device memory for the launch behind it on the
-// stream: a single poller (two thousand workgroups polling one line themselves serialise at the memory side: measured, 87 us instead of 27).
-__global__ void __launch_bounds__(64) k_pose_gate(const unsigned *mailbox, unsigned seq, unsigned *pose_dev) {
-    __shared__ unsigned s_mail[MAILBOX_WORDS];
-    mailbox_wait(mailbox, seq, s_mail, (int)threadIdx.x);
-    __syncthreads();
-    if (threadIdx.x == 0) pose_dev[0] = s_mail[1];
-    if (threadIdx.x < 24) pose_dev[1 + threadIdx.x] = s_mail[mailbox_word_of((int)threadIdx.x)];
-}
-
-// POSTED: the launch is enqueued before its pose exists — behind the classification, which already runs behind the last ICP launch — and
-// takes R / t from what k_pose_gate, one wave in front of it on the stream, read out of a mailbox the host posts the final pose to
-// (xs_mailbox.h; xs_icp_post_pose): what is left between the last ICP
-// reduction and the first integrated voxel is the host's solve + one posted write + one poll instead of those plus a kernel launch
-// (~16 us -> ~4).  The frustum planes (brick test, column clip) stay those of the pose the list was classified with, widened: they
-// only bound the voxels that take the exact tests, and the host posts only after checking that the final pose's planes lie inside
-// them (xs_integrate_pose_covered); otherwise it posts an abandon command and the launch leaves without touching the volume.
 #ifndef XS_INTEGRATE_WAVES
 // Workgroups per CU = waves per SIMD the brick kernel is compiled for.  8 (64 VGPRs, 78 SGPRs) was round 3's choice: with the free-space
 // path and the class look-up next to the walk the instance the pipeline runs then spills 36-48 bytes per lane, and a spill is not free
@@ -1138,22 +1119,9 @@ __global__ void __launch_bounds__(64) k_pose_gate(const unsigned *mailbox, unsig
 // kernel inside the pipeline 33 -> 28 us, S2 unchanged (profiles/r04_ab_integrate_waves.txt).
 #define XS_INTEGRATE_WAVES 6
 #endif
-template <bool BILINEAR, bool POSTED = false, bool SIGN = false>
+template <bool BILINEAR, bool SIGN = false>
 __global__ void __launch_bounds__(256, XS_INTEGRATE_WAVES) k_integrate_bricks(const IntegrateArgs a) {
     PoseRT ps{a.R, a.t};
-    if constexpr (POSTED) {
-        // the pose k_pose_gate (the launch in front of this one) took from the mailbox: word 0 = command (0: run), words 1..24 = R, t
-        const unsigned *pd = a.pose_dev;
-        if (__builtin_amdgcn_readfirstlane((int)pd[0]) != 0) return;   // abandoned (or the gate gave up): nothing is written, nothing is counted
-        auto f = [&](int i) { return __int_as_float(__builtin_amdgcn_readfirstlane((int)pd[1 + i])); };
-#pragma unroll
-        for (int r = 0; r < 3; ++r) {
-            ps.R.data[r].x = cfloat(f(6 * r + 0), f(6 * r + 1));
-            ps.R.data[r].y = cfloat(f(6 * r + 2), f(6 * r + 3));
-            ps.R.data[r].z = cfloat(f(6 * r + 4), f(6 * r + 5));
-        }
-        ps.t.x = cfloat(f(18), f(19)); ps.t.y = cfloat(f(20), f(21)); ps.t.z = cfloat(f(22), f(23));
-    }
 #if defined(XS_EXPERIMENTS) && defined(XS_WG_TIMES)   // measurement only: every workgroup's begin / end on the 100 MHz wall clock, 512 KiB into the tile room of the workspace
     const unsigned long long probe_t0 = wall_clock64();
 #endif
@@ -1247,7 +1215,7 @@ static void set_plane(Frustum &f, int P, const float T[3], const float M[3][3], 
     f.bz[P] = cxk * M[0][2] + cyk * M[1][2] + czk * M[2][2];
     f.slack[P] = sl;
 }
-static void host_frustum(IntegrateArgs &a, float slack_scale = 1.0f) {
+static void host_frustum(IntegrateArgs &a) {
     Frustum &f = a.fr;
     const float vs = a.voxel_size, fx = a.intr.fx, fy = a.intr.fy;
     const float ul = (1.5f - a.intr.cx) - 2.f, uh = ((a.dcols - 0.5f) - a.intr.cx + 1.0f) + 2.f;
@@ -1261,7 +1229,7 @@ static void host_frustum(IntegrateArgs &a, float slack_scale = 1.0f) {
     const float mag0 = fabsf(T[0]) + (fabsf(M[0][0]) + fabsf(M[0][1]) + fabsf(M[0][2])) * ext;
     const float mag1 = fabsf(T[1]) + (fabsf(M[1][0]) + fabsf(M[1][1]) + fabsf(M[1][2])) * ext;
     const float mag2 = fabsf(T[2]) + (fabsf(M[2][0]) + fabsf(M[2][1]) + fabsf(M[2][2])) * ext;
-    const float rel = 2e-3f * slack_scale;
+    const float rel = 2e-3f;
     set_plane(f, 0, T, M, 0.f, 0.f, 1.f, rel * mag2);                                      // c >= 0
     set_plane(f, 1, T, M, fx, 0.f, -ul, rel * (fabsf(fx) * mag0 + fabsf(ul) * mag2));      // fx*X >= ul*c
     set_plane(f, 2, T, M, -fx, 0.f, uh, rel * (fabsf(fx) * mag0 + fabsf(uh) * mag2));      // fx*X <= uh*c
@@ -1467,7 +1435,7 @@ extern "C" int xs_integrate_classify(int rows, int cols, const float *intr4, con
                                      float tranc_dist, int z0, int z1, const float *depth_max_dev, void *workspace, float slack_scale, unsigned flags,
                                      void *stream) {
     xs_integrate_opts o = {};   // the plain entry point: the list alone (no tile table: the integrate call decides the boxes itself)
-    o.struct_bytes = sizeof(o); o.flags = flags; o.mailbox_slack = 2.0f;
+    o.struct_bytes = sizeof(o); o.flags = flags;
     return xs_integrate_classify_ex(rows, cols, intr4, res, voxel_size, Rv2c18, tv2c6, tranc_dist, z0, z1, depth_max_dev, workspace, slack_scale, &o, stream);
 }
 extern "C" int xs_integrate_classify_ex(int rows, int cols, const float *intr4, const int *res, float voxel_size, const float *Rv2c18, const float *tv2c6,
@@ -1487,14 +1455,14 @@ extern "C" int xs_integrate_classify_ex(int rows, int cols, const float *intr4, 
     hipStream_t st = (hipStream_t)stream;
     if (!(flags & XS_INTEGRATE_HEADER_IS_CLEAR)) XS_CHECK(hipMemsetAsync(a.brick_count, 0, WS_LIST_OFFSET, st));
     // the boxes' classes, valid for every pose xs_integrate_list_covers accepts for this list (needs the frame's tile table:
-    // xs_integrate_set_depth_tiles; without it the integrate call classifies with its own pose)
+    // opts->depth_tiles; without it the integrate call classifies with its own pose)
     static const bool env_no_tiles = exp_env_set("XS_INTEGRATE_NO_TILES");
     classes_ahead_forget(workspace);
     // (the 32-bit-offset condition on the tightest pitch: the integrate call tests the real one and decides the boxes itself when it disagrees)
     const bool off32 = ((size_t)a.brick_z * a.Y + BRICK_Y) * ((size_t)res[0] * 4) < (1ull << 32);
     const bool boxes = !env_no_tiles && !(flags & XS_INTEGRATE_NO_TILES) && off32 && depth_tiles;
     if (flags & XS_INTEGRATE_COUNT_CLASSES) a.kflags |= KF_COUNT_CLASSES;
-    // (the caller's completion event — xs_integrate_set_classify_event — rides on the dispatch)
+    // (the caller's completion event — opts->stop_event — rides on the dispatch)
     if (launch_classification(a, res, z1 - z0, workspace, boxes ? depth_tiles : nullptr, box_slack(a, slack_scale), st, (hipEvent_t)opts->stop_event)) {
         ClassesAhead r;
         r.workspace = workspace; r.tiles = depth_tiles; r.slack_scale = slack_scale; r.voxel_size = voxel_size; r.tranc_dist = tranc_dist;
@@ -1525,24 +1493,6 @@ extern "C" int xs_integrate_list_covers(int rows, int cols, const float *intr4, 
     const bool tested_ok = !(f.kflags & KF_NO_TESTED_STREAM) || (l.kflags & KF_NO_TESTED_STREAM);   // (stream_margins: EDGE / SPECKLE classes need the final pose to allow them)
     return box_slack_covers(l, f, res, slack_scale) && tested_ok ? 3 : 1;   // bit 1: the boxes' classes hold for the pose too
 }
-/* Host only: the stricter cover test a POSTED integrate launch needs — it keeps the list pose's widened planes for its column clip too, where
- * a voxel is kept when alpha + b . index >= -slack (the brick test of xs_integrate_list_covers allows 1.5 slack): 1 if every half-space of
- * (Rv2c18, tv2c6), anywhere in the volume, lies inside that of (Rv2c18_list, tv2c6_list) widened by slack_scale.  Implies xs_integrate_list_covers. */
-extern "C" int xs_integrate_pose_covered(int rows, int cols, const float *intr4, const int *res, float voxel_size, const float *Rv2c18_list,
-                                         const float *tv2c6_list, float slack_scale, const float *Rv2c18, const float *tv2c6) {
-    if (!intr4 || !res || !Rv2c18_list || !tv2c6_list || !Rv2c18 || !tv2c6) return 0;
-    IntegrateArgs l, f;
-    classify_args(l, rows, cols, intr4, res, voxel_size, Rv2c18_list, tv2c6_list, 1.0f, 0, res[2], nullptr);
-    classify_args(f, rows, cols, intr4, res, voxel_size, Rv2c18, tv2c6, 1.0f, 0, res[2], nullptr);
-    for (int p = 0; p < 6; ++p) {
-        const double d = fabs((double)l.fr.alpha[p] - f.fr.alpha[p]) + fabs((double)l.fr.bx[p] - f.fr.bx[p]) * res[0] +
-                         fabs((double)l.fr.by[p] - f.fr.by[p]) * res[1] + fabs((double)l.fr.bz[p] - f.fr.bz[p]) * res[2];
-        const double room = (double)slack_scale * l.fr.slack[p] - f.fr.slack[p];
-        if (!(d <= 0.8 * room)) return 0;   // (a fifth of the room left for the float evaluation of the forms and of the roots the clip solves them for)
-    }
-    const bool tested_ok = !(f.kflags & KF_NO_TESTED_STREAM) || (l.kflags & KF_NO_TESTED_STREAM);
-    return box_slack_covers(l, f, res, slack_scale) && tested_ok ? 1 : 0;   // (a posted launch cannot classify again: it needs both)
-}
 extern "C" int xs_integrate_scaled(const float *depth_scaled, size_t scaled_step, int rows, int cols, const float *intr4, int max_weight,
                                    const int *res, float voxel_size, const float *Rv2c18, const float *tv2c6, float tranc_dist,
                                    float *value, int *weight, float *grad, size_t vol_step, float threshold, int z0, int z1,
@@ -1555,7 +1505,7 @@ extern "C" int xs_integrate_scaled_ex(const float *depth_scaled, size_t scaled_s
                                       float *value, int *weight, float *grad, size_t vol_step, float threshold, int z0, int z1,
                                       unsigned long long *updated_dev, const float *depth_max_dev, void *workspace, unsigned flags, void *stream) {
     xs_integrate_opts o = {};   // the plain entry point: flags alone
-    o.struct_bytes = sizeof(o); o.flags = flags; o.mailbox_slack = 2.0f;
+    o.struct_bytes = sizeof(o); o.flags = flags;
     return xs_integrate_scaled_ex2(depth_scaled, scaled_step, rows, cols, intr4, max_weight, res, voxel_size, Rv2c18, tv2c6, tranc_dist, value, weight, grad,
                                    vol_step, threshold, z0, z1, updated_dev, depth_max_dev, workspace, &o, stream);
 }
@@ -1566,6 +1516,9 @@ extern "C" int xs_integrate_scaled_ex2(const float *depth_scaled, size_t scaled_
                                        void *stream) {
     if (!opts || opts->struct_bytes != sizeof(xs_integrate_opts)) return xs_set_error(hipErrorInvalidValue, "xs_integrate_scaled_ex2: opts->struct_bytes is not sizeof(xs_integrate_opts)");
     const unsigned flags = opts->flags;
+    // (bit 16 asked for the posted launch of ABI 2, which took its pose from a mailbox: refused, or an old caller would integrate with the
+    // list pose it passes as arguments)
+    if (flags & 16u) return xs_set_error(hipErrorInvalidValue, "xs_integrate_scaled_ex: flag bit 16 (the posted launch, removed in ABI 3) is not supported");
     const hipEvent_t ev0 = (hipEvent_t)opts->start_event, ev1 = (hipEvent_t)opts->stop_event;
     const DepthTile *depth_tiles = static_cast<const DepthTile *>(opts->depth_tiles);
     if (!depth_scaled || !intr4 || !res || !Rv2c18 || !tv2c6 || !value || !weight || !grad)
@@ -1594,16 +1547,9 @@ extern "C" int xs_integrate_scaled_ex2(const float *depth_scaled, size_t scaled_
     if (flags & XS_INTEGRATE_COUNT_CLASSES) a.kflags |= KF_COUNT_CLASSES;
     if (far_end_first(a)) a.kflags |= KF_FAR_FIRST;
     stream_margins(a);
-    const bool posted = (flags & XS_INTEGRATE_POSE_POSTED) != 0;
-    a.mailbox = nullptr; a.mailbox_seq = 0; a.pose_dev = nullptr;
     a.dt = depth_tiles_view(nullptr, rows, cols); a.box_class = nullptr;
     a.signmap = static_cast<unsigned char *>(opts->signmap);   // (a slab launch marks the bricks of its own planes: the map is indexed by whole-volume coordinates)
-    if (posted) {
-        if (!workspace || !(flags & XS_INTEGRATE_LIST_IS_READY) || !opts->pose_mailbox || !opts->pose_dev)
-            return xs_set_error(hipErrorInvalidValue, "xs_integrate_scaled_ex: a posted launch needs the classified list and a mailbox (xs_integrate_set_pose_mailbox)");
-        a.mailbox = (const unsigned *)opts->pose_mailbox; a.mailbox_seq = opts->mailbox_seq; a.pose_dev = (unsigned *)opts->pose_dev;
-    }
-    host_frustum(a, posted ? opts->mailbox_slack : 1.0f);
+    host_frustum(a);
     const int nz = z1 - z0;
     static const int env_bz = exp_env_int("XS_BRICK_Z", 0);  // tuning aid
     a.brick_z = (env_bz >= 2 && env_bz <= 64) ? env_bz : BRICK_Z;
@@ -1619,17 +1565,16 @@ extern "C" int xs_integrate_scaled_ex2(const float *depth_scaled, size_t scaled_
         const int nb = a.bricks_x * a.bricks_y * a.bricks_z;
         const bool sign = a.signmap != nullptr;
         // the boxes' classes (free space / nothing to write / exact walk) and the list's order: those xs_integrate_classify left for this
-        // list, or decided here with the launch's own pose — from the caller's tile table (xs_integrate_set_depth_tiles) or one built here,
+        // list, or decided here with the launch's own pose — from the caller's tile table (opts->depth_tiles) or one built here,
         // in the workspace
         static const bool env_no_tiles = exp_env_set("XS_INTEGRATE_NO_TILES");   // A/B aid, as the flag
-        // the classes xs_integrate_classify* left hold for this launch only if its pose lies within the slack they were padded for: checked
-        // here (a posted launch is handed the list's own pose and receives a covered one through its mailbox: xs_integrate_pose_covered)
+        // the classes xs_integrate_classify* left hold for this launch only if its pose lies within the slack they were padded for: checked here
         ClassesAhead ca;
         bool classes_ahead = (flags & XS_INTEGRATE_LIST_IS_READY) && classes_ahead_take(workspace, ca) && !(flags & XS_INTEGRATE_RECLASSIFY_BOXES);
         if (classes_ahead)   // ... for this slab of this volume, this camera and band, this frame's tile table?
             classes_ahead = ca.z0 == z0 && ca.z1 == z1 && !memcmp(ca.res, res, sizeof(ca.res)) && ca.rows == rows && ca.cols == cols && !memcmp(ca.intr, intr4, sizeof(ca.intr)) &&
-                            ca.voxel_size == voxel_size && ca.tranc_dist == tranc_dist && (ca.tiles == depth_tiles || posted);
-        if (classes_ahead && !posted) {
+                            ca.voxel_size == voxel_size && ca.tranc_dist == tranc_dist && ca.tiles == depth_tiles;
+        if (classes_ahead) {
             IntegrateArgs l = a;
             load_mat(ca.R18, l.R); load_vec(ca.t6, l.t);
             // (classes decided for a pose whose imaginary parts passed stream_margins do not hold for one whose do not)
@@ -1648,7 +1593,7 @@ extern "C" int xs_integrate_scaled_ex2(const float *depth_scaled, size_t scaled_
             launch_classification(a, res, nz, workspace, use_tiles ? tile_table() : nullptr, BoxSlack{0.f, 0.f, 0.f}, st);
         } else if (use_tiles) {
             if (classes_ahead) bind_ordered_list(a, res, nz, workspace);
-            else if (!posted) launch_box_classes(a, res, nz, workspace, tile_table(), BoxSlack{0.f, 0.f, 0.f}, st, false);   // (a posted launch has no pose yet to classify with)
+            else launch_box_classes(a, res, nz, workspace, tile_table(), BoxSlack{0.f, 0.f, 0.f}, st, false);
         }
         if (a.box_class) a.kflags &= ~(unsigned)KF_FAR_FIRST;   // the list is ordered by class
         // resident workgroups stride over the list: 256 CUs x 8
@@ -1659,25 +1604,19 @@ extern "C" int xs_integrate_scaled_ex2(const float *depth_scaled, size_t scaled_
         // the kernel's own begin / end timestamps), so it adds no marker packets to the stream and times what
         // rocprofv3 times
         // (either event may be null: a completion event alone lets another stream wait for this kernel without a marker packet)
-        void (*kern)(const IntegrateArgs) = sign ? (threshold > 0.0f ? k_integrate_bricks<true, false, true> : k_integrate_bricks<false, false, true>)
+        void (*kern)(const IntegrateArgs) = sign ? (threshold > 0.0f ? k_integrate_bricks<true, true> : k_integrate_bricks<false, true>)
                                                  : (threshold > 0.0f ? k_integrate_bricks<true> : k_integrate_bricks<false>);
-        if (posted) {
-            kern = sign ? (threshold > 0.0f ? k_integrate_bricks<true, true, true> : k_integrate_bricks<false, true, true>)
-                        : (threshold > 0.0f ? k_integrate_bricks<true, true> : k_integrate_bricks<false, true>);
-            hipLaunchKernelGGL(k_pose_gate, dim3(1), dim3(64), 0, st, a.mailbox, a.mailbox_seq, a.pose_dev);
-        }
         static const int env_lds = exp_env_int("XS_INTEGRATE_DYN_LDS", 0);   // experiment: dynamic LDS bytes per workgroup = a cap on the workgroups resident per CU
         if (ev0 || ev1) hipExtLaunchKernelGGL(kern, dim3(g), block, env_lds, st, ev0, ev1, 0, a);
         else hipLaunchKernelGGL(kern, dim3(g), block, env_lds, st, a);
         if (updated_dev && !(flags & XS_INTEGRATE_NO_FOLD))
             hipLaunchKernelGGL(k_fold_count, dim3(1), dim3(FOLD_COUNT_BLOCK), 0, st, a.count_room, updated_dev);
     } else {
-        if (posted) return xs_set_error(hipErrorInvalidValue, "xs_integrate_scaled_ex: posted launch without a brick list");
         int gx = div_up(a.X, 64), gy = div_up(a.Y, 4), zsplit = 1;
         while ((long long)gx * gy * zsplit < 4096 && zsplit < nz && nz / (zsplit * 2) >= 16) zsplit *= 2;
         a.zchunk = div_up(nz, zsplit);
         dim3 grid(gx, gy, div_up(nz, a.zchunk));
-        // (the events xs_integrate_set_timing_events handed over ride on this dispatch too: a caller that waits on the stop event — the
+        // (the events opts->start_event / stop_event name ride on this dispatch too: a caller that waits on the stop event — the
         // orchestrator's auxiliary stream does — must find it recorded whichever kernel ran)
         void (*kern)(const IntegrateArgs) = a.signmap ? (threshold > 0.0f ? k_integrate<true, true> : k_integrate<false, true>)
                                                       : (threshold > 0.0f ? k_integrate<true> : k_integrate<false>);

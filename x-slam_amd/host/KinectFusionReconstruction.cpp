@@ -32,7 +32,6 @@ KinectFusionReconstruction::KinectFusionReconstruction() {
     hipSafeCall(hipEventCreateWithFlags(&surface_done_, hipEventDisableTiming));
     hipSafeCall(hipEventCreateWithFlags(&integrate_done_, hipEventDisableTiming));
     hipSafeCall(hipEventCreateWithFlags(&scale_done_, hipEventDisableTiming));
-    hipSafeCall(hipEventCreateWithFlags(&classify_done_, hipEventDisableTiming));
     hipSafeCall(hipEventCreateWithFlags(&tail_done_, hipEventDisableTiming));
     hipSafeCall(hipEventCreateWithFlags(&surface_done_next_, hipEventDisableTiming));
     hipSafeCall(hipEventCreateWithFlags(&scale_done_next_, hipEventDisableTiming));
@@ -57,14 +56,12 @@ KinectFusionReconstruction::~KinectFusionReconstruction() {
     if (surface_done_next_) (void)hipEventDestroy(surface_done_next_);
     if (scale_done_next_) (void)hipEventDestroy(scale_done_next_);
     if (scale_done_) (void)hipEventDestroy(scale_done_);
-    if (classify_done_) (void)hipEventDestroy(classify_done_);
     if (pinned_counters_) (void)hipHostFree(pinned_counters_);
     if (gather_counts_host_) (void)hipHostFree(gather_counts_host_);
     if (pinned_sums_) (void)hipHostFree(pinned_sums_);
     if (pinned_pairs_) (void)hipHostFree(pinned_pairs_);
     if (pinned_records_) (void)hipHostFree(pinned_records_);
     if (icp_mailbox_) (void)xs_icp_mailbox_free(icp_mailbox_, icp_mailbox_in_device_);
-    if (integrate_mailbox_) (void)xs_icp_mailbox_free(integrate_mailbox_, integrate_mailbox_in_device_);
     if (gn_mailbox_) (void)xs_icp_mailbox_free(gn_mailbox_, gn_mailbox_in_device_);
     if (gn_publish_) (void)hipHostFree(gn_publish_);
     for (int i = 0; i < 2; ++i) {
@@ -77,6 +74,11 @@ KinectFusionReconstruction::~KinectFusionReconstruction() {
 
 // reference :9-73
 void KinectFusionReconstruction::SetYamlParameters(const FlatYaml &config_) {
+    // schedules of the frame's tail that were measured, not adopted and removed: a configuration that asks for one
+    // is refused before anything is allocated, not run as the default under another name
+    for (const char *key : {"integrate_post_pose", "integrate_post_early", "integrate_classify_beside_icp", "integrate_classify_predicted"})
+        if (config_.as<bool>(key, false)) throw std::runtime_error(std::string("retired YAML key (code removed): ") + key);
+    if (config_.as<int>("integrate_classify_early", 0) != 0) throw std::runtime_error("retired YAML key (code removed): integrate_classify_early");
     this->config = config_;
     const int resolutionX = config.as<int>("tsdf_size_x");
     const int resolutionY = config.as<int>("tsdf_size_y");
@@ -140,12 +142,7 @@ void KinectFusionReconstruction::SetYamlParameters(const FlatYaml &config_) {
     icp_post_pose = config.as<bool>("icp_post_pose", true);
     icp_real_current_maps = config.as<bool>("icp_real_current_maps", true);
     integrate_classify_ahead = config.as<bool>("integrate_classify_ahead", true);
-    integrate_classify_beside_icp = config.as<bool>("integrate_classify_beside_icp", false);
-    integrate_classify_early = std::max(0, config.as<int>("integrate_classify_early", 0));
-    integrate_classify_predicted = config.as<bool>("integrate_classify_predicted", false);
     integrate_classify_slack = std::max(1.0f, config.as<float>("integrate_classify_slack", 2.0f));
-    integrate_post_pose = config.as<bool>("integrate_post_pose", false);
-    integrate_post_early = config.as<bool>("integrate_post_early", false);
     raycast_sign_map = config.as<bool>("raycast_sign_map", true);
     raycast_sign_map_shift = std::min(6, std::max(0, config.as<int>("raycast_sign_map_shift", 0)));   // 0: the finest usable one
     icp_lookahead = config.as<int>("icp_lookahead", 1);
@@ -209,8 +206,6 @@ void KinectFusionReconstruction::AllocateBuffers() {
         icp_ws_.create(xs_icp_workspace_bytes());
         check_rc(xs_icp_workspace_init(icp_ws_.ptr(), current_stream()), "icp workspace");
         if (!icp_mailbox_) check_rc(xs_icp_mailbox_alloc(&icp_mailbox_, &icp_mailbox_in_device_), "icp mailbox");
-        if (!integrate_mailbox_) check_rc(xs_icp_mailbox_alloc(&integrate_mailbox_, &integrate_mailbox_in_device_), "integrate mailbox");
-        posted_pose_.create(32);
         icp_sums_.create(64);
         icp_pose_.create(xs_icp_pose_state_bytes());
         ray_ws_.create((size_t)depth_width * depth_height);
@@ -332,7 +327,7 @@ int KinectFusionReconstruction::AlignDepthToReconstruction(const DeviceArray2D<u
 // reference :177-235
 int KinectFusionReconstruction::PoseEstimate(Matrix3frm Rcurr, Vector3cf tcurr, Matrix3frm Rprev_inv, Vector3cf tprev) {
     icp_log.clear();
-    if (!list_predicted_) list_ready_ = false;   // (a list classified for the predicted pose, on the auxiliary stream, stays: SurfaceMeasure)
+    list_ready_ = false;
     if (frame_id == 0) return 0;
     Matrix4cf c2w_prev = inverse(world2camera_record.back());
     Matrix4cf c2w_curr = c2w_prev;
@@ -425,12 +420,7 @@ int KinectFusionReconstruction::PoseEstimate(Matrix3frm Rcurr, Vector3cf tcurr, 
                 EnqueueAnnouncedFrame(false);   // (one stage of the announced next frame's map preparation per iteration, behind this frame's ICP launches)
                 // the last launch is in the queue: the integrate call's brick classification goes in behind it, for the pose that
                 // launch starts from — the final one differs by the last level-0 update, which IntegrateFrame checks is covered
-                // (with integrate_post_pose the integrate kernel follows the classification into the queue, gated on its mailbox: the host's three
-                // launches — classification, gate, integrate — go in while the last, 18 us, ICP launch runs; integrate_post_early puts them in one
-                // iteration earlier, with planes from a pose two updates old: 16 % of those were not covered at slack 2)
-                // (integrate_classify_early = k: k iterations before the last, i.e. for a pose k + 1 updates old — on the auxiliary stream the
-                // classification is then finished long before the final pose is, and the integrate launch needs no wait packet)
-                if ((integrate_post_pose && integrate_post_early ? enqueued == total_iters : n == std::max(0, total_iters - 1 - integrate_classify_early)) && !list_ready_ && integrate_classify_ahead && integrate_split())
+                if (n == total_iters - 1 && !list_ready_ && integrate_classify_ahead && integrate_split())
                     ClassifyAhead(Rcurr, tcurr);
                 const unsigned long long seq = seq_of[n];
                 if (n + 1 < total_iters) {
@@ -440,10 +430,6 @@ int KinectFusionReconstruction::PoseEstimate(Matrix3frm Rcurr, Vector3cf tcurr, 
                 }
                 auto launch_gave_up = [&](xs_wait status) {   // never expected: the launch gave up on its pose, or never published
                     if (next_enqueued) xs_icp_post_pose(mailbox, nullptr, nullptr, last_mail_seq, 1);
-                    if (posted_pending_) {   // the integrate launch gated on this frame's pose leaves too — before the stream is drained, or the drain waits out its gate
-                        xs_icp_post_pose(integrate_mailbox_, nullptr, nullptr, posted_seq_, 1);
-                        posted_pending_ = false;
-                    }
                     hipSafeCall(hipStreamSynchronize(current_stream()));
                     check_rc(xs_icp_workspace_init(icp_ws_.ptr(), current_stream()), "icp workspace");
                     stage_end(ST_ICP);
@@ -651,14 +637,6 @@ void KinectFusionReconstruction::flush_pending_fold(hipStream_t st) {
 }
 
 // reference :237-278
-// the volume-to-camera pose a list is classified for, from a camera-to-world one
-void KinectFusionReconstruction::SetListPose(const Matrix4cf &c2w) {
-    Matrix4cf v2c = inverse(world2volume * c2w);
-    Matrix3frm Rv2c = GetRotation(v2c);
-    Vector3cf tv2c = GetTranslation(v2c);
-    std::memcpy(list_Rv2c_, &device_cast<MatS33>(Rv2c).data[0].x.re, sizeof(list_Rv2c_));
-    std::memcpy(list_tv2c_, &device_cast<devComplex3>(tv2c).x.re, sizeof(list_tv2c_));
-}
 // xs_integrate_classify for the camera pose (Rcurr, tcurr) = camera-to-world, on the main stream (behind the ICP launches)
 void KinectFusionReconstruction::ClassifyAhead(const Matrix3frm &Rcurr, const Vector3cf &tcurr) {
     Matrix4cf c2w;
@@ -668,54 +646,24 @@ void KinectFusionReconstruction::ClassifyAhead(const Matrix3frm &Rcurr, const Ve
         for (int j = 0; j < 3; ++j) c2w(i, j) = Rcurr(i, j);
         c2w(i, 3) = tcurr[i];
     }
-    SetListPose(c2w);
-    // integrate_classify_beside_icp (off by default: measured, no gain — see the header): on the auxiliary stream instead; everything the two
-    // classification kernels read — the scaled depth's maximum, the tile table, the cleared header — was written on that stream.  The integrate
-    // launch then waits for their completion event.
-    const bool beside = integrate_classify_beside_icp && aux_stream_ && integrate_header_clear_;
-    hipStream_t st = beside ? aux_stream_ : current_stream();
+    // the volume-to-camera pose the list is classified for
+    Matrix4cf v2c = inverse(world2volume * c2w);
+    Matrix3frm Rv2c = GetRotation(v2c);
+    Vector3cf tv2c = GetTranslation(v2c);
+    std::memcpy(list_Rv2c_, &device_cast<MatS33>(Rv2c).data[0].x.re, sizeof(list_Rv2c_));
+    std::memcpy(list_tv2c_, &device_cast<devComplex3>(tv2c).x.re, sizeof(list_tv2c_));
+    hipStream_t st = current_stream();
     // the scaled depth's maximum and the cleared header come from the auxiliary stream
-    if (!beside && scale_recorded_ && hipEventQuery(scale_done_) != hipSuccess) hipSafeCall(hipStreamWaitEvent(st, scale_done_, 0));
-    EnqueueClassification(st, beside);
-    EnqueuePostedIntegrate();
-}
-// the two classification kernels for list_Rv2c_ / list_tv2c_ on stream st; with_event: their completion rides on the last dispatch
-// (classify_done_: the stream that integrates is another one)
-void KinectFusionReconstruction::EnqueueClassification(hipStream_t st, bool with_event) {
+    if (scale_recorded_ && hipEventQuery(scale_done_) != hipSuccess) hipSafeCall(hipStreamWaitEvent(st, scale_done_, 0));
     const int res[3] = {volume_resolution.x(), volume_resolution.y(), volume_resolution.z()};
     xs_integrate_opts o = {};
     o.struct_bytes = sizeof(o);
     o.flags = integrate_header_clear_ ? XS_INTEGRATE_HEADER_IS_CLEAR : 0u;
     o.depth_tiles = depth_tiles_.ptr();   // the boxes' classes are decided here too, with the slack's pads (the integrate call checks its pose against them)
-    o.stop_event = with_event ? classify_done_ : nullptr;
     check_rc(xs_integrate_classify_ex(depth_height, depth_width, &kinect_intrinsic.fx, res, voxel_size, list_Rv2c_, list_tv2c_,
                                       tsdf_volume_d_ptr->getTsdfTruncDist(), zo0, zo1, depth_max_.ptr(), integrate_ws_.ptr(), integrate_classify_slack,
                                       &o, st), "integrate classification");
-    classify_recorded_ = with_event;
     list_ready_ = true;
-}
-// integrate_classify_predicted (off by default): the classification for the pose the frame is EXPECTED to end at — the previous pose moved
-// on by the previous frame's motion — at the frame's very start, on the auxiliary stream (behind the header clear and the depth scaling,
-// i.e. under the previous frame's raycast and the first, small ICP launches); IntegrateFrame checks the final pose against the list's and
-// the classes' slack as it does for a list classified behind the last ICP launch, and a frame that moved otherwise classifies again there.
-// It would take the two classification kernels (4.8 + 7.8 us) off the chain between the last ICP reduction and the integrate kernel, but
-// on the benchmark scene — which slides along a wall: the estimated trajectory jitters by more than the slack allows — only a third of
-// the frames are covered at slack 2 and 72 % at slack 6, where the wider pads cost the integrate kernel 4 us; the others classify after
-// the final pose, i.e. later than ClassifyAhead would have: no gain (profiles/r04_ab_classify_predicted.txt).  Same volume bit for bit
-// either way (tested).
-void KinectFusionReconstruction::ClassifyPredicted() {
-    list_predicted_ = false;
-    if (!integrate_classify_predicted || !integrate_classify_ahead || integrate_post_pose || !integrate_split() || !integrate_header_clear_ ||
-        !aux_stream_ || world2camera_record.empty() || use_gtPose)
-        return;
-    Matrix4cf w2c = world2camera_record.back();
-    if (world2camera_record.size() >= 2) {   // constant velocity: W(n+1) = (W(n) W(n-1)^-1) W(n)
-        const Matrix4cf step = w2c * inverse(world2camera_record[world2camera_record.size() - 2]);
-        w2c = step * w2c;
-    }
-    SetListPose(inverse(w2c));
-    EnqueueClassification(aux_stream_, true);
-    list_predicted_ = true;
 }
 
 // this frame's counter slot; entering a half of the ring clears that half (its frames were folded or abandoned at least COUNTER_RING / 2
@@ -729,61 +677,13 @@ unsigned long long *KinectFusionReconstruction::PrepareFrameCounters(hipStream_t
     return frame_counters();
 }
 
-// Behind the classification: the integrate kernel itself, to take the final pose from its mailbox (k_integrate_bricks<., true>).  Everything
-// IntegrateFrame does around its launch happens here; IntegrateFrame then only checks that the final pose is covered and posts it.
-void KinectFusionReconstruction::EnqueuePostedIntegrate() {
-    if (!integrate_post_pose || !integrate_split() || !integrate_mailbox_ || !integrate_mailbox_in_device_ || !list_ready_) return;
-    if (zs0 != zo0 || zs1 != zo1) return;   // (halo bands: several calls per frame)
-    hipStream_t st = current_stream();
-    WaitForClassification(st);
-    unsigned long long *counters = PrepareFrameCounters(st);
-    const int res[3] = {volume_resolution.x(), volume_resolution.y(), volume_resolution.z()};
-    DeviceArray2D<float> value = tsdf_volume_d_ptr->value(), grad = tsdf_volume_d_ptr->grad();
-    DeviceArray2D<int> weight = tsdf_volume_d_ptr->weight();
-    xs_integrate_opts o = {};
-    o.struct_bytes = sizeof(o);
-    hipEvent_t integrate_stop = integrate_done_;
-    if (IntegrateKernelTimedThisFrame()) {
-        integrate_stop = prof_ring_[prof_pending_].ev[ST_INTEGRATE][1];
-        o.start_event = prof_ring_[prof_pending_].ev[ST_INTEGRATE][0];
-        prof_ring_[prof_pending_].used[ST_INTEGRATE] = true;
-    }
-    o.stop_event = integrate_stop;
-    if (++integrate_mail_seq_ == 0u) ++integrate_mail_seq_;
-    posted_seq_ = integrate_mail_seq_;
-    o.pose_mailbox = integrate_mailbox_; o.mailbox_seq = posted_seq_; o.mailbox_slack = integrate_classify_slack; o.pose_dev = posted_pose_.ptr();
-    o.signmap = sign_map_ptr();
-    o.depth_tiles = depth_tiles_.ptr();
-    const bool split = integrate_header_clear_;   // header cleared and count folded on the auxiliary stream (SurfaceMeasure)
-    o.flags = XS_INTEGRATE_POSE_POSTED | XS_INTEGRATE_LIST_IS_READY | XS_INTEGRATE_HEADER_IS_CLEAR | (split ? XS_INTEGRATE_NO_FOLD : 0u);
-    check_rc(xs_integrate_scaled_ex2(depthRawScaled_d.ptr(), depthRawScaled_d.step(), depth_height, depth_width, &kinect_intrinsic.fx, max_integration_weight,
-                                     res, voxel_size, list_Rv2c_, list_tv2c_, tsdf_volume_d_ptr->getTsdfTruncDist(), value.ptr(0), weight.ptr(0), grad.ptr(0),
-                                     value.step(), biInterpolate_threshold, zo0, zo1, counters, depth_max_.ptr(), integrate_ws_.ptr(), &o, st),
-             "integrateTsdfVolume (posted)");
-    posted_pending_ = true;
-    posted_at_ = std::chrono::steady_clock::now();
-    posted_stop_ = integrate_stop;
-    posted_split_ = split;
-}
-
 // A frame whose alignment fails after ClassifyAhead has run never reaches IntegrateFrame: the classification kernel is still in the main
 // stream, has filled the workspace header, and reads the frame's depth maximum — while the retried frame's SurfaceMeasure clears that header
 // and rewrites the maximum on the auxiliary stream, ordered only behind the previous frame's integrate kernel.  So the failure path (rare: a
 // singular system, a launch that timed out) drains the main stream, clears the header there and forgets the list.
-// the list and classes ClassifyAhead left on the auxiliary stream: the stream st reads them next
-void KinectFusionReconstruction::WaitForClassification(hipStream_t st) {
-    if (!classify_recorded_) return;
-    classify_recorded_ = false;
-    if (hipEventQuery(classify_done_) != hipSuccess) hipSafeCall(hipStreamWaitEvent(st, classify_done_, 0));
-}
 void KinectFusionReconstruction::AbandonClassifiedList() {
     if (!list_ready_) return;
     list_ready_ = false;
-    if (classify_recorded_) { classify_recorded_ = false; hipSafeCall(hipStreamSynchronize(aux_stream_)); }
-    if (posted_pending_) {   // the integrate launch waiting for this frame's pose leaves without touching the volume
-        xs_icp_post_pose(integrate_mailbox_, nullptr, nullptr, posted_seq_, 1);
-        posted_pending_ = false;
-    }
     check_rc(xs_integrate_workspace_clear(integrate_ws_.ptr(), current_stream()), "integrate workspace");
     hipSafeCall(hipStreamSynchronize(current_stream()));
     integrate_header_clear_ = true;
@@ -822,29 +722,6 @@ int KinectFusionReconstruction::IntegrateFrame(const DeviceArray2D<ushort> &dept
     const auto t_enter = std::chrono::steady_clock::now();
     auto t_call = t_enter, t_back = t_enter;
     unsigned long long *counters = PrepareFrameCounters(st);
-    // A posted integrate launch is waiting in the stream for this pose (EnqueuePostedIntegrate): if the pose's frustum lies inside the planes
-    // that launch was given, post it — the launch is the frame's integrate call; else tell it to leave and take the plain path below.
-    bool integrated_by_post = false;
-    if (posted_pending_) {
-        posted_pending_ = false;
-        const int res_[3] = {volume_res.x, volume_res.y, volume_res.z};
-        // (a launch whose gate has waited long may have given up — MAILBOX_MAX_POLLS, about a second — and left without writing: a host that
-        // took more than a quarter of that between enqueue and post tells it to leave and integrates the plain way, whatever the gate did)
-        const bool in_time = std::chrono::steady_clock::now() - posted_at_ < std::chrono::milliseconds(250);
-        if (in_time && xs_integrate_pose_covered(depth_frame_d.rows(), depth_frame_d.cols(), &kinect_intrinsic.fx, res_, voxel_size, list_Rv2c_, list_tv2c_,
-                                                 integrate_classify_slack, &device_Rv2c.data[0].x.re, &device_tv2c.x.re)) {
-            xs_icp_post_pose(integrate_mailbox_, &device_Rv2c.data[0].x.re, &device_tv2c.x.re, posted_seq_, 0);
-            integrated_by_post = true;
-            ++posted_accepted_;
-            list_ready_ = false;
-            if (posted_split_) { integrate_header_clear_ = false; pending_fold_ = counters; }
-        } else {   // (never seen: the last ICP update moved the frustum further than the widened planes allow for)
-            xs_icp_post_pose(integrate_mailbox_, nullptr, nullptr, posted_seq_, 1);
-            ++posted_refused_;
-            list_ready_ = false;
-            check_rc(xs_integrate_workspace_clear(integrate_ws_.ptr(), st), "integrate workspace");
-        }
-    }
     // the depth scaling ran on the auxiliary stream behind the map preparation
     // (a wait is a packet the next kernel queues behind: none is enqueued for an event that has already completed — the
     // scaling finished under the ICP loop long ago)
@@ -863,48 +740,44 @@ int KinectFusionReconstruction::IntegrateFrame(const DeviceArray2D<ushort> &dept
     hipEvent_t integrate_stop = integrate_done_;
     xs_integrate_opts o = {};   // everything the integrate calls below take besides their arguments proper (no per-thread setters)
     o.struct_bytes = sizeof(o);
-    if (integrated_by_post) integrate_stop = posted_stop_;
-    else if (IntegrateKernelTimedThisFrame()) {
+    if (IntegrateKernelTimedThisFrame()) {
         integrate_stop = prof_ring_[prof_pending_].ev[ST_INTEGRATE][1];
         o.start_event = prof_ring_[prof_pending_].ev[ST_INTEGRATE][0]; o.stop_event = integrate_stop;
         prof_ring_[prof_pending_].used[ST_INTEGRATE] = true;
     } else if (integrate_split())
         o.stop_event = integrate_stop;
-    if (!integrated_by_post) {
-        o.signmap = sign_map_ptr();   // (a rank of a sharded volume: the owned planes and both halo bands mark it)
-        o.depth_tiles = depth_tiles_.ptr();
-        // owned planes (counted), then the two halo bands every neighbour also integrates: the
-        // update is per voxel and deterministic, so a halo voxel carries the owner's exact bits
-        const int zr[3][2] = {{zo0, zo1}, {zs0, zo0}, {zo1, zs1}};
-        for (int i = 0; i < 3; ++i) {
-            const int za = zr[i][0], zb = zr[i][1];
-            if (zb <= za) continue;
-            const size_t off = (size_t)(za - zs0) * res[1];
-            // header cleared and count folded on the auxiliary stream (SurfaceMeasure) when there is one call per frame
-            const bool split = integrate_split() && integrate_header_clear_ && i == 0;
-            unsigned list_flag = 0;
-            if (i == 0 && list_ready_) {
-                list_ready_ = false; list_predicted_ = false;
-                WaitForClassification(st);
-                const int covers = xs_integrate_list_covers(depth_frame_d.rows(), depth_frame_d.cols(), &kinect_intrinsic.fx, res, voxel_size, list_Rv2c_,
-                                                            list_tv2c_, integrate_classify_slack, &device_Rv2c.data[0].x.re, &device_tv2c.x.re);
-                ++list_cover_counts_[covers & 3];
-                if (covers)   // (bit 1 clear: the list holds but the boxes' classes were padded for a nearer pose — they are decided again, the list stays)
-                    list_flag = XS_INTEGRATE_LIST_IS_READY | XS_INTEGRATE_HEADER_IS_CLEAR | ((covers & 2) ? 0u : XS_INTEGRATE_RECLASSIFY_BOXES);
-                else   // the last update moved the frustum further than the widened list allows for (never seen): start over
-                    check_rc(xs_integrate_workspace_clear(integrate_ws_.ptr(), st), "integrate workspace");
-            }
-            o.flags = (split ? (XS_INTEGRATE_HEADER_IS_CLEAR | XS_INTEGRATE_NO_FOLD) : 0u) | list_flag;
-            if (i == 0) t_call = std::chrono::steady_clock::now();
-            check_rc(xs_integrate_scaled_ex2(depthRawScaled_d.ptr(), depthRawScaled_d.step(), depth_frame_d.rows(), depth_frame_d.cols(),
-                                             &kinect_intrinsic.fx, max_integration_weight, res, voxel_size, &device_Rv2c.data[0].x.re,
-                                             &device_tv2c.x.re, tsdf_volume_d_ptr->getTsdfTruncDist(), value.ptr((int)off), weight.ptr((int)off),
-                                             grad.ptr((int)off), value.step(), biInterpolate_threshold, za, zb, i == 0 ? counters : nullptr,
-                                             depth_max_dev, integrate_ws_.ptr(), &o, st),
-                     "integrateTsdfVolume");
-            if (split) { integrate_header_clear_ = false; pending_fold_ = counters; }
-            if (i == 0) { t_back = std::chrono::steady_clock::now(); o.start_event = nullptr; o.stop_event = nullptr; }   // (the event pair rides on the owned planes' launch only)
+    o.signmap = sign_map_ptr();   // (a rank of a sharded volume: the owned planes and both halo bands mark it)
+    o.depth_tiles = depth_tiles_.ptr();
+    // owned planes (counted), then the two halo bands every neighbour also integrates: the
+    // update is per voxel and deterministic, so a halo voxel carries the owner's exact bits
+    const int zr[3][2] = {{zo0, zo1}, {zs0, zo0}, {zo1, zs1}};
+    for (int i = 0; i < 3; ++i) {
+        const int za = zr[i][0], zb = zr[i][1];
+        if (zb <= za) continue;
+        const size_t off = (size_t)(za - zs0) * res[1];
+        // header cleared and count folded on the auxiliary stream (SurfaceMeasure) when there is one call per frame
+        const bool split = integrate_split() && integrate_header_clear_ && i == 0;
+        unsigned list_flag = 0;
+        if (i == 0 && list_ready_) {
+            list_ready_ = false;
+            const int covers = xs_integrate_list_covers(depth_frame_d.rows(), depth_frame_d.cols(), &kinect_intrinsic.fx, res, voxel_size, list_Rv2c_,
+                                                        list_tv2c_, integrate_classify_slack, &device_Rv2c.data[0].x.re, &device_tv2c.x.re);
+            ++list_cover_counts_[covers & 3];
+            if (covers)   // (bit 1 clear: the list holds but the boxes' classes were padded for a nearer pose — they are decided again, the list stays)
+                list_flag = XS_INTEGRATE_LIST_IS_READY | XS_INTEGRATE_HEADER_IS_CLEAR | ((covers & 2) ? 0u : XS_INTEGRATE_RECLASSIFY_BOXES);
+            else   // the last update moved the frustum further than the widened list allows for (never seen): start over
+                check_rc(xs_integrate_workspace_clear(integrate_ws_.ptr(), st), "integrate workspace");
         }
+        o.flags = (split ? (XS_INTEGRATE_HEADER_IS_CLEAR | XS_INTEGRATE_NO_FOLD) : 0u) | list_flag;
+        if (i == 0) t_call = std::chrono::steady_clock::now();
+        check_rc(xs_integrate_scaled_ex2(depthRawScaled_d.ptr(), depthRawScaled_d.step(), depth_frame_d.rows(), depth_frame_d.cols(),
+                                         &kinect_intrinsic.fx, max_integration_weight, res, voxel_size, &device_Rv2c.data[0].x.re,
+                                         &device_tv2c.x.re, tsdf_volume_d_ptr->getTsdfTruncDist(), value.ptr((int)off), weight.ptr((int)off),
+                                         grad.ptr((int)off), value.step(), biInterpolate_threshold, za, zb, i == 0 ? counters : nullptr,
+                                         depth_max_dev, integrate_ws_.ptr(), &o, st),
+                 "integrateTsdfVolume");
+        if (split) { integrate_header_clear_ = false; pending_fold_ = counters; }
+        if (i == 0) { t_back = std::chrono::steady_clock::now(); o.start_event = nullptr; o.stop_event = nullptr; }   // (the event pair rides on the owned planes' launch only)
     }
 
     if (integrate_split()) integrate_done_now_ = integrate_stop;          // attached to the dispatch above
@@ -914,7 +787,7 @@ int KinectFusionReconstruction::IntegrateFrame(const DeviceArray2D<ushort> &dept
     hits_counter_ = counters + 1;
     CalculatePointCloud(vmaps_g_prev_d[0], nmaps_g_prev_d[0]);
     hits_counter_ = nullptr;
-    if (frame_id > 0 && !use_gtPose && !integrated_by_post) {
+    if (frame_id > 0 && !use_gtPose) {
         const auto t_ray = std::chrono::steady_clock::now();
         auto us = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) { return std::chrono::duration<double, std::micro>(b - a).count(); };
         tail_host_us[0] += us(t_last_sums_, t_enter); tail_host_us[1] += us(t_enter, t_call); tail_host_us[2] += us(t_call, t_back); tail_host_us[3] += us(t_back, t_ray);
@@ -1127,7 +1000,6 @@ void KinectFusionReconstruction::SurfaceMeasure(const DeviceArray2D<ushort> &dep
         stage_end(ST_SCALE);
     }
     list_ready_ = false;
-    ClassifyPredicted();
     current_stream() = main_stream;
     // the main stream picks the maps up — without a wait packet when they are already there (the usual case once the
     // previous frame's tail is the longer of the two)

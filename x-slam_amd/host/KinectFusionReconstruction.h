@@ -59,30 +59,9 @@ public:
     // the integrate call's brick classification enqueued behind the last ICP launch, with the pose that launch starts from (YAML
     // integrate_classify_ahead, default true; single GPU with the posted ICP loop): IntegrateFrame then finds the list ready
     bool integrate_classify_ahead = true;
-    // ... on the auxiliary stream, beside that launch instead of behind it (YAML integrate_classify_beside_icp, default FALSE).  Measured, no
-    // gain: a level-0 ICP launch fills the chip (one 16-wave workgroup per CU, all of its registers and 158 of 160 KB of LDS), so the two
-    // classification kernels do not run beside it but in front of its workgroups — the launch they share the chip with takes 26 us
-    // instead of 17.7 — and an integrate launch that has to wait for another stream's event starts 10 us later than one that follows its
-    // own queue (profiles/r04_ab_classify_beside_icp.txt).
-    bool integrate_classify_beside_icp = false;
-    // the classification at the frame's start, for the pose a constant-velocity model predicts, on the auxiliary stream (YAML
-    // integrate_classify_predicted, default FALSE: measured, no gain on the benchmark scene; not with integrate_post_pose or ground-truth
-    // poses): see ClassifyPredicted
-    bool integrate_classify_predicted = false;
-    bool list_predicted_ = false;              // the list that is ready was classified for a predicted pose (this frame's SurfaceMeasure)
-    int integrate_classify_early = 0;          // YAML integrate_classify_early: that many ICP iterations before the last (a pose that many more updates old)
+    // (the other schedules of the classification and the integrate launch that were measured and not adopted: DESIGN.md Appendix A)
     long long list_cover_counts_[4] = {0, 0, 0, 0};   // what xs_integrate_list_covers said of the lists classified ahead (xs_kf_list_cover_counts)
-    // the integrate kernel itself enqueued behind that classification, handed the final pose through a mailbox of its own and a one-wave gate
-    // kernel (YAML integrate_post_pose, default FALSE; needs integrate_classify_ahead and a mailbox in device memory).  Round 3, first form: all
-    // three launches went in one ICP iteration early (YAML integrate_post_early) — 16 % of the frames were then not covered by the planes of a
-    // pose two updates old at slack 2 and fell back: +0.7 % (profiles/r03_ab_integrate_post.txt).  As it stands they go in while the last ICP launch
-    // runs, with the pose that launch starts from (as the classification alone does): 4.7 % of the frames still fail the posted launch's stricter
-    // coverage test and the kernel starts ~8 us earlier on the others: +0.8 % frames/s, inside the noise (profiles/r03_ab_integrate_post_late.txt)
-    // — still off by default; xs_kf_posted_integrate_counts says how many launches were given their pose and how many were told to leave.
-    bool integrate_post_pose = false;
     long long composite_bytes_ = 0;   // bytes this rank received through the raycast composite's collectives so far (ring all-reduce: 2 (N - 1) / N x size; gather: the other ranks' parts)
-    long long posted_accepted_ = 0, posted_refused_ = 0;   // posted integrate launches that were given their pose / told to leave (xs_kf_posted_integrate_counts)
-    bool integrate_post_early = false;       // YAML integrate_post_early: the posted launch goes in one ICP iteration earlier (list from a pose two updates old)
     float integrate_classify_slack = 2.0f;   // YAML integrate_classify_slack: how much wider than its own the list's frustum slack is (1 = every frame falls back)
     // The sign map of the ray march (include/xslam_amd.h, csrc/xs_signmap.h; YAML raycast_sign_map, default true; raycast_sign_map_shift, default 0 =
     // the finest bricks the march can use: 8^3 voxels at 512^3): the integrate kernel marks the bricks it writes negative values into, the march starts every ray at the first
@@ -111,9 +90,6 @@ public:
     bool list_ready_ = false;
     float list_Rv2c_[18]{}, list_tv2c_[6]{};
     void ClassifyAhead(const Matrix3frm &Rcurr, const Vector3cf &tcurr);
-    void ClassifyPredicted();
-    void SetListPose(const Matrix4cf &c2w);
-    void EnqueueClassification(hipStream_t st, bool with_event);
     bool real_maps_valid_ = false;
 
     bool use_gtPose = false;
@@ -354,16 +330,6 @@ private:
     unsigned long long *pending_fold_ = nullptr;
     double *pinned_records_ = nullptr;   // xs_icp_records_bytes() of host-coherent pinned memory (icp_host_fold)
     void *icp_mailbox_ = nullptr;              // pose mailbox of the posted ICP launches (xs_icp_mailbox_alloc)
-    void *integrate_mailbox_ = nullptr;        // ... and the posted integrate launch's own (never rewritten while its kernel may still poll)
-    int integrate_mailbox_in_device_ = 0;
-    unsigned integrate_mail_seq_ = 0;
-    DeviceArray<unsigned> posted_pose_;        // {command, 24 floats}: the gate kernel's hand-over to the posted integrate launch
-    bool posted_pending_ = false;              // a posted integrate launch is in the stream, waiting for its pose
-    std::chrono::steady_clock::time_point posted_at_{};   // when it was enqueued (a pose that comes too late is not posted: the gate may have given up)
-    unsigned posted_seq_ = 0;
-    hipEvent_t posted_stop_ = nullptr;         // its completion event
-    bool posted_split_ = false;
-    void EnqueuePostedIntegrate();
     long long counters_prepared_for_ = -1;     // the frame whose counter slot has been prepared (ring half cleared)
     unsigned long long *PrepareFrameCounters(hipStream_t st);
     int icp_mailbox_in_device_ = 0;
@@ -387,9 +353,6 @@ public:
     unsigned debug_post_rng_ = 12345u;
 private:
     void AbandonClassifiedList();
-    void WaitForClassification(hipStream_t st);
-    hipEvent_t classify_done_ = nullptr;       // completion of ClassifyAhead's launches on the auxiliary stream (rides on the last dispatch)
-    bool classify_recorded_ = false;
     hipStream_t aux_stream_ = nullptr;         // surface measure of frame k+1 runs here, under raycast / pyramid of frame k
     hipEvent_t surface_done_ = nullptr, integrate_done_ = nullptr, scale_done_ = nullptr;
     hipEvent_t integrate_done_now_ = nullptr;   // the event that marks the last integrate call's completion (integrate_done_, or its dispatch's stop event)

@@ -5,6 +5,7 @@
 #include "KinectFusionReconstruction.h"
 #include <cstring>
 #include <exception>
+#include <memory>
 
 typedef KinectFusionReconstruction KF;
 using xs_host::Matrix4cf;
@@ -105,10 +106,10 @@ void xs_kf_set_stream(void *stream) { xs_host::current_stream() = (hipStream_t)s
 
 void *xs_kf_create_sharded(const char *yaml_text, int rank, int count, void (*collective)(void *, int, void *, long), void *user) {
     try {
-        KF *k = new KF();
+        std::unique_ptr<KF> k(new KF());
         k->SetSharding(rank, count, collective, user);
         k->SetYamlParameters(xs_host::FlatYaml::Load(yaml_text ? yaml_text : ""));
-        return k;
+        return k.release();
     } catch (const std::exception &e) {
         printf("xs_kf_create_sharded: %s\n", e.what());
         return nullptr;
@@ -121,9 +122,9 @@ void xs_kf_shard_planes(void *kf, int *owned2, int *stored2) {
 }
 void *xs_kf_create(const char *yaml_text) {
     try {
-        KF *k = new KF();
+        std::unique_ptr<KF> k(new KF());   // (a configuration SetYamlParameters refuses leaves nothing behind)
         k->SetYamlParameters(xs_host::FlatYaml::Load(yaml_text ? yaml_text : ""));
-        return k;
+        return k.release();
     } catch (const std::exception &e) {
         printf("xs_kf_create: %s\n", e.what());
         return nullptr;
@@ -320,10 +321,6 @@ void xs_kf_rebuild_sign_map(void *kf) { ((KF *)kf)->RebuildSignMap(); }
 long long xs_kf_composite_bytes(void *kf) { return ((KF *)kf)->composite_bytes_; }
 void xs_kf_list_cover_counts(void *kf, long long *counts4) {
     if (counts4) for (int i = 0; i < 4; ++i) counts4[i] = ((KF *)kf)->list_cover_counts_[i];
-}
-void xs_kf_posted_integrate_counts(void *kf, long long *accepted, long long *refused) {
-    if (accepted) *accepted = ((KF *)kf)->posted_accepted_;
-    if (refused) *refused = ((KF *)kf)->posted_refused_;
 }
 
 int xs_kf_save_checkpoint(void *kf, const char *path) { ((KF *)kf)->saveCheckpoint(path); return 0; }

@@ -68,7 +68,6 @@ _SIGS = {
     "xs_kf_composite_bytes": (C.c_longlong, [_vp]),
     "xs_kf_rebuild_sign_map": (None, [_vp]),
     "xs_kf_hint_next_frame": (None, [_vp, _vp, _sz]),
-    "xs_kf_posted_integrate_counts": (None, [_vp, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]),
     "xs_kf_list_cover_counts": (None, [_vp, C.POINTER(C.c_longlong)]),
     "xs_kf_cumulative_counters": (None, [_vp, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]),
     "xs_kf_save_checkpoint": (C.c_int, [_vp, C.c_char_p]),
@@ -158,7 +157,7 @@ class KinectFusion:
                 self.cfg[k.strip()] = v.split("#")[0].strip()
         self.h = _lib.xs_kf_create(text.encode())
         if not self.h:
-            raise ValueError("xs_kf_create failed (missing config key?)")
+            raise ValueError("xs_kf_create failed (missing config key, or a retired one set?)")
         self.res = [int(self.cfg[f"tsdf_size_{a}"]) for a in "xyz"]
         self.width, self.height = int(self.cfg["depth_width"]), int(self.cfg["depth_height"])
         if gt_poses is not None:
@@ -384,12 +383,6 @@ class KinectFusion:
         c = (C.c_longlong * 4)()
         _lib.xs_kf_list_cover_counts(self.h, c)
         return {"neither": int(c[0]), "list_only": int(c[1]), "both": int(c[3])}
-
-    def posted_integrate_counts(self):
-        """(accepted, refused) posted integrate launches so far (integrate_post_pose)."""
-        a, r = C.c_longlong(0), C.c_longlong(0)
-        _lib.xs_kf_posted_integrate_counts(self.h, C.byref(a), C.byref(r))
-        return int(a.value), int(r.value)
 
     def rebuild_sign_map(self):
         """After writing the value array through volume_ptr: the ray march's sign map is rebuilt from the volume."""
