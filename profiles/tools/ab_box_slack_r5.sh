@@ -5,7 +5,7 @@
 cd "$(dirname "$0")/../.." && mkdir -p gpurun_out
 touch x-slam_amd/csrc/xs_tsdf.hip; make -C x-slam_amd/csrc EXTRAFLAGS=-DXS_EXPERIMENTS > /dev/null 2>&1 || exit 1
 run() {
-  XS_BOX_SLACK_AXIAL=$1 XS_BOX_SLACK_LATERAL=$2 timeout -k 10 200 python3 bench.py --workload track --size $3 --steps 60 --warmup 5 --no-s2 --no-cpu-baseline --no-legs 2>/dev/null | python3 -c "
+  XS_BOX_SLACK_AXIAL=$1 XS_BOX_SLACK_LATERAL=$2 timeout -k 10 200 python3 bench.py --full --workload track --size $3 --steps 60 --warmup 5 --no-s2 --no-cpu-baseline --no-legs 2>/dev/null | python3 -c "
 import json,sys
 p=json.loads(sys.stdin.read().strip().splitlines()[-1])
 print('axial $1 lateral $2 size $3: fps', p['value'], 'median', p['value_median_of_repetitions'], 'integrate kernel ms', p['roofline']['kernel_ms'], 'held', p['config']['classes_decided_ahead_held'])"

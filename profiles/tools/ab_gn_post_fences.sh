@@ -6,7 +6,7 @@ make -C x-slam_amd/csrc clean > /dev/null; make -C x-slam_amd/csrc EXTRAFLAGS=-D
 for round in 1 2 3; do
   for twelve in 1 0; do
     if [ $twelve = 1 ]; then export XS_GN_POST_TWELVE_FENCES=1; else unset XS_GN_POST_TWELVE_FENCES; fi
-    python bench.py --workload reloc --steps 30 --warmup 3 2>/dev/null | python -c "
+    python bench.py --full --workload reloc --steps 30 --warmup 3 2>/dev/null | python -c "
 import sys, json
 d = json.loads(sys.stdin.read().strip().splitlines()[-1])
 r = d.get('workloads', {}).get('reloc', d)

@@ -12,5 +12,5 @@ for v in "tp32_b1024:XS_HESS_TILE_PLANES=32 XS_HESS_BLOCKS=1024" "tp64_b1024:XS_
   env $envs python profiles/tools/probe_hess.py 2>/dev/null | grep hessian_ms
   env $envs python profiles/tools/probe_gn.py 1024 2>/dev/null | grep '"n"'
   env $envs python profiles/tools/probe_gn.py 512 2>/dev/null | grep '"n"'
-  env $envs python bench.py --workload reloc --steps 20 --warmup 3 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); r=d['workloads']['reloc']; print('reloc', r['value'], r['ms_per_pass_incl_allreduce_and_host_solve'], r['host_side'])"
+  env $envs python bench.py --full --workload reloc --steps 20 --warmup 3 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); r=d['workloads']['reloc']; print('reloc', r['value'], r['ms_per_pass_incl_allreduce_and_host_solve'], r['host_side'])"
 done

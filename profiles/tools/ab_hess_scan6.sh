@@ -7,7 +7,7 @@ for round in 1 2; do
     env $envs python profiles/tools/probe_hess.py 2>/dev/null | head -1
     env $envs python profiles/tools/probe_gn.py 512 2>/dev/null | head -1
     env $envs python profiles/tools/probe_gn.py 1024 2>/dev/null | head -1
-    env $envs python bench.py --workload reloc --steps 20 --warmup 3 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); r=d['workloads']['reloc']; print('reloc', r['value'], r['ms_per_pass_incl_allreduce_and_host_solve'], r['host_us_per_pass'])"
-    env $envs python bench.py --workload hessian --steps 200 --warmup 10 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('hessian workload', d['value'], d['roofline']['frac'], d['roofline']['kernel_ms'])"
+    env $envs python bench.py --full --workload reloc --steps 20 --warmup 3 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); r=d['workloads']['reloc']; print('reloc', r['value'], r['ms_per_pass_incl_allreduce_and_host_solve'], r['host_us_per_pass'])"
+    env $envs python bench.py --full --workload hessian --steps 200 --warmup 10 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('hessian workload', d['value'], d['roofline']['frac'], d['roofline']['kernel_ms'])"
   done
 done

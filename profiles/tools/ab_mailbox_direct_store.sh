@@ -7,7 +7,7 @@ make -C x-slam_amd/csrc clean > /dev/null; make -C x-slam_amd/csrc EXTRAFLAGS=-D
 for round in 1 2 3; do
   for fenced in 1 0; do
     if [ $fenced = 1 ]; then export XS_MAILBOX_NO_DIRECT_STORE=1; else unset XS_MAILBOX_NO_DIRECT_STORE; fi
-    python bench.py --steps 200 --warmup 10 --no-cpu-baseline --no-s2 --no-csfd --no-legs 2>/dev/null | python -c "
+    python bench.py --full --steps 200 --warmup 10 --no-cpu-baseline --no-s2 --no-csfd --no-legs 2>/dev/null | python -c "
 import sys, json
 d = json.loads(sys.stdin.read().strip().splitlines()[-1])
 i = d['icp_us_per_iteration']; r = d['workloads']['reloc']

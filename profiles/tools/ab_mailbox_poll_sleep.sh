@@ -7,7 +7,7 @@ done
 for round in 1 2 3; do
   for v in 8 2 0; do
     cp /tmp/hip_sleep$v.so x-slam_amd/libxslam_hip.so
-    python bench.py --steps 200 --warmup 10 --no-cpu-baseline --no-s2 --no-csfd --no-legs --workload track 2>/dev/null | python -c "
+    python bench.py --full --steps 200 --warmup 10 --no-cpu-baseline --no-s2 --no-csfd --no-legs --workload track 2>/dev/null | python -c "
 import sys, json
 d = json.loads(sys.stdin.read().strip().splitlines()[-1])
 i = d['icp_us_per_iteration']

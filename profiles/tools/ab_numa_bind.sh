@@ -6,7 +6,7 @@
 for round in 1 2 3; do
   for flag in --no-numa-bind "" remote; do
     if [ "$flag" = remote ]; then export XS_BENCH_BIND_REMOTE=1; f=""; else unset XS_BENCH_BIND_REMOTE; f=$flag; fi
-    python bench.py --steps 200 --warmup 10 --no-cpu-baseline --no-s2 --no-csfd --no-legs $f 2>/dev/null | python -c "
+    python bench.py --full --steps 200 --warmup 10 --no-cpu-baseline --no-s2 --no-csfd --no-legs $f 2>/dev/null | python -c "
 import sys, json
 d = json.loads(sys.stdin.read().strip().splitlines()[-1])
 i = d['icp_us_per_iteration']; r = d['workloads']['reloc']; h = d['host_affinity']

@@ -8,7 +8,7 @@ for v in ${VARIANTS:-"1 0" "1 1" "2 0" "1 0" "1 1"}; do
   touch x-slam_amd/csrc/xs_tsdf.hip; make -C x-slam_amd/csrc EXTRAFLAGS="-DXS_FREE_CHUNK=$1 -DXS_FREE_DMA=$2" > /dev/null 2>&1 || exit 1
   echo "== XS_FREE_CHUNK=$1 XS_FREE_DMA=$2 =="
   timeout -k 10 300 python3 profiles/tools/probe_edge.py 512 1024 2>&1 | grep -E "^n (512|1024) (own|ahead)|identical" | cut -c1-100 | sort | uniq -c || exit 1
-  timeout -k 10 400 python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline 2>/dev/null | python3 -c "
+  timeout -k 10 400 python3 bench.py --full --steps 20 --warmup 5 --no-cpu-baseline 2>/dev/null | python3 -c "
 import json,sys
 p=json.loads(sys.stdin.read().strip().splitlines()[-1])
 s2=p.get('roofline_s2') or {}; l=(p.get('legs') or {}); t=l.get('track_1024') or {}; b=p.get('bilinear') or {}

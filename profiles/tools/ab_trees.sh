@@ -5,7 +5,7 @@
 cd "$(dirname "$0")/../.."
 ROOT=$PWD
 LA=${1:-previous}; LB=${2:-current}
-run() { (cd $1 && timeout -k 10 200 python3 bench.py --workload track --steps $2 --warmup 5 --no-s2 --no-cpu-baseline --no-legs 2>/dev/null) | python3 -c "
+run() { (cd $1 && timeout -k 10 200 python3 bench.py --full --workload track --steps $2 --warmup 5 --no-s2 --no-cpu-baseline --no-legs 2>/dev/null) | python3 -c "
 import json,sys
 p=json.loads(sys.stdin.read().strip().splitlines()[-1])
 b=p.get('bilinear') or {}

@@ -3,7 +3,7 @@
 # headline, integrate kernel, the 1024^3 leg, scene S2's regimes, the bilinear run.
 cd "$(dirname "$0")/../.."
 ROOT=$PWD
-run() { (cd $1 && timeout -k 10 400 python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline 2>/dev/null) | python3 -c "
+run() { (cd $1 && timeout -k 10 400 python3 bench.py --full --steps 20 --warmup 5 --no-cpu-baseline 2>/dev/null) | python3 -c "
 import json,sys
 p=json.loads(sys.stdin.read().strip().splitlines()[-1])
 s2=p.get('roofline_s2') or {}; l=(p.get('legs') or {}); t=l.get('track_1024') or {}; b=p.get('bilinear') or {}

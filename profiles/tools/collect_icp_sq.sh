@@ -2,7 +2,7 @@
 # GPU box, repository root: SQ / instruction-cache counters of the ICP kernels in the headline workload (separate passes; kernel trace only)
 cd "$(dirname "$0")/../.." && export TMPDIR=/tmp
 OUT=gpurun_out/icp_sq; rm -rf $OUT; mkdir -p $OUT
-pass() { local n=$1; shift; timeout -k 10 300 rocprofv3 --pmc "$@" --kernel-trace --output-format csv -d $OUT/$n -- python3 bench.py --workload track --no-s2 --no-cpu-baseline --steps 60 > $OUT/$n.log 2>&1 || { tail -5 $OUT/$n.log; exit 1; }; }
+pass() { local n=$1; shift; timeout -k 10 300 rocprofv3 --pmc "$@" --kernel-trace --output-format csv -d $OUT/$n -- python3 bench.py --full --workload track --no-s2 --no-cpu-baseline --steps 60 > $OUT/$n.log 2>&1 || { tail -5 $OUT/$n.log; exit 1; }; }
 pass a SQC_ICACHE_REQ SQC_ICACHE_HITS SQC_ICACHE_MISSES SQC_ICACHE_MISSES_DUPLICATE
 pass b SQ_WAVES SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_INSTS_VALU SQ_INSTS_SALU SQ_IFETCH SQ_BUSY_CYCLES
 python3 - <<'PY'

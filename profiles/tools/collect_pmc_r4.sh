@@ -14,7 +14,7 @@ export TMPDIR=/tmp
 for C in FETCH_SIZE WRITE_SIZE; do
   rocprofv3 --pmc $C --kernel-trace --output-format csv -d $OUT/s2_$C -- python3 profiles/tools/probe_s2_pmc.py > $OUT/s2_$C.log 2>&1
   rocprofv3 --pmc $C --kernel-trace --output-format csv -d $OUT/calib_$C -- $OUT/calib_stream > $OUT/calib_$C.log 2>&1
-  rocprofv3 --pmc $C --kernel-trace --output-format csv -d $OUT/track_$C -- python3 bench.py --workload track --no-s2 --no-cpu-baseline --no-legs --steps 60 > $OUT/track_$C.log 2>&1
+  rocprofv3 --pmc $C --kernel-trace --output-format csv -d $OUT/track_$C -- python3 bench.py --full --workload track --no-s2 --no-cpu-baseline --no-legs --steps 60 > $OUT/track_$C.log 2>&1
 done
 rocprofv3 --pmc SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_ACTIVE_INST_VALU --kernel-trace --output-format csv -d $OUT/s2_SQ -- python3 profiles/tools/probe_s2_pmc.py > $OUT/s2_SQ.log 2>&1
 python3 profiles/tools/pmc_summary_r4.py $OUT > $OUT/summary.json

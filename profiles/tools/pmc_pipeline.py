@@ -1,5 +1,5 @@
 """Per-kernel HBM read traffic of the whole pipeline from one rocprofv3 --pmc FETCH_SIZE pass over bench.py.
-usage (GPU box):  rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d OUT -- python3 bench.py --steps 30 --no-s2 --no-cpu-baseline
+usage (GPU box):  rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d OUT -- python3 bench.py --full --steps 30 --no-s2 --no-cpu-baseline
                   python3 profiles/tools/pmc_pipeline.py OUT
 FETCH_SIZE is in KiB and under-reports by 2 on gfx950 for these dword-per-lane streams (profiles/r01_integrate_pmc_v3.json)."""
 import csv, glob, json, os, sys

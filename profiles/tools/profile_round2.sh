@@ -7,7 +7,7 @@ set -u
 cd "$(dirname "$0")/../.." && export TMPDIR=/tmp
 OUT=gpurun_out/prof_r02; mkdir -p $OUT
 run() { local name=$1; shift; echo "== $name"; timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/$name -- "$@" > $OUT/$name.log 2>&1; local rc=$?; echo "$name rc=$rc"; [ $rc -ge 124 ] && exit $rc; find $OUT/$name -name '*kernel_stats.csv' -exec cp {} $OUT/${name}_kernel_stats.csv \; ; tail -2 $OUT/$name.log | cut -c1-600; }
-run bench python3 bench.py --no-cpu-baseline --no-csfd
+run bench python3 bench.py --full --no-cpu-baseline --no-csfd
 run s2_probe python3 profiles/tools/probe_s2.py 20
 run hess_probe python3 profiles/tools/probe_hess.py
 run gn_512 python3 profiles/tools/probe_gn.py 512

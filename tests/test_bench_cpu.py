@@ -66,8 +66,8 @@ class _Runner:
         pass
 
 
-def _args(steps, warmup):
-    return argparse.Namespace(steps=steps, warmup=warmup, size=512, scene="s1", replicas=False, force_composite=False, icp_solve=None,
+def _args(steps, warmup, full=True):
+    return argparse.Namespace(steps=steps, warmup=warmup, full=full, size=512, scene="s1", replicas=False, force_composite=False, icp_solve=None,
                               no_post_pose=False, icp_lookahead=None, icp_complex_maps=False, no_classify_ahead=False, integrate_post=False,
                               no_integrate_post=False, classify_slack=None, param=[], no_sign_map=False, sign_map_shift=None, icp_fold=None,
                               host_frames=False, no_look_ahead=False, no_legs=True, no_alt=True, icp_shard_rows=False, native_rccl=False)
@@ -90,6 +90,29 @@ def test_steps_sets_the_timed_frames(bench, monkeypatch, steps):
     assert all(np.isfinite(v).all() for v in dump.values())
     assert dump["track_vmap_model_level0_valid"].shape == (480, 640) and dump["track_vmap_model_level0_valid"].sum() == 480 * 320
     assert (dump["track_vmap_model_level0"][:480, :320, 0] == 0).all()
+
+
+@pytest.mark.parametrize("steps", [1, 200, 2000])
+def test_plain_run_is_the_timed_steps_alone(bench, monkeypatch, steps):
+    """Without --full the headline renders and runs only what its timed steps need: frame 0, the warm-up and the segments on their
+    runners (each announcing the frame after its last), none of the per-stage, level-0, raycast or bilinear passes, and no leg."""
+    rendered = []
+
+    def frame(k):
+        rendered.append(k)
+        return np.zeros((480, 640), np.uint16)
+    torch = types.SimpleNamespace(from_numpy=lambda a: types.SimpleNamespace(cuda=lambda: a),
+                                  cuda=types.SimpleNamespace(synchronize=lambda: None))
+    synth = types.SimpleNamespace(s1_frame=frame, s3_frame=None, s1_params=lambda n: {})
+    monkeypatch.setattr(bench, "raycast_figures", lambda *a, **k: pytest.fail("raycast figures in a plain run"))
+    _Runner.made = []
+    out = bench.track(_args(steps, 10, full=False), torch, synth, None, types.SimpleNamespace(KinectFusion=_Runner), None, 0, 1, lambda: None, {})
+    segs = out["segments"]["frames"]
+    assert sum(segs) == steps == out["steps"] and len(_Runner.made) == len(segs)
+    assert [r.frames for r in _Runner.made] == [1 + 10 + k for k in segs] and [r.timed for r in _Runner.made] == segs
+    assert rendered == list(range(min(10 + 2 + max(segs), bench.T_PERIOD)))
+    assert not {"stages_ms", "raycast", "roofline_icp", "bilinear", "legs", "sustained"} & set(out)
+    assert out["ms_per_step"] > 0 and out["value"] > 0 and "roofline" in out and "icp_us_per_iteration" in out
 
 
 def test_dump_is_float_and_bounded(bench, tmp_path):

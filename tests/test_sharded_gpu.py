@@ -350,7 +350,7 @@ def test_two_ranks_over_rccl_on_two_gpus():
     assert np.array_equal(poses[0].view(np.int32), poses[1].view(np.int32))
     assert np.allclose(poses[0], ref, rtol=0, atol=2e-7)
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "10", "--warmup", "3", "--native-rccl", "--size", "256",
-                        "--reloc-size", "256", "--no-alt"], capture_output=True, text=True, timeout=1200, env=env, cwd=root)
+                        "--reloc-size", "256", "--no-alt", "--full"], capture_output=True, text=True, timeout=1200, env=env, cwd=root)
     assert r.returncode == 0, (r.stdout[-1500:], r.stderr[-3000:])
     out = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
     assert out["n_ranks_seen"] == 2 and out["n_gpus"] == 2 and out["value"] > 0
