@@ -52,7 +52,7 @@ def test_pose_mailbox_layout_host_side():
     """xs_icp_post_pose is host code: the 128-byte mailbox it writes — four 32-byte sectors, each led by the sequence number, the
     command in word 1, the 18 floats of Rcurr then the 6 of tcurr in words 2..7, 9..15, 18..23 and 25..29 (csrc/xs_mailbox.h) — is what the
     posted kernels read; an abandon command carries no pose.  Both an aligned mailbox (MOVDIR64B direct stores where the CPU has them) and
-    an unaligned one (the fenced form)."""
+    an unaligned one (the fenced form).  xs_gn_post_poses writes six such boxes in a row, box k with pose k."""
     import ctypes as C
     import numpy as np
     capi = importlib.import_module("x-slam_amd.capi")
@@ -73,6 +73,27 @@ def test_pose_mailbox_layout_host_side():
         assert np.all(buf[32:] == 0xDEADBEEF) and np.all(raw[:off] == 0xDEADBEEF)
         capi.icp_post_pose(buf.ctypes.data, None, None, 78, cmd=1)
         assert all(buf[w] == 78 for w in (0, 8, 16, 24)) and buf[1] == 1 and not buf[words].any()
+    # xs_gn_post_poses: six such boxes in a row, one post — box k carries pose k, every box the sequence number and the command
+    assert capi._lib.xs_gn_mailbox_bytes() == 6 * 128
+    R6 = (np.arange(108, dtype=np.float32) + 1).reshape(6, 3, 3, 2)
+    t6 = (np.arange(36, dtype=np.float32) + 1001).reshape(6, 3, 2)
+    raw = np.full(6 * 32 + 40, 0xDEADBEEF, np.uint32)
+    base = (-raw.ctypes.data // 4) % 16
+    for off in (base, base + 1):
+        raw[:] = 0xDEADBEEF
+        buf = raw[off:off + 6 * 32 + 8]
+        assert (buf.ctypes.data % 64 == 0) == (off == base)
+        capi.gn_post_poses(buf.ctypes.data, R6, t6, 91, cmd=0)
+        for k in range(6):
+            box = buf[32 * k:32 * k + 32]
+            assert all(box[w] == 91 for w in (0, 8, 16, 24)) and box[1] == 0 and box[17] == 0 and box[30] == 0 and box[31] == 0, k
+            assert np.array_equal(box[words], np.concatenate([R6[k].reshape(-1), t6[k].reshape(-1)]).view(np.uint32)), k
+        assert np.all(buf[6 * 32:] == 0xDEADBEEF) and np.all(raw[:off] == 0xDEADBEEF)
+        capi.gn_post_poses(buf.ctypes.data, None, None, 92, cmd=1)
+        for k in range(6):
+            box = buf[32 * k:32 * k + 32]
+            assert all(box[w] == 92 for w in (0, 8, 16, 24)) and box[1] == 1 and not box[words].any(), k
+        assert np.all(buf[6 * 32:] == 0xDEADBEEF) and np.all(raw[:off] == 0xDEADBEEF)
 
 
 def test_host_fold_of_records_host_side():

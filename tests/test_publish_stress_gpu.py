@@ -1,6 +1,6 @@
 """GPU: the record hand-offs under repetition.  k_icp and the TSDF residual kernels publish one record per workgroup with relaxed
 agent-scope (write-through) stores + s_waitcnt vmcnt(0) + a relaxed ticket, and the last workgroup adds the records after an acquire
-(csrc/xs_icp.hip, csrc/xs_tsdf.hip: block_fold_and_finish) — a protocol that leans on what gfx942 / gfx950 do with such stores, outside
+(csrc/xs_icp.hip, csrc/xs_gn_band.h: block_fold_and_finish) — a protocol that leans on what gfx942 / gfx950 do with such stores, outside
 the HIP memory model.  A stale record would show as a sum that differs from launch to launch: thousands of back-to-back launches on
 fixed inputs must give identical bits.  And the posted-pose loop (a resident launch polling a mailbox the host writes) must neither time
 out nor change a pose when the host is slow."""

@@ -1,6 +1,6 @@
 // xs_band.hip — the band index of a fixed map and the batched Gauss-Newton pass over it (relocalisation).
 //
-// The six-pose Gauss-Newton pass (k_tsdf_gauss_newton, xs_tsdf.hip) scans the whole dense slab to find its band voxels (gt != 0,
+// The six-pose Gauss-Newton pass (k_tsdf_gauss_newton, xs_residual.hip) scans the whole dense slab to find its band voxels (gt != 0,
 // |gt| <= 0.95) and evaluates only those.  The band is a function of gt alone: for a map that does not change, every pass of every query
 // frame scans the same gigabytes to find the same voxels.  Here the scan runs once per map version and RECORDS what it deals out:
 //   k_band_count / k_band_write  walk the slab exactly as the Gauss-Newton kernel does (walk_band with hess_tiling(heavy_body = true): the
@@ -17,10 +17,6 @@
 #include <vector>
 #include "xs_gn_band.h"
 #include "../../include/xslam_amd.h"
-
-#if defined(__HIP_DEVICE_COMPILE__) && !defined(__gfx942__) && !defined(__gfx950__)
-#error "write-through record publish (block_fold_and_finish_of): gfx942 / gfx950 only"
-#endif
 
 static_assert(XS_BAND_MAX_FRAMES == 32, "the header's bound");
 enum { BAND_RECORD_DOUBLES = 32, BAND_POSES_OFFSET = 256 };

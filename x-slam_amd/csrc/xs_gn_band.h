@@ -1,12 +1,18 @@
-// xs_gn_band.h — what the dense residual kernels of xs_tsdf.hip and the band index of xs_band.hip share: the kernel arguments, the
+// xs_gn_band.h — what the dense residual kernels of xs_residual.hip and the band index of xs_band.hip share: the kernel arguments, the
 // record fold (registers -> wave -> LDS -> one record per workgroup -> the last workgroup adds the records in index order), the walk that
 // deals the band voxels (gt != 0, |gt| <= 0.95) of a slab out to the lanes, and the six-pose CSFD residual of the Gauss-Newton pass.
-// Included by exactly those two files; xs_tsdf.hip includes it where the code used to stand, so its kernels compile to the same code.
+// Included by exactly those two files.
 #pragma once
 #include "xs_device.h"
 #include "xs_env.h"
 
 using namespace xs;
+// The record hand-offs of block_fold_and_finish_of (relaxed agent-scope stores + s_waitcnt vmcnt(0) + a relaxed ticket, no release fence) are
+// correct because gfx942 / gfx950 implement an agent-scope atomic store as a write-through (sc1) store that is acknowledged from memory; that is
+// outside the HIP / LLVM memory model, so a file that includes this refuses to build for anything else rather than publish stale records there.
+#if defined(__HIP_DEVICE_COMPILE__) && !defined(__gfx942__) && !defined(__gfx950__)
+#error "write-through record publish: gfx942 / gfx950 only (use a release fence + acq_rel ticket on other targets)"
+#endif
 
 struct HessArgs {
     const float *depth; size_t dstep; int drows, dcols;
@@ -319,5 +325,5 @@ __device__ __forceinline__ void gn_terms_add(const HessArgs &a, const GnPoses &P
     acc[28] += 1.0;
 }
 
-// host: the walk's tiling and grid for the slab [z0, z1) of gt (xs_tsdf.hip; heavy_body: the interleaved form of the six-pose and Hessian kernels)
+// host: the walk's tiling and grid for the slab [z0, z1) of gt (xs_residual.hip; heavy_body: the interleaved form of the six-pose and Hessian kernels)
 int hess_tiling(HessArgs &a, const int *res, const float *gt, int z0, int z1, dim3 &grid, bool heavy_body);

@@ -980,20 +980,11 @@ extern "C" int xs_icp_wait_pairs(const void *pairs_host, unsigned long long seq,
     xs_read_pairs(pairs_host, sums55);
     return 0;
 }
-/* Host side of the mailbox (xs_mailbox.h has the layout and the reasons).  With MOVDIR64B each of the two 64-byte lines goes out as one write,
- * sequence words and payload together; without it: the payload first, a store fence, the four sequence words, a store fence (the poller accepts
- * a 32-byte sector only with its sequence word). */
+/* Host side of the mailbox: one box (xs_mailbox.h has the layout, the order of stores and fences, and the reasons). */
 extern "C" void xs_icp_post_pose(void *mailbox_host, const float *Rcurr18, const float *tcurr6, unsigned mailbox_seq, int cmd) {
-    static const bool direct = mailbox_cpu_has_direct_store() && !exp_env_set("XS_MAILBOX_NO_DIRECT_STORE");
-    alignas(64) unsigned img[MAILBOX_WORDS];
-    mailbox_image(img, Rcurr18, tcurr6, mailbox_seq, cmd);
-    if (direct && (reinterpret_cast<uintptr_t>(mailbox_host) % 64) == 0) {
-        mailbox_store_fence();   // (behind whatever this thread posted before: nothing is pending, so this costs nothing)
-        mailbox_direct_store_64(mailbox_host, img);
-        mailbox_direct_store_64(static_cast<char *>(mailbox_host) + 64, img + 16);
-        return;
-    }
-    mailbox_store_fenced((volatile unsigned *)mailbox_host, img);
+    alignas(64) unsigned img[1][MAILBOX_WORDS];
+    mailbox_image(img[0], Rcurr18, tcurr6, mailbox_seq, cmd);
+    mailbox_post(mailbox_host, img, 1);
 }
 /* A mailbox where polling is cheapest: fine-grained device memory the CPU writes through the large
  * BAR (512 workgroups then poll local memory, not the PCIe link), or — without a large BAR —

@@ -1,5 +1,5 @@
-// xs_mailbox.h — the pose mailbox shared by k_icp<POSE_POSTED> (xs_icp.hip) and the posted Gauss-Newton pass (xs_tsdf.hip).
-// xs_icp_post_pose (host) writes it, a kernel that was enqueued before its pose existed polls it.  128 bytes = four 32-byte
+// xs_mailbox.h — the pose mailbox shared by k_icp<POSE_POSTED> (xs_icp.hip) and the posted Gauss-Newton pass (xs_residual.hip).
+// mailbox_post (host, below: xs_icp_post_pose, xs_gn_post_poses) writes it, a kernel that was enqueued before its pose existed polls it.  128 bytes = four 32-byte
 // SECTORS of eight words, EVERY sector starting with the sequence number:
 //     sector 0 = {seq, cmd, f[0..5]}   sector 1 = {seq, f[6..12]}   sector 2 = {seq, 0, f[13..18]}   sector 3 = {seq, f[19..23], 0, 0}
 // with f = the 18 floats of a complex 3x3 followed by the 6 of a complex 3-vector; cmd 0 = run, 1 = abandon the launch.  A 32-byte sector is the
@@ -30,7 +30,7 @@ __device__ __forceinline__ void mailbox_wait(const unsigned *mailbox, unsigned s
                        s3 = __builtin_amdgcn_readlane(v, 24);
         if (s0 == s1 && s1 == s2 && s2 == s3 && (int)(s0 - seq) >= 0) {
             // every sector of THIS load carries one number: the words are one post's, whole (the host writes a sector's number with or after
-            // its payload: xs_icp_post_pose)
+            // its payload: mailbox_post)
             const unsigned c = __builtin_amdgcn_readlane(v, 1);
             if (s0 == seq) { /* this launch's post: pose or command as posted */ }
             else if (c == 1) cmd_override = 1;   // abandon, addressed to a later launch: leave too
@@ -75,7 +75,9 @@ static inline bool mailbox_cpu_has_direct_store() { return false; }
 static inline void mailbox_store_fence() { __atomic_thread_fence(__ATOMIC_SEQ_CST); }
 }  // namespace xs
 #endif
+#include <cstdint>
 #include <cstring>
+#include "xs_env.h"
 namespace xs {
 // the four sectors of one mailbox as they lie in memory (layout at the top of this file)
 static inline void mailbox_image(unsigned img[MAILBOX_WORDS], const float *R18, const float *t6, unsigned seq, int cmd) {
@@ -87,11 +89,39 @@ static inline void mailbox_image(unsigned img[MAILBOX_WORDS], const float *R18, 
     img[1] = (unsigned)cmd;
     img[0] = img[8] = img[16] = img[24] = seq;
 }
-// the fenced form of a post (no MOVDIR64B): everything but the four sequence words, a store fence, the four sequence words, a store fence
-static inline void mailbox_store_fenced(volatile unsigned *w, const unsigned img[MAILBOX_WORDS]) {
-    for (int i = 0; i < MAILBOX_WORDS; ++i) if (i % 8 != 0) w[i] = img[i];
+// whether posts go out as direct 64-byte stores (the experiment switch: the fenced path on a CPU that has them)
+static inline bool mailbox_direct_stores() {
+    static const bool direct = mailbox_cpu_has_direct_store() && !exp_env_set("XS_MAILBOX_NO_DIRECT_STORE");
+    return direct;
+}
+// The post: `boxes` mailbox images to as many consecutive mailboxes at mailbox_host.  The kernel polls the LAST box and takes its sequence
+// number there to mean that the earlier boxes are complete (k_tsdf_gauss_newton<true> reads them next and checks each one's sequence words;
+// k_icp<POSE_POSTED> has one box), so the earlier boxes are out, behind a store fence if there are any, before the last box can be seen.
+//   direct (MOVDIR64B, mailbox_host 64-byte aligned): every line is one write with its sequence words inside — a fence, both lines of every
+//     earlier box, a fence if there were any, both lines of the last box;
+//   fenced: a sector counts only with its sequence word, so everything but the sequence words of all boxes, a fence, the sequence words of the
+//     earlier boxes, a fence if there were any, the sequence words of the last box, a fence.  Three fences for six boxes, where six posts of
+//     one box took twelve, each of them a round of draining while the launch waits (profiles/r06_ab_gn_post_fences.txt).
+static inline void mailbox_post(void *mailbox_host, const unsigned (*img)[MAILBOX_WORDS], int boxes) {
+    const int last = boxes - 1;
+    if (mailbox_direct_stores() && (reinterpret_cast<uintptr_t>(mailbox_host) % 64) == 0) {
+        unsigned *w = static_cast<unsigned *>(mailbox_host);
+        mailbox_store_fence();   // (behind whatever this thread posted before: nothing is pending, so this costs nothing)
+        for (int k = 0; k < boxes; ++k) {
+            if (k == last && last > 0) mailbox_store_fence();
+            mailbox_direct_store_64(w + (size_t)k * MAILBOX_WORDS, img[k]);
+            mailbox_direct_store_64(w + (size_t)k * MAILBOX_WORDS + 16, img[k] + 16);
+        }
+        return;
+    }
+    volatile unsigned *w = static_cast<volatile unsigned *>(mailbox_host);
+    for (int k = 0; k < boxes; ++k)
+        for (int i = 0; i < MAILBOX_WORDS; ++i) if (i % 8 != 0) w[(size_t)k * MAILBOX_WORDS + i] = img[k][i];
     mailbox_store_fence();
-    for (int i = 0; i < MAILBOX_WORDS; i += 8) w[i] = img[i];
+    for (int k = 0; k < boxes; ++k) {
+        if (k == last && last > 0) mailbox_store_fence();
+        for (int i = 0; i < MAILBOX_WORDS; i += 8) w[(size_t)k * MAILBOX_WORDS + i] = img[k][i];
+    }
     mailbox_store_fence();
 }
 }  // namespace xs

@@ -1,5 +1,5 @@
 // xs_signmap.hip — owner-side operations of the sign map (xs_signmap.h): size, reset, rebuild from a volume.
-// The integrate kernels (xs_tsdf.hip) set its bytes, the single-GPU ray march (xs_raycast.hip) reads them.
+// The integrate kernels (xs_integrate.hip) set its bytes, the single-GPU ray march (xs_raycast.hip) reads them.
 #include "xs_device.h"
 #include "xs_signmap.h"
 #include "../../include/xslam_amd.h"
