@@ -397,6 +397,21 @@ size_t xs_tsdf_band_workspace_bytes(int frames);
 int xs_tsdf_gauss_newton_terms_band(int frames, const float *const *depth_scaled, size_t scaled_step, int rows, int cols, const float *intr4,
                                     float voxel_size, const float *Rv2c108xF, const float *tv2c36xF, float tranc_dist, const xs_band_index *index,
                                     void *workspace, double *out29xF_dev, void *stream);
+/* ---- the exact 6 x 6 pose Hessian of the map-alignment loss in one pass over the index ----
+ * Per query frame 21 dual-complex poses in the layout of xs_compute_local_tsdf_hessian (MatD33 36 floats + devDComplex3 12 floats), one per
+ * pair of se(3) generators (a, b), a <= b, in the order (0,0), (0,1), ..., (5,5): real part v2c (the same bits in all 21), eps1 = -h v2c G_a,
+ * eps2 = -h v2c G_b, eps1 eps2 = h^2 v2c (G_a G_b + G_b G_a) / 2.  Frame f's 29 sums land at out29xF_dev + 29 f:
+ *   [0, 21)  sum loss_ab.hessian(), row-major upper triangle (/ h^2: d2L / dtheta_a dtheta_b of L(inverse(se3Exp(theta) c2v)) at 0)
+ *   [21, 27) sum loss_aa.grad() (/ h: dL / dtheta_a)        [27] sum r^2 (pair (0,0))        [28] count
+ * with the per-voxel loss of xs_compute_local_tsdf_hessian.  A band voxel counts only if all 21 evaluations keep it.  The entries of the
+ * index are dealt out in chunks of 64 (not in the dense walk's segments), and the sums are folded in a fixed order: two launches on the same
+ * inputs give the same bits, and frame f's sums do not depend on `frames`, on f or on the other frames.
+ * Workspace: xs_tsdf_pose_hessian_workspace_bytes(frames) bytes (0 for frames outside 1 .. XS_BAND_MAX_FRAMES), the first 256 zeroed ONCE
+ * after allocation (xs_tsdf_reduce_workspace_init); every launch leaves them zero.  One launch at a time per workspace.  No synchronisation. */
+size_t xs_tsdf_pose_hessian_workspace_bytes(int frames);
+int xs_tsdf_pose_hessian_band(int frames, const float *const *depth_scaled, size_t scaled_step, int rows, int cols, const float *intr4,
+                              float voxel_size, const float *Rv2c36x21xF, const float *tv2c12x21xF, float tranc_dist, const xs_band_index *index,
+                              void *workspace, double *out29xF_dev, void *stream);
 
 /* ---- surface extraction (export; real-valued) ------------------------------------------------ */
 size_t xs_extract_workspace_bytes(const int *res);

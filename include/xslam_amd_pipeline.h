@@ -86,6 +86,24 @@ int xs_kf_relocalize(void *kf, const uint16_t *depth_dev, size_t step_bytes, flo
  * number of frames that succeeded (-1: bad arguments). */
 int xs_kf_relocalize_batch(void *kf, int frames, const uint16_t *const *depth_dev, size_t step_bytes, float *c2v32xF, int iterations, float damping,
                            double *loss_out, int *ok_out);
+/* The exact pose Hessian of the map-alignment loss L = sum r^2 and Newton relocalisation.  One launch of
+ * xs_tsdf_pose_hessian_band over the band index (built as for xs_kf_relocalize_batch) evaluates 21 dual-complex seeded poses per frame.
+ * pose_hessian_terms: out29 = H upper triangle (21, row-major: d2L / dtheta_a dtheta_b, already divided by h^2), g (6: dL / dtheta_a,
+ * divided by h), sum r^2, count — theta the twist of camera2volume <- se3Exp(theta) * camera2volume.  Returns 1, or 0 without a volume.
+ * relocalize_newton / relocalize_newton_batch: xs_kf_relocalize / xs_kf_relocalize_batch with the step (H + damping * diag H) delta = -g;
+ * where that system is not positive definite the frame takes the Gauss-Newton step for that iteration, and fallbacks_out (optional; one int
+ * per frame) counts those iterations.  Results per frame do not depend on the batch.  Loss history and return values as their counterparts'. */
+int xs_kf_pose_hessian_terms(void *kf, const uint16_t *depth_dev, size_t step_bytes, const float *c2v32, double *out29);
+int xs_kf_relocalize_newton(void *kf, const uint16_t *depth_dev, size_t step_bytes, float *c2v32, int iterations, float damping, double *loss_out,
+                            int *fallbacks_out);
+int xs_kf_relocalize_newton_batch(void *kf, int frames, const uint16_t *const *depth_dev, size_t step_bytes, float *c2v32xF, int iterations,
+                                  float damping, double *loss_out, int *ok_out, int *fallbacks_out);
+/* The host's side of a Newton pass.  CPU only.  seeded_poses: the 21 dual-complex volume-to-camera poses of camera2volume c2v32 (pair (a, b),
+ * a <= b, row-major; 36 + 12 floats each, the layout of xs_tsdf_pose_hessian_band); returns 0.  newton_step: s29 as pose_hessian_terms
+ * returns it; solves (H + damping * diag H) delta = -g by Cholesky and applies c2v32 <- se3Exp(delta) * c2v32.  Returns 0 when the step was
+ * taken, -1 (c2v32 untouched) when count < 6 or the system is not positive definite. */
+int xs_host_newton_seeded_poses(const float *c2v32, float *R36x21, float *t12x21);
+int xs_host_newton_step(const double *s29, double damping, float *c2v32);
 /* band voxels in the relocalisation index as last built (0 before the first batch) */
 long long xs_kf_relocalization_index_voxels(void *kf);
 /* ExportPointCloud(max_buffer)  .cpp:334-372 (+ CPointCloud::exportPly, main.cpp:78-80): zero-crossing points of

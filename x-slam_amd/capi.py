@@ -95,6 +95,9 @@ _SIGS = {
     "xs_tsdf_band_workspace_bytes": (_sz, [C.c_int]),
     "xs_tsdf_gauss_newton_terms_band": (C.c_int, [C.c_int, C.POINTER(_vp), _sz, C.c_int, C.c_int, _f32p, C.c_float, _f32p, _f32p, C.c_float,
                                                   C.POINTER(BandIndex), _vp, _vp, _vp]),
+    "xs_tsdf_pose_hessian_workspace_bytes": (_sz, [C.c_int]),
+    "xs_tsdf_pose_hessian_band": (C.c_int, [C.c_int, C.POINTER(_vp), _sz, C.c_int, C.c_int, _f32p, C.c_float, _f32p, _f32p, C.c_float,
+                                            C.POINTER(BandIndex), _vp, _vp, _vp]),
     "xs_tsdf_reduce_workspace_init": (C.c_int, [_vp, _vp]),
     "xs_compute_local_tsdf_hessian": (C.c_int, [_vp, _sz, C.c_int, C.c_int, _f32p, _i32p, C.c_float, _f32p, _f32p, C.c_float, _vp,
                                                 _vp, _vp, _vp, _vp, C.c_int, C.c_int, _vp, _vp, _vp]),
@@ -505,6 +508,21 @@ def tsdf_gauss_newton_terms_band(depths_scaled, scaled_step, rows, cols, intr, v
     P = (_vp * max(F, 1))(*[_ptr(d) for d in depths_scaled])
     check(_lib.xs_tsdf_gauss_newton_terms_band(F, P, scaled_step, rows, cols, k.ctypes.data_as(_f32p), voxel_size, R.ctypes.data_as(_f32p),
                                                t.ctypes.data_as(_f32p), tranc_dist, C.byref(index), _ptr(workspace), _ptr(out29xF), _stream(stream)))
+
+
+def tsdf_pose_hessian_workspace_bytes(frames):
+    return int(_lib.xs_tsdf_pose_hessian_workspace_bytes(int(frames)))
+
+
+def tsdf_pose_hessian_band(depths_scaled, scaled_step, rows, cols, intr, voxel_size, Rv2c21xF, tv2c21xF, tranc_dist, index, workspace, out29xF,
+                           stream=None):
+    """xs_tsdf_pose_hessian_band: F = len(depths_scaled) frames over a built index; Rv2c21xF [F, 21, 3, 3, 4], tv2c21xF [F, 21, 3, 4] (the
+    dual-complex poses of the generator pairs a <= b); frame f's 29 raw sums land at out29xF[29 f : 29 f + 29] (float64 device tensor)."""
+    F = len(depths_scaled)
+    k, R, t = _fa(intr, 4), _fa(Rv2c21xF, 21 * 36 * F), _fa(tv2c21xF, 21 * 12 * F)
+    P = (_vp * max(F, 1))(*[_ptr(d) for d in depths_scaled])
+    check(_lib.xs_tsdf_pose_hessian_band(F, P, scaled_step, rows, cols, k.ctypes.data_as(_f32p), voxel_size, R.ctypes.data_as(_f32p),
+                                         t.ctypes.data_as(_f32p), tranc_dist, C.byref(index), _ptr(workspace), _ptr(out29xF), _stream(stream)))
 
 
 class GnOpts(C.Structure):

@@ -12,6 +12,10 @@
 // Every double addition therefore meets the same operands in the same order as in the dense pass: a frame's 29 sums are bit-identical to
 // xs_tsdf_gauss_newton_terms' for its depth and poses, whatever the other frames of the launch are.  The frames go into workgroups, not
 // registers (the kernel keeps the dense kernel's 29 accumulators); the index is read F times, from the Infinity Cache after the first.
+//
+//   k_band_pose_hessian          the exact 6 x 6 pose Hessian of the same loss in one pass over the index: 21
+//                                dual-complex poses per frame, one per generator pair a <= b, each band voxel evaluated for all of them.
+//                                It has no dense twin to replay: the flat keys / values arrays are dealt out evenly in 64-entry chunks.
 #include <hip/hip_runtime.h>
 #include <string.h>
 #include <vector>
@@ -165,6 +169,126 @@ extern "C" int xs_tsdf_gauss_newton_terms_band(int frames, const float *const *d
     hipStream_t st = (hipStream_t)stream;
     XS_CHECK(hipMemcpyAsync(ws + BAND_POSES_OFFSET, P.data(), P.size() * sizeof(GnPoses), hipMemcpyHostToDevice, st));
     hipLaunchKernelGGL(k_band_gauss_newton, dim3((unsigned)index->nblocks, (unsigned)frames), dim3(64, 4), 0, st, g);
+    XS_CHECK(hipGetLastError());
+    return 0;
+}
+
+// ---- the exact pose Hessian over the index ------------------------------------------------------------------
+// Per query frame 21 dual-complex poses, pair (a, b), a <= b, row-major: real part v2c, eps1 along generator a, eps2 along b, eps1 eps2 the
+// second-order term of the pose's expansion (the host's newton_seeded_poses).  Every band voxel is evaluated for all 21 (tsdf_loss_d, the
+// per-voxel term of k_tsdf_hessian) and counts only if all 21 keep it, so one count serves every entry:
+//   out[0 .. 20]  sum loss_ab.hessian()      out[21 .. 26]  sum loss_aa.grad()      out[27]  sum loss_00.value()      out[28]  count
+// The pair loop is NOT unrolled (one copy of the dual-complex body); a lane parks a voxel's 28 terms in its own column of LDS until the
+// last pair has kept the voxel and then adds them to its 29 double accumulators.
+// Order: the entries are cut into chunks of 64; wave w of workgroup b takes chunks 4 b + w, + 4 nblocks, ... and lane l entry l of each —
+// a function of the index's count alone, so frame f's additions are the same whatever F, its slot or the other frames are; the fold is
+// block_fold_and_finish_of's (registers -> wave -> LDS -> one record per workgroup -> the frame's last workgroup adds the records in
+// index order), one ticket per frame.
+enum { NEWTON_PAIRS = 21, NEWTON_TERMS = 28, NEWTON_POSES_OFFSET = 256 };
+static size_t newton_records_offset() { return NEWTON_POSES_OFFSET + (size_t)XS_BAND_MAX_FRAMES * NEWTON_PAIRS * sizeof(HessPoseD); }
+static_assert(sizeof(HessPoseD) == 48 * sizeof(float), "36 + 12 floats per dual-complex pose");
+
+struct BandHessArgs {
+    HessArgs a;                                  // the residual's fields (depth: each workgroup takes its frame's)
+    const float *depth[XS_BAND_MAX_FRAMES];
+    const unsigned long long *keys;
+    const float *values;
+    long long count;                             // entries of keys / values
+    const HessPoseD *poses;                      // [F][21], in the workspace
+    double *records;                             // [F][nblocks][32]
+    unsigned *tickets;                           // [F], zero between launches
+    double *out;                                 // [F][29]
+};
+__global__ void __launch_bounds__(256) k_band_pose_hessian(const BandHessArgs g) {
+    __shared__ HessPoseD P[NEWTON_PAIRS];
+    __shared__ float s_term[NEWTON_TERMS][256];  // [term][thread]: a thread reads back only what it wrote itself
+    const int f = blockIdx.y, lane = threadIdx.x, wave = threadIdx.y, tid = wave * 64 + lane;
+    {
+        const float *src = reinterpret_cast<const float *>(g.poses + (size_t)f * NEWTON_PAIRS);
+        float *dst = reinterpret_cast<float *>(&P[0]);
+        for (int i = tid; i < (int)(NEWTON_PAIRS * sizeof(HessPoseD) / sizeof(float)); i += 256) dst[i] = src[i];
+        __syncthreads();
+    }
+    HessArgs a = g.a;
+    a.depth = g.depth[f];
+    double acc[29];
+#pragma unroll
+    for (int k = 0; k < 29; ++k) acc[k] = 0.0;
+    const long long nchunks = (g.count + 63) / 64;
+    for (long long c = (long long)blockIdx.x * 4 + wave; c < nchunks; c += 4ll * gridDim.x) {
+        const long long e = c * 64 + lane;
+        if (e >= g.count) continue;              // (the last chunk's tail)
+        const unsigned long long key = g.keys[e];
+        const int x = (int)(key & 0x1fffff), y = (int)((key >> 21) & 0x1fffff), z = (int)(key >> 42);
+        const float gt = g.values[e];
+        bool ok = true;
+        int pa = 0, pb = 0;
+#pragma unroll 1
+        for (int p = 0; p < NEWTON_PAIRS; ++p) {
+            dcfloat loss;
+            if (!tsdf_loss_d(a, P[p], x, y, z, gt, loss)) { ok = false; break; }
+            s_term[p][tid] = loss.hessian();
+            if (pa == pb) s_term[NEWTON_PAIRS + pa][tid] = loss.grad();
+            if (p == 0) s_term[27][tid] = loss.value();
+            if (++pb == 6) { ++pa; pb = pa; }
+        }
+        if (!ok) continue;
+#pragma unroll
+        for (int k = 0; k < NEWTON_TERMS; ++k) acc[k] += (double)s_term[k][tid];
+        acc[28] += 1.0;
+    }
+    block_fold_and_finish_of<29>(acc, g.records + (size_t)f * gridDim.x * BAND_RECORD_DOUBLES, g.tickets + f, g.out + 29 * f, nullptr, 0, false,
+                                 gridDim.x, blockIdx.x);
+}
+
+extern "C" size_t xs_tsdf_pose_hessian_workspace_bytes(int frames) {
+    if (frames < 1 || frames > XS_BAND_MAX_FRAMES) return 0;
+    return newton_records_offset() + (size_t)frames * XS_TSDF_REDUCE_MAX_BLOCKS_C * BAND_RECORD_DOUBLES * sizeof(double);
+}
+
+extern "C" int xs_tsdf_pose_hessian_band(int frames, const float *const *depth_scaled, size_t scaled_step, int rows, int cols, const float *intr4,
+                                         float voxel_size, const float *Rv2c36x21xF, const float *tv2c12x21xF, float tranc_dist,
+                                         const xs_band_index *index, void *workspace, double *out29xF_dev, void *stream) {
+    if (frames < 1 || frames > XS_BAND_MAX_FRAMES) return xs_set_error(hipErrorInvalidValue, "xs_tsdf_pose_hessian_band: frames outside 1 .. XS_BAND_MAX_FRAMES");
+    if (!depth_scaled || !intr4 || !Rv2c36x21xF || !tv2c12x21xF || !index || !workspace || !out29xF_dev)
+        return xs_set_error(hipErrorInvalidValue, "xs_tsdf_pose_hessian_band: null pointer");
+    if (index->nblocks < 1 || index->count < 0 || index->count > index->capacity || (index->count > 0 && (!index->keys || !index->values)))
+        return xs_set_error(hipErrorInvalidValue, "xs_tsdf_pose_hessian_band: the index was not built");
+    if (rows < 4 || cols < 4 || scaled_step < (size_t)cols * sizeof(float)) return xs_set_error(hipErrorInvalidValue, "xs_tsdf_pose_hessian_band: bad depth shape");
+    BandHessArgs g;
+    memset(&g, 0, sizeof(g));
+    for (int f = 0; f < frames; ++f) {
+        if (!depth_scaled[f]) return xs_set_error(hipErrorInvalidValue, "xs_tsdf_pose_hessian_band: null depth");
+        g.depth[f] = depth_scaled[f];
+    }
+    HessArgs &a = g.a;
+    a.depth = depth_scaled[0]; a.dstep = scaled_step; a.drows = rows; a.dcols = cols;
+    a.voxel_size = voxel_size; a.tranc_dist = tranc_dist; a.tranc_dist_inv = 1.0f / tranc_dist;
+    a.intr = Intr{intr4[0], intr4[1], intr4[2], intr4[3]};
+    a.X = index->res[0]; a.Y = index->res[1]; a.Z = index->res[2]; a.z0 = index->z0; a.z1 = index->z1;
+    std::vector<HessPoseD> P((size_t)frames * NEWTON_PAIRS);
+    for (size_t k = 0; k < P.size(); ++k) {
+        const float *p = Rv2c36x21xF + 36 * k, *t = tv2c12x21xF + 12 * k;
+        for (int r = 0; r < 3; ++r) {
+            P[k].R.data[r].x = dcfloat(p[12 * r + 0], p[12 * r + 1], p[12 * r + 2], p[12 * r + 3]);
+            P[k].R.data[r].y = dcfloat(p[12 * r + 4], p[12 * r + 5], p[12 * r + 6], p[12 * r + 7]);
+            P[k].R.data[r].z = dcfloat(p[12 * r + 8], p[12 * r + 9], p[12 * r + 10], p[12 * r + 11]);
+        }
+        P[k].t.x = dcfloat(t[0], t[1], t[2], t[3]);
+        P[k].t.y = dcfloat(t[4], t[5], t[6], t[7]);
+        P[k].t.z = dcfloat(t[8], t[9], t[10], t[11]);
+    }
+    // as many workgroups as give every wave a chunk, at most the record workspace's 4096: a function of the index alone
+    const long long nchunks = (index->count + 63) / 64, want = (nchunks + 3) / 4;
+    const unsigned nblocks = (unsigned)(want < 1 ? 1 : (want > XS_TSDF_REDUCE_MAX_BLOCKS_C ? XS_TSDF_REDUCE_MAX_BLOCKS_C : want));
+    char *ws = static_cast<char *>(workspace);
+    g.tickets = reinterpret_cast<unsigned *>(ws);
+    g.poses = reinterpret_cast<const HessPoseD *>(ws + NEWTON_POSES_OFFSET);
+    g.records = reinterpret_cast<double *>(ws + newton_records_offset());
+    g.keys = index->keys; g.values = index->values; g.count = index->count; g.out = out29xF_dev;
+    hipStream_t st = (hipStream_t)stream;
+    XS_CHECK(hipMemcpyAsync(ws + NEWTON_POSES_OFFSET, P.data(), P.size() * sizeof(HessPoseD), hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(k_band_pose_hessian, dim3(nblocks, (unsigned)frames), dim3(64, 4), 0, st, g);
     XS_CHECK(hipGetLastError());
     return 0;
 }

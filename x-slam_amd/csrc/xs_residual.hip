@@ -31,40 +31,8 @@ __global__ void __launch_bounds__(256) XS_HESS_OCC k_tsdf_hessian(const HessArgs
     __syncthreads();
     double acc[4] = {0.0, 0.0, 0.0, 0.0};
     walk_band(a, [&](int xq, int yq, int z, size_t index, float gt) {
-        const dcfloat gt_tsdf(gt);
-        const dcfloat vgx((float(xq) + 0.5f) * a.voxel_size);
-        const dcfloat vgy((float(yq) + 0.5f) * a.voxel_size);
-        const dcfloat vgz((float(z) + 0.5f) * a.voxel_size);
-        dcfloat3 v_g; v_g.x = vgx; v_g.y = vgy; v_g.z = vgz;
-        dcfloat3 v_c;
-        v_c.x = dot(P.R.data[0], v_g) + P.t.x;
-        v_c.y = dot(P.R.data[1], v_g) + P.t.y;
-        v_c.z = dot(P.R.data[2], v_g) + P.t.z;
-        const dcfloat inv_z = dcfloat(1.0f) / v_c.z;
-        if (inv_z.value() < 0) return;
-        const dcfloat image_x = v_c.x * inv_z * a.intr.fx + a.intr.cx;
-        const dcfloat image_y = v_c.y * inv_z * a.intr.fy + a.intr.cy;
-        const int coo_x = __float2int_rd(image_x.value() - 0.5f), coo_y = __float2int_rd(image_y.value() - 0.5f);
-        if (!(coo_x > 1 && coo_y > 1 && coo_x < a.dcols - 1 && coo_y < a.drows - 1)) return;
-        const int near_x = __float2int_rn(image_x.value()), near_y = __float2int_rn(image_y.value());
-        dcfloat Dp(row_ptr(a.depth, a.dstep, near_y)[near_x]);
-        const dcfloat d00(row_ptr(a.depth, a.dstep, coo_y)[coo_x]), d10(row_ptr(a.depth, a.dstep, coo_y)[coo_x + 1]);
-        const dcfloat d01(row_ptr(a.depth, a.dstep, coo_y + 1)[coo_x]), d11(row_ptr(a.depth, a.dstep, coo_y + 1)[coo_x + 1]);
-        if (d00.value() != 0.0f && d01.value() != 0.0f && d10.value() != 0.0f && d11.value() != 0.0f) {  // :248-251, threshold unused
-            const dcfloat one(1.0f);
-            const dcfloat fa = image_x - dcfloat(float(coo_x) + 0.5f);
-            const dcfloat fb = image_y - dcfloat(float(coo_y) + 0.5f);
-            Dp = d00 * (one - fa) * (one - fb) + d10 * fa * (one - fb) + d01 * (one - fa) * fb + d11 * fa * fb;
-        }
-        if (Dp.value() > 5 || Dp.value() < 0.2) return;
-        const dcfloat xl = (image_x - a.intr.cx) / a.intr.fx;
-        const dcfloat yl = (image_y - a.intr.cy) / a.intr.fy;
-        dcfloat3 v_c_1; v_c_1.x = Dp * xl; v_c_1.y = Dp * yl; v_c_1.z = Dp;
-        const dcfloat distance = norm(v_c_1) - norm(v_c);
-        const dcfloat gt_distance = gt_tsdf * a.tranc_dist;
-        const dcfloat error = (distance - gt_distance) * a.tranc_dist_inv;
-        if (fabsf(error.value()) > 1) return;
-        const dcfloat loss = error * error;
+        dcfloat loss;
+        if (!tsdf_loss_d(a, P, xq, yq, z, gt, loss)) return;   // (xs_gn_band.h: shared with k_band_pose_hessian)
         if (a.real_out) {
             a.real_out[index] = loss.value(); a.grad_out[index] = loss.grad();
             a.hess_out[index] = loss.hessian(); a.count_out[index] = 1;

@@ -3,6 +3,7 @@
 // launcher shim.  One stream, no per-frame allocation, synchronisation only where the host
 // needs a result (the 6x6 normal equations of each ICP iteration).
 #include "KinectFusionReconstruction.h"
+#include "newton_host.hpp"
 #include <chrono>
 #include <algorithm>
 #include <cmath>
@@ -1329,13 +1330,10 @@ void KinectFusionReconstruction::BandIndexPrepare() {
     band_generation_ = volume_generation;
 }
 
-int KinectFusionReconstruction::RelocalizeGaussNewtonBatch(const std::vector<DeviceArray2D<ushort>> &depths, Matrix4cf *camera2volume, int iterations,
-                                                           float damping, int *ok, std::vector<double> *loss_history) {
+// What the batched loops share: the band index, the Gauss-Newton band workspace and sums, and every frame's depth scaled once (not per
+// pass) into band_depth_.  Returns the scaled depths' common step.
+size_t KinectFusionReconstruction::BandBatchPrepare(const std::vector<DeviceArray2D<ushort>> &depths) {
     const int F = (int)depths.size();
-    for (int f = 0; f < F; ++f) ok[f] = 0;
-    if (!tsdf_volume_d_ptr || F == 0) return 0;
-    const int passes = iterations + (loss_history ? 1 : 0);
-    if (passes <= 0) { for (int f = 0; f < F; ++f) ok[f] = 1; return F; }
     hipStream_t st = current_stream();
     BandIndexPrepare();
     const size_t ws_bytes = xs_tsdf_band_workspace_bytes(XS_BAND_MAX_FRAMES);
@@ -1354,6 +1352,19 @@ int KinectFusionReconstruction::RelocalizeGaussNewtonBatch(const std::vector<Dev
     const size_t scaled_step = band_depth_[0].step();
     for (int f = 1; f < F; ++f)
         if (band_depth_[(size_t)f].step() != scaled_step) { std::cout << "error::KinectFusionReconstruction, batch: depth steps differ" << std::endl; exit(-1); }
+    return scaled_step;
+}
+
+int KinectFusionReconstruction::RelocalizeGaussNewtonBatch(const std::vector<DeviceArray2D<ushort>> &depths, Matrix4cf *camera2volume, int iterations,
+                                                           float damping, int *ok, std::vector<double> *loss_history) {
+    const int F = (int)depths.size();
+    for (int f = 0; f < F; ++f) ok[f] = 0;
+    if (!tsdf_volume_d_ptr || F == 0) return 0;
+    const int passes = iterations + (loss_history ? 1 : 0);
+    if (passes <= 0) { for (int f = 0; f < F; ++f) ok[f] = 1; return F; }
+    hipStream_t st = current_stream();
+    const int rows = depths[0].rows(), cols = depths[0].cols();
+    const size_t scaled_step = BandBatchPrepare(depths);
     const bool sharded = shard_count > 1 && collective;
     std::vector<int> active(F);
     for (int f = 0; f < F; ++f) active[(size_t)f] = f;
@@ -1387,6 +1398,97 @@ int KinectFusionReconstruction::RelocalizeGaussNewtonBatch(const std::vector<Dev
         }
         active.swap(next);
     }
+    for (int f = 0; f < F; ++f) succeeded += ok[f];
+    return succeeded;
+}
+
+
+// ---- exact-Hessian (Newton) relocalisation over the band index ----
+// One launch of xs_tsdf_pose_hessian_band for the n frames `frames` of the prepared batch (band_depth_), at most XS_BAND_MAX_FRAMES: the
+// seeded poses, in shard mode the all-reduce of the n x 29 sums, the copy and the stream drain; raw: the kernel's sums.
+void KinectFusionReconstruction::PoseHessianLaunch(const int *frames, int n, const Matrix4cf *camera2volume, size_t scaled_step, int rows, int cols, double *raw) {
+    hipStream_t st = current_stream();
+    const size_t ws_bytes = xs_tsdf_pose_hessian_workspace_bytes(XS_BAND_MAX_FRAMES);
+    if (newton_ws_.size() < ws_bytes) {
+        newton_ws_.create(ws_bytes);
+        check_rc(xs_tsdf_reduce_workspace_init(newton_ws_.ptr(), st), "pose Hessian workspace");   // (zeroes the tickets: once)
+    }
+    if (newton_sums_.size() < (size_t)XS_BAND_MAX_FRAMES * 29) newton_sums_.create((size_t)XS_BAND_MAX_FRAMES * 29);
+    std::vector<float> R((size_t)n * 21 * 36), t((size_t)n * 21 * 12);
+    std::vector<const float *> dptr((size_t)n);
+    for (int i = 0; i < n; ++i) {
+        newton_seeded_poses(camera2volume[frames[i]], reinterpret_cast<float (*)[36]>(&R[(size_t)i * 21 * 36]), reinterpret_cast<float (*)[12]>(&t[(size_t)i * 21 * 12]));
+        dptr[(size_t)i] = band_depth_[(size_t)frames[i]].ptr();
+    }
+    check_rc(xs_tsdf_pose_hessian_band(n, dptr.data(), scaled_step, rows, cols, &kinect_intrinsic.fx, voxel_size, R.data(), t.data(),
+                                       tsdf_volume_d_ptr->getTsdfTruncDist(), &band_, newton_ws_.ptr(), newton_sums_.ptr(), st), "PoseHessianBand");
+    if (shard_count > 1 && collective) collective(collective_user, 0, newton_sums_.ptr(), (long)n * 29);
+    hipSafeCall(hipMemcpyAsync(raw, newton_sums_.ptr(), (size_t)n * 29 * sizeof(double), hipMemcpyDeviceToHost, st));
+    hipSafeCall(hipStreamSynchronize(st));
+}
+
+int KinectFusionReconstruction::PoseHessianTerms(const DeviceArray2D<ushort> &depth_frame_d, const Matrix4cf &camera2volume, double out29[29]) {
+    if (!tsdf_volume_d_ptr) return 0;
+    const std::vector<DeviceArray2D<ushort>> depths(1, depth_frame_d);
+    const size_t scaled_step = BandBatchPrepare(depths);
+    const int frame = 0;
+    double raw[29];
+    PoseHessianLaunch(&frame, 1, &camera2volume, scaled_step, depth_frame_d.rows(), depth_frame_d.cols(), raw);
+    newton_scale_sums(raw, out29);
+    return 1;
+}
+
+// RelocalizeGaussNewtonBatch's loop with the Newton step: a pass is one pose-Hessian launch per chunk of the frames still active; a frame
+// whose damped Hessian is not positive definite takes, for that iteration, the Gauss-Newton step of gn_loop_step on the six-pose band sums of
+// its pose (one more launch, F = 1), and fallbacks[f] counts it.
+int KinectFusionReconstruction::RelocalizeNewtonBatch(const std::vector<DeviceArray2D<ushort>> &depths, Matrix4cf *camera2volume, int iterations,
+                                                      float damping, int *ok, std::vector<double> *loss_history, int *fallbacks) {
+    const int F = (int)depths.size();
+    for (int f = 0; f < F; ++f) { ok[f] = 0; if (fallbacks) fallbacks[f] = 0; }
+    if (!tsdf_volume_d_ptr || F == 0) return 0;
+    const int passes = iterations + (loss_history ? 1 : 0);
+    if (passes <= 0) { for (int f = 0; f < F; ++f) ok[f] = 1; return F; }
+    hipStream_t st = current_stream();
+    const int rows = depths[0].rows(), cols = depths[0].cols();
+    const size_t scaled_step = BandBatchPrepare(depths);
+    const bool sharded = shard_count > 1 && collective;
+    std::vector<int> active(F);
+    for (int f = 0; f < F; ++f) active[(size_t)f] = f;
+    std::vector<double> raw((size_t)XS_BAND_MAX_FRAMES * 29);
+    for (int p = 0; p < passes && !active.empty(); ++p) {
+        std::vector<int> next;
+        for (size_t c0 = 0; c0 < active.size(); c0 += XS_BAND_MAX_FRAMES) {   // one launch per chunk of the frames still active
+            const int n = (int)std::min(active.size() - c0, (size_t)XS_BAND_MAX_FRAMES);
+            PoseHessianLaunch(&active[c0], n, camera2volume, scaled_step, rows, cols, raw.data());
+            for (int i = 0; i < n; ++i) {
+                const int f = active[c0 + (size_t)i];
+                double s[29];
+                newton_scale_sums(&raw[(size_t)i * 29], s);
+                if (loss_history) loss_history[f].push_back(s[28] > 0 ? s[27] / s[28] : 0.0);
+                if (p == iterations) { ok[f] = 1; continue; }   // the final loss pass
+                if (s[28] < 6) continue;                        // nothing to align to: the frame fails
+                if (!newton_step(s, (double)damping, camera2volume[f])) {
+                    // not positive definite: this iteration's step is Gauss-Newton's, from the six-pose sums at the same pose
+                    float R6[6][18], t6[6][6];
+                    gn_seeded_poses(camera2volume[f], R6, t6);
+                    const float *d = band_depth_[(size_t)f].ptr();
+                    check_rc(xs_tsdf_gauss_newton_terms_band(1, &d, scaled_step, rows, cols, &kinect_intrinsic.fx, voxel_size, &R6[0][0], &t6[0][0],
+                                                             tsdf_volume_d_ptr->getTsdfTruncDist(), &band_, band_ws_.ptr(), band_sums_.ptr(), st), "GaussNewtonTermsBand");
+                    if (sharded) collective(collective_user, 0, band_sums_.ptr(), 29);
+                    double gn_raw[29], gn[29];
+                    hipSafeCall(hipMemcpyAsync(gn_raw, band_sums_.ptr(), 29 * sizeof(double), hipMemcpyDeviceToHost, st));
+                    hipSafeCall(hipStreamSynchronize(st));
+                    gn_scale_sums(gn_raw, gn);
+                    if (fallbacks) ++fallbacks[f];
+                    if (gn_loop_step(gn, p, iterations, damping, camera2volume[f], nullptr) != 0) continue;   // that failed too
+                }
+                if (p + 1 == passes) ok[f] = 1;   // (no loss pass: the last step ends the loop)
+                else next.push_back(f);
+            }
+        }
+        active.swap(next);
+    }
+    int succeeded = 0;
     for (int f = 0; f < F; ++f) succeeded += ok[f];
     return succeeded;
 }

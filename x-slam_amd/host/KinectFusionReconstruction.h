@@ -209,6 +209,14 @@ public:
     // loss_history: null, or F vectors (each gets the losses RelocalizeGaussNewton would give it).  Returns the number of frames that succeeded.
     int RelocalizeGaussNewtonBatch(const std::vector<DeviceArray2D<ushort>> &depths, Matrix4cf *camera2volume, int iterations, float damping,
                                    int *ok, std::vector<double> *loss_history = nullptr);
+    // The exact pose Hessian and Newton relocalisation: one launch of xs_tsdf_pose_hessian_band over the band index gives,
+    // per frame, the 6 x 6 Hessian and the gradient of L = sum r^2 in the twist of camera2volume <- se3Exp(theta) * camera2volume (21 dual-complex
+    // seeded poses, newton_host.hpp).  PoseHessianTerms fills {H upper triangle (21), g (6), sum r^2, count}, divided by h^2 / h.  The loops are
+    // RelocalizeGaussNewtonBatch's with the step (H + damping diag H) delta = -g; a frame whose damped Hessian is not positive definite takes the
+    // Gauss-Newton step for that iteration (fallbacks[f] counts them).  No posted poses: copy + stream drain per pass.  Sharded: the sums are all-reduced.
+    int PoseHessianTerms(const DeviceArray2D<ushort> &depth_frame_d, const Matrix4cf &camera2volume, double out29[29]);
+    int RelocalizeNewtonBatch(const std::vector<DeviceArray2D<ushort>> &depths, Matrix4cf *camera2volume, int iterations, float damping, int *ok,
+                              std::vector<double> *loss_history = nullptr, int *fallbacks = nullptr);
     long long RelocalizationIndexVoxels() const { return band_generation_ >= 0 ? band_.count : 0; }   // the index as last built, 0 before any
     // bumped by everything that writes the volume: integrate calls, loadCheckpoint, xs_kf_volume_ptr(kf, 0, .), RebuildSignMap (the band index is rebuilt
     // when its generation differs)
@@ -276,6 +284,10 @@ private:
     DeviceArray<unsigned char> gn_ws_;         // reduce workspace of the Gauss-Newton / Hessian kernels
     const float *GaussNewtonDenseView();       // the owned planes as the dense array the Gauss-Newton kernels index (packed into gn_dense_ when pitched)
     void BandIndexPrepare();                   // (re)builds band_ when the volume changed since it was built
+    size_t BandBatchPrepare(const std::vector<DeviceArray2D<ushort>> &depths);   // index, workspace and scaled depths of a batch
+    void PoseHessianLaunch(const int *frames, int n, const Matrix4cf *camera2volume, size_t scaled_step, int rows, int cols, double *raw);
+    DeviceArray<unsigned char> newton_ws_;     // xs_tsdf_pose_hessian_workspace_bytes(XS_BAND_MAX_FRAMES), tickets zeroed once
+    DeviceArray<double> newton_sums_;          // XS_BAND_MAX_FRAMES x 29
     xs_band_index band_ = {};                  // band index of the owned planes (RelocalizeGaussNewtonBatch)
     long long band_generation_ = -1;           // the volume_generation it was built at
     DeviceArray<unsigned long long> band_keys_;

@@ -3,6 +3,7 @@
 #include "../csrc/xs_complex.h"
 #include "DoubleComplex.h"
 #include "KinectFusionReconstruction.h"
+#include "newton_host.hpp"
 #include <cstring>
 #include <exception>
 #include <memory>
@@ -187,6 +188,52 @@ int xs_kf_relocalize_batch(void *kf, int frames, const uint16_t *const *depth_de
             for (size_t i = 0; i < hist[(size_t)f].size() && i <= (size_t)iterations; ++i) loss_out[(size_t)f * (iterations + 1) + i] = hist[(size_t)f][i];
     }
     return n;
+}
+int xs_host_newton_seeded_poses(const float *c2v32, float *R36x21, float *t12x21) {
+    if (!c2v32 || !R36x21 || !t12x21) return -1;
+    Matrix4cf m;
+    std::memcpy(static_cast<void *>(&m), c2v32, 32 * sizeof(float));
+    xs_host::newton_seeded_poses(m, reinterpret_cast<float (*)[36]>(R36x21), reinterpret_cast<float (*)[12]>(t12x21));
+    return 0;
+}
+int xs_host_newton_step(const double *s29, double damping, float *c2v32) {
+    if (!s29 || !c2v32) return -1;
+    Matrix4cf m;
+    std::memcpy(static_cast<void *>(&m), c2v32, 32 * sizeof(float));
+    if (!xs_host::newton_step(s29, damping, m)) return -1;
+    std::memcpy(c2v32, &m, 32 * sizeof(float));
+    return 0;
+}
+int xs_kf_pose_hessian_terms(void *kf, const uint16_t *depth_dev, size_t step_bytes, const float *c2v32, double *out29) {
+    KF *k = (KF *)kf;
+    Matrix4cf m;
+    std::memcpy(static_cast<void *>(&m), c2v32, 32 * sizeof(float));
+    return k->PoseHessianTerms(wrap_depth(k, depth_dev, step_bytes), m, out29);
+}
+int xs_kf_relocalize_newton_batch(void *kf, int frames, const uint16_t *const *depth_dev, size_t step_bytes, float *c2v32xF, int iterations, float damping,
+                                  double *loss_out, int *ok_out, int *fallbacks_out) {
+    KF *k = (KF *)kf;
+    if (frames < 0 || (frames > 0 && (!depth_dev || !c2v32xF || !ok_out))) return -1;
+    std::vector<DeviceArray2D<ushort>> depths;
+    std::vector<Matrix4cf> m((size_t)frames);
+    for (int f = 0; f < frames; ++f) {
+        depths.push_back(wrap_depth(k, depth_dev[f], step_bytes));
+        std::memcpy(static_cast<void *>(&m[(size_t)f]), c2v32xF + 32 * (size_t)f, 32 * sizeof(float));
+    }
+    std::vector<std::vector<double>> hist(loss_out ? (size_t)frames : 0);
+    const int n = k->RelocalizeNewtonBatch(depths, m.data(), iterations, damping, ok_out, loss_out ? hist.data() : nullptr, fallbacks_out);
+    for (int f = 0; f < frames; ++f) {
+        std::memcpy(c2v32xF + 32 * (size_t)f, &m[(size_t)f], 32 * sizeof(float));
+        if (loss_out)
+            for (size_t i = 0; i < hist[(size_t)f].size() && i <= (size_t)iterations; ++i) loss_out[(size_t)f * (iterations + 1) + i] = hist[(size_t)f][i];
+    }
+    return n;
+}
+int xs_kf_relocalize_newton(void *kf, const uint16_t *depth_dev, size_t step_bytes, float *c2v32, int iterations, float damping, double *loss_out,
+                            int *fallbacks_out) {
+    int ok = 0;
+    const int n = xs_kf_relocalize_newton_batch(kf, 1, &depth_dev, step_bytes, c2v32, iterations, damping, loss_out, &ok, fallbacks_out);
+    return n < 0 ? n : ok;
 }
 long long xs_kf_relocalization_index_voxels(void *kf) { return ((KF *)kf)->RelocalizationIndexVoxels(); }
 long long xs_kf_export_point_cloud(void *kf, int max_buffer, float *points_host, float *normals_host) {

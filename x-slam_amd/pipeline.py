@@ -37,6 +37,11 @@ _SIGS = {
     "xs_kf_gauss_newton_terms": (C.c_int, [_vp, _vp, _sz, _f32p, _f64p]),
     "xs_kf_relocalize": (C.c_int, [_vp, _vp, _sz, _f32p, C.c_int, C.c_float, _f64p]),
     "xs_kf_relocalize_batch": (C.c_int, [_vp, C.c_int, C.POINTER(_vp), _sz, _f32p, C.c_int, C.c_float, _f64p, _i32p]),
+    "xs_kf_pose_hessian_terms": (C.c_int, [_vp, _vp, _sz, _f32p, _f64p]),
+    "xs_kf_relocalize_newton": (C.c_int, [_vp, _vp, _sz, _f32p, C.c_int, C.c_float, _f64p, _i32p]),
+    "xs_kf_relocalize_newton_batch": (C.c_int, [_vp, C.c_int, C.POINTER(_vp), _sz, _f32p, C.c_int, C.c_float, _f64p, _i32p, _i32p]),
+    "xs_host_newton_seeded_poses": (C.c_int, [_f32p, _f32p, _f32p]),
+    "xs_host_newton_step": (C.c_int, [_f64p, C.c_double, _f32p]),
     "xs_kf_relocalization_index_voxels": (C.c_longlong, [_vp]),
     "xs_kf_export_point_cloud": (C.c_longlong, [_vp, C.c_int, _f32p, _f32p]),
     "xs_kf_export_ply": (C.c_longlong, [_vp, C.c_int, C.c_char_p]),
@@ -131,6 +136,24 @@ def host_complex(op_code, a, b=None):
     return out
 
 
+def host_newton_seeded_poses(c2v):
+    """The 21 dual-complex seeded poses of a Newton pass for camera2volume c2v [4, 4, 2]: (R [21, 3, 3, 4], t [21, 3, 4]) float32, pair
+    (a, b), a <= b, row-major (CPU; no GPU involved)."""
+    m = np.ascontiguousarray(c2v, dtype=np.float32).reshape(32)
+    R, t = np.zeros((21, 3, 3, 4), np.float32), np.zeros((21, 3, 4), np.float32)
+    _lib.xs_host_newton_seeded_poses(m.ctypes.data_as(_f32p), R.ctypes.data_as(_f32p), t.ctypes.data_as(_f32p))
+    return R, t
+
+
+def host_newton_step(s29, damping, c2v):
+    """One Newton step on the 29 scaled sums of pose_hessian: (taken, c2v [4, 4, 2]); not taken (c2v unchanged) when count < 6 or
+    H + damping diag(H) is not positive definite (CPU)."""
+    s = np.ascontiguousarray(s29, dtype=np.float64).reshape(29)
+    m = np.ascontiguousarray(c2v, dtype=np.float32).reshape(32).copy()
+    rc = _lib.xs_host_newton_step(s.ctypes.data_as(_f64p), float(damping), m.ctypes.data_as(_f32p))
+    return rc == 0, m.reshape(4, 4, 2)
+
+
 def flat_yaml_get(text, key):
     buf = C.create_string_buffer(1024)
     n = _lib.xs_flat_yaml_get(text.encode(), key.encode(), buf, 1024)
@@ -208,22 +231,58 @@ class KinectFusion:
         ok = _lib.xs_kf_gauss_newton_terms(self.h, depth_dev.data_ptr(), self.width * 2, m.ctypes.data_as(_f32p), out.ctypes.data_as(_f64p))
         return out if ok == 1 else None
 
-    def relocalize(self, depth_dev, c2v, iterations=5, damping=1e-3):
-        """Gauss-Newton refinement of camera2volume against the map: (ok, refined c2v [4, 4, 2], loss history)."""
+    def pose_hessian_terms(self, depth_dev, c2v):
+        """29 doubles: H upper triangle (21), g (6), sum r^2, count — the exact Hessian and the gradient of L = sum r^2 in the twist of
+        c2v <- se3Exp(theta) c2v, from one launch over the map's band index."""
+        m = np.ascontiguousarray(c2v, dtype=np.float32).reshape(32)
+        out = np.zeros(29, np.float64)
+        ok = _lib.xs_kf_pose_hessian_terms(self.h, depth_dev.data_ptr(), self.width * 2, m.ctypes.data_as(_f32p), out.ctypes.data_as(_f64p))
+        return out if ok == 1 else None
+
+    def pose_hessian(self, depth_dev, c2v):
+        """(H [6, 6] symmetric, g [6], sum r^2, count) of pose_hessian_terms."""
+        s = self.pose_hessian_terms(depth_dev, c2v)
+        if s is None:
+            return None
+        H = np.zeros((6, 6))
+        H[np.triu_indices(6)] = s[:21]
+        H = H + np.triu(H, 1).T
+        return H, s[21:27].copy(), float(s[27]), int(s[28])
+
+    def relocalize(self, depth_dev, c2v, iterations=5, damping=1e-3, method="gauss_newton"):
+        """Refinement of camera2volume against the map: (ok, refined c2v [4, 4, 2], loss history).  method "gauss_newton" (first-order
+        seeds) or "newton" (the exact Hessian; the return then gains the number of iterations that fell back to Gauss-Newton)."""
         m = np.ascontiguousarray(c2v, dtype=np.float32).reshape(32).copy()
         hist = np.zeros(iterations + 1, np.float64)
+        if method == "newton":
+            fb = C.c_int(0)
+            ok = _lib.xs_kf_relocalize_newton(self.h, depth_dev.data_ptr(), self.width * 2, m.ctypes.data_as(_f32p), iterations, damping,
+                                              hist.ctypes.data_as(_f64p), C.cast(C.byref(fb), _i32p))
+            return ok == 1, m.reshape(4, 4, 2), hist, int(fb.value)
+        if method != "gauss_newton":
+            raise ValueError(f"relocalize: unknown method {method!r}")
         ok = _lib.xs_kf_relocalize(self.h, depth_dev.data_ptr(), self.width * 2, m.ctypes.data_as(_f32p), iterations, damping,
                                    hist.ctypes.data_as(_f64p))
         return ok == 1, m.reshape(4, 4, 2), hist
 
-    def relocalize_batch(self, depths, c2vs, iterations=5, damping=1e-3):
+    def relocalize_batch(self, depths, c2vs, iterations=5, damping=1e-3, method="gauss_newton"):
         """relocalize for F depth frames at once over the map's band index: (ok [F] bool, refined c2v [F, 4, 4, 2], loss histories
-        [F, iterations + 1]).  Frame f's results equal relocalize(depths[f], c2vs[f], ...) bit for bit."""
+        [F, iterations + 1]; with method "newton" also the fallback counts [F]).  Frame f's results equal
+        relocalize(depths[f], c2vs[f], ..., method=method) bit for bit."""
         F = len(depths)
         m = np.ascontiguousarray(c2vs, dtype=np.float32).reshape(F * 32).copy()
         hist = np.zeros((F, iterations + 1), np.float64)
         ok = np.zeros(F, np.int32)
         P = (_vp * max(F, 1))(*[d if isinstance(d, int) else d.data_ptr() for d in depths])
+        if method == "newton":
+            fb = np.zeros(max(F, 1), np.int32)
+            n = _lib.xs_kf_relocalize_newton_batch(self.h, F, P, self.width * 2, m.ctypes.data_as(_f32p), iterations, damping,
+                                                   hist.ctypes.data_as(_f64p), ok.ctypes.data_as(_i32p), fb.ctypes.data_as(_i32p))
+            if n < 0:
+                raise ValueError("xs_kf_relocalize_newton_batch: bad arguments")
+            return ok == 1, m.reshape(F, 4, 4, 2), hist, fb[:F]
+        if method != "gauss_newton":
+            raise ValueError(f"relocalize_batch: unknown method {method!r}")
         n = _lib.xs_kf_relocalize_batch(self.h, F, P, self.width * 2, m.ctypes.data_as(_f32p), iterations, damping, hist.ctypes.data_as(_f64p),
                                         ok.ctypes.data_as(_i32p))
         if n < 0:
