@@ -412,6 +412,23 @@ size_t xs_tsdf_pose_hessian_workspace_bytes(int frames);
 int xs_tsdf_pose_hessian_band(int frames, const float *const *depth_scaled, size_t scaled_step, int rows, int cols, const float *intr4,
                               float voxel_size, const float *Rv2c36x21xF, const float *tv2c12x21xF, float tranc_dist, const xs_band_index *index,
                               void *workspace, double *out29xF_dev, void *stream);
+/* ---- the real-valued alignment loss of one depth frame at many poses in one pass over the index ----
+ * `poses` (1 .. XS_SCORE_MAX_POSES) real volume-to-camera poses, host arrays Rv2c9xP + 9 p / tv2c3xP + 3 p in the layout of
+ * xs_compute_local_tsdf_loss.  Pose p's two doubles land at out2xP_dev + 2 p: {sum loss, count}, the shape of that kernel's out2.  A band
+ * voxel's float loss and its keep / drop decision are those of xs_compute_local_tsdf_loss, so pose p's count EQUALS the count that call
+ * returns for the pose on the dense gt the index was built from, and its sum adds the same float terms: each 64-entry chunk of the index in a
+ * six-level pairwise float tree across the wave, everything after that in double — |sum - dense sum| <= 8 * 2^-24 * dense sum.  The order is a
+ * function of the index's count alone: two launches on the same inputs give the same bits, and pose p's two numbers do not depend on
+ * `poses`, on p or on the other poses.  No floating-point atomics.  An index with count 0 yields zeros.
+ * Workspace: xs_tsdf_score_poses_workspace_bytes(poses) bytes (0 for poses outside 1 .. XS_SCORE_MAX_POSES): one arrival ticket per tile of
+ * 64 poses in its first 256 bytes, the poses, the records.  Zero the first 256 bytes ONCE after allocation (xs_tsdf_reduce_workspace_init);
+ * every launch leaves each ticket at zero again.  One launch at a time per workspace; after a launch that did not complete (a device
+ * fault), zero them again.  No synchronisation. */
+#define XS_SCORE_MAX_POSES 4096
+size_t xs_tsdf_score_poses_workspace_bytes(int poses);
+int xs_tsdf_score_poses_band(int poses, const float *depth_scaled, size_t scaled_step, int rows, int cols, const float *intr4,
+                             float voxel_size, const float *Rv2c9xP, const float *tv2c3xP, float tranc_dist,
+                             const xs_band_index *index, void *workspace, double *out2xP_dev, void *stream);
 
 /* ---- surface extraction (export; real-valued) ------------------------------------------------ */
 size_t xs_extract_workspace_bytes(const int *res);

@@ -104,6 +104,19 @@ int xs_kf_relocalize_newton_batch(void *kf, int frames, const uint16_t *const *d
  * taken, -1 (c2v32 untouched) when count < 6 or the system is not positive definite. */
 int xs_host_newton_seeded_poses(const float *c2v32, float *R36x21, float *t12x21);
 int xs_host_newton_step(const double *s29, double damping, float *c2v32);
+/* Global relocalisation: the camera is lost and there are pose hypotheses.
+ * score_poses: the real-valued alignment loss of one depth frame at `poses` camera2volume hypotheses c2v32xP + 32 p, in one launch of
+ * xs_tsdf_score_poses_band over the band index (built as for xs_kf_relocalize_batch) per chunk of XS_SCORE_MAX_POSES; out2xP + 2 p =
+ * {sum loss, count} at the real part of inverse(c2v) — what xs_compute_local_tsdf_loss gives for that pose on the dense map: the count
+ * exactly, the sum within 8 * 2^-24 of it.  In shard mode the sums are all-reduced.  Returns 1, 0 without a volume, -1 on bad arguments.
+ * relocalize_global: scores the candidates, keeps the min(keep, poses) with the highest truncated-quadratic inlier score S = count - sum loss
+ * (ties: the lower index), refines them with xs_kf_relocalize_batch's loop (`iterations`, `damping`, the same depth in every slot), scores
+ * the refined poses and writes to best_c2v32 the one with the highest S among those whose loop ended ok.  report8 = {the winner's candidate
+ * index, its S before refinement, its S after, sum loss after, count after, how many of the kept ended ok, band voxels in the index, 0}.
+ * Returns 1; 0 when none of the kept ended ok (best_c2v32 untouched, report8[0] = -1); -1 on bad arguments. */
+int xs_kf_score_poses(void *kf, const uint16_t *depth_dev, size_t step_bytes, int poses, const float *c2v32xP, double *out2xP);
+int xs_kf_relocalize_global(void *kf, const uint16_t *depth_dev, size_t step_bytes, int poses, const float *c2v32xP, int keep, int iterations,
+                            float damping, float *best_c2v32, double *report8);
 /* band voxels in the relocalisation index as last built (0 before the first batch) */
 long long xs_kf_relocalization_index_voxels(void *kf);
 /* ExportPointCloud(max_buffer)  .cpp:334-372 (+ CPointCloud::exportPly, main.cpp:78-80): zero-crossing points of

@@ -98,6 +98,9 @@ _SIGS = {
     "xs_tsdf_pose_hessian_workspace_bytes": (_sz, [C.c_int]),
     "xs_tsdf_pose_hessian_band": (C.c_int, [C.c_int, C.POINTER(_vp), _sz, C.c_int, C.c_int, _f32p, C.c_float, _f32p, _f32p, C.c_float,
                                             C.POINTER(BandIndex), _vp, _vp, _vp]),
+    "xs_tsdf_score_poses_workspace_bytes": (_sz, [C.c_int]),
+    "xs_tsdf_score_poses_band": (C.c_int, [C.c_int, _vp, _sz, C.c_int, C.c_int, _f32p, C.c_float, _f32p, _f32p, C.c_float, C.POINTER(BandIndex), _vp,
+                                           _vp, _vp]),
     "xs_tsdf_reduce_workspace_init": (C.c_int, [_vp, _vp]),
     "xs_compute_local_tsdf_hessian": (C.c_int, [_vp, _sz, C.c_int, C.c_int, _f32p, _i32p, C.c_float, _f32p, _f32p, C.c_float, _vp,
                                                 _vp, _vp, _vp, _vp, C.c_int, C.c_int, _vp, _vp, _vp]),
@@ -523,6 +526,23 @@ def tsdf_pose_hessian_band(depths_scaled, scaled_step, rows, cols, intr, voxel_s
     P = (_vp * max(F, 1))(*[_ptr(d) for d in depths_scaled])
     check(_lib.xs_tsdf_pose_hessian_band(F, P, scaled_step, rows, cols, k.ctypes.data_as(_f32p), voxel_size, R.ctypes.data_as(_f32p),
                                          t.ctypes.data_as(_f32p), tranc_dist, C.byref(index), _ptr(workspace), _ptr(out29xF), _stream(stream)))
+
+
+SCORE_MAX_POSES = 4096   # XS_SCORE_MAX_POSES
+
+
+def tsdf_score_poses_workspace_bytes(poses):
+    return int(_lib.xs_tsdf_score_poses_workspace_bytes(int(poses)))
+
+
+def tsdf_score_poses_band(depth_scaled, scaled_step, rows, cols, intr, voxel_size, Rv2cxP, tv2cxP, tranc_dist, index, workspace, out2xP, stream=None):
+    """xs_tsdf_score_poses_band: one depth frame at P real poses over a built index; Rv2cxP [P, 3, 3], tv2cxP [P, 3]; pose p's {sum loss,
+    count} land at out2xP[2 p : 2 p + 2] (float64 device tensor)."""
+    R = np.ascontiguousarray(Rv2cxP, dtype=np.float32).reshape(-1)
+    P = R.size // 9
+    k, R, t = _fa(intr, 4), _fa(R, 9 * P), _fa(tv2cxP, 3 * P)
+    check(_lib.xs_tsdf_score_poses_band(P, _ptr(depth_scaled), scaled_step, rows, cols, k.ctypes.data_as(_f32p), voxel_size, R.ctypes.data_as(_f32p),
+                                        t.ctypes.data_as(_f32p), tranc_dist, C.byref(index), _ptr(workspace), _ptr(out2xP), _stream(stream)))
 
 
 class GnOpts(C.Structure):

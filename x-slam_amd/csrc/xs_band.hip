@@ -16,8 +16,13 @@
 //   k_band_pose_hessian          the exact 6 x 6 pose Hessian of the same loss in one pass over the index: 21
 //                                dual-complex poses per frame, one per generator pair a <= b, each band voxel evaluated for all of them.
 //                                It has no dense twin to replay: the flat keys / values arrays are dealt out evenly in 64-entry chunks.
+//
+//   k_band_score_poses           the real-valued loss of ONE depth frame at up to 4096 poses in one pass over the index (DESIGN.md section
+//                                4.17): lane = band voxel, the poses in tiles of 64 looped over per chunk, each pose's sum and count kept by
+//                                lane (p mod 64) of the wave.  The first question of a relocaliser: which of these hypotheses sees this map?
 #include <hip/hip_runtime.h>
 #include <string.h>
+#include <type_traits>
 #include <vector>
 #include "xs_gn_band.h"
 #include "../../include/xslam_amd.h"
@@ -289,6 +294,167 @@ extern "C" int xs_tsdf_pose_hessian_band(int frames, const float *const *depth_s
     hipStream_t st = (hipStream_t)stream;
     XS_CHECK(hipMemcpyAsync(ws + NEWTON_POSES_OFFSET, P.data(), P.size() * sizeof(HessPoseD), hipMemcpyHostToDevice, st));
     hipLaunchKernelGGL(k_band_pose_hessian, dim3(nblocks, (unsigned)frames), dim3(64, 4), 0, st, g);
+    XS_CHECK(hipGetLastError());
+    return 0;
+}
+
+// ---- many poses, one frame: the alignment loss of every pose hypothesis in one pass over the index -----------
+// The entries are cut into chunks of 64 as for k_band_pose_hessian: wave w of workgroup (b, tile) takes chunks 4 b + w, + 4 nblocks, ...;
+// lane l decodes entry l of the chunk once and then meets the tile's poses 64 tile .. 64 tile + 63 one after the other.  The pose index is
+// wave-uniform (a loop counter through readfirstlane): the twelve floats of a pose arrive by scalar loads and stay in scalar registers.  Per
+// (chunk, pose): loss where tsdf_loss_f keeps the voxel, 0 where it drops it (and in the tail of the last chunk), folded across the wave in a
+// fixed six-level pairwise tree — the same additions whatever the other lanes hold — the count by ballot + popcount; lane (p mod 64) adds both
+// to the accumulators it keeps in registers for pose p, one double and one unsigned.  Then per workgroup: the four waves' accumulators in
+// wave order, one record of 64 doubles + 64 counts, an arrival ticket per tile, and the tile's last workgroup adds the records in index
+// order (block_fold_and_finish_of's scheme and hand-off, 64 poses wide).  Every step's order is a function of the index's count alone.
+enum { SCORE_TILE = 64, SCORE_POSES_OFFSET = 256, SCORE_MAX_BLOCKS = 1024, SCORE_RECORD_BYTES = SCORE_TILE * (sizeof(double) + sizeof(unsigned)) };
+static_assert(XS_SCORE_MAX_POSES / SCORE_TILE * sizeof(unsigned) == SCORE_POSES_OFFSET, "one ticket per tile in the first 256 bytes");
+static_assert(sizeof(HessPoseF) == 12 * sizeof(float), "twelve floats per real pose");
+static size_t score_records_offset() { return SCORE_POSES_OFFSET + (size_t)XS_SCORE_MAX_POSES * sizeof(HessPoseF); }
+
+// all 64 lanes, all of them active: v[l] + v[l ^ 1], then ^ 2, 4, 8 (DPP within a row of 16), 16, 32 — a pairwise tree, the same bits in every lane
+// (float addition commutes)
+__device__ __forceinline__ float wave_tree_sum_f32(float v) {
+    auto dpp = [](float x, auto ctrl) { return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), decltype(ctrl)::value, 0xf, 0xf, false)); };
+    v += dpp(v, std::integral_constant<int, 0xb1>());    // quad_perm [1, 0, 3, 2]
+    v += dpp(v, std::integral_constant<int, 0x4e>());    // quad_perm [2, 3, 0, 1]
+    v += dpp(v, std::integral_constant<int, 0x141>());   // row_half_mirror: quad q with quad q ^ 1 (a quad's lanes are equal by now)
+    v += dpp(v, std::integral_constant<int, 0x140>());   // row_mirror: the row's halves
+    v += __shfl_xor(v, 16, 64);
+    v += __shfl_xor(v, 32, 64);
+    return v;
+}
+
+struct BandScoreArgs {
+    HessArgs a;                                  // the residual's fields
+    const unsigned long long *keys;
+    const float *values;
+    long long count;                             // entries of keys / values
+    int poses;
+    const HessPoseF *poses_dev;                  // [poses], in the workspace
+    char *records;                               // [tiles][nblocks]{64 doubles, 64 unsigned}
+    unsigned *tickets;                           // [tiles], zero between launches
+    double *out;                                 // [poses][2]
+};
+__global__ void __launch_bounds__(256) k_band_score_poses(const BandScoreArgs g) {
+    __shared__ double s_sum[4][SCORE_TILE];
+    __shared__ unsigned s_cnt[4][SCORE_TILE];
+    __shared__ unsigned s_last;
+    const int lane = threadIdx.x, wave = __builtin_amdgcn_readfirstlane(threadIdx.y), tid = wave * 64 + lane;
+    const unsigned nblocks = gridDim.x, bid = blockIdx.x, tile = blockIdx.y;
+    const int p0 = (int)tile * SCORE_TILE, np = min(SCORE_TILE, g.poses - p0);   // (the last tile may be partial: its other lanes keep zeros)
+    const HessPoseF *__restrict__ poses = g.poses_dev + p0;
+    double acc = 0.0;
+    unsigned cnt = 0;
+    const long long nchunks = (g.count + 63) / 64;
+    for (long long c = (long long)bid * 4 + wave; c < nchunks; c += 4ll * nblocks) {
+        const long long e = c * 64 + lane;
+        const bool valid = e < g.count;          // (the last chunk's tail: masked, and it adds zeros)
+        unsigned long long key = 0;
+        float gt = 0.f;
+        if (valid) { key = g.keys[e]; gt = g.values[e]; }
+        const int x = (int)(key & 0x1fffff), y = (int)((key >> 21) & 0x1fffff), z = (int)(key >> 42);
+#pragma unroll 1
+        for (int j = 0; j < np; ++j) {
+            const HessPoseF P = poses[__builtin_amdgcn_readfirstlane(j)];
+            float loss = 0.f;
+            const bool kept = valid && tsdf_loss_f(g.a, P, x, y, z, gt, loss);
+            const float s = wave_tree_sum_f32(kept ? loss : 0.f);
+            const unsigned n = (unsigned)__popcll(__ballot(kept));
+            if (lane == j) { acc += (double)s; cnt += n; }
+        }
+    }
+    // the four waves in wave order, then one record per workgroup: pose lane's sum and count, stored by the lanes of wave 0
+    s_sum[wave][lane] = acc;
+    s_cnt[wave][lane] = cnt;
+    __syncthreads();
+    char *tile_records = g.records + (size_t)tile * nblocks * SCORE_RECORD_BYTES;
+    if (tid < SCORE_TILE) {
+        const double s = ((s_sum[0][tid] + s_sum[1][tid]) + s_sum[2][tid]) + s_sum[3][tid];
+        const unsigned n = ((s_cnt[0][tid] + s_cnt[1][tid]) + s_cnt[2][tid]) + s_cnt[3][tid];
+        char *rec = tile_records + (size_t)bid * SCORE_RECORD_BYTES;
+        __hip_atomic_store(reinterpret_cast<double *>(rec) + tid, s, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_store(reinterpret_cast<unsigned *>(rec + SCORE_TILE * sizeof(double)) + tid, n, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    // the hand-off of block_fold_and_finish_of (xs_gn_band.h): write-through record stores by wave 0, acknowledged, then its first lane's ticket
+    if (wave == 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    if (tid == 0) {
+        const unsigned tk = __hip_atomic_fetch_add(g.tickets + tile, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        s_last = tk == nblocks - 1 ? 1u : 0u;
+        if (s_last) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    }
+    __syncthreads();
+    if (!s_last) return;
+    // the tile's last workgroup: thread (q, l) adds pose l's records q, q + 4, ... in that order, eight loads in flight; the four row groups are
+    // then added in group order
+    {
+        const int l = tid % SCORE_TILE, q = tid / SCORE_TILE;
+        double s = 0.0;
+        unsigned long long n = 0;
+        auto rsum = [&](unsigned b) { return reinterpret_cast<const double *>(tile_records + (size_t)b * SCORE_RECORD_BYTES)[l]; };
+        auto rcnt = [&](unsigned b) { return reinterpret_cast<const unsigned *>(tile_records + (size_t)b * SCORE_RECORD_BYTES + SCORE_TILE * sizeof(double))[l]; };
+        unsigned b = q;
+        for (; b + 4 * 7 < nblocks; b += 4 * 8) {
+            double v[8]; unsigned m[8];
+#pragma unroll
+            for (int k = 0; k < 8; ++k) { v[k] = rsum(b + 4 * k); m[k] = rcnt(b + 4 * k); }
+#pragma unroll
+            for (int k = 0; k < 8; ++k) { s += v[k]; n += m[k]; }
+        }
+        for (; b < nblocks; b += 4) { s += rsum(b); n += rcnt(b); }
+        __shared__ unsigned long long s_n[4][SCORE_TILE];
+        s_sum[q][l] = s;   // (wave 0 read its workgroup's own sums before the ticket's barrier)
+        s_n[q][l] = n;
+        __syncthreads();
+        if (tid < np) {
+            g.out[2 * (size_t)(p0 + tid)] = ((s_sum[0][tid] + s_sum[1][tid]) + s_sum[2][tid]) + s_sum[3][tid];
+            g.out[2 * (size_t)(p0 + tid) + 1] = (double)(((s_n[0][tid] + s_n[1][tid]) + s_n[2][tid]) + s_n[3][tid]);
+        }
+        // the ticket goes back to zero for the next launch on this workspace (xs_tsdf_reduce_workspace_init zeroes it once)
+        if (tid == 0) __hip_atomic_store(g.tickets + tile, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+}
+
+extern "C" size_t xs_tsdf_score_poses_workspace_bytes(int poses) {
+    if (poses < 1 || poses > XS_SCORE_MAX_POSES) return 0;
+    const size_t tiles = ((size_t)poses + SCORE_TILE - 1) / SCORE_TILE;
+    return score_records_offset() + tiles * SCORE_MAX_BLOCKS * SCORE_RECORD_BYTES;
+}
+
+extern "C" int xs_tsdf_score_poses_band(int poses, const float *depth_scaled, size_t scaled_step, int rows, int cols, const float *intr4,
+                                        float voxel_size, const float *Rv2c9xP, const float *tv2c3xP, float tranc_dist,
+                                        const xs_band_index *index, void *workspace, double *out2xP_dev, void *stream) {
+    if (poses < 1 || poses > XS_SCORE_MAX_POSES) return xs_set_error(hipErrorInvalidValue, "xs_tsdf_score_poses_band: poses outside 1 .. XS_SCORE_MAX_POSES");
+    if (!depth_scaled || !intr4 || !Rv2c9xP || !tv2c3xP || !index || !workspace || !out2xP_dev)
+        return xs_set_error(hipErrorInvalidValue, "xs_tsdf_score_poses_band: null pointer");
+    if (index->nblocks < 1 || index->count < 0 || index->count > index->capacity || (index->count > 0 && (!index->keys || !index->values)))
+        return xs_set_error(hipErrorInvalidValue, "xs_tsdf_score_poses_band: the index was not built");
+    if (rows < 4 || cols < 4 || scaled_step < (size_t)cols * sizeof(float)) return xs_set_error(hipErrorInvalidValue, "xs_tsdf_score_poses_band: bad depth shape");
+    BandScoreArgs g;
+    memset(&g, 0, sizeof(g));
+    HessArgs &a = g.a;
+    a.depth = depth_scaled; a.dstep = scaled_step; a.drows = rows; a.dcols = cols;
+    a.voxel_size = voxel_size; a.tranc_dist = tranc_dist; a.tranc_dist_inv = 1.0f / tranc_dist;
+    a.intr = Intr{intr4[0], intr4[1], intr4[2], intr4[3]};
+    a.X = index->res[0]; a.Y = index->res[1]; a.Z = index->res[2]; a.z0 = index->z0; a.z1 = index->z1;
+    std::vector<HessPoseF> P((size_t)poses);
+    for (int p = 0; p < poses; ++p) {
+        for (int i = 0; i < 9; ++i) P[(size_t)p].R[i] = Rv2c9xP[9 * (size_t)p + i];
+        for (int i = 0; i < 3; ++i) P[(size_t)p].t[i] = tv2c3xP[3 * (size_t)p + i];
+    }
+    // as many workgroups per tile as give every wave a chunk, at most the record workspace's 1024: a function of the index alone
+    const long long nchunks = (index->count + 63) / 64, want = (nchunks + 3) / 4;
+    const unsigned nblocks = (unsigned)(want < 1 ? 1 : (want > SCORE_MAX_BLOCKS ? SCORE_MAX_BLOCKS : want));
+    const unsigned tiles = ((unsigned)poses + SCORE_TILE - 1) / SCORE_TILE;
+    char *ws = static_cast<char *>(workspace);
+    g.tickets = reinterpret_cast<unsigned *>(ws);
+    g.poses_dev = reinterpret_cast<const HessPoseF *>(ws + SCORE_POSES_OFFSET);
+    g.records = ws + score_records_offset();
+    g.keys = index->keys; g.values = index->values; g.count = index->count; g.poses = poses; g.out = out2xP_dev;
+    hipStream_t st = (hipStream_t)stream;
+    XS_CHECK(hipMemcpyAsync(ws + SCORE_POSES_OFFSET, P.data(), P.size() * sizeof(HessPoseF), hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(k_band_score_poses, dim3(nblocks, tiles), dim3(64, 4), 0, st, g);
     XS_CHECK(hipGetLastError());
     return 0;
 }

@@ -1,7 +1,7 @@
 // xs_gn_band.h — what the dense residual kernels of xs_residual.hip and the band index of xs_band.hip share: the kernel arguments, the
 // record fold (registers -> wave -> LDS -> one record per workgroup -> the last workgroup adds the records in index order), the walk that
-// deals the band voxels (gt != 0, |gt| <= 0.95) of a slab out to the lanes, the six-pose CSFD residual of the Gauss-Newton pass and the
-// dual-complex squared residual of the Hessian kernels.
+// deals the band voxels (gt != 0, |gt| <= 0.95) of a slab out to the lanes, the six-pose CSFD residual of the Gauss-Newton pass, the
+// dual-complex squared residual of the Hessian kernels and the real-valued one of the loss kernels.
 // Included by exactly those two files.
 #pragma once
 #include "xs_device.h"
@@ -364,6 +364,42 @@ __device__ __forceinline__ bool tsdf_loss_d(const HessArgs &a, const HessPoseD &
     const dcfloat gt_distance = gt_tsdf * a.tranc_dist;
     const dcfloat error = (distance - gt_distance) * a.tranc_dist_inv;
     if (fabsf(error.value()) > 1) return false;
+    loss = error * error;
+    return true;
+}
+
+// ---- the real-valued squared residual of the loss kernels (k_tsdf_loss, k_band_score_poses) ----
+// One band voxel's loss = error^2 at the real pose P, the float twin of tsdf_loss_d: projection, the inv_z < 0 gate, the image gate, nearest
+// and bilinear depth, the 0.2 - 5 m gate and the |error| > 1 gate of ComputeLocalTsdfLossKernel (TsdfFusion.cu:335-410).  False where a gate
+// drops the voxel.  Both kernels take a voxel's float and its keep / drop decision from here, so their counts are equal and their sums add the
+// same terms.
+__device__ __forceinline__ bool tsdf_loss_f(const HessArgs &a, const HessPoseF &P, int xq, int yq, int z, float gt, float &loss) {
+    const float vgx = (float(xq) + 0.5f) * a.voxel_size, vgy = (float(yq) + 0.5f) * a.voxel_size, vgz = (float(z) + 0.5f) * a.voxel_size;
+    const float vcx = (P.R[0] * vgx + P.R[1] * vgy + P.R[2] * vgz) + P.t[0];
+    const float vcy = (P.R[3] * vgx + P.R[4] * vgy + P.R[5] * vgz) + P.t[1];
+    const float vcz = (P.R[6] * vgx + P.R[7] * vgy + P.R[8] * vgz) + P.t[2];
+    const float inv_z = 1.0f / vcz;
+    if (inv_z < 0) return false;
+    const float image_x = vcx * inv_z * a.intr.fx + a.intr.cx;
+    const float image_y = vcy * inv_z * a.intr.fy + a.intr.cy;
+    const int coo_x = __float2int_rd(image_x - 0.5f), coo_y = __float2int_rd(image_y - 0.5f);
+    if (!(coo_x > 1 && coo_y > 1 && coo_x < a.dcols - 1 && coo_y < a.drows - 1)) return false;
+    const int near_x = __float2int_rn(image_x), near_y = __float2int_rn(image_y);
+    float Dp = row_ptr(a.depth, a.dstep, near_y)[near_x];
+    const float d00 = row_ptr(a.depth, a.dstep, coo_y)[coo_x], d10 = row_ptr(a.depth, a.dstep, coo_y)[coo_x + 1];
+    const float d01 = row_ptr(a.depth, a.dstep, coo_y + 1)[coo_x], d11 = row_ptr(a.depth, a.dstep, coo_y + 1)[coo_x + 1];
+    if (d00 != 0.0f && d01 != 0.0f && d10 != 0.0f && d11 != 0.0f) {
+        const float one = 1.0f;
+        const float fa = image_x - (float(coo_x) + 0.5f), fb = image_y - (float(coo_y) + 0.5f);
+        Dp = d00 * (one - fa) * (one - fb) + d10 * fa * (one - fb) + d01 * (one - fa) * fb + d11 * fa * fb;
+    }
+    if (Dp > 5 || Dp < 0.2) return false;
+    const float xl = (image_x - a.intr.cx) / a.intr.fx, yl = (image_y - a.intr.cy) / a.intr.fy;
+    const float v1x = Dp * xl, v1y = Dp * yl, v1z = Dp;
+    const float distance = sqrtf(v1x * v1x + v1y * v1y + v1z * v1z) - sqrtf(vcx * vcx + vcy * vcy + vcz * vcz);
+    const float gt_distance = gt * a.tranc_dist;
+    const float error = (distance - gt_distance) * a.tranc_dist_inv;
+    if (fabsf(error) > 1) return false;
     loss = error * error;
     return true;
 }

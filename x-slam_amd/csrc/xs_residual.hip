@@ -45,33 +45,8 @@ __global__ void __launch_bounds__(256) XS_HESS_OCC k_tsdf_hessian(const HessArgs
 __global__ void __launch_bounds__(256) k_tsdf_loss(const HessArgs a, const HessPoseF P) {
     double acc[2] = {0.0, 0.0};
     walk_band(a, [&](int xq, int yq, int z, size_t index, float gt_tsdf) {
-        const float vgx = (float(xq) + 0.5f) * a.voxel_size, vgy = (float(yq) + 0.5f) * a.voxel_size, vgz = (float(z) + 0.5f) * a.voxel_size;
-        const float vcx = (P.R[0] * vgx + P.R[1] * vgy + P.R[2] * vgz) + P.t[0];
-        const float vcy = (P.R[3] * vgx + P.R[4] * vgy + P.R[5] * vgz) + P.t[1];
-        const float vcz = (P.R[6] * vgx + P.R[7] * vgy + P.R[8] * vgz) + P.t[2];
-        const float inv_z = 1.0f / vcz;
-        if (inv_z < 0) return;
-        const float image_x = vcx * inv_z * a.intr.fx + a.intr.cx;
-        const float image_y = vcy * inv_z * a.intr.fy + a.intr.cy;
-        const int coo_x = __float2int_rd(image_x - 0.5f), coo_y = __float2int_rd(image_y - 0.5f);
-        if (!(coo_x > 1 && coo_y > 1 && coo_x < a.dcols - 1 && coo_y < a.drows - 1)) return;
-        const int near_x = __float2int_rn(image_x), near_y = __float2int_rn(image_y);
-        float Dp = row_ptr(a.depth, a.dstep, near_y)[near_x];
-        const float d00 = row_ptr(a.depth, a.dstep, coo_y)[coo_x], d10 = row_ptr(a.depth, a.dstep, coo_y)[coo_x + 1];
-        const float d01 = row_ptr(a.depth, a.dstep, coo_y + 1)[coo_x], d11 = row_ptr(a.depth, a.dstep, coo_y + 1)[coo_x + 1];
-        if (d00 != 0.0f && d01 != 0.0f && d10 != 0.0f && d11 != 0.0f) {
-            const float one = 1.0f;
-            const float fa = image_x - (float(coo_x) + 0.5f), fb = image_y - (float(coo_y) + 0.5f);
-            Dp = d00 * (one - fa) * (one - fb) + d10 * fa * (one - fb) + d01 * (one - fa) * fb + d11 * fa * fb;
-        }
-        if (Dp > 5 || Dp < 0.2) return;
-        const float xl = (image_x - a.intr.cx) / a.intr.fx, yl = (image_y - a.intr.cy) / a.intr.fy;
-        const float v1x = Dp * xl, v1y = Dp * yl, v1z = Dp;
-        const float distance = sqrtf(v1x * v1x + v1y * v1y + v1z * v1z) - sqrtf(vcx * vcx + vcy * vcy + vcz * vcz);
-        const float gt_distance = gt_tsdf * a.tranc_dist;
-        const float error = (distance - gt_distance) * a.tranc_dist_inv;
-        if (fabsf(error) > 1) return;
-        const float loss = error * error;
+        float loss;
+        if (!tsdf_loss_f(a, P, xq, yq, z, gt_tsdf, loss)) return;   // (xs_gn_band.h: shared with k_band_score_poses)
         if (a.real_out) { a.real_out[index] = loss; a.count_out[index] = 1; }
         acc[0] += loss; acc[1] += 1.0;
     });

@@ -4,6 +4,7 @@
 // needs a result (the 6x6 normal equations of each ICP iteration).
 #include "KinectFusionReconstruction.h"
 #include "newton_host.hpp"
+#include "score_host.hpp"
 #include <chrono>
 #include <algorithm>
 #include <cmath>
@@ -1491,6 +1492,70 @@ int KinectFusionReconstruction::RelocalizeNewtonBatch(const std::vector<DeviceAr
     int succeeded = 0;
     for (int f = 0; f < F; ++f) succeeded += ok[f];
     return succeeded;
+}
+
+// ---- many pose hypotheses against the map in one band pass, and global relocalisation ----
+int KinectFusionReconstruction::ScorePoses(const DeviceArray2D<ushort> &depth_frame_d, const Matrix4cf *camera2volume, int P, double *out2xP) {
+    if (!tsdf_volume_d_ptr || P < 0) return 0;
+    if (P == 0) return 1;
+    hipStream_t st = current_stream();
+    BandIndexPrepare();
+    const size_t ws_bytes = xs_tsdf_score_poses_workspace_bytes(XS_SCORE_MAX_POSES);
+    if (score_ws_.size() < ws_bytes) {
+        score_ws_.create(ws_bytes);
+        check_rc(xs_tsdf_reduce_workspace_init(score_ws_.ptr(), st), "score workspace");   // (zeroes the tickets: once)
+    }
+    if (score_sums_.size() < (size_t)XS_SCORE_MAX_POSES * 2) score_sums_.create((size_t)XS_SCORE_MAX_POSES * 2);
+    const int rows = depth_frame_d.rows(), cols = depth_frame_d.cols();
+    score_depth_.create(rows, cols);   // the depth is scaled once, not per chunk
+    check_rc(xs_scale_depth(depth_frame_d.ptr(), depth_frame_d.step(), rows, cols, score_depth_.ptr(), score_depth_.step(), st), "scaleDepth");
+    const bool sharded = shard_count > 1 && collective;
+    std::vector<float> R, t;
+    for (int p0 = 0; p0 < P; p0 += XS_SCORE_MAX_POSES) {
+        const int n = std::min(P - p0, (int)XS_SCORE_MAX_POSES);
+        R.resize((size_t)n * 9); t.resize((size_t)n * 3);
+        for (int i = 0; i < n; ++i) {
+            const Matrix4cf inv = inverse(camera2volume[p0 + i]);   // (newton_seeded_poses' real parts: the same inverse, its real part as float)
+            for (int r = 0; r < 3; ++r) {
+                for (int c = 0; c < 3; ++c) R[(size_t)i * 9 + (size_t)r * 3 + c] = inv.m[r][c].real();
+                t[(size_t)i * 3 + r] = inv.m[r][3].real();
+            }
+        }
+        check_rc(xs_tsdf_score_poses_band(n, score_depth_.ptr(), score_depth_.step(), rows, cols, &kinect_intrinsic.fx, voxel_size, R.data(), t.data(),
+                                          tsdf_volume_d_ptr->getTsdfTruncDist(), &band_, score_ws_.ptr(), score_sums_.ptr(), st), "ScorePosesBand");
+        if (sharded) collective(collective_user, 0, score_sums_.ptr(), (long)n * 2);
+        hipSafeCall(hipMemcpyAsync(out2xP + 2 * (size_t)p0, score_sums_.ptr(), (size_t)n * 2 * sizeof(double), hipMemcpyDeviceToHost, st));
+        hipSafeCall(hipStreamSynchronize(st));   // (the chunk's host arrays and the workspace are free again)
+    }
+    return 1;
+}
+
+int KinectFusionReconstruction::RelocalizeGlobal(const DeviceArray2D<ushort> &depth_frame_d, const Matrix4cf *candidates, int P, int keep, int iterations,
+                                                 float damping, Matrix4cf &best, double report[8]) {
+    for (int i = 0; i < 8; ++i) report[i] = 0.0;
+    report[0] = -1.0;
+    if (!tsdf_volume_d_ptr || P <= 0 || keep <= 0) return 0;
+    std::vector<double> before((size_t)P * 2);
+    if (!ScorePoses(depth_frame_d, candidates, P, before.data())) return 0;
+    report[6] = (double)band_.count;
+    const std::vector<int> top = score_top_k(before.data(), P, keep);
+    const int K = (int)top.size();
+    std::vector<Matrix4cf> refined((size_t)K);
+    for (int k = 0; k < K; ++k) refined[(size_t)k] = candidates[top[(size_t)k]];
+    const std::vector<DeviceArray2D<ushort>> depths((size_t)K, depth_frame_d);   // the same image in every slot
+    std::vector<int> ok((size_t)K, 0);
+    report[5] = (double)RelocalizeGaussNewtonBatch(depths, refined.data(), iterations, damping, ok.data(), nullptr);
+    std::vector<double> after((size_t)K * 2);
+    ScorePoses(depth_frame_d, refined.data(), K, after.data());
+    const int w = score_winner(after.data(), ok.data(), K);
+    if (w < 0) return 0;
+    best = refined[(size_t)w];
+    report[0] = (double)top[(size_t)w];
+    report[1] = score_S(&before[2 * (size_t)top[(size_t)w]]);
+    report[2] = score_S(&after[2 * (size_t)w]);
+    report[3] = after[2 * (size_t)w];
+    report[4] = after[2 * (size_t)w + 1];
+    return 1;
 }
 
 // reference :334-372

@@ -217,6 +217,17 @@ public:
     int PoseHessianTerms(const DeviceArray2D<ushort> &depth_frame_d, const Matrix4cf &camera2volume, double out29[29]);
     int RelocalizeNewtonBatch(const std::vector<DeviceArray2D<ushort>> &depths, Matrix4cf *camera2volume, int iterations, float damping, int *ok,
                               std::vector<double> *loss_history = nullptr, int *fallbacks = nullptr);
+    // Global relocalisation: the camera is lost and there are pose hypotheses.  ScorePoses evaluates the real-valued
+    // alignment loss of one depth frame at P camera2volume poses in one pass over the band index per chunk of XS_SCORE_MAX_POSES
+    // (xs_tsdf_score_poses_band): out2xP + 2 p = {sum loss, count} at the real part of inverse(camera2volume[p]) — the bits newton_seeded_poses
+    // puts in its real parts.  Sharded: a chunk's 2 n doubles are all-reduced.  Returns 1, or 0 without a volume.
+    // RelocalizeGlobal scores the P candidates, keeps the min(keep, P) with the highest S = count - sum loss (score_host.hpp), refines them with
+    // RelocalizeGaussNewtonBatch (the same depth in every slot), scores the refined poses and returns in `best` the one with the highest S
+    // among those whose loop ended ok.  report: {winner's candidate index, its S before, its S after, sum loss after, count after, number of
+    // the kept that ended ok, band voxels in the index, 0}.  Returns 1, or 0 with `best` untouched when none ended ok.
+    int ScorePoses(const DeviceArray2D<ushort> &depth_frame_d, const Matrix4cf *camera2volume, int P, double *out2xP);
+    int RelocalizeGlobal(const DeviceArray2D<ushort> &depth_frame_d, const Matrix4cf *candidates, int P, int keep, int iterations, float damping,
+                         Matrix4cf &best, double report[8]);
     long long RelocalizationIndexVoxels() const { return band_generation_ >= 0 ? band_.count : 0; }   // the index as last built, 0 before any
     // bumped by everything that writes the volume: integrate calls, loadCheckpoint, xs_kf_volume_ptr(kf, 0, .), RebuildSignMap (the band index is rebuilt
     // when its generation differs)
@@ -288,6 +299,9 @@ private:
     void PoseHessianLaunch(const int *frames, int n, const Matrix4cf *camera2volume, size_t scaled_step, int rows, int cols, double *raw);
     DeviceArray<unsigned char> newton_ws_;     // xs_tsdf_pose_hessian_workspace_bytes(XS_BAND_MAX_FRAMES), tickets zeroed once
     DeviceArray<double> newton_sums_;          // XS_BAND_MAX_FRAMES x 29
+    DeviceArray<unsigned char> score_ws_;      // xs_tsdf_score_poses_workspace_bytes(XS_SCORE_MAX_POSES), tickets zeroed once
+    DeviceArray<double> score_sums_;           // XS_SCORE_MAX_POSES x 2
+    DeviceArray2D<float> score_depth_;         // ScorePoses' scaled depth
     xs_band_index band_ = {};                  // band index of the owned planes (RelocalizeGaussNewtonBatch)
     long long band_generation_ = -1;           // the volume_generation it was built at
     DeviceArray<unsigned long long> band_keys_;

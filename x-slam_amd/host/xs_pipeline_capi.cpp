@@ -235,6 +235,25 @@ int xs_kf_relocalize_newton(void *kf, const uint16_t *depth_dev, size_t step_byt
     const int n = xs_kf_relocalize_newton_batch(kf, 1, &depth_dev, step_bytes, c2v32, iterations, damping, loss_out, &ok, fallbacks_out);
     return n < 0 ? n : ok;
 }
+int xs_kf_score_poses(void *kf, const uint16_t *depth_dev, size_t step_bytes, int poses, const float *c2v32xP, double *out2xP) {
+    KF *k = (KF *)kf;
+    if (poses < 0 || (poses > 0 && (!depth_dev || !c2v32xP || !out2xP))) return -1;
+    std::vector<Matrix4cf> m((size_t)poses);
+    for (int p = 0; p < poses; ++p) std::memcpy(static_cast<void *>(&m[(size_t)p]), c2v32xP + 32 * (size_t)p, 32 * sizeof(float));
+    return k->ScorePoses(wrap_depth(k, depth_dev, step_bytes), m.data(), poses, out2xP);
+}
+int xs_kf_relocalize_global(void *kf, const uint16_t *depth_dev, size_t step_bytes, int poses, const float *c2v32xP, int keep, int iterations,
+                            float damping, float *best_c2v32, double *report8) {
+    KF *k = (KF *)kf;
+    if (poses < 0 || !report8 || !best_c2v32 || (poses > 0 && (!depth_dev || !c2v32xP))) return -1;
+    std::vector<Matrix4cf> m((size_t)poses);
+    for (int p = 0; p < poses; ++p) std::memcpy(static_cast<void *>(&m[(size_t)p]), c2v32xP + 32 * (size_t)p, 32 * sizeof(float));
+    Matrix4cf best;
+    std::memcpy(static_cast<void *>(&best), best_c2v32, 32 * sizeof(float));
+    const int rc = k->RelocalizeGlobal(wrap_depth(k, depth_dev, step_bytes), m.data(), poses, keep, iterations, damping, best, report8);
+    std::memcpy(best_c2v32, &best, 32 * sizeof(float));
+    return rc;
+}
 long long xs_kf_relocalization_index_voxels(void *kf) { return ((KF *)kf)->RelocalizationIndexVoxels(); }
 long long xs_kf_export_point_cloud(void *kf, int max_buffer, float *points_host, float *normals_host) {
     const auto pc = ((KF *)kf)->ExportPointCloud(max_buffer);

@@ -42,6 +42,8 @@ _SIGS = {
     "xs_kf_relocalize_newton_batch": (C.c_int, [_vp, C.c_int, C.POINTER(_vp), _sz, _f32p, C.c_int, C.c_float, _f64p, _i32p, _i32p]),
     "xs_host_newton_seeded_poses": (C.c_int, [_f32p, _f32p, _f32p]),
     "xs_host_newton_step": (C.c_int, [_f64p, C.c_double, _f32p]),
+    "xs_kf_score_poses": (C.c_int, [_vp, _vp, _sz, C.c_int, _f32p, _f64p]),
+    "xs_kf_relocalize_global": (C.c_int, [_vp, _vp, _sz, C.c_int, _f32p, C.c_int, C.c_int, C.c_float, _f32p, _f64p]),
     "xs_kf_relocalization_index_voxels": (C.c_longlong, [_vp]),
     "xs_kf_export_point_cloud": (C.c_longlong, [_vp, C.c_int, _f32p, _f32p]),
     "xs_kf_export_ply": (C.c_longlong, [_vp, C.c_int, C.c_char_p]),
@@ -152,6 +154,49 @@ def host_newton_step(s29, damping, c2v):
     m = np.ascontiguousarray(c2v, dtype=np.float32).reshape(32).copy()
     rc = _lib.xs_host_newton_step(s.ctypes.data_as(_f64p), float(damping), m.ctypes.data_as(_f32p))
     return rc == 0, m.reshape(4, 4, 2)
+
+
+def _halton(i, base):
+    """The radical inverse of the integer i >= 1 in `base` (float64)."""
+    f, r = 1.0, 0.0
+    while i > 0:
+        f /= base
+        r += f * (i % base)
+        i //= base
+    return r
+
+
+def _se3_exp(xi):
+    """The exponential of the real twist (v, omega) as a 4 x 4 matrix, float64."""
+    v, w = np.asarray(xi[:3], np.float64), np.asarray(xi[3:], np.float64)
+    th = float(np.linalg.norm(w))
+    K = np.array([[0.0, -w[2], w[1]], [w[2], 0.0, -w[0]], [-w[1], w[0], 0.0]])
+    if th < 1e-12:
+        R, V = np.eye(3) + K, np.eye(3) + K
+    else:
+        R = np.eye(3) + np.sin(th) / th * K + (1 - np.cos(th)) / th ** 2 * K @ K
+        V = np.eye(3) + (1 - np.cos(th)) / th ** 2 * K + (th - np.sin(th)) / th ** 3 * K @ K
+    T = np.eye(4)
+    T[:3, :3], T[:3, 3] = R, V @ v
+    return T
+
+
+POSE_CANDIDATE_PRIMES = (2, 3, 5, 7, 11, 13)
+
+
+def pose_candidates(center_c2v, box_t, box_r, n):
+    """n camera2volume hypotheses [n, 4, 4, 2] float32 (zero imaginary parts) around center_c2v ([4, 4, 2] or real [4, 4]) for
+    KinectFusion.relocalize_global: candidate i = center @ se3Exp(twist_i), a camera-frame move by the twist
+    (u[:3] * box_t metres, u[3:] * box_r radians) with u_j = 2 halton(i + 1, prime_j) - 1 in (-1, 1), primes 2, 3, 5, 7, 11, 13 — a
+    low-discrepancy cover of the box, the same for every call (CPU, numpy)."""
+    c = np.asarray(center_c2v, np.float64)
+    c = c[..., 0] if c.ndim == 3 else c
+    assert c.shape == (4, 4)
+    out = np.zeros((int(n), 4, 4, 2), np.float32)
+    for i in range(int(n)):
+        u = np.array([2.0 * _halton(i + 1, b) - 1.0 for b in POSE_CANDIDATE_PRIMES])
+        out[i, ..., 0] = c @ _se3_exp(np.concatenate([u[:3] * float(box_t), u[3:] * float(box_r)]))
+    return out
 
 
 def flat_yaml_get(text, key):
@@ -288,6 +333,35 @@ class KinectFusion:
         if n < 0:
             raise ValueError("xs_kf_relocalize_batch: bad arguments")
         return ok == 1, m.reshape(F, 4, 4, 2), hist
+
+    def score_poses(self, depth_dev, c2vs):
+        """The alignment loss of one depth frame at P camera2volume hypotheses c2vs [P, 4, 4, 2] in one pass over the map's band index per
+        4096 poses: (sum loss [P], count [P]) float64 — per pose what xs_compute_local_tsdf_loss gives on the dense map."""
+        m = np.ascontiguousarray(c2vs, dtype=np.float32).reshape(-1)
+        P = m.size // 32
+        assert m.size == 32 * P
+        out = np.zeros((max(P, 1), 2), np.float64)
+        rc = _lib.xs_kf_score_poses(self.h, depth_dev.data_ptr(), self.width * 2, P, m.ctypes.data_as(_f32p), out.ctypes.data_as(_f64p))
+        if rc != 1:
+            raise ValueError("xs_kf_score_poses: bad arguments" if rc < 0 else "xs_kf_score_poses: no volume")
+        return out[:P, 0].copy(), out[:P, 1].copy()
+
+    def relocalize_global(self, depth_dev, candidates, keep=8, iterations=10, damping=1e-3):
+        """Global relocalisation from pose hypotheses candidates [P, 4, 4, 2] (pose_candidates makes them): score all, refine the `keep`
+        with the highest S = count - sum loss by Gauss-Newton, return the refined pose with the highest S: (ok, c2v [4, 4, 2], report).
+        Not ok (none of the kept converged): c2v is candidates[0] and the report's index is -1."""
+        m = np.ascontiguousarray(candidates, dtype=np.float32).reshape(-1)
+        P = m.size // 32
+        assert m.size == 32 * P and P > 0
+        best = m[:32].copy()
+        rep = np.zeros(8, np.float64)
+        rc = _lib.xs_kf_relocalize_global(self.h, depth_dev.data_ptr(), self.width * 2, P, m.ctypes.data_as(_f32p), int(keep), int(iterations),
+                                          float(damping), best.ctypes.data_as(_f32p), rep.ctypes.data_as(_f64p))
+        if rc < 0:
+            raise ValueError("xs_kf_relocalize_global: bad arguments")
+        report = dict(index=int(rep[0]), S_before=float(rep[1]), S_after=float(rep[2]), sum_loss_after=float(rep[3]), count_after=float(rep[4]),
+                      refined_ok=int(rep[5]), index_voxels=int(rep[6]))
+        return rc == 1, best.reshape(4, 4, 2), report
 
     def relocalization_index_voxels(self):
         """Band voxels in the relocalisation index as last built by relocalize_batch (0 before the first)."""
