@@ -430,6 +430,48 @@ int xs_tsdf_score_poses_band(int poses, const float *depth_scaled, size_t scaled
                              float voxel_size, const float *Rv2c9xP, const float *tv2c3xP, float tranc_dist,
                              const xs_band_index *index, void *workspace, double *out2xP_dev, void *stream);
 
+/* ---- what a hypothetical camera would see of the map: next best view (xs_view.hip) ----------------------------
+ * No counterpart in the reference.  The OBSERVATION GRID condenses the value and weight volumes into two bits per voxel:
+ *   0 UNKNOWN  weight < min_weight        1 FREE  weight >= min_weight and value >= 0        2 OCCUPIED  weight >= min_weight and value < 0
+ * (min_weight below 1 means 1, as in xs_mesh_opts; -0.0f is FREE).  The integrate step leaves weight 0 exactly where nothing was fused and
+ * writes tsdf = 1 with weight >= 1 into the free space in front of a surface, so the grid is a function of the stored volumes alone.
+ * Layout (the library's own business; use xs_view_grid_expand to read it): one 16-byte word per brick of 4 x 4 x 4 voxels, bricks in x, y,
+ * z order, two bits per voxel at bit 2 (lx + 4 ly + 16 lz); bricks that overhang the volume are padded and the padding is never read as a
+ * state.  Behind the bricks the buffer holds the staging area xs_score_views copies a launch's poses into.
+ * xs_view_grid_bytes: the buffer's size (16-byte aligned device memory), 0 for a resolution with a non-positive axis.  Host only.
+ * xs_view_grid_build: the whole volume (value and weight with one row pitch vol_step, rows in (z * Y + y) order); reads 8 bytes per voxel
+ * once, by 16-byte loads where the pointers and the pitch are 16-byte aligned.  No synchronisation.
+ * xs_view_grid_expand: one byte per voxel, states_dev[(z * Y + y) * X + x]: tests and viewers.  No synchronisation. */
+size_t xs_view_grid_bytes(const int *res);
+int xs_view_grid_build(const float *value, const int *weight, size_t vol_step, const int *res, int min_weight, void *grid, void *stream);
+int xs_view_grid_expand(const void *grid, const int *res, unsigned char *states_dev, void *stream);
+/* xs_score_views: `poses` (1 .. XS_VIEW_MAX_POSES) real camera-to-volume poses, host arrays Rc2v9xP + 9 p (row-major) / tc2v3xP + 3 p, each
+ * casting a lattice of rays_x x rays_y rays of a rows x cols camera with intrinsics intr4 through the grid, all in one launch.  The call
+ * zeroes out4xP_dev[4 p .. 4 p + 3] on the stream and the launch leaves there {unknown, free, hits, frontier} of pose p:
+ *   ray (i, j):  u = (float(i) + 0.5f) * (float(cols) / float(rays_x)),  v = (float(j) + 0.5f) * (float(rows) / float(rays_y)),
+ *                dx = (u - cx) / fx,  dy = (v - cy) / fy,  d[c] = (R[c][0] * dx + R[c][1] * dy) + R[c][2]   (not normalised: t is depth along
+ *                the camera's z)
+ *   sample k = 0, 1, ... while t_k < t_far:  t_k = t_near + float(k) * step (no running sum),  p[c] = tc2v[c] + t_k * d[c],
+ *                voxel floor(p[c] / voxel_size) by an IEEE divide, as in the raycast
+ *   a sample whose voxel lies outside [0, res) counts nothing and does not end the ray; otherwise its state counts: UNKNOWN adds 1 to
+ *   `unknown`, and 1 to `frontier` if the ray's previous in-volume sample was FREE; FREE adds 1 to `free`; OCCUPIED adds 1 to `hits` and ends
+ *   the ray.
+ * Every operation is a separate IEEE float operation in this order (the library is built -ffp-contract=off) and the counters are integers,
+ * added by integer atomics: the result is a pure function of the inputs — a float32 model on the host reproduces it exactly, two launches
+ * give the same bits, and pose p's four numbers do not depend on `poses`, on p or on the other poses.  No floating-point atomics.
+ * hipErrorInvalidValue, with nothing launched and out4xP_dev untouched: poses outside 1 .. XS_VIEW_MAX_POSES; a lattice dimension below 1 or
+ * above cols / rows; step < 0 (or, after the default, not positive); t_far <= t_near; more than 4096 samples per ray; rays_x * rays_y *
+ * samples >= 2^32.  One launch at a time per grid (the poses' staging area).  No synchronisation. */
+#define XS_VIEW_MAX_POSES 4096
+typedef struct xs_view_opts {
+    unsigned struct_bytes;     /* sizeof(xs_view_opts) */
+    int rays_x, rays_y;        /* the ray lattice; 0, 0 = 80 x 60 */
+    float t_near, t_far;       /* depth range along the camera's z; 0, 0 = 0.2, 5.0 (xs_scale_depth's valid range) */
+    float step;                /* depth increment per sample; 0 = voxel_size */
+} xs_view_opts;
+int xs_score_views(int poses, const float *Rc2v9xP, const float *tc2v3xP, const float *intr4, int rows, int cols, const int *res,
+                   float voxel_size, const void *grid, const xs_view_opts *opts, unsigned *out4xP_dev, void *stream);
+
 /* ---- surface extraction (export; real-valued) ------------------------------------------------ */
 size_t xs_extract_workspace_bytes(const int *res);
 /* size_t extractPoints(value_volume, weight_volume, grad_volume, volume_resolution, voxel_size,

@@ -117,6 +117,21 @@ int xs_host_newton_step(const double *s29, double damping, float *c2v32);
 int xs_kf_score_poses(void *kf, const uint16_t *depth_dev, size_t step_bytes, int poses, const float *c2v32xP, double *out2xP);
 int xs_kf_relocalize_global(void *kf, const uint16_t *depth_dev, size_t step_bytes, int poses, const float *c2v32xP, int keep, int iterations,
                             float damping, float *best_c2v32, double *report8);
+/* Next best view: where should the camera go next?
+ * score_views: what the camera would see from each of `poses` hypothetical camera2volume poses c2v32xP + 32 p (the layout xs_kf_score_poses
+ * takes; the real parts are used): a lattice of rays per pose marched through the observation grid of the volume — two bits per voxel,
+ * unknown / free / occupied at weight gate min_weight (below 1 means 1), allocated on first use and rebuilt after anything wrote the volume
+ * or when min_weight changes — in one launch of xs_score_views (xslam_amd.h: the contract) per chunk of XS_VIEW_MAX_POSES.  out4xP + 4 p =
+ * {unknown, free, hits, frontier} samples of pose p.  opts: an xs_view_opts of xslam_amd.h, or NULL for the defaults (80 x 60 rays of the
+ * level-0 camera, depths 0.2 .. 5.0 in steps of a voxel).  Returns 1, 0 without a volume, -1 on bad arguments or options, -2 in shard mode
+ * (nothing is done: occlusion along a ray is not additive over z-slabs, and a composite like the raycast's is not built).
+ * next_best_view: scores the poses and returns the index of the one with the most unknown samples among those with hits >= min_hits (a
+ * view with no known surface in it cannot be tracked, so it cannot win); ties go to the lower index; -1 when no pose qualifies or there is
+ * no volume, -2 in shard mode, -3 on bad arguments or options.  out4xP (optional) receives the counts. */
+struct xs_view_opts;
+int xs_kf_score_views(void *kf, int poses, const float *c2v32xP, const struct xs_view_opts *opts, int min_weight, unsigned *out4xP);
+int xs_kf_next_best_view(void *kf, int poses, const float *c2v32xP, const struct xs_view_opts *opts, int min_weight, unsigned min_hits,
+                         unsigned *out4xP);
 /* band voxels in the relocalisation index as last built (0 before the first batch) */
 long long xs_kf_relocalization_index_voxels(void *kf);
 /* ExportPointCloud(max_buffer)  .cpp:334-372 (+ CPointCloud::exportPly, main.cpp:78-80): zero-crossing points of

@@ -59,7 +59,16 @@ class BandIndex(C.Structure):
                 ("nblocks", C.c_int), ("res", C.c_int * 3), ("z0", C.c_int), ("z1", C.c_int)]
 
 
+class ViewOpts(C.Structure):
+    """xs_view_opts (include/xslam_amd.h)."""
+    _fields_ = [("struct_bytes", C.c_uint), ("rays_x", C.c_int), ("rays_y", C.c_int), ("t_near", C.c_float), ("t_far", C.c_float), ("step", C.c_float)]
+
+
 _SIGS = {
+    "xs_view_grid_bytes": (_sz, [_i32p]),
+    "xs_view_grid_build": (C.c_int, [_vp, _vp, _sz, _i32p, C.c_int, _vp, _vp]),
+    "xs_view_grid_expand": (C.c_int, [_vp, _i32p, _vp, _vp]),
+    "xs_score_views": (C.c_int, [C.c_int, _f32p, _f32p, _f32p, C.c_int, C.c_int, _i32p, C.c_float, _vp, C.POINTER(ViewOpts), _vp, _vp]),
     "xs_integrate_scaled_ex2": (C.c_int, [_vp, _sz, C.c_int, C.c_int, _f32p, C.c_int, _i32p, C.c_float, _f32p, _f32p, C.c_float, _vp, _vp, _vp,
                                          _sz, C.c_float, C.c_int, C.c_int, _vp, _vp, _vp, C.POINTER(IntegrateOpts), _vp]),
     "xs_integrate_classify_ex": (C.c_int, [C.c_int, C.c_int, _f32p, _i32p, C.c_float, _f32p, _f32p, C.c_float, C.c_int, C.c_int, _vp, _vp,
@@ -543,6 +552,48 @@ def tsdf_score_poses_band(depth_scaled, scaled_step, rows, cols, intr, voxel_siz
     k, R, t = _fa(intr, 4), _fa(R, 9 * P), _fa(tv2cxP, 3 * P)
     check(_lib.xs_tsdf_score_poses_band(P, _ptr(depth_scaled), scaled_step, rows, cols, k.ctypes.data_as(_f32p), voxel_size, R.ctypes.data_as(_f32p),
                                         t.ctypes.data_as(_f32p), tranc_dist, C.byref(index), _ptr(workspace), _ptr(out2xP), _stream(stream)))
+
+
+VIEW_MAX_POSES = 4096   # XS_VIEW_MAX_POSES
+VIEW_UNKNOWN, VIEW_FREE, VIEW_OCCUPIED = 0, 1, 2
+
+
+def view_opts(rays=(0, 0), t_near=0.0, t_far=0.0, step=None):
+    """An xs_view_opts; zeros (step None) are the library's defaults: 80 x 60 rays, depths 0.2 .. 5.0, a voxel per step."""
+    o = ViewOpts()
+    o.struct_bytes = C.sizeof(ViewOpts)
+    o.rays_x, o.rays_y = int(rays[0]), int(rays[1])
+    o.t_near, o.t_far, o.step = float(t_near), float(t_far), 0.0 if step is None else float(step)
+    return o
+
+
+def view_grid_bytes(res):
+    """xs_view_grid_bytes (host only): the observation grid's buffer for a resolution, 0 for an invalid one."""
+    r = np.ascontiguousarray(res, dtype=np.int32).reshape(-1)
+    assert r.size == 3
+    return int(_lib.xs_view_grid_bytes(r.ctypes.data_as(_i32p)))
+
+
+def view_grid_build(value, weight, vol_step, res, grid, min_weight=1, stream=None):
+    """xs_view_grid_build: the two-bit observation grid of the whole volume into `grid` (view_grid_bytes(res) bytes of device memory)."""
+    r = _ia(res, 3)
+    check(_lib.xs_view_grid_build(_ptr(value), _ptr(weight), vol_step, r.ctypes.data_as(_i32p), int(min_weight), _ptr(grid), _stream(stream)))
+
+
+def view_grid_expand(grid, res, states, stream=None):
+    """xs_view_grid_expand: one byte per voxel into `states` (X * Y * Z uint8 on the device, index (z * Y + y) * X + x)."""
+    r = _ia(res, 3)
+    check(_lib.xs_view_grid_expand(_ptr(grid), r.ctypes.data_as(_i32p), _ptr(states), _stream(stream)))
+
+
+def score_views(Rc2vxP, tc2vxP, intr, rows, cols, res, voxel_size, grid, out4xP, opts=None, stream=None):
+    """xs_score_views: P real camera-to-volume poses Rc2vxP [P, 3, 3], tc2vxP [P, 3] against a built grid in one launch; pose p's
+    {unknown, free, hits, frontier} land at out4xP[4 p : 4 p + 4] (uint32 device tensor of 4 P words).  opts: view_opts(...) or None."""
+    R = np.ascontiguousarray(Rc2vxP, dtype=np.float32).reshape(-1)
+    P = R.size // 9
+    k, R, t, r = _fa(intr, 4), _fa(R, 9 * P), _fa(tc2vxP, 3 * P), _ia(res, 3)
+    check(_lib.xs_score_views(P, R.ctypes.data_as(_f32p), t.ctypes.data_as(_f32p), k.ctypes.data_as(_f32p), rows, cols, r.ctypes.data_as(_i32p),
+                              voxel_size, _ptr(grid), C.byref(opts) if opts is not None else None, _ptr(out4xP), _stream(stream)))
 
 
 class GnOpts(C.Structure):

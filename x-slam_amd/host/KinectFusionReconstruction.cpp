@@ -5,6 +5,7 @@
 #include "KinectFusionReconstruction.h"
 #include "newton_host.hpp"
 #include "score_host.hpp"
+#include "view_host.hpp"
 #include <chrono>
 #include <algorithm>
 #include <cmath>
@@ -1556,6 +1557,63 @@ int KinectFusionReconstruction::RelocalizeGlobal(const DeviceArray2D<ushort> &de
     report[3] = after[2 * (size_t)w];
     report[4] = after[2 * (size_t)w + 1];
     return 1;
+}
+
+// ---- candidate views against the map in one launch, and the next best view ----
+// The observation grid follows the volume the way BandIndexPrepare's index does.  False when the resolution has no grid.
+bool KinectFusionReconstruction::ViewGridPrepare(int min_weight) {
+    const int mw = min_weight < 1 ? 1 : min_weight;
+    const int res[3] = {volume_resolution[0], volume_resolution[1], volume_resolution[2]};
+    const size_t bytes = xs_view_grid_bytes(res);
+    if (bytes == 0) return false;
+    if (view_grid_.size() < bytes) { view_grid_.create(bytes); view_generation_ = -1; }
+    if (view_generation_ == volume_generation && view_min_weight_ == mw) return true;
+    const DeviceArray2D<float> value = tsdf_volume_d_ptr->value();
+    const DeviceArray2D<int> weight = tsdf_volume_d_ptr->weight();
+    if (value.step() != weight.step()) { std::cout << "error::KinectFusionReconstruction, observation grid: value and weight pitches differ" << std::endl; exit(-1); }
+    check_rc(xs_view_grid_build(value.ptr(), weight.ptr(), value.step(), res, mw, view_grid_.ptr(), current_stream()), "ViewGridBuild");
+    view_generation_ = volume_generation;
+    view_min_weight_ = mw;
+    return true;
+}
+
+int KinectFusionReconstruction::ScoreViews(const Matrix4cf *camera2volume, int P, const xs_view_opts *opts, int min_weight, unsigned *out4xP) {
+    if (shard_count > 1) return -2;   // a ray's occlusion is not additive over the ranks' z-slabs
+    if (P < 0 || (P > 0 && (!camera2volume || !out4xP))) return -1;
+    if (!tsdf_volume_d_ptr) return 0;
+    if (P == 0) return 1;
+    hipStream_t st = current_stream();
+    if (!ViewGridPrepare(min_weight)) return -1;
+    if (view_counts_.size() < (size_t)XS_VIEW_MAX_POSES * 4) view_counts_.create((size_t)XS_VIEW_MAX_POSES * 4);
+    const int res[3] = {volume_resolution[0], volume_resolution[1], volume_resolution[2]};
+    std::vector<float> R, t;
+    for (int p0 = 0; p0 < P; p0 += XS_VIEW_MAX_POSES) {
+        const int n = std::min(P - p0, (int)XS_VIEW_MAX_POSES);
+        R.resize((size_t)n * 9); t.resize((size_t)n * 3);
+        for (int i = 0; i < n; ++i)
+            for (int r = 0; r < 3; ++r) {
+                for (int c = 0; c < 3; ++c) R[(size_t)i * 9 + (size_t)r * 3 + c] = camera2volume[p0 + i].m[r][c].real();
+                t[(size_t)i * 3 + r] = camera2volume[p0 + i].m[r][3].real();
+            }
+        const int rc = xs_score_views(n, R.data(), t.data(), &kinect_intrinsic.fx, depth_height, depth_width, res, voxel_size, view_grid_.ptr(), opts,
+                                      view_counts_.ptr(), st);
+        if (rc == (int)hipErrorInvalidValue) return -1;   // the options: nothing was launched
+        check_rc(rc, "ScoreViews");
+        hipSafeCall(hipMemcpyAsync(out4xP + 4 * (size_t)p0, view_counts_.ptr(), (size_t)n * 4 * sizeof(unsigned), hipMemcpyDeviceToHost, st));
+        hipSafeCall(hipStreamSynchronize(st));   // (the grid's pose staging area and the counts are free again)
+    }
+    return 1;
+}
+
+int KinectFusionReconstruction::NextBestView(const Matrix4cf *camera2volume, int P, const xs_view_opts *opts, int min_weight, unsigned min_hits,
+                                             unsigned *out4xP) {
+    std::vector<unsigned> own;
+    if (!out4xP && P > 0) { own.resize((size_t)P * 4); out4xP = own.data(); }
+    const int rc = ScoreViews(camera2volume, P, opts, min_weight, out4xP);
+    if (rc == -1) return -3;   // (-1 is "no pose qualifies" here)
+    if (rc < 0) return rc;
+    if (rc == 0) return -1;
+    return next_best_view(out4xP, P, min_hits);
 }
 
 // reference :334-372

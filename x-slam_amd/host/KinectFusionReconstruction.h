@@ -228,6 +228,16 @@ public:
     int ScorePoses(const DeviceArray2D<ushort> &depth_frame_d, const Matrix4cf *camera2volume, int P, double *out2xP);
     int RelocalizeGlobal(const DeviceArray2D<ushort> &depth_frame_d, const Matrix4cf *candidates, int P, int keep, int iterations, float damping,
                          Matrix4cf &best, double report[8]);
+    // Next best view: what would the camera see from each of P hypothetical camera2volume poses?  ScoreViews casts a
+    // lattice of rays per pose through the observation grid of the volume (two bits per voxel: unknown / free / occupied at `min_weight`;
+    // allocated on first use, rebuilt when volume_generation or min_weight differ from what it was built at) in one launch of xs_score_views
+    // per chunk of XS_VIEW_MAX_POSES: out4xP + 4 p = {unknown, free, hits, frontier} at the real part of camera2volume[p].  opts: null for the
+    // defaults (80 x 60 rays of the level-0 camera, depths 0.2 .. 5.0 in steps of a voxel).  NextBestView scores and returns the index of the
+    // pose with the most unknown samples among those with hits >= min_hits (view_host.hpp), -1 when none qualifies; out4xP may be null.
+    // ScoreViews returns 1 when it ran, 0 without a volume, -1 on bad arguments or options; NextBestView -3 on those and -1 without a volume.
+    // Both return -2 in shard mode with nothing done: occlusion along a ray is not additive over z-slabs.
+    int ScoreViews(const Matrix4cf *camera2volume, int P, const xs_view_opts *opts, int min_weight, unsigned *out4xP);
+    int NextBestView(const Matrix4cf *camera2volume, int P, const xs_view_opts *opts, int min_weight, unsigned min_hits, unsigned *out4xP);
     long long RelocalizationIndexVoxels() const { return band_generation_ >= 0 ? band_.count : 0; }   // the index as last built, 0 before any
     // bumped by everything that writes the volume: integrate calls, loadCheckpoint, xs_kf_volume_ptr(kf, 0, .), RebuildSignMap (the band index is rebuilt
     // when its generation differs)
@@ -302,6 +312,11 @@ private:
     DeviceArray<unsigned char> score_ws_;      // xs_tsdf_score_poses_workspace_bytes(XS_SCORE_MAX_POSES), tickets zeroed once
     DeviceArray<double> score_sums_;           // XS_SCORE_MAX_POSES x 2
     DeviceArray2D<float> score_depth_;         // ScorePoses' scaled depth
+    bool ViewGridPrepare(int min_weight);      // (re)builds view_grid_ when the volume or min_weight changed since it was built
+    DeviceArray<unsigned char> view_grid_;     // xs_view_grid_bytes(resolution): the observation grid + a launch's poses
+    DeviceArray<unsigned> view_counts_;        // XS_VIEW_MAX_POSES x 4
+    long long view_generation_ = -1;           // the volume_generation view_grid_ was built at
+    int view_min_weight_ = 0;                  // and the min_weight
     xs_band_index band_ = {};                  // band index of the owned planes (RelocalizeGaussNewtonBatch)
     long long band_generation_ = -1;           // the volume_generation it was built at
     DeviceArray<unsigned long long> band_keys_;

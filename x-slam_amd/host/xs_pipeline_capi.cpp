@@ -254,6 +254,19 @@ int xs_kf_relocalize_global(void *kf, const uint16_t *depth_dev, size_t step_byt
     std::memcpy(best_c2v32, &best, 32 * sizeof(float));
     return rc;
 }
+static std::vector<Matrix4cf> poses_of(const float *c2v32xP, int poses) {
+    std::vector<Matrix4cf> m((size_t)(poses > 0 ? poses : 0));
+    for (int p = 0; p < poses; ++p) std::memcpy(static_cast<void *>(&m[(size_t)p]), c2v32xP + 32 * (size_t)p, 32 * sizeof(float));
+    return m;
+}
+int xs_kf_score_views(void *kf, int poses, const float *c2v32xP, const xs_view_opts *opts, int min_weight, unsigned *out4xP) {
+    if (poses < 0 || (poses > 0 && (!c2v32xP || !out4xP))) return -1;
+    return ((KF *)kf)->ScoreViews(poses_of(c2v32xP, poses).data(), poses, opts, min_weight, out4xP);
+}
+int xs_kf_next_best_view(void *kf, int poses, const float *c2v32xP, const xs_view_opts *opts, int min_weight, unsigned min_hits, unsigned *out4xP) {
+    if (poses < 0 || (poses > 0 && !c2v32xP)) return -3;
+    return ((KF *)kf)->NextBestView(poses_of(c2v32xP, poses).data(), poses, opts, min_weight, min_hits, out4xP);
+}
 long long xs_kf_relocalization_index_voxels(void *kf) { return ((KF *)kf)->RelocalizationIndexVoxels(); }
 long long xs_kf_export_point_cloud(void *kf, int max_buffer, float *points_host, float *normals_host) {
     const auto pc = ((KF *)kf)->ExportPointCloud(max_buffer);

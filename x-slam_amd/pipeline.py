@@ -44,6 +44,8 @@ _SIGS = {
     "xs_host_newton_step": (C.c_int, [_f64p, C.c_double, _f32p]),
     "xs_kf_score_poses": (C.c_int, [_vp, _vp, _sz, C.c_int, _f32p, _f64p]),
     "xs_kf_relocalize_global": (C.c_int, [_vp, _vp, _sz, C.c_int, _f32p, C.c_int, C.c_int, C.c_float, _f32p, _f64p]),
+    "xs_kf_score_views": (C.c_int, [_vp, C.c_int, _f32p, C.POINTER(capi.ViewOpts), C.c_int, C.POINTER(C.c_uint)]),
+    "xs_kf_next_best_view": (C.c_int, [_vp, C.c_int, _f32p, C.POINTER(capi.ViewOpts), C.c_int, C.c_uint, C.POINTER(C.c_uint)]),
     "xs_kf_relocalization_index_voxels": (C.c_longlong, [_vp]),
     "xs_kf_export_point_cloud": (C.c_longlong, [_vp, C.c_int, _f32p, _f32p]),
     "xs_kf_export_ply": (C.c_longlong, [_vp, C.c_int, C.c_char_p]),
@@ -362,6 +364,44 @@ class KinectFusion:
         report = dict(index=int(rep[0]), S_before=float(rep[1]), S_after=float(rep[2]), sum_loss_after=float(rep[3]), count_after=float(rep[4]),
                       refined_ok=int(rep[5]), index_voxels=int(rep[6]))
         return rc == 1, best.reshape(4, 4, 2), report
+
+    @staticmethod
+    def _view_call(name, rc, bad):
+        if rc == -2:
+            raise capi.XsError(f"{name}: not available in shard mode (occlusion along a ray is not additive over z-slabs)")
+        if rc == bad:
+            raise ValueError(f"{name}: bad arguments or options")
+
+    def score_views(self, c2vs, rays=(80, 60), t_near=0.2, t_far=5.0, step=None, min_weight=1):
+        """What the camera would see from P hypothetical camera2volume poses c2vs [P, 4, 4, 2] (real parts; pose_candidates makes them), one
+        launch over the volume's two-bit observation grid per 4096 poses: uint32 [P, 4] = {unknown, free, hits, frontier} samples per pose
+        along rays[0] x rays[1] rays, depths t_near .. t_far in increments of `step` (None: a voxel).  XsError in shard mode."""
+        m = np.ascontiguousarray(c2vs, dtype=np.float32).reshape(-1)
+        P = m.size // 32
+        assert m.size == 32 * P
+        out = np.zeros((max(P, 1), 4), np.uint32)
+        opts = capi.view_opts(rays, t_near, t_far, step)
+        rc = _lib.xs_kf_score_views(self.h, P, m.ctypes.data_as(_f32p), C.byref(opts), int(min_weight), out.ctypes.data_as(C.POINTER(C.c_uint)))
+        self._view_call("xs_kf_score_views", rc, -1)
+        if rc != 1:
+            raise ValueError("xs_kf_score_views: no volume")
+        return out[:P].copy()
+
+    def next_best_view(self, candidates, min_hits=None, rays=(80, 60), t_near=0.2, t_far=5.0, step=None, min_weight=1):
+        """The candidate ([P, 4, 4, 2]) that sees the most unknown space among those with at least min_hits rays ending on a known surface
+        (None: a quarter of the rays): (index, counts uint32 [P, 4] as score_views returns them); index -1 when no candidate qualifies.
+        XsError in shard mode."""
+        m = np.ascontiguousarray(candidates, dtype=np.float32).reshape(-1)
+        P = m.size // 32
+        assert m.size == 32 * P
+        if min_hits is None:
+            min_hits = int(rays[0]) * int(rays[1]) // 4
+        out = np.zeros((max(P, 1), 4), np.uint32)
+        opts = capi.view_opts(rays, t_near, t_far, step)
+        rc = _lib.xs_kf_next_best_view(self.h, P, m.ctypes.data_as(_f32p), C.byref(opts), int(min_weight), int(min_hits),
+                                       out.ctypes.data_as(C.POINTER(C.c_uint)))
+        self._view_call("xs_kf_next_best_view", rc, -3)
+        return int(rc), out[:P].copy()
 
     def relocalization_index_voxels(self):
         """Band voxels in the relocalisation index as last built by relocalize_batch (0 before the first)."""
