@@ -439,7 +439,11 @@ void bilateral(const uint16_t *src, size_t sstep, int rows, int cols, float *dst
                 for (int cx = std::max(x - D / 2, 0); cx < tx; ++cx) {
                     int tmp = row_ptr(src, sstep, cy)[cx];
                     float space2 = (x - cx) * (x - cx) + (y - cy) * (y - cy);
-                    float color2 = (value - tmp) * (value - tmp);
+                    // The reference squares the int difference (Map.cu:183): signed overflow, undefined, from 46341 mm on (a 60000
+                    // or 65535 outlier beside a measured depth).  The difference is exact in float and the float product rounds the
+                    // exact square once, as the int-to-float conversion does: the same bits wherever the reference is defined.
+                    float diff = float(value - tmp);
+                    float color2 = diff * diff;
                     float w = expf(-(space2 * sigma_space2_inv_half + color2 * sigma_color2_inv_half));
                     sum1 += tmp * w;
                     sum2 += w;

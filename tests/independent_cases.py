@@ -1,6 +1,8 @@
 """The cases that hold a kernel implementation (the CPU oracle on the CPU suite, the HIP kernels through the C ABI on
 the GPU suite) against tests/independent_f64.py: values against the float64 model, CSFD derivatives (imaginary parts / h)
 against float64 central differences.  Test infrastructure."""
+import ctypes as C
+
 import numpy as np
 
 import independent_f64 as ind
@@ -57,6 +59,46 @@ class OracleBackend:
         res = _res(prm, res)
         return self.o.tsdf_gn_terms(depth_m, res, prm["tsdf_voxel_size"], Rs, ts, tranc_dist(prm), intr_of(prm), gt, z0=z0, z1=z1)
 
+
+    # ---- map preparation on pitched host buffers (tests/map_cases.py: Pitched), explicit rows / cols and byte pitches ----
+    def _a(self, buf, u16=False):
+        return C.cast(buf.addr, C.POINTER(C.c_uint16 if u16 else C.c_float))
+
+    def bilateral_p(self, src, dst, rows, cols):
+        self.o._bilateral(self._a(src, True), src.pitch, rows, cols, self._a(dst), dst.pitch)
+
+    def pyr_down_p(self, src, dst, srows, scols):
+        self.o._pyr_down(self._a(src), src.pitch, srows, scols, self._a(dst), dst.pitch)
+
+    def create_vmap_p(self, intr, depth, vmap, rows, cols):
+        k = np.ascontiguousarray(intr, np.float32)
+        self.o._create_vmap(k.ctypes.data_as(C.POINTER(C.c_float)), self._a(depth), depth.pitch, rows, cols, self._a(vmap), vmap.pitch)
+
+    def create_nmap_p(self, vmap, nmap, rows, cols):
+        assert vmap.pitch == nmap.pitch                                 # one map_step in the ABI
+        self.o._create_nmap(rows, cols, self._a(vmap), self._a(nmap), vmap.pitch)
+
+    def resize_p(self, src, dst, srows, scols, normalize):
+        self.o._resize_map(1 if normalize else 0, srows, scols, self._a(src), src.pitch, self._a(dst), dst.pitch)
+
+    def create_vnmaps_p(self, intrs, depths, vmaps, nmaps, rows0, cols0, vreal=None, nreal=None):
+        """The oracle has no fused launch: per level createVMap then createNMap (what the launch stands for), the real planes copied
+        from what those wrote."""
+        for l, (k, d, v, n) in enumerate(zip(intrs, depths, vmaps, nmaps)):
+            rows, cols = rows0 >> l, cols0 >> l
+            self.create_vmap_p(k, d, v, rows, cols)
+            self.create_nmap_p(v, n, rows, cols)
+            for cplx, real in ((v, vreal), (n, nreal)):
+                if real is not None:
+                    c, r = cplx.image[..., 0], real[l].image
+                    keep = np.tile(np.isnan(c[:rows]), (3, 1))
+                    keep[:rows] = False
+                    r[...] = np.where(keep, r, c)
+
+    def resize_pyramid_p(self, vmap0, nmap0, rows0, cols0, vmap1, nmap1, vmap2, nmap2):
+        for m0, m1, m2, nrm in ((vmap0, vmap1, vmap2, False), (nmap0, nmap1, nmap2, True)):
+            self.resize_p(m0, m1, rows0, cols0, nrm)
+            self.resize_p(m1, m2, rows0 // 2, cols0 // 2, nrm)
 
 class GpuBackend:
     """The HIP kernels through the C ABI (x-slam_amd/capi.py)."""
@@ -178,6 +220,62 @@ class GpuBackend:
         return out.cpu().numpy().reshape(F, 29)
 
 
+    # ---- map preparation on pitched buffers (tests/map_cases.py: Pitched): the whole buffer, guard rows and padding included, goes
+    # to the device and comes back; the kernels get the address of image row 0 ----
+    def _up(self, *bufs):
+        ts = [self.t.from_numpy(b.a).cuda() for b in bufs]
+        return ts, [t.data_ptr() + b.pitch for t, b in zip(ts, bufs)]
+
+    def _down(self, bufs, ts):
+        self.t.cuda.synchronize()
+        for b, t in zip(bufs, ts):
+            b.a[...] = t.cpu().numpy()
+
+    def bilateral_p(self, src, dst, rows, cols):
+        ts, (s, d) = self._up(src, dst)
+        self.c.bilateral_filter(s, src.pitch, rows, cols, d, dst.pitch)
+        self._down([dst], ts[1:])
+
+    def pyr_down_p(self, src, dst, srows, scols):
+        ts, (s, d) = self._up(src, dst)
+        self.c.pyr_down(s, src.pitch, srows, scols, d, dst.pitch)
+        self._down([dst], ts[1:])
+
+    def create_vmap_p(self, intr, depth, vmap, rows, cols):
+        ts, (s, d) = self._up(depth, vmap)
+        self.c.create_vmap(intr, s, depth.pitch, rows, cols, d, vmap.pitch)
+        self._down([vmap], ts[1:])
+
+    def create_nmap_p(self, vmap, nmap, rows, cols):
+        assert vmap.pitch == nmap.pitch
+        ts, (s, d) = self._up(vmap, nmap)
+        self.c.create_nmap(s, d, vmap.pitch, rows, cols)
+        self._down([nmap], ts[1:])
+
+    def resize_p(self, src, dst, srows, scols, normalize):
+        ts, (s, d) = self._up(src, dst)
+        (self.c.resize_nmap if normalize else self.c.resize_vmap)(s, src.pitch, srows, scols, d, dst.pitch)
+        self._down([dst], ts[1:])
+
+    def create_vnmaps_p(self, intrs, depths, vmaps, nmaps, rows0, cols0, vreal=None, nreal=None):
+        bufs = list(depths) + list(vmaps) + list(nmaps) + (list(vreal) + list(nreal) if vreal is not None else [])
+        ts, ps = self._up(*bufs)
+        n = len(depths)
+        kw = {}
+        if vreal is not None:
+            kw = dict(vreal=ps[3 * n:4 * n], nreal=ps[4 * n:5 * n], real_steps=[b.pitch for b in vreal])
+            assert [b.pitch for b in vreal] == [b.pitch for b in nreal]
+        assert [b.pitch for b in vmaps] == [b.pitch for b in nmaps]
+        self.c.create_vnmaps(intrs, ps[:n], [b.pitch for b in depths], rows0, cols0, ps[n:2 * n], ps[2 * n:3 * n], [b.pitch for b in vmaps], **kw)
+        self._down(bufs[n:], ts[n:])
+
+    def resize_pyramid_p(self, vmap0, nmap0, rows0, cols0, vmap1, nmap1, vmap2, nmap2):
+        bufs = [vmap0, nmap0, vmap1, nmap1, vmap2, nmap2]
+        assert vmap0.pitch == nmap0.pitch and vmap1.pitch == nmap1.pitch and vmap2.pitch == nmap2.pitch
+        ts, ps = self._up(*bufs)
+        self.c.resize_pyramid(ps[0], ps[1], vmap0.pitch, rows0, cols0, ps[2], ps[3], vmap1.pitch, ps[4], ps[5], vmap2.pitch)
+        self._down(bufs[2:], ts[2:])
+
 def _res(prm, res):
     n = prm["tsdf_size_x"]
     return [n, n, n] if res is None else [int(r) for r in res]
@@ -269,7 +367,8 @@ def check_raycast(be, n=128, scene="s3", seed=(2, 3), threshold=0.0, samples=200
 
 
 def check_icp(be, n=128, scene="s3", seed=(2, 3), threshold=0.0, level=0):
-    """27 complex sums of one ICP iteration (frame 2 against the model maps raycast at the pose of frame 1)."""
+    """27 complex sums of one ICP iteration (frame 2 against the model maps raycast at the pose of frame 1).  The current-frame maps and
+    the resized model maps are the backend's own; they are themselves held against the float64 model in tests/map_cases.py."""
     prm, states = two_frames(be, n, scene, seed, threshold)
     T1 = s1_transforms(1, prm, seed=seed)
     pv, pn, _ = be.raycast(states[2], prm, T1)

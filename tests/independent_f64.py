@@ -327,3 +327,157 @@ def central(f, step):
     fp, _ = f(+step, dec)
     fm, _ = f(-step, dec)
     return f0, (fp - fm) / (2 * step), (fp - 2 * f0 + fm) / (step * step), dec
+
+
+# ------------------------------------------------------------------------------------------------
+# Map preparation — XKinectFusion/src/Map.cu.  Images are [rows, cols]; vertex / normal maps [3, rows, cols] (x, y, z planes).
+SIGMA_SPACE2_INV_HALF = F32(0.5) / (F32(4.5) * F32(4.5))                 # :5, :267 (float32 constants, as the launcher forms them)
+SIGMA_COLOR2_INV_HALF = F32(0.5) / (F32(30) * F32(30))                   # :4, :268
+
+
+def _window(img, r, fill=0):
+    """For every shift (dy, dx) in [-r, r]^2, rows outer as the kernels' loops run: (dy, dx, tap, visited).  tap[y, x] = img[y + dy, x + dx];
+    visited where the clipped loops of bilateralKernel / pyrDownKernel reach it: 0 <= cy < rows - 1 and 0 <= cx < cols - 1 (the upper
+    bound min(y - D/2 + D, rows - 1) is exclusive, :172-179 and :213-221: the last row and column are never read)."""
+    rows, cols = img.shape
+    pad = np.full((rows + 2 * r, cols + 2 * r), fill, img.dtype)
+    pad[r:r + rows, r:r + cols] = img
+    yy, xx = np.mgrid[0:rows, 0:cols]
+    for dy in range(-r, r + 1):
+        for dx in range(-r, r + 1):
+            cy, cx = yy + dy, xx + dx
+            yield dy, dx, pad[r + dy:r + dy + rows, r + dx:r + dx + cols], (cy >= 0) & (cy < rows - 1) & (cx >= 0) & (cx < cols - 1)
+
+
+def bilateral(depth_u16, band=None):
+    """bilateralKernel :155-191 before the conversion to an integer: (q, amin), q = sum tmp * w / sum w in float64 over the taps visited,
+    w = exp(-(space2 * sigma_space2_inv_half + color2 * sigma_color2_inv_half)), amin = the smallest exponent argument over those taps
+    (where it is large every float32 weight is 0 and the kernel divides 0 by 0).  band = (lo, hi): also the number of visited taps
+    per pixel whose argument lies in (lo, hi).  The colour distance is taken as the number (value - tmp)^2."""
+    v = np.asarray(depth_u16).astype(np.float64)
+    s1, s2 = np.zeros(v.shape), np.zeros(v.shape)
+    amin = np.full(v.shape, np.inf)
+    nband = np.zeros(v.shape, np.int64)
+    for dy, dx, tmp, vis in _window(v, 6):
+        arg = (dx * dx + dy * dy) * float(SIGMA_SPACE2_INV_HALF) + (v - tmp) ** 2 * float(SIGMA_COLOR2_INV_HALF)   # :182-186
+        w = np.where(vis, np.exp(-arg), 0.0)
+        s1 += tmp * w                                                    # :188-189
+        s2 += w
+        amin = np.where(vis, np.minimum(amin, arg), amin)
+        if band is not None:
+            nband += vis & (arg > band[0]) & (arg < band[1])
+    with np.errstate(invalid="ignore", divide="ignore"):
+        q = s1 / s2
+    return (q, amin) if band is None else (q, amin, nband)
+
+
+def bilateral_f32(depth_u16):
+    """The same quotient with every operation of :180-192 rounded to float32 and the taps added in the kernel's order (rows outer,
+    columns inner) — one legitimate float32 evaluation, the measure of how far such evaluations may lie from bilateral()'s q."""
+    v = np.asarray(depth_u16).astype(np.int64)
+    s1, s2 = np.zeros(v.shape, F32), np.zeros(v.shape, F32)
+    with np.errstate(under="ignore"):
+        for dy, dx, tmp, vis in _window(v, 6):
+            space2 = F32(dx * dx + dy * dy)
+            color2 = ((v - tmp) ** 2).astype(F32)
+            w = np.exp(-(space2 * SIGMA_SPACE2_INV_HALF + color2 * SIGMA_COLOR2_INV_HALF))
+            assert w.dtype == F32
+            s1 = np.where(vis, s1 + tmp.astype(F32) * w, s1)
+            s2 = np.where(vis, s2 + w, s2)
+        with np.errstate(invalid="ignore", divide="ignore"):
+            return (s1 / s2).astype(np.float64)
+
+
+def bilateral_post(r):
+    """:192-196 on an integer candidate r = __float2int_rn(sum1 / sum2): 0 outside [200, 5000] mm, then the clamp to a short."""
+    r = np.asarray(r, np.int64)
+    r = np.where((r > 5000) | (r < 200), 0, r)
+    return np.clip(r, 0, 32767)
+
+
+def pyr_down(depth_re):
+    """pyrDownKernel :202-230, exact: int64 [rows // 2, cols // 2] from the real parts of the source (any float values)."""
+    r = np.rint(np.asarray(depth_re, np.float64)).astype(np.int64)      # :211, :222 __float2int_rn, ties to even
+    srows, scols = r.shape
+    drows, dcols = srows // 2, scols // 2                                # :275
+    sel = (slice(0, 2 * drows, 2), slice(0, 2 * dcols, 2))               # the window of (y, x) is centred on source pixel (2y, 2x)
+    center = r[sel]
+    s, n = np.zeros((drows, dcols), np.int64), np.zeros((drows, dcols), np.int64)
+    for dy, dx, val, vis in _window(r, 2):
+        use = vis[sel] & (np.abs(val[sel] - center) < 90)               # :223 |val - center| < 3 * sigma_color
+        s += np.where(use, val[sel], 0)
+        n += use
+    return np.sign(s) * (np.abs(s) // n)                                 # :228 C integer division
+
+
+def vertex_map(intr, depth_c):
+    """computeVmapKernel :8-29 for a complex depth [rows, cols, 2] in mm: (value [3, rows, cols], first-order part [3, rows, cols],
+    sentinel [rows, cols]).  Every operation is linear in z, so the imaginary part passes through the same factors."""
+    fx, fy, cx, cy = (float(F32(v)) for v in intr)
+    d = np.asarray(depth_c, np.float64)
+    rows, cols = d.shape[:2]
+    z, dz = d[..., 0] / 1000.0, d[..., 1] / 1000.0                       # :16
+    v, u = np.mgrid[0:rows, 0:cols].astype(np.float64)
+    kx, ky = (u - cx) / fx, (v - cy) / fy                                # :19-20
+    return np.stack([z * kx, z * ky, z]), np.stack([dz * kx, dz * ky, dz]), z == 0   # :18 tests the real part only
+
+
+def _at(m, dtype):
+    m = np.asarray(m)
+    rows = m.shape[0] // 3
+    m = m.reshape(3, rows, m.shape[1], 2).astype(dtype)
+    return m[..., 0], m[..., 1]
+
+
+def _norm3(v):
+    return np.sqrt((v * v).sum(0))
+
+
+def normal_map(vmap, d=0.0, h=1.0, dtype=np.float64):
+    """computeNmapKernel :32-70 on the vertex map as given ([3 * rows, cols, 2] float32): (normal [3, rows, cols], sentinel [rows, cols],
+    kappa [rows, cols], dscale [rows, cols]).  The three taps are taken at Re + d * Im / h; d is a scalar or one offset per output
+    pixel [rows, cols].  kappa = |a| |b| / |a x b| (a = v01 - v00, b = v10 - v00) is the condition number of the direction; dscale =
+    (|v01'| + |v00'|) / |a| + (|v10'| + |v00'|) / |b| with v' = Im / h is the size of the relative change of the two edges per unit seed."""
+    re, im = _at(vmap, dtype)
+    rows, cols = re.shape[1:]
+    sh = lambda a, dy, dx: np.pad(a, ((0, 0), (0, dy), (0, dx)), constant_values=np.nan)[:, dy:dy + rows, dx:dx + cols]
+    k = np.asarray(d, dtype) / dtype(h)
+    tap = lambda dy, dx: sh(re, dy, dx) + k * sh(im, dy, dx)
+    v00, v01, v10 = tap(0, 0), tap(0, 1), tap(1, 0)                      # :47-58
+    nan = lambda dy, dx: np.isnan(sh(re, dy, dx)[0])
+    sentinel = nan(0, 0) | nan(0, 1) | nan(1, 0)                         # :51 (x plane only), and :41 the last row / column (padded NaN)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        a, b = v01 - v00, v10 - v00
+        m = np.stack([a[1] * b[2] - a[2] * b[1], a[2] * b[0] - a[0] * b[2], a[0] * b[1] - a[1] * b[0]])   # :60 cross
+        n = m / _norm3(m)                                                # :60 normalized
+        kappa = _norm3(a) * _norm3(b) / _norm3(m)
+        dn = lambda dy, dx: _norm3(sh(im, dy, dx)) / abs(dtype(h))
+        dscale = (dn(0, 1) + dn(0, 0)) / _norm3(a) + (dn(1, 0) + dn(0, 0)) / _norm3(b)
+    return n, sentinel, kappa, dscale
+
+
+def resize(m, normalize, d=0.0, h=1.0, dtype=np.float64):
+    """resizeMapKernel<normalize> :105-152 on a map [3 * srows, cols, 2]: (out [3, srows // 2, scols // 2], sentinel, mag, dmag).
+    out = the mean of the 2 x 2 block of each plane (then normalized); the sentinel is set if any of the four x-plane entries is NaN
+    (:124-127).  mag [3, ...] = sum |x_i| / 4 per component and dmag the same of the first-order parts Im / h: the sizes the
+    rounding of the three additions is relative to.  d: a scalar or one offset per output pixel."""
+    re, im = _at(m, dtype)
+    drows, dcols = re.shape[1] // 2, re.shape[2] // 2                    # :238-239: an odd source drops its last row / column
+    blk = lambda a: [a[:, i:2 * drows:2, j:2 * dcols:2] for i in (0, 1) for j in (0, 1)]   # x00 x01 x10 x11
+    k = np.asarray(d, dtype) / dtype(h)
+    taps = [r + k * i for r, i in zip(blk(re), blk(im))]
+    sentinel = np.isnan(np.stack([t[0] for t in blk(re)])).any(0)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        out = (taps[0] + taps[1] + taps[2] + taps[3]) / dtype(4)         # :131, :138, :145
+        mag = sum(np.abs(t) for t in blk(re)) / dtype(4)
+        dmag = sum(np.abs(t) for t in blk(im)) / dtype(4) / abs(dtype(h))
+        if normalize:
+            out = out / _norm3(out)                                      # :146-147
+    return out, sentinel, mag, dmag
+
+
+def central4(f, step):
+    """Fourth-order central difference (-f(2s) + 8 f(s) - 8 f(-s) + f(-2s)) / 12 s of an array-valued f(d); s may hold one step per
+    element.  The map kernels' derivatives are checked to a few float32 ulps times the condition number: the second-order stencil
+    cannot be both that exact and above float64 round-off where kappa reaches the hundreds."""
+    return (-f(2 * step) + 8 * f(step) - 8 * f(-step) + f(-2 * step)) / (12 * step)
