@@ -237,12 +237,34 @@ __device__ __forceinline__ double pair_swap(double v) {
     return __longlong_as_double(((unsigned long long)(unsigned)hi << 32) | (unsigned)lo);
 }
 
-// the per-wave partial sums of a workgroup, added in wave order
-template <int WAVES>
-__device__ __forceinline__ double wave_order_sum(const double (*smem)[NP], int k) {
-    double t = smem[0][k];
+// two neighbouring doubles moved as one 16-byte value (a record chunk, a pair of sums)
+struct alignas(16) d2 { double x, y; };
+
+// The per-wave partial sums of a workgroup, added in wave order — values k0 (even) and k0 + 1 together: one 16-byte LDS read per slot
+// fetches both, the reads go out ten slots at a time before anything is added, and the two chains advance side by side.  (One value
+// at a time this was two ladders of read -> wait -> add, 2 x 19 dependent steps on the sixteen-wave instance, with two or three reads
+// in flight.)  The register tie after each batch keeps the next batch's reads behind it and both chains in step — without it the compiler
+// sinks the y chain into the caller's guarded store and reads that half again, value by value; it never sits between the reads of a batch.
+// smem rows are 448 bytes apart and 16-byte aligned.
+template <int SLOTS>
+__device__ __forceinline__ d2 wave_order_sum2(const double (*smem)[NP], int k0) {
+    constexpr int BATCH = 10;
+    const d2 *p = reinterpret_cast<const d2 *>(&smem[0][k0]);
+    d2 t = {0.0, 0.0};
 #pragma unroll
-    for (int w = 1; w < WAVES; ++w) t += smem[w][k];
+    for (int w0 = 0; w0 < SLOTS; w0 += BATCH) {
+        d2 v[BATCH];
+#pragma unroll
+        for (int k = 0; k < BATCH; ++k)
+            if (w0 + k < SLOTS) v[k] = p[(w0 + k) * (NP / 2)];
+#pragma unroll
+        for (int k = 0; k < BATCH; ++k)
+            if (w0 + k < SLOTS) {
+                if (w0 + k == 0) t = v[k];
+                else { t.x += v[k].x; t.y += v[k].y; }
+            }
+        asm volatile("" : "+v"(t.x), "+v"(t.y));
+    }
     return t;
 }
 
@@ -373,7 +395,7 @@ __global__ void __launch_bounds__(64 * WAVES)
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int tiles_x = (a.cols + 63) / 64;
     const int ntiles = tiles_x * (a.y1 - a.y0);
-    __shared__ double smem[SLOTS][NP];
+    __shared__ __attribute__((aligned(16))) double smem[SLOTS][NP];   // (wave_order_sum2 reads it in 16-byte pairs)
     // one LDS buffer for the fold's tile and, afterwards, the last workgroup's row-group sums
     constexpr int PV = (NS + 1 + PASSES - 1) / PASSES;   // eight-wave instance: 55, 28 or 19 values per pass
     constexpr int RS = 68;                               // ... in rows 68 floats apart
@@ -550,12 +572,10 @@ __global__ void __launch_bounds__(64 * WAVES)
         // no last workgroup gathering 512 records from memory.  The host spins on the sequence words and adds the
         // records in index order (xs_icp_sum_records): the same deterministic association for every launch.
         if (threadIdx.x < 64) {
-            struct alignas(16) d2 { double x, y; };
             if (threadIdx.x < NP / 2) {
                 const int k0 = 2 * threadIdx.x, k1 = k0 + 1;
-                d2 v;
-                v.x = wave_order_sum<SLOTS>(smem, k0);
-                v.y = k1 <= NS ? wave_order_sum<SLOTS>(smem, k1) : 0.0;
+                d2 v = wave_order_sum2<SLOTS>(smem, k0);
+                if (k1 > NS) v.y = 0.0;   // (the pad column of smem is never written)
                 if (k1 <= NS) reinterpret_cast<d2 *>(a.host_records)[(size_t)blockIdx.x * (NP / 2) + threadIdx.x] = v;
                 else a.host_records[(size_t)blockIdx.x * NP + k0] = v.x;      // the count; the pad word is the sequence slot
             }
@@ -573,8 +593,9 @@ __global__ void __launch_bounds__(64 * WAVES)
         // six hundred do).
         const int k0 = 2 * threadIdx.x, k1 = k0 + 1;
         double *rec = a.partials + (size_t)blockIdx.x * NP;
-        __hip_atomic_store(rec + k0, wave_order_sum<SLOTS>(smem, k0), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __hip_atomic_store(rec + k1, k1 <= NS ? wave_order_sum<SLOTS>(smem, k1) : 0.0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        const d2 v = wave_order_sum2<SLOTS>(smem, k0);
+        __hip_atomic_store(rec + k0, v.x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_store(rec + k1, k1 <= NS ? v.y : 0.0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // (the pad column of smem is never written)
     }
     // publish: the storing wave waits until its write-through stores are acknowledged, then its first lane takes a ticket
     // (same wave, program order: no barrier in between); the atomic is performed at agent scope after the records are in memory
@@ -604,7 +625,6 @@ __global__ void __launch_bounds__(64 * WAVES)
         // flight, and the row groups are then added in group order — a fixed association, so
         // deterministic — leaving two or three memory round trips where a plain loop had sixteen.  (Level 0's 600 records
         // are 269 KB through one CU's 64 B / clk: ~1.8 us of the 3.4 us this takes is that, whatever the depth.)
-        struct alignas(16) d2 { double x, y; };
         // (eight waves: twice the threads, so eighteen row groups with sixteen loads each in flight — the same bytes in
         // flight per workgroup at half the registers per lane, which is what lets this instance run at four waves per SIMD)
         constexpr int G = WAVES == 16 ? 36 : (WAVES == 8 ? 18 : 9), DEPTH = WAVES == 16 ? 8 : (WAVES == 8 ? 16 : 32);
@@ -640,16 +660,29 @@ __global__ void __launch_bounds__(64 * WAVES)
         XS_STAMP(8);
         if (threadIdx.x < 28) {
             d2 t = s_red[0][threadIdx.x];
+#ifdef XS_ICP_TAIL_BASELINE
 #pragma unroll
-            for (int gg = 1; gg < G; ++gg) {
-                t.x += s_red[gg][threadIdx.x].x; t.y += s_red[gg][threadIdx.x].y;
-                // (both chains advance together: left alone the compiler sinks the y chain into the guarded store below, keeps all G
-                // y values live across the x chain — 36 x 4 registers at sixteen waves — and spills them: five dependent scratch reloads,
-                // 2-3.5 us at the very end of every level-0 launch, profiles/r03_icp_phases.txt)
-#ifndef XS_ICP_TAIL_BASELINE
+            for (int gg = 1; gg < G; ++gg) { t.x += s_red[gg][threadIdx.x].x; t.y += s_red[gg][threadIdx.x].y; }
+#else
+            // The group sums are read nine at a time — all reads of a batch go out before its first addition — and added in group
+            // order, both chains side by side.  Both chains are tied to registers after every batch: left alone the compiler sinks
+            // the y chain into the guarded store below, keeps all G y values live across the x chain — 36 x 4 registers at sixteen
+            // waves — and spills them: five dependent scratch reloads, 2-3.5 us at the very end of every level-0 launch
+            // (profiles/r03_icp_phases.txt).  The tie used to follow every addition, and no LDS read moved across it: 35 round trips
+            // of read -> wait -> add where four batches do (profiles/icp_tail_chain.txt).
+            constexpr int BATCH = 9;
+#pragma unroll
+            for (int g0 = 1; g0 < G; g0 += BATCH) {
+                d2 v[BATCH];
+#pragma unroll
+                for (int k = 0; k < BATCH; ++k)
+                    if (g0 + k < G) v[k] = s_red[g0 + k][threadIdx.x];
+#pragma unroll
+                for (int k = 0; k < BATCH; ++k)
+                    if (g0 + k < G) { t.x += v[k].x; t.y += v[k].y; }
                 asm volatile("" : "+v"(t.x), "+v"(t.y));
-#endif
             }
+#endif
             if (a.pairs) {
                 // Every sum leaves as ONE 16-byte store {sequence number, sum}: a store of one lane cannot be seen in halves, so the host
                 // needs no word that is ordered behind the others — and the kernel no wait for its stores' acknowledgement, barrier and
