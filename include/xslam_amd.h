@@ -472,6 +472,62 @@ typedef struct xs_view_opts {
 int xs_score_views(int poses, const float *Rc2v9xP, const float *tc2v3xP, const float *intr4, int rows, int cols, const int *res,
                    float voxel_size, const void *grid, const xs_view_opts *opts, unsigned *out4xP_dev, void *stream);
 
+/* ---- clearance and reachability from the observation grid (xs_reach.hip) ----------------------------------------
+ * No counterpart in the reference.  Integer arithmetic on the grid's states throughout: every result is a pure function of the inputs, two
+ * runs give equal bytes, no floating-point atomics.  `grid` is the observation grid as xs_view_grid_build leaves it; the volumes are not read.
+ * CLEARANCE FIELD.  Obstacles: the OCCUPIED voxels; with unknown_blocks = 1 also the UNKNOWN voxels and every voxel position outside
+ * [0, res) (outside the volume nothing is known).  The padding bits of overhanging bricks are never read as a state.
+ *   field[(z * Y + y) * X + x] (uint16, dense) = min(d2, R * R), R = max_radius in voxels (1 .. XS_CLEARANCE_MAX_RADIUS), d2 the least
+ *   dx * dx + dy * dy + dz * dz from the voxel to an obstacle voxel: 0 on obstacles, R * R everywhere when there is no obstacle at all.
+ * Three plain launches on the stream (a distance along x per voxel, then a windowed minimum of f(j) + (j - i)^2 over |j - i| <= R along y
+ * and along z; exact under the cap, since an obstacle within distance R lies in the R-cube and every other candidate is above R * R);
+ * the intermediates live in `workspace` (xs_clearance_workspace_bytes: three bytes per voxel; 256-byte aligned device memory).
+ * xs_clearance_bytes: the field's size, 2 bytes per voxel.  Both sizes are 0 for a resolution with a non-positive axis, or with Y or Z above
+ * 65535.  Host only.
+ * xs_clearance_build: hipErrorInvalidValue, with nothing launched and `field` untouched, for max_radius outside 1 .. 255, unknown_blocks
+ * other than 0 or 1, such a resolution, or a null pointer.  No synchronisation. */
+#define XS_CLEARANCE_MAX_RADIUS 255
+size_t xs_clearance_bytes(const int *res);
+size_t xs_clearance_workspace_bytes(const int *res);
+int xs_clearance_build(const void *grid, const int *res, int max_radius, int unknown_blocks, void *workspace, unsigned short *field_dev, void *stream);
+/* REACHABILITY.  A voxel is PASSABLE iff its state is FREE and field >= r2 (r2 an integer, 1 .. R * R of the field the caller built: a body
+ * of squared radius r2 voxels fits there).  REACHED is the union of the 6-connected (face-neighbour) components of the passable set that hold
+ * a seed.  `reach` (xs_reach_bytes(res) bytes, 8-byte aligned device memory) holds both as one 64-bit mask per brick of 4 x 4 x 4 voxels,
+ * bricks in the grid's order, voxel (lx, ly, lz) at bit lx + 4 ly + 16 lz, overhang bits clear: the reached words first, the passable
+ * words behind them, then the flood's control words.
+ * xs_reach_passable: the passable words alone (what a start is snapped over before the flood).  No synchronisation.
+ * xs_reach_flood: `seeds` (1 .. XS_REACH_MAX_SEEDS) integer voxels, host array seeds3xN + 3 k = (x, y, z).  A seed outside the volume or not
+ * passable contributes nothing (no error); duplicates are harmless.  Builds the passable words, clears the reached words, sets the seeds'
+ * bits and runs rounds as plain launches: a lane owns one brick word, grows it to its in-brick fixpoint, pulls the facing bits of the six
+ * neighbouring words, writes its own word only and sets a `changed` word with a plain store if it grew.  Words only gain bits, so in-place
+ * update needs no atomics and the result does not depend on scheduling (the number of rounds may).  The host reads the changed words back
+ * after each batch of rounds and stops after the first round that changed nothing: THE CALL SYNCHRONISES THE STREAM.  *rounds_out (optional)
+ * receives the number of rounds up to and including that one.
+ * xs_reach_expand: out_dev[(z * Y + y) * X + x] = 0 or 1 from the reached words (passable = 0) or the passable words (passable = 1): tests
+ * and viewers.  No synchronisation.
+ * hipErrorInvalidValue with nothing written: seeds outside 1 .. 64, r2 < 1 (or above 255 * 255), a bad resolution, null pointers. */
+#define XS_REACH_MAX_SEEDS 64
+size_t xs_reach_bytes(const int *res);
+int xs_reach_passable(const void *grid, const unsigned short *field_dev, const int *res, int r2, void *reach, void *stream);
+int xs_reach_flood(const void *grid, const unsigned short *field_dev, const int *res, int r2, const int *seeds3xN, int seeds, void *reach,
+                   int *rounds_out, void *stream);
+int xs_reach_expand(const void *reach, const int *res, int passable, unsigned char *out_dev, void *stream);
+/* POINT QUERY.  n >= 1 points in volume coordinates (float32 metres, device array points3xN_dev + 3 i).  The voxel s of a point is
+ * floor(p[c] / voxel_size) per axis by an IEEE divide, as in the raycast and xs_score_views, tested against [0, res) before anything is
+ * fetched (a NaN is outside).  Per point: reachable_dev[i] (0 or 1) and clear2_dev[i] (a field value):
+ *   outside the volume                               (0, 0)
+ *   s is in the mask                                 (1, field[s])
+ *   otherwise, snap > 0 (voxels, <= XS_REACH_MAX_SNAP): the voxel v of the mask with |v - s|_inf <= snap that has the least |v - s|^2,
+ *                                                    ties to the lowest linear index (z * Y + y) * X + x:   (1, field[v])
+ *   no such voxel, or snap = 0                       (0, field[s])
+ * The mask is the reached words of `reach`, or with over_passable = 1 the passable words.  voxel3xN_dev (optional, int32) receives the
+ * answering voxel (s or v), (-1, -1, -1) where the answer is 0.  hipErrorInvalidValue with nothing written: n < 1, snap outside 0 .. 16,
+ * voxel_size not positive, a bad resolution, null pointers.  No synchronisation. */
+#define XS_REACH_MAX_SNAP 16
+int xs_reach_query(int n, const float *points3xN_dev, const int *res, float voxel_size, const void *reach, int over_passable,
+                   const unsigned short *field_dev, int snap, unsigned char *reachable_dev, unsigned short *clear2_dev, int *voxel3xN_dev,
+                   void *stream);
+
 /* ---- surface extraction (export; real-valued) ------------------------------------------------ */
 size_t xs_extract_workspace_bytes(const int *res);
 /* size_t extractPoints(value_volume, weight_volume, grad_volume, volume_resolution, voxel_size,

@@ -132,6 +132,26 @@ struct xs_view_opts;
 int xs_kf_score_views(void *kf, int poses, const float *c2v32xP, const struct xs_view_opts *opts, int min_weight, unsigned *out4xP);
 int xs_kf_next_best_view(void *kf, int poses, const float *c2v32xP, const struct xs_view_opts *opts, int min_weight, unsigned min_hits,
                          unsigned *out4xP);
+/* Clearance and reachability of candidate views: can the camera be at a candidate, and get there?
+ * clearance_field: the field of xs_clearance_build (xslam_amd.h: the contract) over the observation grid at weight gate min_weight, R =
+ * max_radius_vox (1 .. 255), unknown_blocks 0 or 1: host_out[(z * Y + y) * X + x] = min(d^2, R^2) to the nearest obstacle voxel.
+ * reachable: the body's radius becomes rv = radius_m / voxel_size (a float32 divide), r2 = max(1, (int)ceilf(rv * rv)), R the smallest integer
+ * with R * R >= r2 (bad arguments if R exceeds 255).  The start is the real translation of start_c2v32 (NULL: the current camera2volume),
+ * its voxel snapped to the nearest passable voxel (FREE and field >= r2) within snap_vox (0 .. 16; ties as xs_reach_query breaks them) — the
+ * camera's own voxel is usually UNKNOWN, the sensor observes nothing at its own centre.  No such voxel: nothing is reachable, which is a
+ * result.  The known free space the body fits in is flooded from there; reachable[p] = 1 iff the centre voxel of pose c2v32xP + 32 p (not
+ * snapped) was reached, clear2[p] the field's value there (0 outside the volume).  The field, the flood and the grid are cached and
+ * redone when the volume, min_weight, unknown_blocks, R, r2 or the snapped seed change.
+ * Both return 1 when they ran, 0 without a volume, -1 on bad arguments, -2 in shard mode (nothing is done: distance and connectivity are
+ * not additive over z-slabs, and a halo exchange is not built).
+ * next_reachable_view: xs_kf_next_best_view's scoring and rule restricted to the candidates reachable from the current camera;
+ * `reachable` (optional) receives the flags.  The index, -1 when no reachable pose qualifies or there is no volume, -2 in shard mode, -3 on
+ * bad arguments or options.  xs_kf_next_best_view itself and its results do not change. */
+int xs_kf_clearance_field(void *kf, int max_radius_vox, int unknown_blocks, int min_weight, uint16_t *host_out);
+int xs_kf_reachable(void *kf, const float *start_c2v32_or_null, float radius_m, int snap_vox, int unknown_blocks, int min_weight, int P, const float *c2v32xP,
+                    unsigned char *reachable, unsigned short *clear2);
+int xs_kf_next_reachable_view(void *kf, int poses, const float *c2v32xP, const struct xs_view_opts *opts, int min_weight, unsigned min_hits, unsigned *out4xP,
+                              float radius_m, int snap_vox, int unknown_blocks, unsigned char *reachable);
 /* band voxels in the relocalisation index as last built (0 before the first batch) */
 long long xs_kf_relocalization_index_voxels(void *kf);
 /* ExportPointCloud(max_buffer)  .cpp:334-372 (+ CPointCloud::exportPly, main.cpp:78-80): zero-crossing points of

@@ -69,6 +69,14 @@ _SIGS = {
     "xs_view_grid_build": (C.c_int, [_vp, _vp, _sz, _i32p, C.c_int, _vp, _vp]),
     "xs_view_grid_expand": (C.c_int, [_vp, _i32p, _vp, _vp]),
     "xs_score_views": (C.c_int, [C.c_int, _f32p, _f32p, _f32p, C.c_int, C.c_int, _i32p, C.c_float, _vp, C.POINTER(ViewOpts), _vp, _vp]),
+    "xs_clearance_bytes": (_sz, [_i32p]),
+    "xs_clearance_workspace_bytes": (_sz, [_i32p]),
+    "xs_clearance_build": (C.c_int, [_vp, _i32p, C.c_int, C.c_int, _vp, _vp, _vp]),
+    "xs_reach_bytes": (_sz, [_i32p]),
+    "xs_reach_passable": (C.c_int, [_vp, _vp, _i32p, C.c_int, _vp, _vp]),
+    "xs_reach_flood": (C.c_int, [_vp, _vp, _i32p, C.c_int, _i32p, C.c_int, _vp, _i32p, _vp]),
+    "xs_reach_expand": (C.c_int, [_vp, _i32p, C.c_int, _vp, _vp]),
+    "xs_reach_query": (C.c_int, [C.c_int, _vp, _i32p, C.c_float, _vp, C.c_int, _vp, C.c_int, _vp, _vp, _vp, _vp]),
     "xs_integrate_scaled_ex2": (C.c_int, [_vp, _sz, C.c_int, C.c_int, _f32p, C.c_int, _i32p, C.c_float, _f32p, _f32p, C.c_float, _vp, _vp, _vp,
                                          _sz, C.c_float, C.c_int, C.c_int, _vp, _vp, _vp, C.POINTER(IntegrateOpts), _vp]),
     "xs_integrate_classify_ex": (C.c_int, [C.c_int, C.c_int, _f32p, _i32p, C.c_float, _f32p, _f32p, C.c_float, C.c_int, C.c_int, _vp, _vp,
@@ -594,6 +602,68 @@ def score_views(Rc2vxP, tc2vxP, intr, rows, cols, res, voxel_size, grid, out4xP,
     k, R, t, r = _fa(intr, 4), _fa(R, 9 * P), _fa(tc2vxP, 3 * P), _ia(res, 3)
     check(_lib.xs_score_views(P, R.ctypes.data_as(_f32p), t.ctypes.data_as(_f32p), k.ctypes.data_as(_f32p), rows, cols, r.ctypes.data_as(_i32p),
                               voxel_size, _ptr(grid), C.byref(opts) if opts is not None else None, _ptr(out4xP), _stream(stream)))
+
+
+CLEARANCE_MAX_RADIUS, REACH_MAX_SEEDS, REACH_MAX_SNAP = 255, 64, 16   # XS_CLEARANCE_MAX_RADIUS, XS_REACH_MAX_SEEDS, XS_REACH_MAX_SNAP
+
+
+def _res3(res):
+    r = np.ascontiguousarray(res, dtype=np.int32).reshape(-1)
+    assert r.size == 3
+    return r
+
+
+def clearance_bytes(res):
+    """xs_clearance_bytes (host only): the clearance field, 2 bytes per voxel; 0 for an invalid resolution."""
+    return int(_lib.xs_clearance_bytes(_res3(res).ctypes.data_as(_i32p)))
+
+
+def clearance_workspace_bytes(res):
+    """xs_clearance_workspace_bytes (host only): the intermediates of xs_clearance_build; 0 for an invalid resolution."""
+    return int(_lib.xs_clearance_workspace_bytes(_res3(res).ctypes.data_as(_i32p)))
+
+
+def reach_bytes(res):
+    """xs_reach_bytes (host only): the reached and passable words of a resolution; 0 for an invalid one."""
+    return int(_lib.xs_reach_bytes(_res3(res).ctypes.data_as(_i32p)))
+
+
+def clearance_build(grid, res, max_radius, unknown_blocks, workspace, field, stream=None):
+    """xs_clearance_build: field[(z Y + y) X + x] (uint16 device tensor) = min(d^2, R^2) to the nearest obstacle of a built observation grid."""
+    r = _res3(res)
+    check(_lib.xs_clearance_build(_ptr(grid), r.ctypes.data_as(_i32p), int(max_radius), int(unknown_blocks), _ptr(workspace), _ptr(field), _stream(stream)))
+
+
+def reach_passable(grid, field, res, r2, reach, stream=None):
+    """xs_reach_passable: the passable words (FREE and field >= r2) of `reach` alone."""
+    r = _res3(res)
+    check(_lib.xs_reach_passable(_ptr(grid), _ptr(field), r.ctypes.data_as(_i32p), int(r2), _ptr(reach), _stream(stream)))
+
+
+def reach_flood(grid, field, res, r2, seeds, reach, stream=None):
+    """xs_reach_flood: the passable voxels 6-connected to one of `seeds` ([N, 3] integer voxels (x, y, z), N = 1 .. 64) into the reached
+    words of `reach`.  Synchronises the stream.  Returns the number of rounds."""
+    r = _res3(res)
+    s = np.ascontiguousarray(seeds, dtype=np.int32).reshape(-1)
+    assert s.size % 3 == 0
+    rounds = C.c_int(-1)
+    check(_lib.xs_reach_flood(_ptr(grid), _ptr(field), r.ctypes.data_as(_i32p), int(r2), s.ctypes.data_as(_i32p), s.size // 3, _ptr(reach),
+                              C.byref(rounds), _stream(stream)))
+    return int(rounds.value)
+
+
+def reach_expand(reach, res, out, passable=False, stream=None):
+    """xs_reach_expand: one byte (0 or 1) per voxel into `out` from the reached words, or the passable ones."""
+    r = _res3(res)
+    check(_lib.xs_reach_expand(_ptr(reach), r.ctypes.data_as(_i32p), int(bool(passable)), _ptr(out), _stream(stream)))
+
+
+def reach_query(n, points, res, voxel_size, reach, field, reachable, clear2, snap=0, over_passable=False, voxel=None, stream=None):
+    """xs_reach_query: n points (float32 device tensor of 3 n metres in volume coordinates) -> reachable (uint8) and clear2 (uint16); voxel
+    (optional int32 device tensor of 3 n) receives the answering voxels."""
+    r = _res3(res)
+    check(_lib.xs_reach_query(int(n), _ptr(points), r.ctypes.data_as(_i32p), float(voxel_size), _ptr(reach), int(bool(over_passable)), _ptr(field),
+                              int(snap), _ptr(reachable), _ptr(clear2), _ptr(voxel), _stream(stream)))
 
 
 class GnOpts(C.Structure):

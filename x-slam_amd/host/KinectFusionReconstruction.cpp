@@ -1616,6 +1616,114 @@ int KinectFusionReconstruction::NextBestView(const Matrix4cf *camera2volume, int
     return next_best_view(out4xP, P, min_hits);
 }
 
+// ---- clearance and reachability of candidate views ----
+// The field follows the grid, the grid the volume.  False when the resolution has no field.
+bool KinectFusionReconstruction::ClearancePrepare(int R, int unknown_blocks, int min_weight) {
+    const int mw = min_weight < 1 ? 1 : min_weight;
+    const int res[3] = {volume_resolution[0], volume_resolution[1], volume_resolution[2]};
+    const size_t bytes = xs_clearance_bytes(res), ws = xs_clearance_workspace_bytes(res);
+    if (bytes == 0 || !ViewGridPrepare(mw)) return false;
+    if (clear_field_.size() < bytes) { clear_field_.create(bytes); clear_generation_ = -1; }
+    if (clear_ws_.size() < ws) clear_ws_.create(ws);
+    if (clear_generation_ == volume_generation && clear_min_weight_ == mw && clear_R_ == R && clear_unknown_ == unknown_blocks) return true;
+    check_rc(xs_clearance_build(view_grid_.ptr(), res, R, unknown_blocks, clear_ws_.ptr(), reinterpret_cast<unsigned short *>(clear_field_.ptr()),
+                                current_stream()), "ClearanceBuild");
+    clear_generation_ = volume_generation;
+    clear_min_weight_ = mw; clear_R_ = R; clear_unknown_ = unknown_blocks;
+    reach_generation_ = -1;   // (the flood was over another field)
+    return true;
+}
+
+int KinectFusionReconstruction::ClearanceField(int max_radius_vox, int unknown_blocks, int min_weight, unsigned short *host_out) {
+    if (shard_count > 1) return -2;   // a distance is not additive over the ranks' z-slabs
+    if (!host_out || max_radius_vox < 1 || max_radius_vox > XS_CLEARANCE_MAX_RADIUS || (unknown_blocks != 0 && unknown_blocks != 1)) return -1;
+    if (!tsdf_volume_d_ptr) return 0;
+    if (!ClearancePrepare(max_radius_vox, unknown_blocks, min_weight)) return -1;
+    hipStream_t st = current_stream();
+    const int res[3] = {volume_resolution[0], volume_resolution[1], volume_resolution[2]};
+    hipSafeCall(hipMemcpyAsync(host_out, clear_field_.ptr(), xs_clearance_bytes(res), hipMemcpyDeviceToHost, st));
+    hipSafeCall(hipStreamSynchronize(st));
+    return 1;
+}
+
+// n points through xs_reach_query against reach_ and clear_field_, in chunks of 4096; the answers on the host when the call returns
+int KinectFusionReconstruction::ReachQuery(const float *points3xN, int n, int over_passable, int snap, unsigned char *reachable, unsigned short *clear2,
+                                           int *voxel) {
+    enum { CHUNK = 4096, POINTS = 0, VOXEL = CHUNK * 12, CLEAR2 = VOXEL + CHUNK * 12, FLAGS = CLEAR2 + CHUNK * 2, BYTES = FLAGS + CHUNK };
+    if (reach_io_.size() < (size_t)BYTES) reach_io_.create(BYTES);
+    hipStream_t st = current_stream();
+    const int res[3] = {volume_resolution[0], volume_resolution[1], volume_resolution[2]};
+    unsigned char *io = reach_io_.ptr();
+    for (int p0 = 0; p0 < n; p0 += CHUNK) {
+        const int m = std::min(n - p0, (int)CHUNK);
+        hipSafeCall(hipMemcpyAsync(io + POINTS, points3xN + 3 * (size_t)p0, (size_t)m * 12, hipMemcpyHostToDevice, st));
+        const int rc = xs_reach_query(m, reinterpret_cast<const float *>(io + POINTS), res, voxel_size, reach_.ptr(), over_passable,
+                                      reinterpret_cast<const unsigned short *>(clear_field_.ptr()), snap, io + FLAGS, reinterpret_cast<unsigned short *>(io + CLEAR2),
+                                      reinterpret_cast<int *>(io + VOXEL), st);
+        if (rc == (int)hipErrorInvalidValue) return -1;
+        check_rc(rc, "ReachQuery");
+        if (reachable) hipSafeCall(hipMemcpyAsync(reachable + p0, io + FLAGS, (size_t)m, hipMemcpyDeviceToHost, st));
+        if (clear2) hipSafeCall(hipMemcpyAsync(clear2 + p0, io + CLEAR2, (size_t)m * 2, hipMemcpyDeviceToHost, st));
+        if (voxel) hipSafeCall(hipMemcpyAsync(voxel + 3 * (size_t)p0, io + VOXEL, (size_t)m * 12, hipMemcpyDeviceToHost, st));
+        hipSafeCall(hipStreamSynchronize(st));   // (the staging area is free again)
+    }
+    return 1;
+}
+
+int KinectFusionReconstruction::Reachable(const Matrix4cf *start, float radius_m, int snap_vox, int unknown_blocks, int min_weight, int P,
+                                          const Matrix4cf *camera2volume, unsigned char *reachable, unsigned short *clear2) {
+    if (shard_count > 1) return -2;   // connectivity is not additive over the ranks' z-slabs
+    int r2 = 0, R = 0;
+    if (P < 0 || (P > 0 && (!camera2volume || !reachable || !clear2)) || snap_vox < 0 || snap_vox > XS_REACH_MAX_SNAP ||
+        (unknown_blocks != 0 && unknown_blocks != 1) || !reach_radius(radius_m, voxel_size, r2, R))
+        return -1;
+    if (!tsdf_volume_d_ptr) return 0;
+    const int mw = min_weight < 1 ? 1 : min_weight;
+    if (!ClearancePrepare(R, unknown_blocks, mw)) return -1;
+    hipStream_t st = current_stream();
+    const int res[3] = {volume_resolution[0], volume_resolution[1], volume_resolution[2]};
+    const size_t bytes = xs_reach_bytes(res);
+    if (bytes == 0) return -1;
+    if (reach_.size() < bytes) { reach_.create(bytes); reach_generation_ = -1; }
+    const unsigned short *field = reinterpret_cast<const unsigned short *>(clear_field_.ptr());
+    const bool same_field = reach_generation_ == volume_generation && reach_min_weight_ == mw && reach_R_ == R && reach_unknown_ == unknown_blocks && reach_r2_ == r2;
+    // the passable words (those of the last flood, if it was over this field at this r2), and the start snapped over them
+    if (!same_field) check_rc(xs_reach_passable(view_grid_.ptr(), field, res, r2, reach_.ptr(), st), "ReachPassable");
+    const Matrix4cf from = start ? *start : getCamera2Volume();
+    const float p[3] = {from.m[0][3].real(), from.m[1][3].real(), from.m[2][3].real()};
+    int seed[3] = {-1, -1, -1};
+    unsigned char found = 0;
+    if (ReachQuery(p, 1, 1, snap_vox, &found, nullptr, seed) < 0) return -1;
+    if (!found) seed[0] = seed[1] = seed[2] = -1;   // (outside the volume as a seed: contributes nothing, and nothing is reached)
+    if (!same_field || seed[0] != reach_seed_[0] || seed[1] != reach_seed_[1] || seed[2] != reach_seed_[2]) {
+        reach_generation_ = -1;
+        check_rc(xs_reach_flood(view_grid_.ptr(), field, res, r2, seed, 1, reach_.ptr(), nullptr, st), "ReachFlood");
+        reach_generation_ = volume_generation;
+        reach_min_weight_ = mw; reach_R_ = R; reach_unknown_ = unknown_blocks; reach_r2_ = r2;
+        reach_seed_[0] = seed[0]; reach_seed_[1] = seed[1]; reach_seed_[2] = seed[2];
+    }
+    if (P == 0) return 1;
+    std::vector<float> pts((size_t)P * 3);
+    for (int i = 0; i < P; ++i)
+        for (int c = 0; c < 3; ++c) pts[(size_t)i * 3 + c] = camera2volume[i].m[c][3].real();
+    return ReachQuery(pts.data(), P, 0, 0, reachable, clear2, nullptr);
+}
+
+int KinectFusionReconstruction::NextReachableView(const Matrix4cf *camera2volume, int P, const xs_view_opts *opts, int min_weight, unsigned min_hits,
+                                                  unsigned *out4xP, float radius_m, int snap_vox, int unknown_blocks, unsigned char *reachable) {
+    std::vector<unsigned> own;
+    std::vector<unsigned char> own_flags;
+    std::vector<unsigned short> clear2((size_t)(P > 0 ? P : 0));
+    if (!out4xP && P > 0) { own.resize((size_t)P * 4); out4xP = own.data(); }
+    if (!reachable && P > 0) { own_flags.resize((size_t)P); reachable = own_flags.data(); }
+    int rc = Reachable(nullptr, radius_m, snap_vox, unknown_blocks, min_weight, P, camera2volume, reachable, clear2.data());
+    if (rc == 1) rc = ScoreViews(camera2volume, P, opts, min_weight, out4xP);
+    if (rc == -1) return -3;   // (-1 is "no pose qualifies" here)
+    if (rc < 0) return rc;
+    if (rc == 0) return -1;
+    return next_reachable_view(out4xP, reachable, P, min_hits);
+}
+
 // reference :334-372
 KinectFusionReconstruction::CPointCloud KinectFusionReconstruction::ExportPointCloud(int max_buffer) {
     CPointCloud res;

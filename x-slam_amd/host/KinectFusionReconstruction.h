@@ -238,6 +238,23 @@ public:
     // Both return -2 in shard mode with nothing done: occlusion along a ray is not additive over z-slabs.
     int ScoreViews(const Matrix4cf *camera2volume, int P, const xs_view_opts *opts, int min_weight, unsigned *out4xP);
     int NextBestView(const Matrix4cf *camera2volume, int P, const xs_view_opts *opts, int min_weight, unsigned min_hits, unsigned *out4xP);
+    // Clearance and reachability: can the camera be at a candidate, and get there?  ClearanceField builds (or takes
+    // from its cache) the field of xs_clearance_build over the observation grid at `min_weight` — min(d^2, R^2) per voxel to the nearest
+    // obstacle, R = max_radius_vox — and copies its X * Y * Z uint16 to host_out.  Reachable floods the known free space a body of
+    // radius_m fits in (r2 and R by view_host.hpp's reach_radius) from `start` (null: the current camera2volume), whose translation's voxel is
+    // first snapped to the nearest passable voxel within snap_vox (the sensor observes nothing at its own centre); no such voxel: nothing is
+    // reachable, which is a result.  reachable[p] = 1 iff the centre voxel of camera2volume[p] (not snapped) was reached, clear2[p] the
+    // field there (0 outside the volume).  NextReachableView scores like NextBestView and picks by the same rule among the reachable
+    // candidates (view_host.hpp's next_reachable_view), starting from the current camera; reachable (optional) receives the flags.
+    // The field, the reach buffer and the flood are cached and redone when volume_generation, min_weight, unknown_blocks, R, r2 or the
+    // snapped seed differ from what they were built with.  ClearanceField and Reachable return 1 when they ran, 0 without a volume, -1 on
+    // bad arguments (R or snap out of range among them); NextReachableView -3 on those and -1 when nobody qualifies or there is no volume.
+    // All return -2 in shard mode with nothing done: distance and connectivity are not additive over z-slabs.
+    int ClearanceField(int max_radius_vox, int unknown_blocks, int min_weight, unsigned short *host_out);
+    int Reachable(const Matrix4cf *start, float radius_m, int snap_vox, int unknown_blocks, int min_weight, int P, const Matrix4cf *camera2volume,
+                  unsigned char *reachable, unsigned short *clear2);
+    int NextReachableView(const Matrix4cf *camera2volume, int P, const xs_view_opts *opts, int min_weight, unsigned min_hits, unsigned *out4xP,
+                          float radius_m, int snap_vox, int unknown_blocks, unsigned char *reachable);
     long long RelocalizationIndexVoxels() const { return band_generation_ >= 0 ? band_.count : 0; }   // the index as last built, 0 before any
     // bumped by everything that writes the volume: integrate calls, loadCheckpoint, xs_kf_volume_ptr(kf, 0, .), RebuildSignMap (the band index is rebuilt
     // when its generation differs)
@@ -317,6 +334,16 @@ private:
     DeviceArray<unsigned> view_counts_;        // XS_VIEW_MAX_POSES x 4
     long long view_generation_ = -1;           // the volume_generation view_grid_ was built at
     int view_min_weight_ = 0;                  // and the min_weight
+    bool ClearancePrepare(int R, int unknown_blocks, int min_weight);   // view_grid_ and clear_field_ in step with the volume and the arguments
+    int ReachQuery(const float *points3xN, int n, int over_passable, int snap, unsigned char *reachable, unsigned short *clear2, int *voxel);
+    DeviceArray<unsigned char> clear_field_;   // xs_clearance_bytes(resolution)
+    DeviceArray<unsigned char> clear_ws_;      // xs_clearance_workspace_bytes(resolution)
+    long long clear_generation_ = -1;          // what clear_field_ was built with: volume_generation, min_weight, R, unknown_blocks
+    int clear_min_weight_ = 0, clear_R_ = 0, clear_unknown_ = -1;
+    DeviceArray<unsigned char> reach_;         // xs_reach_bytes(resolution): reached and passable words
+    DeviceArray<unsigned char> reach_io_;      // a query's points and answers
+    long long reach_generation_ = -1;          // what the flood in reach_ ran with: the field's key, r2 and the snapped seed
+    int reach_min_weight_ = 0, reach_R_ = 0, reach_unknown_ = -1, reach_r2_ = 0, reach_seed_[3] = {-1, -1, -1};
     xs_band_index band_ = {};                  // band index of the owned planes (RelocalizeGaussNewtonBatch)
     long long band_generation_ = -1;           // the volume_generation it was built at
     DeviceArray<unsigned long long> band_keys_;

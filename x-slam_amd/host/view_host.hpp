@@ -1,7 +1,8 @@
-// view_host.hpp — the host's side of next-best-view selection: which of the candidate views that xs_score_views
+// view_host.hpp — the host's side of next-best-view selection (DESIGN.md sections 4.18 and 4.19): which of the candidate views that xs_score_views
 // has counted {unknown, free, hits, frontier} for the camera should go to next.  Pure host code, no device call and no HIP header: the
 // orchestrator uses it behind the launch and tests/cxx/view_selftest.cpp runs it under the sanitizers without a GPU.
 #pragma once
+#include <cmath>
 #include <cstddef>
 
 namespace xs_host {
@@ -17,6 +18,35 @@ inline int next_best_view(const unsigned *out4xP, int P, unsigned min_hits) {
         if (best < 0 || o[0] > out4xP[4 * (size_t)best]) best = p;
     }
     return best;
+}
+
+// The same rule restricted to the candidates a body can get to: reachable[p] != 0 says the centre voxel of pose p
+// was reached by the flood from the camera.  -1 when no reachable pose qualifies (or P <= 0, or reachable is null).
+inline int next_reachable_view(const unsigned *out4xP, const unsigned char *reachable, int P, unsigned min_hits) {
+    int best = -1;
+    if (!reachable) return best;
+    for (int p = 0; p < P; ++p) {
+        const unsigned *o = out4xP + 4 * (size_t)p;
+        if (!reachable[p] || o[2] < min_hits) continue;
+        if (best < 0 || o[0] > out4xP[4 * (size_t)best]) best = p;
+    }
+    return best;
+}
+
+// A body's radius in metres as the clearance field's integers: rv = radius_m / voxel_size (one float32 divide), r2 = max(1, (int)ceilf(rv * rv))
+// (a voxel is passable where field >= r2), R the smallest integer with R * R >= r2 (the field's cap).  False, with nothing written, for
+// a radius or a voxel size that is negative, zero (the voxel size), not finite, or that needs R above 255.
+inline bool reach_radius(float radius_m, float voxel_size, int &r2, int &R) {
+    if (!(voxel_size > 0.f) || !(radius_m >= 0.f) || !std::isfinite(radius_m) || !std::isfinite(voxel_size)) return false;
+    const float rv = radius_m / voxel_size;
+    const float sq = std::ceil(rv * rv);
+    if (!(sq <= 65025.f)) return false;
+    const int q = (int)sq < 1 ? 1 : (int)sq;
+    int r = 1;
+    while (r * r < q) ++r;
+    if (r > 255) return false;
+    r2 = q; R = r;
+    return true;
 }
 
 }  // namespace xs_host

@@ -267,6 +267,22 @@ int xs_kf_next_best_view(void *kf, int poses, const float *c2v32xP, const xs_vie
     if (poses < 0 || (poses > 0 && !c2v32xP)) return -3;
     return ((KF *)kf)->NextBestView(poses_of(c2v32xP, poses).data(), poses, opts, min_weight, min_hits, out4xP);
 }
+int xs_kf_clearance_field(void *kf, int max_radius_vox, int unknown_blocks, int min_weight, uint16_t *host_out) {
+    return ((KF *)kf)->ClearanceField(max_radius_vox, unknown_blocks, min_weight, host_out);
+}
+int xs_kf_reachable(void *kf, const float *start_c2v32_or_null, float radius_m, int snap_vox, int unknown_blocks, int min_weight, int P, const float *c2v32xP,
+                    unsigned char *reachable, unsigned short *clear2) {
+    if (P < 0 || (P > 0 && (!c2v32xP || !reachable || !clear2))) return -1;
+    const std::vector<Matrix4cf> start = poses_of(start_c2v32_or_null, start_c2v32_or_null ? 1 : 0);
+    return ((KF *)kf)->Reachable(start.empty() ? nullptr : start.data(), radius_m, snap_vox, unknown_blocks, min_weight, P, poses_of(c2v32xP, P).data(),
+                                 reachable, clear2);
+}
+int xs_kf_next_reachable_view(void *kf, int poses, const float *c2v32xP, const xs_view_opts *opts, int min_weight, unsigned min_hits, unsigned *out4xP,
+                              float radius_m, int snap_vox, int unknown_blocks, unsigned char *reachable) {
+    if (poses < 0 || (poses > 0 && !c2v32xP)) return -3;
+    return ((KF *)kf)->NextReachableView(poses_of(c2v32xP, poses).data(), poses, opts, min_weight, min_hits, out4xP, radius_m, snap_vox, unknown_blocks,
+                                         reachable);
+}
 long long xs_kf_relocalization_index_voxels(void *kf) { return ((KF *)kf)->RelocalizationIndexVoxels(); }
 long long xs_kf_export_point_cloud(void *kf, int max_buffer, float *points_host, float *normals_host) {
     const auto pc = ((KF *)kf)->ExportPointCloud(max_buffer);

@@ -46,6 +46,10 @@ _SIGS = {
     "xs_kf_relocalize_global": (C.c_int, [_vp, _vp, _sz, C.c_int, _f32p, C.c_int, C.c_int, C.c_float, _f32p, _f64p]),
     "xs_kf_score_views": (C.c_int, [_vp, C.c_int, _f32p, C.POINTER(capi.ViewOpts), C.c_int, C.POINTER(C.c_uint)]),
     "xs_kf_next_best_view": (C.c_int, [_vp, C.c_int, _f32p, C.POINTER(capi.ViewOpts), C.c_int, C.c_uint, C.POINTER(C.c_uint)]),
+    "xs_kf_clearance_field": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_uint16)]),
+    "xs_kf_reachable": (C.c_int, [_vp, _f32p, C.c_float, C.c_int, C.c_int, C.c_int, C.c_int, _f32p, C.POINTER(C.c_ubyte), C.POINTER(C.c_uint16)]),
+    "xs_kf_next_reachable_view": (C.c_int, [_vp, C.c_int, _f32p, C.POINTER(capi.ViewOpts), C.c_int, C.c_uint, C.POINTER(C.c_uint), C.c_float, C.c_int,
+                                            C.c_int, C.POINTER(C.c_ubyte)]),
     "xs_kf_relocalization_index_voxels": (C.c_longlong, [_vp]),
     "xs_kf_export_point_cloud": (C.c_longlong, [_vp, C.c_int, _f32p, _f32p]),
     "xs_kf_export_ply": (C.c_longlong, [_vp, C.c_int, C.c_char_p]),
@@ -402,6 +406,59 @@ class KinectFusion:
                                        out.ctypes.data_as(C.POINTER(C.c_uint)))
         self._view_call("xs_kf_next_best_view", rc, -3)
         return int(rc), out[:P].copy()
+
+    def clearance_field(self, max_radius_vox=8, unknown_blocks=True, min_weight=1):
+        """How far the nearest obstacle is: uint16 [Z, Y, X] = min(d^2, R^2) in voxels, R = max_radius_vox (1 .. 255), to the nearest OCCUPIED
+        voxel — with unknown_blocks also the nearest UNKNOWN voxel or position outside the volume — of the observation grid at min_weight.
+        XsError in shard mode."""
+        out = np.zeros((self.res[2], self.res[1], self.res[0]), np.uint16)
+        rc = _lib.xs_kf_clearance_field(self.h, int(max_radius_vox), int(bool(unknown_blocks)), int(min_weight), out.ctypes.data_as(C.POINTER(C.c_uint16)))
+        self._reach_call("xs_kf_clearance_field", rc, -1)
+        if rc != 1:
+            raise ValueError("xs_kf_clearance_field: no volume")
+        return out
+
+    @staticmethod
+    def _reach_call(name, rc, bad):
+        if rc == -2:
+            raise capi.XsError(f"{name}: not available in shard mode (distance and connectivity are not additive over z-slabs)")
+        if rc == bad:
+            raise ValueError(f"{name}: bad arguments or options")
+
+    def reachable(self, c2vs, radius_m, start=None, snap_vox=4, unknown_blocks=True, min_weight=1):
+        """Which of the P camera2volume poses c2vs [P, 4, 4, 2] a body of radius_m can get to from `start` ([4, 4, 2]; None: the current
+        camera2volume) through known free space: (reachable bool [P], clear2 uint16 [P] — the clearance field at each pose's centre voxel,
+        squared voxels, capped at the R the radius needs).  The start is snapped to the nearest passable voxel within snap_vox voxels; the
+        candidates are not snapped.  XsError in shard mode."""
+        m = np.ascontiguousarray(c2vs, dtype=np.float32).reshape(-1)
+        P = m.size // 32
+        assert m.size == 32 * P
+        flags, clear2 = np.zeros(max(P, 1), np.uint8), np.zeros(max(P, 1), np.uint16)
+        s = None if start is None else np.ascontiguousarray(start, dtype=np.float32).reshape(32)
+        rc = _lib.xs_kf_reachable(self.h, None if s is None else s.ctypes.data_as(_f32p), float(radius_m), int(snap_vox), int(bool(unknown_blocks)),
+                                  int(min_weight), P, m.ctypes.data_as(_f32p), flags.ctypes.data_as(C.POINTER(C.c_ubyte)),
+                                  clear2.ctypes.data_as(C.POINTER(C.c_uint16)))
+        self._reach_call("xs_kf_reachable", rc, -1)
+        if rc != 1:
+            raise ValueError("xs_kf_reachable: no volume")
+        return flags[:P].astype(bool), clear2[:P].copy()
+
+    def next_reachable_view(self, candidates, radius_m, min_hits=None, rays=(80, 60), t_near=0.2, t_far=5.0, step=None, min_weight=1, snap_vox=4,
+                            unknown_blocks=True):
+        """next_best_view among the candidates a body of radius_m can get to from the current camera through known free space: (index, counts
+        uint32 [P, 4], reachable bool [P]); index -1 when no reachable candidate qualifies.  XsError in shard mode."""
+        m = np.ascontiguousarray(candidates, dtype=np.float32).reshape(-1)
+        P = m.size // 32
+        assert m.size == 32 * P
+        if min_hits is None:
+            min_hits = int(rays[0]) * int(rays[1]) // 4
+        out, flags = np.zeros((max(P, 1), 4), np.uint32), np.zeros(max(P, 1), np.uint8)
+        opts = capi.view_opts(rays, t_near, t_far, step)
+        rc = _lib.xs_kf_next_reachable_view(self.h, P, m.ctypes.data_as(_f32p), C.byref(opts), int(min_weight), int(min_hits),
+                                            out.ctypes.data_as(C.POINTER(C.c_uint)), float(radius_m), int(snap_vox), int(bool(unknown_blocks)),
+                                            flags.ctypes.data_as(C.POINTER(C.c_ubyte)))
+        self._reach_call("xs_kf_next_reachable_view", rc, -3)
+        return int(rc), out[:P].copy(), flags[:P].astype(bool)
 
     def relocalization_index_voxels(self):
         """Band voxels in the relocalisation index as last built by relocalize_batch (0 before the first)."""
