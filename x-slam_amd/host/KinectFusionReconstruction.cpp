@@ -2,31 +2,10 @@
 // of XKinectFusion/src/KinectFusionReconstruction.cpp:9-332 (cited per method) over the
 // launcher shim.  One stream, no per-frame allocation, synchronisation only where the host
 // needs a result (the 6x6 normal equations of each ICP iteration).
-#include "KinectFusionReconstruction.h"
-#include "newton_host.hpp"
-#include "score_host.hpp"
-#include "view_host.hpp"
-#include <chrono>
-#include <algorithm>
+#include "kf_internal.hpp"
 #include <cmath>
-#include <cstdio>
-#include <cstring>
-#include <fstream>
-#include <iostream>
 
 using namespace xs_host;
-
-// The poll budget of every wait for a published result (xs_host_wait).  The wait also watches the stream, so the budget only ends a wait whose
-// stream is still busy after this many polls (tens of seconds).
-static constexpr long long kWaitPolls = 2000000000LL;
-// A wait that ended without its result where none can be spared: one line naming the site and what happened, then exit(-1) (the hipSafeCall /
-// check_rc convention).
-[[noreturn]] static void wait_fatal(const char *site, const xs_wait_result &w) {
-    std::cout << "error::KinectFusionReconstruction, " << site << ": " << xs_wait_str(w.status);
-    if (w.status == xs_wait::failed) std::cout << " (" << hipGetErrorString(w.error) << ")";
-    std::cout << std::endl;
-    exit(-1);
-}
 
 KinectFusionReconstruction::KinectFusionReconstruction() {
     depth_width = 0;
@@ -65,8 +44,8 @@ KinectFusionReconstruction::~KinectFusionReconstruction() {
     if (pinned_pairs_) (void)hipHostFree(pinned_pairs_);
     if (pinned_records_) (void)hipHostFree(pinned_records_);
     if (icp_mailbox_) (void)xs_icp_mailbox_free(icp_mailbox_, icp_mailbox_in_device_);
-    if (gn_mailbox_) (void)xs_icp_mailbox_free(gn_mailbox_, gn_mailbox_in_device_);
-    if (gn_publish_) (void)hipHostFree(gn_publish_);
+    if (reloc_.gn_mailbox) (void)xs_icp_mailbox_free(reloc_.gn_mailbox, reloc_.gn_mailbox_in_device);
+    if (reloc_.gn_publish) (void)hipHostFree(reloc_.gn_publish);
     for (int i = 0; i < 2; ++i) {
         if (ingest_pinned_[i]) { (void)hipEventSynchronize(ingest_done_[i]); (void)hipHostFree(ingest_pinned_[i]); (void)hipEventDestroy(ingest_done_[i]); }
     }
@@ -159,12 +138,12 @@ void KinectFusionReconstruction::SetYamlParameters(const FlatYaml &config_) {
     profile_integrate_every = std::max(1, config.as<int>("profile_integrate_every", 4));
     AllocateBuffers();
     tsdf_volume_d_ptr = new TsdfVolume(Vector3i(resolutionX, resolutionY, zs1 - zs0), voxel_size, thres_range);
+    invalidate_derived_maps();   // (another volume object: volume_generation alone does not tell)
     if (sign_map_on()) {
         // the sign map of the ray march (include/xslam_amd.h), with the finest bricks the march can use for this camera and volume — or none
         const int finest = xs_raycast_signmap_shift(&kinect_intrinsic.fx, voxel_size, tsdf_volume_d_ptr->getTsdfTruncDist());
         raycast_sign_map_shift = finest ? std::max(raycast_sign_map_shift, finest) : 0;   // (a finer one than the march can use is coarsened)
-        const int res[3] = {volume_resolution[0], volume_resolution[1], volume_resolution[2]};
-        const size_t bytes = raycast_sign_map_shift ? xs_signmap_bytes(res, raycast_sign_map_shift) : 0;
+        const size_t bytes = raycast_sign_map_shift ? xs_signmap_bytes(res3(), raycast_sign_map_shift) : 0;
         if (bytes) { sign_map_.create(bytes); RebuildSignMap(); }   // (from the volume as it is: empty)
         else raycast_sign_map = false;
     }
@@ -204,8 +183,7 @@ void KinectFusionReconstruction::AllocateBuffers() {
     // short division; a constant that fails its check keeps the bracketed reciprocals + divide, same results
     xs_const_div_prepare(voxel_size);
     {
-        const int res[3] = {volume_resolution[0], volume_resolution[1], volume_resolution[2]};
-        integrate_ws_.create(xs_integrate_workspace_bytes(res, zs1 - zs0));
+        integrate_ws_.create(xs_integrate_workspace_bytes(res3(), zs1 - zs0));
         icp_ws_.create(xs_icp_workspace_bytes());
         check_rc(xs_icp_workspace_init(icp_ws_.ptr(), current_stream()), "icp workspace");
         if (!icp_mailbox_) check_rc(xs_icp_mailbox_alloc(&icp_mailbox_, &icp_mailbox_in_device_), "icp mailbox");
@@ -241,6 +219,7 @@ void KinectFusionReconstruction::ReleaseBuffers() {
     real_maps_valid_ = false;
     delete tsdf_volume_d_ptr;
     tsdf_volume_d_ptr = nullptr;
+    invalidate_derived_maps();
 }
 
 // reference :125-145
@@ -658,12 +637,11 @@ void KinectFusionReconstruction::ClassifyAhead(const Matrix3frm &Rcurr, const Ve
     hipStream_t st = current_stream();
     // the scaled depth's maximum and the cleared header come from the auxiliary stream
     if (scale_recorded_ && hipEventQuery(scale_done_) != hipSuccess) hipSafeCall(hipStreamWaitEvent(st, scale_done_, 0));
-    const int res[3] = {volume_resolution.x(), volume_resolution.y(), volume_resolution.z()};
     xs_integrate_opts o = {};
     o.struct_bytes = sizeof(o);
     o.flags = integrate_header_clear_ ? XS_INTEGRATE_HEADER_IS_CLEAR : 0u;
     o.depth_tiles = depth_tiles_.ptr();   // the boxes' classes are decided here too, with the slack's pads (the integrate call checks its pose against them)
-    check_rc(xs_integrate_classify_ex(depth_height, depth_width, &kinect_intrinsic.fx, res, voxel_size, list_Rv2c_, list_tv2c_,
+    check_rc(xs_integrate_classify_ex(depth_height, depth_width, &kinect_intrinsic.fx, res3(), voxel_size, list_Rv2c_, list_tv2c_,
                                       tsdf_volume_d_ptr->getTsdfTruncDist(), zo0, zo1, depth_max_.ptr(), integrate_ws_.ptr(), integrate_classify_slack,
                                       &o, st), "integrate classification");
     list_ready_ = true;
@@ -1105,846 +1083,15 @@ int KinectFusionReconstruction::CalculatePointCloud(MapArr &xyz_g_d, MapArr &nor
     return 0;
 }
 
-// The six seeded volume-to-camera poses of one Gauss-Newton pass: v2c_k = inverse(se3Exp(i h e_k) * camera2volume), k = 0 .. 5.
-// For a single seeded generator se3Exp takes its small-angle branch and is EXACTLY I + i h G_k (G_k: unit translation along axis k, or the hat matrix
-// of axis k - 3), whose inverse is I - i h G_k up to a REAL term h^2 G_k^2 (1e-14: below the rounding of every entry it would touch).  So
-//     v2c_k = v2c - i h (v2c G_k),        v2c = inverse(camera2volume) once,
-// and v2c G_k is a column of v2c (translations) or two columns of its rotation swapped and signed (rotations): one 4x4 inverse and a few dozen products
-// instead of six complex 4x4 products and six complex 4x4 cofactor inverses (4.9 -> 0.5 us on the build container's core; the host's side of a pass is
-// what stands between two kernels).  The six poses share their real parts bit for bit by construction (the kernel counts a voxel only if every seeded
-// evaluation keeps it); the imaginary parts equal those of the long form to rounding (tests/test_gauss_newton_gpu.py: the oracle twin, which inverts in
-// double, and the analytic seeds of the per-pass test).
-static void gn_seeded_poses(const xs_host::Matrix4cf &camera2volume, float R[6][18], float t[6][6]) {
-    using namespace xs_host;
-    const Matrix4cf v2c = inverse(camera2volume);
-    const hostComplex ih(0.f, (float)H_);
-    for (int k = 0; k < 6; ++k) {
-        hostComplex Rk[3][3], tk[3];
-        for (int i = 0; i < 3; ++i) { for (int j = 0; j < 3; ++j) Rk[i][j] = v2c.m[i][j]; tk[i] = v2c.m[i][3]; }
-        if (k < 3) {
-            for (int i = 0; i < 3; ++i) tk[i] = tk[i] - ih * v2c.m[i][k];                    // (v2c G_k): column 3 = column k of the rotation
-        } else {
-            const int a = k - 3, b = (a + 1) % 3, c = (a + 2) % 3;                           // hat(e_a): (c, b) = +1, (b, c) = -1
-            for (int i = 0; i < 3; ++i) {
-                Rk[i][b] = Rk[i][b] - ih * v2c.m[i][c];                                      // (R hat)(i, b) = R(i, c)
-                Rk[i][c] = Rk[i][c] + ih * v2c.m[i][b];                                      // (R hat)(i, c) = -R(i, b)
-            }
-        }
-        for (int i = 0; i < 3; ++i) {
-            for (int j = 0; j < 3; ++j) { R[k][(i * 3 + j) * 2] = Rk[i][j].real(); R[k][(i * 3 + j) * 2 + 1] = Rk[i][j].imag(); }
-            t[k][2 * i] = tk[i].real(); t[k][2 * i + 1] = tk[i].imag();
-        }
-    }
-}
-// What every pass of a frame shares: the scaled depth (once per frame, not per pass) and this rank's owned planes as the dense array the
-// kernel indexes (a pitched volume is packed first); the pinned record and the mailbox of the loop protocol.
-const float *KinectFusionReconstruction::GaussNewtonPrepare(const DeviceArray2D<ushort> &depth_frame_d) {
-    hipStream_t st = current_stream();
-    depthRawScaled_d.create(depth_frame_d.rows(), depth_frame_d.cols());
-    check_rc(xs_scale_depth(depth_frame_d.ptr(), depth_frame_d.step(), depth_frame_d.rows(), depth_frame_d.cols(), depthRawScaled_d.ptr(),
-                            depthRawScaled_d.step(), st), "scaleDepth");
-    if (gn_sums_.size() < 32) gn_sums_.create(32);
-    if (gn_ws_.size() < xs_tsdf_reduce_workspace_bytes()) {
-        gn_ws_.create(xs_tsdf_reduce_workspace_bytes());
-        check_rc(xs_tsdf_reduce_workspace_init(gn_ws_.ptr(), st), "reduce workspace");
-    }
-    if (!gn_publish_) {
-        hipSafeCall(hipHostMalloc((void **)&gn_publish_, xs_gn_publish_bytes(), hipHostMallocCoherent | hipHostMallocMapped));
-        std::memset(gn_publish_, 0, xs_gn_publish_bytes());
-    }
-    if (!gn_mailbox_ && gn_post_pose) check_rc(xs_icp_mailbox_alloc(&gn_mailbox_, &gn_mailbox_in_device_), "Gauss-Newton mailbox");
-    return GaussNewtonDenseView();
-}
-const float *KinectFusionReconstruction::GaussNewtonDenseView() {
-    hipStream_t st = current_stream();
-    DeviceArray2D<float> value = tsdf_volume_d_ptr->value();
-    const size_t row_bytes = (size_t)volume_resolution[0] * sizeof(float), plane_rows = (size_t)volume_resolution[1];
-    const float *gt = reinterpret_cast<const float *>(reinterpret_cast<const char *>(value.ptr()) + (size_t)(zo0 - zs0) * plane_rows * value.step());
-    if (value.step() != row_bytes) {
-        const size_t rows = (size_t)(zo1 - zo0) * plane_rows;
-        if (gn_dense_.size() < rows * volume_resolution[0]) gn_dense_.create(rows * volume_resolution[0]);
-        hipSafeCall(hipMemcpy2DAsync(gn_dense_.ptr(), row_bytes, gt, value.step(), row_bytes, rows, hipMemcpyDeviceToDevice, st));
-        gt = gn_dense_.ptr();
-    }
-    return gt;
-}
-// One pass enqueued: the kernel over the owned planes (poses as arguments, or — R null — from the mailbox with number mail_seq), in shard
-// mode the all-reduce of the 29 sums on the stream and then their publication; single GPU: the kernel's last workgroup publishes.  The host
-// reads the record with GaussNewtonWait(seq).
-void KinectFusionReconstruction::GaussNewtonEnqueue(const DeviceArray2D<ushort> &depth_frame_d, const float *gt, const float (*R)[18], const float (*t)[6],
-                                                    unsigned mail_seq, unsigned long long seq) {
-    hipStream_t st = current_stream();
-    const int res[3] = {volume_resolution[0], volume_resolution[1], volume_resolution[2]};
-    const bool sharded = shard_count > 1 && collective;
-    xs_gn_opts o = {};
-    o.struct_bytes = sizeof(o);
-    o.pose_mailbox = R ? nullptr : gn_mailbox_; o.mailbox_seq = mail_seq;
-    if (!sharded) { o.publish_host = gn_publish_; o.publish_seq = seq; }
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    if (profiling && gn_events_.size() < 64) {   // (level 1 or 2: the kernel's own duration, for bench.py's host_us_per_pass)
-        hipSafeCall(hipEventCreate(&e0)); hipSafeCall(hipEventCreate(&e1));
-        gn_events_.push_back({e0, e1});
-        hipSafeCall(hipEventRecord(e0, st));
-    }
-    check_rc(xs_tsdf_gauss_newton_terms_ex(depthRawScaled_d.ptr(), depthRawScaled_d.step(), depth_frame_d.rows(), depth_frame_d.cols(), &kinect_intrinsic.fx,
-                                           res, voxel_size, R ? &R[0][0] : nullptr, t ? &t[0][0] : nullptr, tsdf_volume_d_ptr->getTsdfTruncDist(), gt, zo0,
-                                           zo1, gn_ws_.ptr(), gn_sums_.ptr(), &o, st), "GaussNewtonTerms");
-    if (e1) hipSafeCall(hipEventRecord(e1, st));
-    if (sharded) {
-        collective(collective_user, 0, gn_sums_.ptr(), 29);
-        if (gn_publish_sharded) check_rc(xs_gn_publish_sums(gn_sums_.ptr(), 29, gn_publish_, seq, st), "GaussNewtonTerms");
-        else {   // (YAML gn_publish_sharded: false — the round-5 way: copy + stream drain, then the record is filled by the host itself)
-            hipSafeCall(hipMemcpyAsync(gn_publish_, gn_sums_.ptr(), 29 * sizeof(double), hipMemcpyDeviceToHost, st));
-            hipSafeCall(hipStreamSynchronize(st));
-            reinterpret_cast<volatile unsigned long long *>(gn_publish_)[32] = seq;
-        }
-    }
-}
-// the kernel's sums of the seeded imaginary parts -> derivative sums: divided by h^2 (J^T J) and h (J^T r)
-static void gn_scale_sums(const double *raw, double out29[29]) {
-    const double ih = 1.0 / (double)(float)H_;
-    for (int i = 0; i < 21; ++i) out29[i] = raw[i] * ih * ih;
-    for (int i = 21; i < 27; ++i) out29[i] = raw[i] * ih;
-    out29[27] = raw[27]; out29[28] = raw[28];
-}
-// One host step of the Gauss-Newton loop on pass p's sums: the loss goes into the history; then 1 = the loop is finished (p was the final loss
-// pass), -1 = it failed (nothing to align to, or the damped system is not positive definite), 0 = camera2volume took the step, go on.
-static int gn_loop_step(const double s[29], int p, int iterations, float damping, xs_host::Matrix4cf &camera2volume, std::vector<double> *loss_history) {
-    using namespace xs_host;
-    if (loss_history) loss_history->push_back(s[28] > 0 ? s[27] / s[28] : 0.0);
-    if (p == iterations) return 1;                        // the final loss pass
-    if (s[28] < 6) return -1;                             // nothing to align to
-    double A[36], b[6], x[6];
-    int q = 0;
-    for (int j = 0; j < 6; ++j)
-        for (int k = j; k < 6; ++k, ++q) { A[j * 6 + k] = s[q]; A[k * 6 + j] = s[q]; }
-    for (int k = 0; k < 6; ++k) { A[k * 6 + k] *= 1.0 + (double)damping; b[k] = -s[21 + k]; }
-    if (!solve_spd6(A, b, x)) return -1;
-    hostComplex xi[6];
-    for (int k = 0; k < 6; ++k) xi[k] = hostComplex((float)x[k], 0.f);
-    camera2volume = se3Exp(xi) * camera2volume;
-    return 0;
-}
-// spins on the record's sequence word; false if the launch reported that it left without summing (abandoned, or its poses never came),
-// fatal if the stream failed or drained without publishing
-bool KinectFusionReconstruction::GaussNewtonWait(unsigned long long seq, double out29[29]) {
-    const xs_wait_result w = xs_host_wait([&] { return xs_poll_word(gn_publish_ + 32, seq); }, kWaitPolls, current_stream());
-    if (w.status == xs_wait::left) return false;
-    if (w.status != xs_wait::published) wait_fatal("Gauss-Newton pass", w);
-    gn_scale_sums(gn_publish_, out29);
-    return true;
-}
-void KinectFusionReconstruction::GaussNewtonCollectEvents() {
-    for (auto &e : gn_events_) {
-        float ms = 0.f;
-        if (hipEventSynchronize(e.second) == hipSuccess && hipEventElapsedTime(&ms, e.first, e.second) == hipSuccess) { gn_kernel_ms += ms; ++gn_kernel_calls; }
-        (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second);
-    }
-    gn_events_.clear();
-}
-
-// BASELINE config 5 (see the header): one pass of xs_tsdf_gauss_newton_terms for the six seeded poses
-int KinectFusionReconstruction::GaussNewtonTerms(const DeviceArray2D<ushort> &depth_frame_d, const Matrix4cf &camera2volume, double out29[29]) {
-    if (!tsdf_volume_d_ptr) return 0;
-    const float *gt = GaussNewtonPrepare(depth_frame_d);
-    float R[6][18], t[6][6];
-    gn_seeded_poses(camera2volume, R, t);
-    const unsigned long long seq = ++gn_seq_;
-    GaussNewtonEnqueue(depth_frame_d, gt, R, t, 0u, seq);
-    const bool ok = GaussNewtonWait(seq, out29);
-    GaussNewtonCollectEvents();
-    return ok ? 1 : 0;
-}
-
-// The Gauss-Newton loop with the ICP loop's protocol (round 6): the depth is scaled once per frame; a pass's sums reach the host through a
-// pinned record the kernel's last workgroup writes (no copy, no stream drain); and pass n + 1 is in the queue BEFORE the host waits for pass
-// n — its kernel resident, polling a mailbox for the six poses the host posts after the solve — so what stands between two kernels is the
-// record's way to the host, the 6x6 solve, six pose inversions and one posted write (YAML gn_post_pose, default true; single GPU with a mailbox
-// in device memory — a sharded rank enqueues pass n + 1 after the solve, its all-reduce on the stream in front of the publication).
-int KinectFusionReconstruction::RelocalizeGaussNewton(const DeviceArray2D<ushort> &depth_frame_d, Matrix4cf &camera2volume, int iterations,
-                                                      float damping, std::vector<double> *loss_history) {
-    if (!tsdf_volume_d_ptr) return 0;
-    const int passes = iterations + (loss_history ? 1 : 0);   // (the last one only reports the loss the loop ended at)
-    if (passes <= 0) return 1;
-    const float *gt = GaussNewtonPrepare(depth_frame_d);
-    const bool ahead = gn_post_pose && shard_count == 1 && gn_mailbox_ && gn_mailbox_in_device_;
-    float R[6][18], t[6][6];
-    gn_seeded_poses(camera2volume, R, t);
-    unsigned long long seq = ++gn_seq_;
-    GaussNewtonEnqueue(depth_frame_d, gt, R, t, 0u, seq);
-    int rc = 1;
-    const auto t_begin = std::chrono::steady_clock::now();
-    int done = 0;
-    for (int p = 0; p < passes; ++p) {
-        unsigned long long next_seq = 0;
-        unsigned next_mail = 0;
-        if (ahead && p + 1 < passes) {
-            next_seq = ++gn_seq_; next_mail = ++gn_mail_seq_;
-            if (next_mail == 0) next_mail = ++gn_mail_seq_;   // (0 is the mailbox's initial content)
-            GaussNewtonEnqueue(depth_frame_d, gt, nullptr, nullptr, next_mail, next_seq);
-        }
-        auto leave = [&](int code) {   // the loop ends here: a launch that is waiting for its poses is told to leave, and has left before its buffers are reused
-            if (next_seq) {
-                xs_gn_post_poses(gn_mailbox_, nullptr, nullptr, next_mail, 1);
-                double ignore[29];
-                (void)GaussNewtonWait(next_seq, ignore);
-            }
-            rc = code;
-        };
-        double s[29];
-        if (!GaussNewtonWait(seq, s)) { leave(0); break; }
-        ++done;
-        if (p > 0 && ahead) { gn_poll_us += gn_publish_[30] * 0.01; ++gn_poll_passes; }   // (this pass was enqueued ahead: what its kernel waited for its poses, 100 MHz ticks)
-        const int step = gn_loop_step(s, p, iterations, damping, camera2volume, loss_history);
-        if (step > 0) break;
-        if (step < 0) { leave(0); break; }
-        if (p + 1 < passes) {
-            gn_seeded_poses(camera2volume, R, t);
-            if (next_seq) { xs_gn_post_poses(gn_mailbox_, &R[0][0], &t[0][0], next_mail, 0); seq = next_seq; }
-            else { seq = ++gn_seq_; GaussNewtonEnqueue(depth_frame_d, gt, R, t, 0u, seq); }
-        }
-    }
-    gn_pass_us += std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t_begin).count();
-    gn_passes += done;
-    GaussNewtonCollectEvents();
-    return rc;
-}
-
-// The band index of the owned planes, rebuilt when anything wrote the volume since it was built (volume_generation).  Count, then fill: the
-// arrays grow to the count when they are too small.
-void KinectFusionReconstruction::BandIndexPrepare() {
-    if (band_generation_ == volume_generation && band_.nblocks > 0) return;
-    hipStream_t st = current_stream();
-    const int res[3] = {volume_resolution[0], volume_resolution[1], volume_resolution[2]};
-    const float *gt = GaussNewtonDenseView();
-    const size_t segs_bytes = xs_tsdf_band_segs_bytes(res, zo0, zo1);
-    if (segs_bytes == 0) { std::cout << "error::KinectFusionReconstruction, relocalisation index: bad slab" << std::endl; exit(-1); }
-    if (band_segs_.size() < segs_bytes / sizeof(long long)) band_segs_.create(segs_bytes / sizeof(long long));
-    for (int attempt = 0;; ++attempt) {
-        band_.keys = band_keys_.ptr(); band_.values = band_values_.ptr(); band_.segs = band_segs_.ptr();
-        band_.capacity = (long long)std::min(band_keys_.size(), band_values_.size());
-        const int rc = xs_tsdf_band_build(gt, res, zo0, zo1, &band_, st);
-        if (rc == 0) break;
-        if (rc != XS_BAND_OVER_CAPACITY || attempt > 0) check_rc(rc, "relocalisation index");
-        band_keys_.create((size_t)band_.count);
-        band_values_.create((size_t)band_.count);
-    }
-    band_generation_ = volume_generation;
-}
-
-// What the batched loops share: the band index, the Gauss-Newton band workspace and sums, and every frame's depth scaled once (not per
-// pass) into band_depth_.  Returns the scaled depths' common step.
-size_t KinectFusionReconstruction::BandBatchPrepare(const std::vector<DeviceArray2D<ushort>> &depths) {
-    const int F = (int)depths.size();
-    hipStream_t st = current_stream();
-    BandIndexPrepare();
-    const size_t ws_bytes = xs_tsdf_band_workspace_bytes(XS_BAND_MAX_FRAMES);
-    if (band_ws_.size() < ws_bytes) {
-        band_ws_.create(ws_bytes);
-        check_rc(xs_tsdf_reduce_workspace_init(band_ws_.ptr(), st), "band workspace");   // (zeroes the tickets: once)
-    }
-    if (band_sums_.size() < (size_t)XS_BAND_MAX_FRAMES * 29) band_sums_.create((size_t)XS_BAND_MAX_FRAMES * 29);
-    if ((int)band_depth_.size() < F) band_depth_.resize((size_t)F);
-    const int rows = depths[0].rows(), cols = depths[0].cols();
-    for (int f = 0; f < F; ++f) {   // the depth is scaled once per frame, not per pass
-        band_depth_[(size_t)f].create(rows, cols);
-        check_rc(xs_scale_depth(depths[(size_t)f].ptr(), depths[(size_t)f].step(), rows, cols, band_depth_[(size_t)f].ptr(), band_depth_[(size_t)f].step(), st),
-                 "scaleDepth");
-    }
-    const size_t scaled_step = band_depth_[0].step();
-    for (int f = 1; f < F; ++f)
-        if (band_depth_[(size_t)f].step() != scaled_step) { std::cout << "error::KinectFusionReconstruction, batch: depth steps differ" << std::endl; exit(-1); }
-    return scaled_step;
-}
-
-int KinectFusionReconstruction::RelocalizeGaussNewtonBatch(const std::vector<DeviceArray2D<ushort>> &depths, Matrix4cf *camera2volume, int iterations,
-                                                           float damping, int *ok, std::vector<double> *loss_history) {
-    const int F = (int)depths.size();
-    for (int f = 0; f < F; ++f) ok[f] = 0;
-    if (!tsdf_volume_d_ptr || F == 0) return 0;
-    const int passes = iterations + (loss_history ? 1 : 0);
-    if (passes <= 0) { for (int f = 0; f < F; ++f) ok[f] = 1; return F; }
-    hipStream_t st = current_stream();
-    const int rows = depths[0].rows(), cols = depths[0].cols();
-    const size_t scaled_step = BandBatchPrepare(depths);
-    const bool sharded = shard_count > 1 && collective;
-    std::vector<int> active(F);
-    for (int f = 0; f < F; ++f) active[(size_t)f] = f;
-    std::vector<float> R((size_t)XS_BAND_MAX_FRAMES * 108), t((size_t)XS_BAND_MAX_FRAMES * 36);
-    std::vector<const float *> dptr(XS_BAND_MAX_FRAMES);
-    std::vector<double> raw((size_t)XS_BAND_MAX_FRAMES * 29);
-    int succeeded = 0;
-    for (int p = 0; p < passes && !active.empty(); ++p) {
-        std::vector<int> next;
-        for (size_t c0 = 0; c0 < active.size(); c0 += XS_BAND_MAX_FRAMES) {   // one launch per chunk of the frames still active
-            const int n = (int)std::min(active.size() - c0, (size_t)XS_BAND_MAX_FRAMES);
-            for (int i = 0; i < n; ++i) {
-                const int f = active[c0 + (size_t)i];
-                gn_seeded_poses(camera2volume[f], reinterpret_cast<float (*)[18]>(&R[(size_t)i * 108]), reinterpret_cast<float (*)[6]>(&t[(size_t)i * 36]));
-                dptr[(size_t)i] = band_depth_[(size_t)f].ptr();
-            }
-            check_rc(xs_tsdf_gauss_newton_terms_band(n, dptr.data(), scaled_step, rows, cols, &kinect_intrinsic.fx, voxel_size, R.data(), t.data(),
-                                                     tsdf_volume_d_ptr->getTsdfTruncDist(), &band_, band_ws_.ptr(), band_sums_.ptr(), st), "GaussNewtonTermsBand");
-            if (sharded) collective(collective_user, 0, band_sums_.ptr(), (long)n * 29);   // the per-pass all-reduce of GaussNewtonEnqueue, F x 29 wide
-            hipSafeCall(hipMemcpyAsync(raw.data(), band_sums_.ptr(), (size_t)n * 29 * sizeof(double), hipMemcpyDeviceToHost, st));
-            hipSafeCall(hipStreamSynchronize(st));
-            for (int i = 0; i < n; ++i) {
-                const int f = active[c0 + (size_t)i];
-                double s[29];
-                gn_scale_sums(&raw[(size_t)i * 29], s);
-                const int step = gn_loop_step(s, p, iterations, damping, camera2volume[f], loss_history ? &loss_history[f] : nullptr);
-                if (step == 0 && p + 1 == passes) ok[f] = 1;   // (no loss pass: the last step ends the loop, as in RelocalizeGaussNewton)
-                if (step > 0) ok[f] = 1;
-                if (step == 0 && p + 1 < passes) next.push_back(f);
-            }
-        }
-        active.swap(next);
-    }
-    for (int f = 0; f < F; ++f) succeeded += ok[f];
-    return succeeded;
-}
-
-
-// ---- exact-Hessian (Newton) relocalisation over the band index ----
-// One launch of xs_tsdf_pose_hessian_band for the n frames `frames` of the prepared batch (band_depth_), at most XS_BAND_MAX_FRAMES: the
-// seeded poses, in shard mode the all-reduce of the n x 29 sums, the copy and the stream drain; raw: the kernel's sums.
-void KinectFusionReconstruction::PoseHessianLaunch(const int *frames, int n, const Matrix4cf *camera2volume, size_t scaled_step, int rows, int cols, double *raw) {
-    hipStream_t st = current_stream();
-    const size_t ws_bytes = xs_tsdf_pose_hessian_workspace_bytes(XS_BAND_MAX_FRAMES);
-    if (newton_ws_.size() < ws_bytes) {
-        newton_ws_.create(ws_bytes);
-        check_rc(xs_tsdf_reduce_workspace_init(newton_ws_.ptr(), st), "pose Hessian workspace");   // (zeroes the tickets: once)
-    }
-    if (newton_sums_.size() < (size_t)XS_BAND_MAX_FRAMES * 29) newton_sums_.create((size_t)XS_BAND_MAX_FRAMES * 29);
-    std::vector<float> R((size_t)n * 21 * 36), t((size_t)n * 21 * 12);
-    std::vector<const float *> dptr((size_t)n);
-    for (int i = 0; i < n; ++i) {
-        newton_seeded_poses(camera2volume[frames[i]], reinterpret_cast<float (*)[36]>(&R[(size_t)i * 21 * 36]), reinterpret_cast<float (*)[12]>(&t[(size_t)i * 21 * 12]));
-        dptr[(size_t)i] = band_depth_[(size_t)frames[i]].ptr();
-    }
-    check_rc(xs_tsdf_pose_hessian_band(n, dptr.data(), scaled_step, rows, cols, &kinect_intrinsic.fx, voxel_size, R.data(), t.data(),
-                                       tsdf_volume_d_ptr->getTsdfTruncDist(), &band_, newton_ws_.ptr(), newton_sums_.ptr(), st), "PoseHessianBand");
-    if (shard_count > 1 && collective) collective(collective_user, 0, newton_sums_.ptr(), (long)n * 29);
-    hipSafeCall(hipMemcpyAsync(raw, newton_sums_.ptr(), (size_t)n * 29 * sizeof(double), hipMemcpyDeviceToHost, st));
-    hipSafeCall(hipStreamSynchronize(st));
-}
-
-int KinectFusionReconstruction::PoseHessianTerms(const DeviceArray2D<ushort> &depth_frame_d, const Matrix4cf &camera2volume, double out29[29]) {
-    if (!tsdf_volume_d_ptr) return 0;
-    const std::vector<DeviceArray2D<ushort>> depths(1, depth_frame_d);
-    const size_t scaled_step = BandBatchPrepare(depths);
-    const int frame = 0;
-    double raw[29];
-    PoseHessianLaunch(&frame, 1, &camera2volume, scaled_step, depth_frame_d.rows(), depth_frame_d.cols(), raw);
-    newton_scale_sums(raw, out29);
-    return 1;
-}
-
-// RelocalizeGaussNewtonBatch's loop with the Newton step: a pass is one pose-Hessian launch per chunk of the frames still active; a frame
-// whose damped Hessian is not positive definite takes, for that iteration, the Gauss-Newton step of gn_loop_step on the six-pose band sums of
-// its pose (one more launch, F = 1), and fallbacks[f] counts it.
-int KinectFusionReconstruction::RelocalizeNewtonBatch(const std::vector<DeviceArray2D<ushort>> &depths, Matrix4cf *camera2volume, int iterations,
-                                                      float damping, int *ok, std::vector<double> *loss_history, int *fallbacks) {
-    const int F = (int)depths.size();
-    for (int f = 0; f < F; ++f) { ok[f] = 0; if (fallbacks) fallbacks[f] = 0; }
-    if (!tsdf_volume_d_ptr || F == 0) return 0;
-    const int passes = iterations + (loss_history ? 1 : 0);
-    if (passes <= 0) { for (int f = 0; f < F; ++f) ok[f] = 1; return F; }
-    hipStream_t st = current_stream();
-    const int rows = depths[0].rows(), cols = depths[0].cols();
-    const size_t scaled_step = BandBatchPrepare(depths);
-    const bool sharded = shard_count > 1 && collective;
-    std::vector<int> active(F);
-    for (int f = 0; f < F; ++f) active[(size_t)f] = f;
-    std::vector<double> raw((size_t)XS_BAND_MAX_FRAMES * 29);
-    for (int p = 0; p < passes && !active.empty(); ++p) {
-        std::vector<int> next;
-        for (size_t c0 = 0; c0 < active.size(); c0 += XS_BAND_MAX_FRAMES) {   // one launch per chunk of the frames still active
-            const int n = (int)std::min(active.size() - c0, (size_t)XS_BAND_MAX_FRAMES);
-            PoseHessianLaunch(&active[c0], n, camera2volume, scaled_step, rows, cols, raw.data());
-            for (int i = 0; i < n; ++i) {
-                const int f = active[c0 + (size_t)i];
-                double s[29];
-                newton_scale_sums(&raw[(size_t)i * 29], s);
-                if (loss_history) loss_history[f].push_back(s[28] > 0 ? s[27] / s[28] : 0.0);
-                if (p == iterations) { ok[f] = 1; continue; }   // the final loss pass
-                if (s[28] < 6) continue;                        // nothing to align to: the frame fails
-                if (!newton_step(s, (double)damping, camera2volume[f])) {
-                    // not positive definite: this iteration's step is Gauss-Newton's, from the six-pose sums at the same pose
-                    float R6[6][18], t6[6][6];
-                    gn_seeded_poses(camera2volume[f], R6, t6);
-                    const float *d = band_depth_[(size_t)f].ptr();
-                    check_rc(xs_tsdf_gauss_newton_terms_band(1, &d, scaled_step, rows, cols, &kinect_intrinsic.fx, voxel_size, &R6[0][0], &t6[0][0],
-                                                             tsdf_volume_d_ptr->getTsdfTruncDist(), &band_, band_ws_.ptr(), band_sums_.ptr(), st), "GaussNewtonTermsBand");
-                    if (sharded) collective(collective_user, 0, band_sums_.ptr(), 29);
-                    double gn_raw[29], gn[29];
-                    hipSafeCall(hipMemcpyAsync(gn_raw, band_sums_.ptr(), 29 * sizeof(double), hipMemcpyDeviceToHost, st));
-                    hipSafeCall(hipStreamSynchronize(st));
-                    gn_scale_sums(gn_raw, gn);
-                    if (fallbacks) ++fallbacks[f];
-                    if (gn_loop_step(gn, p, iterations, damping, camera2volume[f], nullptr) != 0) continue;   // that failed too
-                }
-                if (p + 1 == passes) ok[f] = 1;   // (no loss pass: the last step ends the loop)
-                else next.push_back(f);
-            }
-        }
-        active.swap(next);
-    }
-    int succeeded = 0;
-    for (int f = 0; f < F; ++f) succeeded += ok[f];
-    return succeeded;
-}
-
-// ---- many pose hypotheses against the map in one band pass, and global relocalisation ----
-int KinectFusionReconstruction::ScorePoses(const DeviceArray2D<ushort> &depth_frame_d, const Matrix4cf *camera2volume, int P, double *out2xP) {
-    if (!tsdf_volume_d_ptr || P < 0) return 0;
-    if (P == 0) return 1;
-    hipStream_t st = current_stream();
-    BandIndexPrepare();
-    const size_t ws_bytes = xs_tsdf_score_poses_workspace_bytes(XS_SCORE_MAX_POSES);
-    if (score_ws_.size() < ws_bytes) {
-        score_ws_.create(ws_bytes);
-        check_rc(xs_tsdf_reduce_workspace_init(score_ws_.ptr(), st), "score workspace");   // (zeroes the tickets: once)
-    }
-    if (score_sums_.size() < (size_t)XS_SCORE_MAX_POSES * 2) score_sums_.create((size_t)XS_SCORE_MAX_POSES * 2);
-    const int rows = depth_frame_d.rows(), cols = depth_frame_d.cols();
-    score_depth_.create(rows, cols);   // the depth is scaled once, not per chunk
-    check_rc(xs_scale_depth(depth_frame_d.ptr(), depth_frame_d.step(), rows, cols, score_depth_.ptr(), score_depth_.step(), st), "scaleDepth");
-    const bool sharded = shard_count > 1 && collective;
-    std::vector<float> R, t;
-    for (int p0 = 0; p0 < P; p0 += XS_SCORE_MAX_POSES) {
-        const int n = std::min(P - p0, (int)XS_SCORE_MAX_POSES);
-        R.resize((size_t)n * 9); t.resize((size_t)n * 3);
-        for (int i = 0; i < n; ++i) {
-            const Matrix4cf inv = inverse(camera2volume[p0 + i]);   // (newton_seeded_poses' real parts: the same inverse, its real part as float)
-            for (int r = 0; r < 3; ++r) {
-                for (int c = 0; c < 3; ++c) R[(size_t)i * 9 + (size_t)r * 3 + c] = inv.m[r][c].real();
-                t[(size_t)i * 3 + r] = inv.m[r][3].real();
-            }
-        }
-        check_rc(xs_tsdf_score_poses_band(n, score_depth_.ptr(), score_depth_.step(), rows, cols, &kinect_intrinsic.fx, voxel_size, R.data(), t.data(),
-                                          tsdf_volume_d_ptr->getTsdfTruncDist(), &band_, score_ws_.ptr(), score_sums_.ptr(), st), "ScorePosesBand");
-        if (sharded) collective(collective_user, 0, score_sums_.ptr(), (long)n * 2);
-        hipSafeCall(hipMemcpyAsync(out2xP + 2 * (size_t)p0, score_sums_.ptr(), (size_t)n * 2 * sizeof(double), hipMemcpyDeviceToHost, st));
-        hipSafeCall(hipStreamSynchronize(st));   // (the chunk's host arrays and the workspace are free again)
-    }
-    return 1;
-}
-
-int KinectFusionReconstruction::RelocalizeGlobal(const DeviceArray2D<ushort> &depth_frame_d, const Matrix4cf *candidates, int P, int keep, int iterations,
-                                                 float damping, Matrix4cf &best, double report[8]) {
-    for (int i = 0; i < 8; ++i) report[i] = 0.0;
-    report[0] = -1.0;
-    if (!tsdf_volume_d_ptr || P <= 0 || keep <= 0) return 0;
-    std::vector<double> before((size_t)P * 2);
-    if (!ScorePoses(depth_frame_d, candidates, P, before.data())) return 0;
-    report[6] = (double)band_.count;
-    const std::vector<int> top = score_top_k(before.data(), P, keep);
-    const int K = (int)top.size();
-    std::vector<Matrix4cf> refined((size_t)K);
-    for (int k = 0; k < K; ++k) refined[(size_t)k] = candidates[top[(size_t)k]];
-    const std::vector<DeviceArray2D<ushort>> depths((size_t)K, depth_frame_d);   // the same image in every slot
-    std::vector<int> ok((size_t)K, 0);
-    report[5] = (double)RelocalizeGaussNewtonBatch(depths, refined.data(), iterations, damping, ok.data(), nullptr);
-    std::vector<double> after((size_t)K * 2);
-    ScorePoses(depth_frame_d, refined.data(), K, after.data());
-    const int w = score_winner(after.data(), ok.data(), K);
-    if (w < 0) return 0;
-    best = refined[(size_t)w];
-    report[0] = (double)top[(size_t)w];
-    report[1] = score_S(&before[2 * (size_t)top[(size_t)w]]);
-    report[2] = score_S(&after[2 * (size_t)w]);
-    report[3] = after[2 * (size_t)w];
-    report[4] = after[2 * (size_t)w + 1];
-    return 1;
-}
-
-// ---- candidate views against the map in one launch, and the next best view ----
-// The observation grid follows the volume the way BandIndexPrepare's index does.  False when the resolution has no grid.
-bool KinectFusionReconstruction::ViewGridPrepare(int min_weight) {
-    const int mw = min_weight < 1 ? 1 : min_weight;
-    const int res[3] = {volume_resolution[0], volume_resolution[1], volume_resolution[2]};
-    const size_t bytes = xs_view_grid_bytes(res);
-    if (bytes == 0) return false;
-    if (view_grid_.size() < bytes) { view_grid_.create(bytes); view_generation_ = -1; }
-    if (view_generation_ == volume_generation && view_min_weight_ == mw) return true;
-    const DeviceArray2D<float> value = tsdf_volume_d_ptr->value();
-    const DeviceArray2D<int> weight = tsdf_volume_d_ptr->weight();
-    if (value.step() != weight.step()) { std::cout << "error::KinectFusionReconstruction, observation grid: value and weight pitches differ" << std::endl; exit(-1); }
-    check_rc(xs_view_grid_build(value.ptr(), weight.ptr(), value.step(), res, mw, view_grid_.ptr(), current_stream()), "ViewGridBuild");
-    view_generation_ = volume_generation;
-    view_min_weight_ = mw;
-    return true;
-}
-
-int KinectFusionReconstruction::ScoreViews(const Matrix4cf *camera2volume, int P, const xs_view_opts *opts, int min_weight, unsigned *out4xP) {
-    if (shard_count > 1) return -2;   // a ray's occlusion is not additive over the ranks' z-slabs
-    if (P < 0 || (P > 0 && (!camera2volume || !out4xP))) return -1;
-    if (!tsdf_volume_d_ptr) return 0;
-    if (P == 0) return 1;
-    hipStream_t st = current_stream();
-    if (!ViewGridPrepare(min_weight)) return -1;
-    if (view_counts_.size() < (size_t)XS_VIEW_MAX_POSES * 4) view_counts_.create((size_t)XS_VIEW_MAX_POSES * 4);
-    const int res[3] = {volume_resolution[0], volume_resolution[1], volume_resolution[2]};
-    std::vector<float> R, t;
-    for (int p0 = 0; p0 < P; p0 += XS_VIEW_MAX_POSES) {
-        const int n = std::min(P - p0, (int)XS_VIEW_MAX_POSES);
-        R.resize((size_t)n * 9); t.resize((size_t)n * 3);
-        for (int i = 0; i < n; ++i)
-            for (int r = 0; r < 3; ++r) {
-                for (int c = 0; c < 3; ++c) R[(size_t)i * 9 + (size_t)r * 3 + c] = camera2volume[p0 + i].m[r][c].real();
-                t[(size_t)i * 3 + r] = camera2volume[p0 + i].m[r][3].real();
-            }
-        const int rc = xs_score_views(n, R.data(), t.data(), &kinect_intrinsic.fx, depth_height, depth_width, res, voxel_size, view_grid_.ptr(), opts,
-                                      view_counts_.ptr(), st);
-        if (rc == (int)hipErrorInvalidValue) return -1;   // the options: nothing was launched
-        check_rc(rc, "ScoreViews");
-        hipSafeCall(hipMemcpyAsync(out4xP + 4 * (size_t)p0, view_counts_.ptr(), (size_t)n * 4 * sizeof(unsigned), hipMemcpyDeviceToHost, st));
-        hipSafeCall(hipStreamSynchronize(st));   // (the grid's pose staging area and the counts are free again)
-    }
-    return 1;
-}
-
-int KinectFusionReconstruction::NextBestView(const Matrix4cf *camera2volume, int P, const xs_view_opts *opts, int min_weight, unsigned min_hits,
-                                             unsigned *out4xP) {
-    std::vector<unsigned> own;
-    if (!out4xP && P > 0) { own.resize((size_t)P * 4); out4xP = own.data(); }
-    const int rc = ScoreViews(camera2volume, P, opts, min_weight, out4xP);
-    if (rc == -1) return -3;   // (-1 is "no pose qualifies" here)
-    if (rc < 0) return rc;
-    if (rc == 0) return -1;
-    return next_best_view(out4xP, P, min_hits);
-}
-
-// ---- clearance and reachability of candidate views ----
-// The field follows the grid, the grid the volume.  False when the resolution has no field.
-bool KinectFusionReconstruction::ClearancePrepare(int R, int unknown_blocks, int min_weight) {
-    const int mw = min_weight < 1 ? 1 : min_weight;
-    const int res[3] = {volume_resolution[0], volume_resolution[1], volume_resolution[2]};
-    const size_t bytes = xs_clearance_bytes(res), ws = xs_clearance_workspace_bytes(res);
-    if (bytes == 0 || !ViewGridPrepare(mw)) return false;
-    if (clear_field_.size() < bytes) { clear_field_.create(bytes); clear_generation_ = -1; }
-    if (clear_ws_.size() < ws) clear_ws_.create(ws);
-    if (clear_generation_ == volume_generation && clear_min_weight_ == mw && clear_R_ == R && clear_unknown_ == unknown_blocks) return true;
-    check_rc(xs_clearance_build(view_grid_.ptr(), res, R, unknown_blocks, clear_ws_.ptr(), reinterpret_cast<unsigned short *>(clear_field_.ptr()),
-                                current_stream()), "ClearanceBuild");
-    clear_generation_ = volume_generation;
-    clear_min_weight_ = mw; clear_R_ = R; clear_unknown_ = unknown_blocks;
-    reach_generation_ = -1;   // (the flood was over another field)
-    return true;
-}
-
-int KinectFusionReconstruction::ClearanceField(int max_radius_vox, int unknown_blocks, int min_weight, unsigned short *host_out) {
-    if (shard_count > 1) return -2;   // a distance is not additive over the ranks' z-slabs
-    if (!host_out || max_radius_vox < 1 || max_radius_vox > XS_CLEARANCE_MAX_RADIUS || (unknown_blocks != 0 && unknown_blocks != 1)) return -1;
-    if (!tsdf_volume_d_ptr) return 0;
-    if (!ClearancePrepare(max_radius_vox, unknown_blocks, min_weight)) return -1;
-    hipStream_t st = current_stream();
-    const int res[3] = {volume_resolution[0], volume_resolution[1], volume_resolution[2]};
-    hipSafeCall(hipMemcpyAsync(host_out, clear_field_.ptr(), xs_clearance_bytes(res), hipMemcpyDeviceToHost, st));
-    hipSafeCall(hipStreamSynchronize(st));
-    return 1;
-}
-
-// n points through xs_reach_query against reach_ and clear_field_, in chunks of 4096; the answers on the host when the call returns
-int KinectFusionReconstruction::ReachQuery(const float *points3xN, int n, int over_passable, int snap, unsigned char *reachable, unsigned short *clear2,
-                                           int *voxel) {
-    enum { CHUNK = 4096, POINTS = 0, VOXEL = CHUNK * 12, CLEAR2 = VOXEL + CHUNK * 12, FLAGS = CLEAR2 + CHUNK * 2, BYTES = FLAGS + CHUNK };
-    if (reach_io_.size() < (size_t)BYTES) reach_io_.create(BYTES);
-    hipStream_t st = current_stream();
-    const int res[3] = {volume_resolution[0], volume_resolution[1], volume_resolution[2]};
-    unsigned char *io = reach_io_.ptr();
-    for (int p0 = 0; p0 < n; p0 += CHUNK) {
-        const int m = std::min(n - p0, (int)CHUNK);
-        hipSafeCall(hipMemcpyAsync(io + POINTS, points3xN + 3 * (size_t)p0, (size_t)m * 12, hipMemcpyHostToDevice, st));
-        const int rc = xs_reach_query(m, reinterpret_cast<const float *>(io + POINTS), res, voxel_size, reach_.ptr(), over_passable,
-                                      reinterpret_cast<const unsigned short *>(clear_field_.ptr()), snap, io + FLAGS, reinterpret_cast<unsigned short *>(io + CLEAR2),
-                                      reinterpret_cast<int *>(io + VOXEL), st);
-        if (rc == (int)hipErrorInvalidValue) return -1;
-        check_rc(rc, "ReachQuery");
-        if (reachable) hipSafeCall(hipMemcpyAsync(reachable + p0, io + FLAGS, (size_t)m, hipMemcpyDeviceToHost, st));
-        if (clear2) hipSafeCall(hipMemcpyAsync(clear2 + p0, io + CLEAR2, (size_t)m * 2, hipMemcpyDeviceToHost, st));
-        if (voxel) hipSafeCall(hipMemcpyAsync(voxel + 3 * (size_t)p0, io + VOXEL, (size_t)m * 12, hipMemcpyDeviceToHost, st));
-        hipSafeCall(hipStreamSynchronize(st));   // (the staging area is free again)
-    }
-    return 1;
-}
-
-int KinectFusionReconstruction::Reachable(const Matrix4cf *start, float radius_m, int snap_vox, int unknown_blocks, int min_weight, int P,
-                                          const Matrix4cf *camera2volume, unsigned char *reachable, unsigned short *clear2) {
-    if (shard_count > 1) return -2;   // connectivity is not additive over the ranks' z-slabs
-    int r2 = 0, R = 0;
-    if (P < 0 || (P > 0 && (!camera2volume || !reachable || !clear2)) || snap_vox < 0 || snap_vox > XS_REACH_MAX_SNAP ||
-        (unknown_blocks != 0 && unknown_blocks != 1) || !reach_radius(radius_m, voxel_size, r2, R))
-        return -1;
-    if (!tsdf_volume_d_ptr) return 0;
-    const int mw = min_weight < 1 ? 1 : min_weight;
-    if (!ClearancePrepare(R, unknown_blocks, mw)) return -1;
-    hipStream_t st = current_stream();
-    const int res[3] = {volume_resolution[0], volume_resolution[1], volume_resolution[2]};
-    const size_t bytes = xs_reach_bytes(res);
-    if (bytes == 0) return -1;
-    if (reach_.size() < bytes) { reach_.create(bytes); reach_generation_ = -1; }
-    const unsigned short *field = reinterpret_cast<const unsigned short *>(clear_field_.ptr());
-    const bool same_field = reach_generation_ == volume_generation && reach_min_weight_ == mw && reach_R_ == R && reach_unknown_ == unknown_blocks && reach_r2_ == r2;
-    // the passable words (those of the last flood, if it was over this field at this r2), and the start snapped over them
-    if (!same_field) check_rc(xs_reach_passable(view_grid_.ptr(), field, res, r2, reach_.ptr(), st), "ReachPassable");
-    const Matrix4cf from = start ? *start : getCamera2Volume();
-    const float p[3] = {from.m[0][3].real(), from.m[1][3].real(), from.m[2][3].real()};
-    int seed[3] = {-1, -1, -1};
-    unsigned char found = 0;
-    if (ReachQuery(p, 1, 1, snap_vox, &found, nullptr, seed) < 0) return -1;
-    if (!found) seed[0] = seed[1] = seed[2] = -1;   // (outside the volume as a seed: contributes nothing, and nothing is reached)
-    if (!same_field || seed[0] != reach_seed_[0] || seed[1] != reach_seed_[1] || seed[2] != reach_seed_[2]) {
-        reach_generation_ = -1;
-        check_rc(xs_reach_flood(view_grid_.ptr(), field, res, r2, seed, 1, reach_.ptr(), nullptr, st), "ReachFlood");
-        reach_generation_ = volume_generation;
-        reach_min_weight_ = mw; reach_R_ = R; reach_unknown_ = unknown_blocks; reach_r2_ = r2;
-        reach_seed_[0] = seed[0]; reach_seed_[1] = seed[1]; reach_seed_[2] = seed[2];
-    }
-    if (P == 0) return 1;
-    std::vector<float> pts((size_t)P * 3);
-    for (int i = 0; i < P; ++i)
-        for (int c = 0; c < 3; ++c) pts[(size_t)i * 3 + c] = camera2volume[i].m[c][3].real();
-    return ReachQuery(pts.data(), P, 0, 0, reachable, clear2, nullptr);
-}
-
-int KinectFusionReconstruction::NextReachableView(const Matrix4cf *camera2volume, int P, const xs_view_opts *opts, int min_weight, unsigned min_hits,
-                                                  unsigned *out4xP, float radius_m, int snap_vox, int unknown_blocks, unsigned char *reachable) {
-    std::vector<unsigned> own;
-    std::vector<unsigned char> own_flags;
-    std::vector<unsigned short> clear2((size_t)(P > 0 ? P : 0));
-    if (!out4xP && P > 0) { own.resize((size_t)P * 4); out4xP = own.data(); }
-    if (!reachable && P > 0) { own_flags.resize((size_t)P); reachable = own_flags.data(); }
-    int rc = Reachable(nullptr, radius_m, snap_vox, unknown_blocks, min_weight, P, camera2volume, reachable, clear2.data());
-    if (rc == 1) rc = ScoreViews(camera2volume, P, opts, min_weight, out4xP);
-    if (rc == -1) return -3;   // (-1 is "no pose qualifies" here)
-    if (rc < 0) return rc;
-    if (rc == 0) return -1;
-    return next_reachable_view(out4xP, reachable, P, min_hits);
-}
-
-// reference :334-372
-KinectFusionReconstruction::CPointCloud KinectFusionReconstruction::ExportPointCloud(int max_buffer) {
-    CPointCloud res;
-    if (max_buffer <= 0 || !tsdf_volume_d_ptr) return res;
-    DeviceArray<float3> cloud_buffer, normal_buffer;
-    cloud_buffer.create(max_buffer);
-    normal_buffer.create(max_buffer);
-    int3 volume_res;
-    volume_res.x = volume_resolution.x();
-    volume_res.y = volume_resolution.y();
-    volume_res.z = volume_resolution.z();
-    // a rank of a sharded run reports the crossings of the planes it owns (the +z neighbour of its last
-    // plane is in its halo); the single-GPU case is the whole volume
-    const int z1 = std::min(zo1, volume_res.z - 1);
-    PtrSz<float3> cloud; cloud.data = cloud_buffer.ptr(); cloud.size = (size_t)max_buffer;
-    const size_t num_points = extractPoints(tsdf_volume_d_ptr->value(), tsdf_volume_d_ptr->weight(), tsdf_volume_d_ptr->grad(), volume_res,
-                                            voxel_size, cloud, zs0, zo0, std::max(z1, zo0));
-    if (num_points == 0) return res;
-    cloud.size = num_points;
-    PtrSz<float3> normal; normal.data = normal_buffer.ptr(); normal.size = num_points;
-    extractNormals(tsdf_volume_d_ptr->value(), tsdf_volume_d_ptr->weight(), tsdf_volume_d_ptr->grad(), volume_res, voxel_size, cloud, normal,
-                   zs0, zs1);
-    res.positions.resize(3 * num_points);
-    res.normals.resize(3 * num_points);
-    hipSafeCall(hipMemcpy(res.positions.data(), cloud_buffer.ptr(), num_points * sizeof(float3), hipMemcpyDeviceToHost));
-    hipSafeCall(hipMemcpy(res.normals.data(), normal_buffer.ptr(), num_points * sizeof(float3), hipMemcpyDeviceToHost));
-    return res;
-}
-bool KinectFusionReconstruction::CPointCloud::exportPly(const std::string &filename) const {
-    std::ofstream file_out{filename};
-    if (!file_out.is_open()) return false;
-    file_out << "ply\nformat ascii 1.0\ncomment Created by myself\nelement vertex " << size() << "\n";
-    file_out << "property float x\nproperty float y\nproperty float z\nproperty float nx\nproperty float ny\nproperty float nz\nend_header\n";
-    for (size_t i = 0; i < size(); ++i)
-        file_out << positions[3 * i] << " " << positions[3 * i + 1] << " " << positions[3 * i + 2] << " " << normals[3 * i] << " "
-                 << normals[3 * i + 1] << " " << normals[3 * i + 2] << "\n";
-    return true;
-}
-
-KinectFusionReconstruction::CMesh KinectFusionReconstruction::ExportMesh(int min_weight) {
-    CMesh m;
-    if (!tsdf_volume_d_ptr) return m;
-    if (sign_map_stale_) { RebuildSignMap(); sign_map_stale_ = false; }   // (the map must be a superset of the negative voxels)
-    const int res[3] = {volume_resolution.x(), volume_resolution.y(), volume_resolution.z()};
-    const bool seeded = csfd_seed_row >= 0 && csfd_seed_row < 4 && csfd_seed_col >= 0 && csfd_seed_col < 4;
-    m.has_im = seeded;   // (also for an empty mesh: a rank without surface still says whether its vertices would carry derivatives)
-    DeviceArray2D<float> value = tsdf_volume_d_ptr->value(), grad = tsdf_volume_d_ptr->grad();
-    DeviceArray2D<int> weight = tsdf_volume_d_ptr->weight();
-    // (TsdfVolume allocates the three arrays alike: one pitch)
-    xs_mesh_opts o{};
-    o.struct_bytes = sizeof(o);
-    o.zs0 = zs0; o.zs1 = zs1;
-    o.z0 = zo0; o.z1 = std::max(std::min(zo1, res[2] - 1), zo0);   // (as ExportPointCloud)
-    o.min_weight = min_weight; o.want_normals = 1;
-    o.signmap = sign_map_ptr(); o.signmap_shift = raycast_sign_map_shift;
-    DeviceArray<unsigned char> ws;
-    ws.create(xs_mesh_workspace_bytes(res, &o));
-    const float *g = seeded ? grad.ptr(0) : nullptr;
-    size_t nv = 0, nt = 0;
-    int rc = xs_extract_mesh(value.ptr(0), weight.ptr(0), g, value.step(), res, voxel_size, &o, nullptr, nullptr, nullptr, nullptr, 0, nullptr, 0,
-                             ws.ptr(), &nv, &nt, current_stream());
-    if (rc == 0) return m;   // (nothing fits in no room only when there is nothing)
-    if (rc != XS_MESH_OVER_CAPACITY) check_rc(rc, "mesh count");
-    DeviceArray<float> verts, vim, normals;
-    DeviceArray<unsigned long long> keys;
-    DeviceArray<int> tris;
-    verts.create(3 * nv); normals.create(3 * nv); keys.create(nv); tris.create(3 * std::max<size_t>(nt, 1));
-    if (seeded) vim.create(3 * nv);
-    size_t nv2 = 0, nt2 = 0;
-    check_rc(xs_extract_mesh(value.ptr(0), weight.ptr(0), g, value.step(), res, voxel_size, &o, verts.ptr(), seeded ? vim.ptr() : nullptr,
-                             normals.ptr(), keys.ptr(), nv, tris.ptr(), nt, ws.ptr(), &nv2, &nt2, current_stream()), "mesh");
-    m.positions.resize(3 * nv); m.normals.resize(3 * nv); m.edge_keys.resize(nv); m.triangles.resize(3 * nt);
-    hipSafeCall(hipMemcpy(m.positions.data(), verts.ptr(), 3 * nv * sizeof(float), hipMemcpyDeviceToHost));
-    hipSafeCall(hipMemcpy(m.normals.data(), normals.ptr(), 3 * nv * sizeof(float), hipMemcpyDeviceToHost));
-    hipSafeCall(hipMemcpy(m.edge_keys.data(), keys.ptr(), nv * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-    if (nt) hipSafeCall(hipMemcpy(m.triangles.data(), tris.ptr(), 3 * nt * sizeof(int), hipMemcpyDeviceToHost));
-    if (seeded) {
-        m.vertex_im.resize(3 * nv);
-        hipSafeCall(hipMemcpy(m.vertex_im.data(), vim.ptr(), 3 * nv * sizeof(float), hipMemcpyDeviceToHost));
-    }
-    return m;
-}
-bool KinectFusionReconstruction::CMesh::exportPly(const std::string &filename) const {
-    std::ofstream f(filename, std::ios::binary);
-    if (!f.is_open()) return false;
-    const bool d = has_im;
-    f << "ply\nformat binary_little_endian 1.0\nelement vertex " << vertices() << "\n";
-    f << "property float x\nproperty float y\nproperty float z\nproperty float nx\nproperty float ny\nproperty float nz\n";
-    if (d) f << "property float dx\nproperty float dy\nproperty float dz\n";
-    f << "element face " << faces() << "\nproperty list uchar int vertex_indices\nend_header\n";
-    std::vector<float> row(d ? 9 : 6);   // (x86 / the hosts this builds for are little-endian: the floats go out as they are)
-    for (size_t i = 0; i < vertices(); ++i) {
-        for (int k = 0; k < 3; ++k) { row[k] = positions[3 * i + k]; row[3 + k] = normals[3 * i + k]; if (d) row[6 + k] = vertex_im[3 * i + k]; }
-        f.write(reinterpret_cast<const char *>(row.data()), (std::streamsize)(row.size() * sizeof(float)));
-    }
-    char face[13];
-    face[0] = 3;
-    for (size_t t = 0; t < faces(); ++t) {
-        std::memcpy(face + 1, &triangles[3 * t], 12);
-        f.write(face, 13);
-    }
-    return (bool)f;
-}
-
 void KinectFusionReconstruction::synchronize() { hipSafeCall(hipStreamSynchronize(current_stream())); }
 
-long long KinectFusionReconstruction::lastUpdatedVoxels() { return last_frame_counter(0); }
-long long KinectFusionReconstruction::lastRaycastHits() { return last_frame_counter(1); }
-long long KinectFusionReconstruction::last_frame_counter(int which) {
-    if (counter_frame_ == 0) return 0;
-    unsigned long long h[2] = {0, 0};
-    synchronize();
-    flush_pending_fold(current_stream());
-    hipSafeCall(hipStreamSynchronize(current_stream()));
-    hipSafeCall(hipMemcpy(h, counters_.ptr() + 2 * (size_t)((counter_frame_ - 1) % COUNTER_RING), sizeof(h), hipMemcpyDeviceToHost));
-    return (long long)h[which];
-}
-
-// ---- volume checkpoint --------------------------------------------------------------------
-// reference :438-447 writes raw float32 values; here X*Y*Z of them (the reference's count uses
-// res[2] twice)
-void KinectFusionReconstruction::saveTSDFVolume(const std::string &tsdf_filename) {
-    std::vector<float> tsdf;
-    tsdf_volume_d_ptr->downloadTSDFWithoutGrad(tsdf);
-    std::ofstream f(tsdf_filename, std::ios::binary);
-    f.write(reinterpret_cast<const char *>(tsdf.data()), (std::streamsize)(tsdf.size() * sizeof(float)));
-}
-namespace {
-// Volume checkpoint, version 2.  Layout: header, n_poses x Matrix4cf, then value / grad / weight of the stored planes
-// [zs0, zs1) as dense rows of X elements (a rank of a sharded run saves and restores its own planes).
-struct CkptHeader {
-    char magic[8];
-    int res[3];
-    float voxel_size, tranc_dist;
-    int frame_id, n_poses;
-    int zs0, zs1;        // planes held in this file
-    int shard_rank, shard_count;
-};
-const int CKPT_MAX_POSES = 1 << 24;   // a sanity bound on the pose record (16 M frames), not a format limit
-// one device <- host copy of a dense array into the EXISTING pitched buffer (no reallocation, no temporaries)
-template <class T>
-void restore_rows(DeviceArray2D<T> dst, const std::vector<T> &src, int cols, size_t rows) {
-    hipSafeCall(hipMemcpy2D(dst.ptr(), dst.step(), src.data(), (size_t)cols * sizeof(T), (size_t)cols * sizeof(T), rows, hipMemcpyHostToDevice));
-}
-}  // namespace
-void KinectFusionReconstruction::saveCheckpoint(const std::string &filename) {
-    std::vector<float> v, g;
-    std::vector<int> w;
-    tsdf_volume_d_ptr->downloadTSDFWithGrad(v, g);
-    tsdf_volume_d_ptr->downloadWeight(w);
-    CkptHeader h{};
-    std::snprintf(h.magic, sizeof(h.magic), "XSTSDF2");
-    for (int i = 0; i < 3; ++i) h.res[i] = volume_resolution[i];
-    h.voxel_size = voxel_size; h.tranc_dist = tsdf_volume_d_ptr->getTsdfTruncDist(); h.frame_id = frame_id;
-    h.n_poses = (int)world2camera_record.size();
-    h.zs0 = zs0; h.zs1 = zs1; h.shard_rank = shard_rank; h.shard_count = shard_count;
-    std::ofstream f(filename, std::ios::binary);
-    f.write(reinterpret_cast<const char *>(&h), sizeof(h));
-    f.write(reinterpret_cast<const char *>(world2camera_record.data()), (std::streamsize)(h.n_poses * sizeof(Matrix4cf)));
-    f.write(reinterpret_cast<const char *>(v.data()), (std::streamsize)(v.size() * 4));
-    f.write(reinterpret_cast<const char *>(g.data()), (std::streamsize)(g.size() * 4));
-    f.write(reinterpret_cast<const char *>(w.data()), (std::streamsize)(w.size() * 4));
-}
-// Nothing of *this is touched until the whole file has been read and validated: magic, volume geometry (resolution,
-// voxel size, truncation distance), the planes it holds against the planes this instance stores, a sane pose count and
-// the exact file length.  Returns false (state unchanged) on any mismatch.
 // The sign map from the volume alone (allocation, checkpoint, anything that wrote the value array without the integrate kernels).
 void KinectFusionReconstruction::RebuildSignMap() {
     ++volume_generation;   // the documented "the volume was written" call: the relocalisation index is rebuilt too
     if (!sign_map_on() || !sign_map_.ptr() || !tsdf_volume_d_ptr) return;
-    const int res[3] = {volume_resolution.x(), volume_resolution.y(), volume_resolution.z()};
     DeviceArray2D<float> value = tsdf_volume_d_ptr->value();
-    check_rc(xs_signmap_rebuild_slab(sign_map_.ptr(), res, raycast_sign_map_shift, tsdf_volume_d_ptr->getTsdfTruncDist(), value.ptr(0), value.step(),
+    check_rc(xs_signmap_rebuild_slab(sign_map_.ptr(), res3(), raycast_sign_map_shift, tsdf_volume_d_ptr->getTsdfTruncDist(), value.ptr(0), value.step(),
                                      zs0, zs1, current_stream()), "sign map");
-}
-
-bool KinectFusionReconstruction::loadCheckpoint(const std::string &filename) {
-    std::ifstream f(filename, std::ios::binary);
-    if (!f || !tsdf_volume_d_ptr) return false;
-    f.seekg(0, std::ios::end);
-    const long long file_bytes = (long long)f.tellg();
-    f.seekg(0, std::ios::beg);
-    CkptHeader h{};
-    if (file_bytes < (long long)sizeof(h)) return false;
-    f.read(reinterpret_cast<char *>(&h), sizeof(h));
-    if (!f || std::memcmp(h.magic, "XSTSDF2", 8) != 0) return false;
-    for (int i = 0; i < 3; ++i) if (h.res[i] != volume_resolution[i]) return false;
-    if (h.voxel_size != voxel_size || h.tranc_dist != tsdf_volume_d_ptr->getTsdfTruncDist()) return false;
-    if (h.zs0 != zs0 || h.zs1 != zs1 || h.shard_rank != shard_rank || h.shard_count != shard_count) return false;
-    if (h.n_poses < 1 || h.n_poses > CKPT_MAX_POSES || h.frame_id < 0) return false;
-    const int X = h.res[0];
-    const size_t rows = (size_t)h.res[1] * (size_t)(h.zs1 - h.zs0), n = rows * (size_t)X;
-    const long long expect = (long long)sizeof(h) + (long long)h.n_poses * (long long)sizeof(Matrix4cf) + 3LL * (long long)n * 4LL;
-    if (file_bytes != expect) return false;            // truncated or trailing bytes
-    std::vector<Matrix4cf> poses((size_t)h.n_poses);
-    f.read(reinterpret_cast<char *>(poses.data()), (std::streamsize)(poses.size() * sizeof(Matrix4cf)));
-    std::vector<float> v(n), g(n);
-    std::vector<int> w(n);
-    f.read(reinterpret_cast<char *>(v.data()), (std::streamsize)(n * 4));
-    f.read(reinterpret_cast<char *>(g.data()), (std::streamsize)(n * 4));
-    f.read(reinterpret_cast<char *>(w.data()), (std::streamsize)(n * 4));
-    if (!f) return false;
-    DeviceArray2D<float> dv = tsdf_volume_d_ptr->value(), dg = tsdf_volume_d_ptr->grad();
-    DeviceArray2D<int> dw = tsdf_volume_d_ptr->weight();
-    if ((size_t)dv.rows() != rows || dv.cols() != X || (size_t)dg.rows() != rows || (size_t)dw.rows() != rows) return false;
-    // validated: commit
-    synchronize();
-    restore_rows(dv, v, X, rows);
-    restore_rows(dg, g, X, rows);
-    restore_rows(dw, w, X, rows);
-    ++volume_generation;
-    RebuildSignMap();    // the volume was written behind the integrate kernels' back
-    world2camera_record.swap(poses);
-    world2camera = world2camera_record.back();
-    frame_id = h.frame_id;
-    // previous-frame maps are derived state: regenerate them from the restored volume and pose (in a sharded run every
-    // rank must load its own file before the next frame: the raycast composite is a collective)
-    CalculatePointCloud(vmaps_g_prev_d[0], nmaps_g_prev_d[0]);
-    ModelMapPyramid();
-    synchronize();
-    return true;
 }
 
 // ---- per-stage HIP event timing (on the stream the kernels are launched on) -----------------

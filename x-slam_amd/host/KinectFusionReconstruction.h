@@ -161,6 +161,7 @@ public:
 
     int getFrame() const { return frame_id; }
     int getVolumeSize() const { return volume_resolution[0] * volume_resolution[1] * volume_resolution[2]; }
+    const int *res3() const { return volume_resolution.v; }   // the resolution as the launchers take it
     Matrix4cf getCamera2Volume() { return world2volume * xs_host::inverse(world2camera); }
 
     void AllocateBuffers();
@@ -204,7 +205,7 @@ public:
     // Batched relocalisation against a fixed map: the band voxels of the owned planes are compacted once per volume
     // generation into an index in the six-pose kernel's own dealing order (xs_tsdf_band_build), and every pass evaluates the index for all frames
     // still active, at most XS_BAND_MAX_FRAMES per launch (xs_tsdf_gauss_newton_terms_band).  Frame f's sums are bit-identical to the dense pass's,
-    // and the host step is RelocalizeGaussNewton's own (gn_loop_step): ok[f], camera2volume[f] and loss_history[f] are what RelocalizeGaussNewton
+    // and the host step is RelocalizeGaussNewton's own (gn_host.hpp: damped_spd6_step inside gn_batch_loop): ok[f], camera2volume[f] and loss_history[f] are what RelocalizeGaussNewton
     // returns for that frame alone.  A frame that fails or finishes drops out of the launches.  In shard mode the F x 29 sums are all-reduced.
     // loss_history: null, or F vectors (each gets the losses RelocalizeGaussNewton would give it).  Returns the number of frames that succeeded.
     int RelocalizeGaussNewtonBatch(const std::vector<DeviceArray2D<ushort>> &depths, Matrix4cf *camera2volume, int iterations, float damping,
@@ -255,7 +256,7 @@ public:
                   unsigned char *reachable, unsigned short *clear2);
     int NextReachableView(const Matrix4cf *camera2volume, int P, const xs_view_opts *opts, int min_weight, unsigned min_hits, unsigned *out4xP,
                           float radius_m, int snap_vox, int unknown_blocks, unsigned char *reachable);
-    long long RelocalizationIndexVoxels() const { return band_generation_ >= 0 ? band_.count : 0; }   // the index as last built, 0 before any
+    long long RelocalizationIndexVoxels() const { return reloc_.band_key.generation >= 0 ? reloc_.band.count : 0; }   // the index as last built, 0 before any
     // bumped by everything that writes the volume: integrate calls, loadCheckpoint, xs_kf_volume_ptr(kf, 0, .), RebuildSignMap (the band index is rebuilt
     // when its generation differs)
     long long volume_generation = 0;
@@ -311,47 +312,64 @@ private:
     DeviceArray<unsigned char> icp_ws_;        // per-workgroup partial records of the ICP reduction
     DeviceArray<double> icp_sums_;             // 27 complex sums + inlier count
     DeviceArray<unsigned char> icp_pose_;      // device-resident pose of the ICP loop (xs_icp_iterate)
-    DeviceArray<double> gn_sums_;              // 29 Gauss-Newton sums (+ pad)
-    double *gn_publish_ = nullptr;             // pinned: the 29 sums + sequence word a pass publishes (xs_gn_publish_bytes)
-    void *gn_mailbox_ = nullptr;               // the six-pose mailbox of the passes enqueued ahead (xs_gn_post_poses)
-    int gn_mailbox_in_device_ = 0;
-    unsigned long long gn_seq_ = 0;
-    unsigned gn_mail_seq_ = 0;
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> gn_events_;
-    DeviceArray<float> gn_dense_;              // packed copy of the owned planes when the volume is pitched
-    DeviceArray<unsigned char> gn_ws_;         // reduce workspace of the Gauss-Newton / Hessian kernels
-    const float *GaussNewtonDenseView();       // the owned planes as the dense array the Gauss-Newton kernels index (packed into gn_dense_ when pitched)
-    void BandIndexPrepare();                   // (re)builds band_ when the volume changed since it was built
+    // What each derived map was built with (generation -1: not built, or no longer to be trusted); a map is rebuilt when its key differs.
+    struct BandKey { long long generation = -1; bool operator==(const BandKey &o) const { return generation == o.generation; } };
+    struct GridKey { long long generation = -1; int min_weight = 0; bool operator==(const GridKey &o) const { return generation == o.generation && min_weight == o.min_weight; } };
+    struct ClearKey { GridKey grid; int R = 0, unknown = -1; bool operator==(const ClearKey &o) const { return grid == o.grid && R == o.R && unknown == o.unknown; } };
+    struct ReachKey {   // the field flooded, the body's r2 and the snapped seed
+        ClearKey field; int r2 = 0, seed[3] = {-1, -1, -1};
+        bool operator==(const ReachKey &o) const { return field == o.field && r2 == o.r2 && seed[0] == o.seed[0] && seed[1] == o.seed[1] && seed[2] == o.seed[2]; }
+    };
+    // Relocalisation against the map (kf_relocalize.cpp): nothing the frame path touches.
+    struct Reloc {
+        DeviceArray<double> gn_sums;               // 29 Gauss-Newton sums (+ pad)
+        double *gn_publish = nullptr;              // pinned: the 29 sums + sequence word a pass publishes (xs_gn_publish_bytes)
+        void *gn_mailbox = nullptr;                // the six-pose mailbox of the passes enqueued ahead (xs_gn_post_poses)
+        int gn_mailbox_in_device = 0;
+        unsigned long long gn_seq = 0;
+        unsigned gn_mail_seq = 0;
+        std::vector<std::pair<hipEvent_t, hipEvent_t>> gn_events;
+        DeviceArray<float> gn_dense;               // packed copy of the owned planes when the volume is pitched
+        DeviceArray<unsigned char> gn_ws;          // reduce workspace of the dense Gauss-Newton kernel
+        xs_band_index band = {};                   // band index of the owned planes (RelocalizeGaussNewtonBatch)
+        BandKey band_key;                          // the volume_generation it was built at
+        DeviceArray<unsigned long long> band_keys;
+        DeviceArray<float> band_values;
+        DeviceArray<long long> band_segs;
+        DeviceArray<unsigned char> band_ws;        // xs_tsdf_band_workspace_bytes(XS_BAND_MAX_FRAMES)
+        DeviceArray<double> band_sums;             // XS_BAND_MAX_FRAMES x 29
+        std::vector<DeviceArray2D<float>> band_depth;   // the batch's scaled depths, one per frame
+        DeviceArray<unsigned char> newton_ws;      // xs_tsdf_pose_hessian_workspace_bytes(XS_BAND_MAX_FRAMES)
+        DeviceArray<double> newton_sums;           // XS_BAND_MAX_FRAMES x 29
+        DeviceArray<unsigned char> score_ws;       // xs_tsdf_score_poses_workspace_bytes(XS_SCORE_MAX_POSES)
+        DeviceArray<double> score_sums;            // XS_SCORE_MAX_POSES x 2
+        DeviceArray2D<float> score_depth;          // ScorePoses' scaled depth
+    } reloc_;
+    const float *GaussNewtonDenseView();       // the owned planes as the dense array the Gauss-Newton kernels index (packed into gn_dense when pitched)
+    void BandIndexPrepare();                   // (re)builds the band index when the volume changed since it was built
     size_t BandBatchPrepare(const std::vector<DeviceArray2D<ushort>> &depths);   // index, workspace and scaled depths of a batch
+    void GaussNewtonBandLaunch(const int *frames, int n, const Matrix4cf *camera2volume, size_t scaled_step, int rows, int cols, double *raw);
     void PoseHessianLaunch(const int *frames, int n, const Matrix4cf *camera2volume, size_t scaled_step, int rows, int cols, double *raw);
-    DeviceArray<unsigned char> newton_ws_;     // xs_tsdf_pose_hessian_workspace_bytes(XS_BAND_MAX_FRAMES), tickets zeroed once
-    DeviceArray<double> newton_sums_;          // XS_BAND_MAX_FRAMES x 29
-    DeviceArray<unsigned char> score_ws_;      // xs_tsdf_score_poses_workspace_bytes(XS_SCORE_MAX_POSES), tickets zeroed once
-    DeviceArray<double> score_sums_;           // XS_SCORE_MAX_POSES x 2
-    DeviceArray2D<float> score_depth_;         // ScorePoses' scaled depth
-    bool ViewGridPrepare(int min_weight);      // (re)builds view_grid_ when the volume or min_weight changed since it was built
-    DeviceArray<unsigned char> view_grid_;     // xs_view_grid_bytes(resolution): the observation grid + a launch's poses
-    DeviceArray<unsigned> view_counts_;        // XS_VIEW_MAX_POSES x 4
-    long long view_generation_ = -1;           // the volume_generation view_grid_ was built at
-    int view_min_weight_ = 0;                  // and the min_weight
-    bool ClearancePrepare(int R, int unknown_blocks, int min_weight);   // view_grid_ and clear_field_ in step with the volume and the arguments
+    void ensure_reduce_workspace(DeviceArray<unsigned char> &ws, size_t bytes, const char *what);   // grown when too small, its tickets zeroed only then
+    void fetch_sums(double *device_sums, size_t count, double *host_sums);   // all-reduce when sharded, copy to the host, stream drain
+    // View planning over the map (kf_planning.cpp): nothing the frame path touches.
+    struct Planning {
+        DeviceArray<unsigned char> view_grid;      // xs_view_grid_bytes(resolution): the observation grid + a launch's poses
+        DeviceArray<unsigned> view_counts;         // XS_VIEW_MAX_POSES x 4
+        GridKey grid_key;
+        DeviceArray<unsigned char> clear_field;    // xs_clearance_bytes(resolution)
+        DeviceArray<unsigned char> clear_ws;       // xs_clearance_workspace_bytes(resolution)
+        ClearKey clear_key;
+        DeviceArray<unsigned char> reach;          // xs_reach_bytes(resolution): reached and passable words
+        DeviceArray<unsigned char> reach_io;       // a query's points and answers
+        ReachKey reach_key;
+    } plan_;
+    bool ViewGridPrepare(int min_weight);      // (re)builds the observation grid when the volume or min_weight changed since it was built
+    bool ClearancePrepare(int R, int unknown_blocks, int min_weight);   // grid and clearance field in step with the volume and the arguments
     int ReachQuery(const float *points3xN, int n, int over_passable, int snap, unsigned char *reachable, unsigned short *clear2, int *voxel);
-    DeviceArray<unsigned char> clear_field_;   // xs_clearance_bytes(resolution)
-    DeviceArray<unsigned char> clear_ws_;      // xs_clearance_workspace_bytes(resolution)
-    long long clear_generation_ = -1;          // what clear_field_ was built with: volume_generation, min_weight, R, unknown_blocks
-    int clear_min_weight_ = 0, clear_R_ = 0, clear_unknown_ = -1;
-    DeviceArray<unsigned char> reach_;         // xs_reach_bytes(resolution): reached and passable words
-    DeviceArray<unsigned char> reach_io_;      // a query's points and answers
-    long long reach_generation_ = -1;          // what the flood in reach_ ran with: the field's key, r2 and the snapped seed
-    int reach_min_weight_ = 0, reach_R_ = 0, reach_unknown_ = -1, reach_r2_ = 0, reach_seed_[3] = {-1, -1, -1};
-    xs_band_index band_ = {};                  // band index of the owned planes (RelocalizeGaussNewtonBatch)
-    long long band_generation_ = -1;           // the volume_generation it was built at
-    DeviceArray<unsigned long long> band_keys_;
-    DeviceArray<float> band_values_;
-    DeviceArray<long long> band_segs_;
-    DeviceArray<unsigned char> band_ws_;       // xs_tsdf_band_workspace_bytes(XS_BAND_MAX_FRAMES), tickets zeroed once
-    DeviceArray<double> band_sums_;            // XS_BAND_MAX_FRAMES x 29
-    std::vector<DeviceArray2D<float>> band_depth_;   // the batch's scaled depths, one per frame
+    // the volume object was replaced or released: whatever was derived from the old one is rebuilt on next use (the Gauss-Newton mailbox and
+    // sequence numbers stay)
+    void invalidate_derived_maps() { reloc_.band_key = BandKey{}; plan_.grid_key = GridKey{}; plan_.clear_key = ClearKey{}; plan_.reach_key = ReachKey{}; }
     DeviceArray2D<ushort> depth_ingest_d_;     // device copy of a host frame (ProcessFrameHost)
     ushort *ingest_pinned_[2] = {nullptr, nullptr};
     hipEvent_t ingest_done_[2] = {nullptr, nullptr};

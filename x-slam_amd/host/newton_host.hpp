@@ -2,7 +2,7 @@
 // xs_tsdf_pose_hessian_band and the step taken on its 29 sums.  Pure host code, no device call: the orchestrator
 // uses it between launches and the C ABI exposes it as xs_host_newton_seeded_poses / xs_host_newton_step so it is tested without a GPU.
 #pragma once
-#include "host_algebra.hpp"
+#include "gn_host.hpp"
 
 namespace xs_host {
 
@@ -66,21 +66,9 @@ inline void newton_scale_sums(const double *raw, double out29[29]) {
     out29[27] = raw[27]; out29[28] = raw[28];
 }
 
-// One Newton step on the scaled sums s = {H upper triangle (21), g (6), sum r^2, count}: (H + damping diag(H)) delta = -g by Cholesky, then
-// camera2volume <- se3Exp(delta) camera2volume.  false, camera2volume untouched: fewer than six voxels, or the damped system is not positive
-// definite (away from the optimum the exact Hessian can be indefinite; the caller then takes a Gauss-Newton step).
-inline bool newton_step(const double s[29], double damping, Matrix4cf &camera2volume) {
-    if (s[28] < 6) return false;
-    double A[36], b[6], x[6];
-    int q = 0;
-    for (int j = 0; j < 6; ++j)
-        for (int k = j; k < 6; ++k, ++q) { A[j * 6 + k] = s[q]; A[k * 6 + j] = s[q]; }
-    for (int k = 0; k < 6; ++k) { A[k * 6 + k] *= 1.0 + damping; b[k] = -s[21 + k]; }
-    if (!solve_spd6(A, b, x)) return false;
-    hostComplex xi[6];
-    for (int k = 0; k < 6; ++k) xi[k] = hostComplex((float)x[k], 0.f);
-    camera2volume = se3Exp(xi) * camera2volume;
-    return true;
-}
+// One Newton step on the scaled sums s = {H upper triangle (21), g (6), sum r^2, count}: gn_host.hpp's damped step with the exact Hessian.
+// false, camera2volume untouched: fewer than six voxels, or the damped system is not positive definite (away from the optimum the exact
+// Hessian can be indefinite; the caller then takes a Gauss-Newton step).
+inline bool newton_step(const double s[29], double damping, Matrix4cf &camera2volume) { return damped_spd6_step(s, damping, camera2volume); }
 
 }  // namespace xs_host
