@@ -528,6 +528,48 @@ int xs_reach_query(int n, const float *points3xN_dev, const int *res, float voxe
                    const unsigned short *field_dev, int snap, unsigned char *reachable_dev, unsigned short *clear2_dev, int *voxel3xN_dev,
                    void *stream);
 
+/* ---- travel cost and shortest collision-free path over the reached set (xs_travel.hip) --------------------------
+ * No counterpart in the reference.  Integer arithmetic throughout, no atomics: every result is a pure function of the inputs and two runs
+ * give equal bytes.  DOMAIN: the REACHED voxels, read from the reached words of `reach` as xs_reach_flood leaves them.
+ * MOVES: the 26 neighbour offsets o = (dx, dy, dz) != 0, components in {-1, 0, 1}; the cost w(o) is 3, 4 or 5 for one, two or three non-zero
+ * components (the <3, 4, 5> chamfer metric: a unit is a third of a voxel edge).  v -> v + o is ALLOWED iff v + o is in the domain and so is
+ * every v + o', o' being o with a non-empty proper subset of its non-zero components set to zero (the 2 face neighbours of an edge move, the
+ * 6 face and edge neighbours of a corner move): the body never squeezes between two obstacle voxels that touch diagonally.  The rule is
+ * symmetric in v and v + o, and an allowed diagonal move implies a 6-connected detour.
+ * FIELD.  travel[(z * Y + y) * X + x] (uint16, dense; xs_travel_bytes(res): 2 bytes per voxel, 0 for a bad resolution) is 0 at every seed
+ * that is in the domain, elsewhere the least sum of w over paths of allowed moves from a seed if that sum is <= limit (0 .. XS_TRAVEL_MAX;
+ * 0: the seeds only), and XS_TRAVEL_NONE otherwise.  Sums are formed in 32 bits and a candidate above the limit is dropped, never stored:
+ * the field is the unique fixpoint of d[v] = min(d[v], d[u] + w) under that cap.
+ * xs_travel_build: `seeds` (1 .. XS_REACH_MAX_SEEDS) integer voxels, host array seeds3xN + 3 k = (x, y, z); a seed outside the volume or
+ * outside the domain contributes nothing.  Fills the field with 0xFF, writes the seeds' zeros and runs rounds as plain launches: a
+ * workgroup owns a tile of 8 x 8 x 8 voxels (2 x 2 x 2 bricks), returns at once if none of its reached words has a bit, otherwise holds the
+ * tile with a one-voxel apron in LDS, relaxes it there until nothing in the tile changes, writes back its own voxels that fell and sets the
+ * round's `changed` word with a plain store.  Aprons are re-read from global memory every round; a stale value delays a distance by a
+ * round and never invents one, so the result does not depend on scheduling (the number of rounds may).  The host reads the changed words
+ * (in `workspace`: xs_travel_workspace_bytes() of device memory, 4-byte aligned, not the reach buffer) after each batch of rounds and
+ * stops after the first round that changed nothing: THE CALL SYNCHRONISES THE STREAM.  *rounds_out (optional) receives the number of
+ * rounds up to and including that one.
+ * xs_travel_query: n >= 1 integer voxels (int32 device array voxel3xN_dev + 3 i = (x, y, z), e.g. the answering voxels of xs_reach_query):
+ * out_dev[i] = travel[v], XS_TRAVEL_NONE outside the volume.  No synchronisation.
+ * xs_travel_path: n targets (1 .. XS_TRAVEL_MAX_TARGETS, int32 device array), one lane each.  From a target t with travel[t] != NONE: while
+ * travel[v] != 0, step to v + o for the allowed move with travel[v + o] + w(o) = travel[v] that has the lowest index k = (dz + 1) * 9 +
+ * (dy + 1) * 3 + (dx + 1) (one exists at a fixpoint).  The path is the voxels visited, t first and the seed last; path3_dev[(i * capacity
+ * + s) * 3 ..] receives voxel s of target i for s < min(length, capacity), slots beyond that are untouched; len_dev[i] receives the full
+ * length even when it exceeds capacity: 1 when t is a seed, 0 when travel[t] = NONE or t is outside the volume.  `limit` (that of the
+ * build) only bounds the walk's trip count, at limit / 3 + 2, so that a corrupt field cannot spin it.  No synchronisation.
+ * hipErrorInvalidValue with nothing launched and the outputs untouched: null pointers, a bad resolution, seeds outside 1 .. 64, limit
+ * outside 0 .. 65534, n outside its range, capacity < 1. */
+#define XS_TRAVEL_NONE 65535
+#define XS_TRAVEL_MAX 65534
+#define XS_TRAVEL_MAX_TARGETS 64
+size_t xs_travel_bytes(const int *res);
+size_t xs_travel_workspace_bytes(void);
+int xs_travel_build(const void *reach, const int *res, const int *seeds3xN, int seeds, int limit, unsigned short *travel_dev, void *workspace,
+                    int *rounds_out, void *stream);
+int xs_travel_query(int n, const int *voxel3xN_dev, const int *res, const unsigned short *travel_dev, unsigned short *out_dev, void *stream);
+int xs_travel_path(int n, const int *target3xN_dev, const int *res, const void *reach, const unsigned short *travel_dev, int limit, int capacity,
+                   int *path3_dev, int *len_dev, void *stream);
+
 /* ---- surface extraction (export; real-valued) ------------------------------------------------ */
 size_t xs_extract_workspace_bytes(const int *res);
 /* size_t extractPoints(value_volume, weight_volume, grad_volume, volume_resolution, voxel_size,

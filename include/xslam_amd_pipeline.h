@@ -152,6 +152,27 @@ int xs_kf_reachable(void *kf, const float *start_c2v32_or_null, float radius_m, 
                     unsigned char *reachable, unsigned short *clear2);
 int xs_kf_next_reachable_view(void *kf, int poses, const float *c2v32xP, const struct xs_view_opts *opts, int min_weight, unsigned min_hits, unsigned *out4xP,
                               float radius_m, int snap_vox, int unknown_blocks, unsigned char *reachable);
+/* Travel cost and shortest collision-free path to a candidate view: how far is it, and which way?  The field of
+ * xs_travel_build (xslam_amd.h: the contract; the <3, 4, 5> chamfer metric over the reached voxels without corner cutting, a unit is a third
+ * of a voxel edge) is built from the snapped start of xs_kf_reachable, whose start arguments all three calls share, up to the limit
+ * 65534 for max_travel_m <= 0 or not finite, otherwise min(65534, (int)floorf(3 * max_travel_m / voxel_size)) in float32.
+ * travel: xs_kf_reachable plus travel3[p], the uint16 cost at the centre voxel of pose p (not snapped), 65535 where unreachable or beyond
+ * the limit.  Returns as xs_kf_reachable does.
+ * path_to: the number of voxels of the path from the start to the centre voxel of target_c2v32, START FIRST AND TARGET LAST; voxels3 (int32)
+ * and points3 (float32, the voxel centres (v + 0.5) * voxel_size in volume coordinates) are optional.  0 when the target is not reached (or
+ * beyond the limit, or there is no volume), -1 on bad arguments (capacity < 1 among them), -2 in shard mode, -4 with nothing written when the
+ * path is longer than `capacity`; *needed_out (optional) receives the path's length whenever a walk ran.
+ * next_view_by_travel: xs_kf_next_best_view's scoring; among the poses with a cost and hits >= min_hits the one with the largest
+ * unknown / (travel + bias3), bias3 = max(1, (int)ceilf(3 * bias_m / voxel_size)), compared exactly in 64-bit integers, ties to the lower
+ * index.  bias_m (>= 0, finite) is the fixed cost of taking any view at all.  travel3_out (optional) receives the costs.  Returns as
+ * xs_kf_next_reachable_view does.  The field is cached and redone when the flood or the limit change.  In shard mode all three return -2
+ * and do nothing.  xs_kf_next_best_view, xs_kf_reachable, xs_kf_next_reachable_view and their results do not change. */
+int xs_kf_travel(void *kf, const float *start_c2v32_or_null, float radius_m, int snap_vox, int unknown_blocks, int min_weight, float max_travel_m, int P,
+                 const float *c2v32xP, unsigned char *reachable, unsigned short *clear2, unsigned short *travel3);
+int xs_kf_path_to(void *kf, const float *start_c2v32_or_null, float radius_m, int snap_vox, int unknown_blocks, int min_weight, float max_travel_m,
+                  const float *target_c2v32, int capacity, int *voxels3, float *points3, int *needed_out);
+int xs_kf_next_view_by_travel(void *kf, int poses, const float *c2v32xP, const struct xs_view_opts *opts, int min_weight, unsigned min_hits, unsigned *out4xP,
+                              float radius_m, int snap_vox, int unknown_blocks, float max_travel_m, float bias_m, unsigned short *travel3_out);
 /* band voxels in the relocalisation index as last built (0 before the first batch) */
 long long xs_kf_relocalization_index_voxels(void *kf);
 /* ExportPointCloud(max_buffer)  .cpp:334-372 (+ CPointCloud::exportPly, main.cpp:78-80): zero-crossing points of

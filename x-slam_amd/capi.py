@@ -77,6 +77,11 @@ _SIGS = {
     "xs_reach_flood": (C.c_int, [_vp, _vp, _i32p, C.c_int, _i32p, C.c_int, _vp, _i32p, _vp]),
     "xs_reach_expand": (C.c_int, [_vp, _i32p, C.c_int, _vp, _vp]),
     "xs_reach_query": (C.c_int, [C.c_int, _vp, _i32p, C.c_float, _vp, C.c_int, _vp, C.c_int, _vp, _vp, _vp, _vp]),
+    "xs_travel_bytes": (_sz, [_i32p]),
+    "xs_travel_workspace_bytes": (_sz, []),
+    "xs_travel_build": (C.c_int, [_vp, _i32p, _i32p, C.c_int, C.c_int, _vp, _vp, _i32p, _vp]),
+    "xs_travel_query": (C.c_int, [C.c_int, _vp, _i32p, _vp, _vp, _vp]),
+    "xs_travel_path": (C.c_int, [C.c_int, _vp, _i32p, _vp, _vp, C.c_int, C.c_int, _vp, _vp, _vp]),
     "xs_integrate_scaled_ex2": (C.c_int, [_vp, _sz, C.c_int, C.c_int, _f32p, C.c_int, _i32p, C.c_float, _f32p, _f32p, C.c_float, _vp, _vp, _vp,
                                          _sz, C.c_float, C.c_int, C.c_int, _vp, _vp, _vp, C.POINTER(IntegrateOpts), _vp]),
     "xs_integrate_classify_ex": (C.c_int, [C.c_int, C.c_int, _f32p, _i32p, C.c_float, _f32p, _f32p, C.c_float, C.c_int, C.c_int, _vp, _vp,
@@ -664,6 +669,47 @@ def reach_query(n, points, res, voxel_size, reach, field, reachable, clear2, sna
     r = _res3(res)
     check(_lib.xs_reach_query(int(n), _ptr(points), r.ctypes.data_as(_i32p), float(voxel_size), _ptr(reach), int(bool(over_passable)), _ptr(field),
                               int(snap), _ptr(reachable), _ptr(clear2), _ptr(voxel), _stream(stream)))
+
+
+TRAVEL_NONE, TRAVEL_MAX, TRAVEL_MAX_TARGETS = 65535, 65534, 64   # XS_TRAVEL_NONE, XS_TRAVEL_MAX, XS_TRAVEL_MAX_TARGETS
+
+
+def travel_bytes(res):
+    """xs_travel_bytes (host only): the travel field, 2 bytes per voxel; 0 for an invalid resolution."""
+    return int(_lib.xs_travel_bytes(_res3(res).ctypes.data_as(_i32p)))
+
+
+def travel_workspace_bytes():
+    """xs_travel_workspace_bytes (host only): the control words of xs_travel_build."""
+    return int(_lib.xs_travel_workspace_bytes())
+
+
+def travel_build(reach, res, seeds, limit, travel, workspace, stream=None):
+    """xs_travel_build: travel[(z Y + y) X + x] (uint16 device tensor) = the least <3, 4, 5> chamfer cost without corner cutting from one of
+    `seeds` ([N, 3] integer voxels, N = 1 .. 64) over the reached words of a flooded `reach`, 65535 beyond `limit` (0 .. 65534) or where
+    not reached.  Synchronises the stream.  Returns the number of rounds."""
+    r = _res3(res)
+    s = np.ascontiguousarray(seeds, dtype=np.int32).reshape(-1)
+    assert s.size % 3 == 0
+    rounds = C.c_int(0)
+    check(_lib.xs_travel_build(_ptr(reach), r.ctypes.data_as(_i32p), s.ctypes.data_as(_i32p), s.size // 3, int(limit), _ptr(travel), _ptr(workspace),
+                               C.byref(rounds), _stream(stream)))
+    return int(rounds.value)
+
+
+def travel_query(n, voxels, res, travel, out, stream=None):
+    """xs_travel_query: n integer voxels (int32 device tensor of 3 n) -> out (uint16): travel[v], 65535 outside the volume."""
+    r = _res3(res)
+    check(_lib.xs_travel_query(int(n), _ptr(voxels), r.ctypes.data_as(_i32p), _ptr(travel), _ptr(out), _stream(stream)))
+
+
+def travel_path(n, targets, res, reach, travel, limit, capacity, path, lengths, stream=None):
+    """xs_travel_path: n targets (1 .. 64; int32 device tensor of 3 n) -> path (int32, n x capacity x 3: the voxels from the target down to
+    the seed, slots beyond a path's length untouched) and lengths (int32 [n], the full lengths)."""
+    r = _res3(res)
+    check(_lib.xs_travel_path(int(n), _ptr(targets), r.ctypes.data_as(_i32p), _ptr(reach), _ptr(travel), int(limit), int(capacity), _ptr(path),
+                              _ptr(lengths), _stream(stream)))
+
 
 
 class GnOpts(C.Structure):

@@ -26,23 +26,12 @@
 #include <stdint.h>
 #include <string.h>
 #include "xs_device.h"
+#include "xs_reach.h"
 #include "../../include/xslam_amd.h"
 
 enum { REACH_FREE = 1, REACH_OCCUPIED = 2, CLEAR_STRIP = 256, CLEAR_APRON = 256, CLEAR_WORDS = (CLEAR_STRIP + 2 * CLEAR_APRON) / 32,
        CLEAR_NONE8 = 255, CLEAR_NONE16 = 65535, REACH_ROUNDS_PER_BATCH = 8, REACH_CONTROL_BYTES = 256 };
 static_assert(XS_REACH_MAX_SEEDS == 64 && XS_REACH_MAX_SNAP == 16 && XS_CLEARANCE_MAX_RADIUS == 255, "the header's bounds");
-
-struct ReachDims { int X, Y, Z, BX, BY, BZ; };
-// false for a resolution the grid cannot index or whose y / z extents do not fit a launch's grid dimensions
-static bool reach_dims(const int *res, ReachDims &d) {
-    if (!res || res[0] < 1 || res[1] < 1 || res[2] < 1) return false;
-    d.X = res[0]; d.Y = res[1]; d.Z = res[2];
-    d.BX = (d.X + 3) / 4; d.BY = (d.Y + 3) / 4; d.BZ = (d.Z + 3) / 4;
-    if (d.Y > 65535 || d.Z > 65535) return false;
-    return (unsigned long long)d.BX * (unsigned long long)d.BY * (unsigned long long)d.BZ < (1ull << 31);
-}
-static size_t reach_voxels(const ReachDims &d) { return (size_t)d.X * (size_t)d.Y * (size_t)d.Z; }
-static size_t reach_bricks(const ReachDims &d) { return (size_t)d.BX * (size_t)d.BY * (size_t)d.BZ; }
 
 // ---- clearance ---------------------------------------------------------------------------------------------------------------------------
 extern "C" size_t xs_clearance_bytes(const int *res) {
@@ -181,7 +170,6 @@ extern "C" size_t xs_reach_bytes(const int *res) {
     ReachDims d;
     return reach_dims(res, d) ? reach_bricks(d) * 16 + REACH_CONTROL_BYTES : 0;
 }
-__host__ __device__ static inline unsigned long long *reach_passable_of(void *reach, size_t nbricks) { return static_cast<unsigned long long *>(reach) + nbricks; }
 
 __global__ void __launch_bounds__(256) k_reach_passable(const uint4 *__restrict__ grid, const uint16_t *__restrict__ field, ReachDims d, unsigned r2,
                                                         unsigned nbricks, unsigned long long *__restrict__ passable) {
@@ -200,8 +188,6 @@ __global__ void __launch_bounds__(256) k_reach_passable(const uint4 *__restrict_
     const unsigned long long m = __ballot(pass);
     if (l == 0) passable[b] = m;
 }
-
-struct ReachSeeds { int n; int v[3 * XS_REACH_MAX_SEEDS]; };
 
 __global__ void k_reach_seed(ReachSeeds s, ReachDims d, const unsigned long long *__restrict__ passable, unsigned long long *__restrict__ reach) {
     if (threadIdx.x != 0 || blockIdx.x != 0) return;

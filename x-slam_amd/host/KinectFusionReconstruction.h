@@ -256,6 +256,22 @@ public:
                   unsigned char *reachable, unsigned short *clear2);
     int NextReachableView(const Matrix4cf *camera2volume, int P, const xs_view_opts *opts, int min_weight, unsigned min_hits, unsigned *out4xP,
                           float radius_m, int snap_vox, int unknown_blocks, unsigned char *reachable);
+    // Travel cost and shortest collision-free path: how far is a candidate, and which way?  Travel is Reachable plus
+    // travel3[p], the uint16 cost of xs_travel_build's field (include/xslam_amd.h: the contract; units of a third of a voxel edge) at the centre
+    // voxel of camera2volume[p] (not snapped), 65535 where unreachable or beyond the limit view_host.hpp's travel_limit derives from
+    // max_travel_m (<= 0: none).  The field is built from the flood's snapped seed.  PathTo returns the number of voxels of the path from the
+    // start to the centre voxel of `target`, start first and target last: voxels3 (int32) and points3 (the voxel centres (v + 0.5) voxel_size in
+    // volume coordinates) are optional; 0 when the target is not reached (or beyond the limit, or there is no volume), -1 on bad arguments, -4
+    // with nothing written when the path is longer than `capacity`; *needed_out (optional) receives the length whenever a walk ran.
+    // NextViewByTravel scores like NextBestView and picks by view_host.hpp's next_view_by_travel with bias3 = travel_bias(bias_m), starting
+    // from the current camera; travel3_out (optional) receives the costs.  Its return codes are NextReachableView's.  The field is cached
+    // under the flood's key and the limit.  All three return -2 in shard mode and do nothing.
+    int Travel(const Matrix4cf *start, float radius_m, int snap_vox, int unknown_blocks, int min_weight, float max_travel_m, int P,
+               const Matrix4cf *camera2volume, unsigned char *reachable, unsigned short *clear2, unsigned short *travel3);
+    int PathTo(const Matrix4cf *start, float radius_m, int snap_vox, int unknown_blocks, int min_weight, float max_travel_m, const Matrix4cf &target,
+               int capacity, int *voxels3, float *points3, int *needed_out);
+    int NextViewByTravel(const Matrix4cf *camera2volume, int P, const xs_view_opts *opts, int min_weight, unsigned min_hits, unsigned *out4xP,
+                         float radius_m, int snap_vox, int unknown_blocks, float max_travel_m, float bias_m, unsigned short *travel3_out);
     long long RelocalizationIndexVoxels() const { return reloc_.band_key.generation >= 0 ? reloc_.band.count : 0; }   // the index as last built, 0 before any
     // bumped by everything that writes the volume: integrate calls, loadCheckpoint, xs_kf_volume_ptr(kf, 0, .), RebuildSignMap (the band index is rebuilt
     // when its generation differs)
@@ -320,6 +336,7 @@ private:
         ClearKey field; int r2 = 0, seed[3] = {-1, -1, -1};
         bool operator==(const ReachKey &o) const { return field == o.field && r2 == o.r2 && seed[0] == o.seed[0] && seed[1] == o.seed[1] && seed[2] == o.seed[2]; }
     };
+    struct TravelKey { ReachKey reach; int limit = -1; bool operator==(const TravelKey &o) const { return reach == o.reach && limit == o.limit; } };
     // Relocalisation against the map (kf_relocalize.cpp): nothing the frame path touches.
     struct Reloc {
         DeviceArray<double> gn_sums;               // 29 Gauss-Newton sums (+ pad)
@@ -363,13 +380,21 @@ private:
         DeviceArray<unsigned char> reach;          // xs_reach_bytes(resolution): reached and passable words
         DeviceArray<unsigned char> reach_io;       // a query's points and answers
         ReachKey reach_key;
+        DeviceArray<unsigned char> travel;         // xs_travel_bytes(resolution): the travel field over the reached words
+        DeviceArray<unsigned char> travel_ws;      // xs_travel_workspace_bytes()
+        DeviceArray<unsigned char> travel_io;      // a cost query's voxels and answers
+        DeviceArray<unsigned char> path_io;        // a path's target, length and voxels
+        TravelKey travel_key;
     } plan_;
     bool ViewGridPrepare(int min_weight);      // (re)builds the observation grid when the volume or min_weight changed since it was built
     bool ClearancePrepare(int R, int unknown_blocks, int min_weight);   // grid and clearance field in step with the volume and the arguments
     int ReachQuery(const float *points3xN, int n, int over_passable, int snap, unsigned char *reachable, unsigned short *clear2, int *voxel);
+    int ReachPrepare(const Matrix4cf *start, float radius_m, int snap_vox, int unknown_blocks, int min_weight);   // plan_.reach in step with the arguments
+    bool TravelPrepare(int limit);             // the travel field in step with plan_.reach and the limit
+    void reach_forget() { plan_.reach_key = ReachKey{}; plan_.travel_key = TravelKey{}; }   // the flood is not to be trusted, nor what was built over it
     // the volume object was replaced or released: whatever was derived from the old one is rebuilt on next use (the Gauss-Newton mailbox and
     // sequence numbers stay)
-    void invalidate_derived_maps() { reloc_.band_key = BandKey{}; plan_.grid_key = GridKey{}; plan_.clear_key = ClearKey{}; plan_.reach_key = ReachKey{}; }
+    void invalidate_derived_maps() { reloc_.band_key = BandKey{}; plan_.grid_key = GridKey{}; plan_.clear_key = ClearKey{}; reach_forget(); }
     DeviceArray2D<ushort> depth_ingest_d_;     // device copy of a host frame (ProcessFrameHost)
     ushort *ingest_pinned_[2] = {nullptr, nullptr};
     hipEvent_t ingest_done_[2] = {nullptr, nullptr};

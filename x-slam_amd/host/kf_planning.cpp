@@ -68,7 +68,7 @@ bool KinectFusionReconstruction::ClearancePrepare(int R, int unknown_blocks, int
     check_rc(xs_clearance_build(plan_.view_grid.ptr(), res3(), R, unknown_blocks, plan_.clear_ws.ptr(), reinterpret_cast<unsigned short *>(plan_.clear_field.ptr()),
                                 current_stream()), "ClearanceBuild");
     plan_.clear_key = key;
-    plan_.reach_key = ReachKey{};   // (the flood was over another field)
+    reach_forget();   // (the flood was over another field)
     return true;
 }
 
@@ -106,13 +106,12 @@ int KinectFusionReconstruction::ReachQuery(const float *points3xN, int n, int ov
     return 1;
 }
 
-int KinectFusionReconstruction::Reachable(const Matrix4cf *start, float radius_m, int snap_vox, int unknown_blocks, int min_weight, int P,
-                                          const Matrix4cf *camera2volume, unsigned char *reachable, unsigned short *clear2) {
+// The checks of Reachable's start and body, then the field, the passable words, the snapped seed and the flood, each from its cache when its
+// key holds.  1 when plan_.reach is in step with the arguments, otherwise what Reachable returns.
+int KinectFusionReconstruction::ReachPrepare(const Matrix4cf *start, float radius_m, int snap_vox, int unknown_blocks, int min_weight) {
     if (shard_count > 1) return -2;   // connectivity is not additive over the ranks' z-slabs
     int r2 = 0, R = 0;
-    if (P < 0 || (P > 0 && (!camera2volume || !reachable || !clear2)) || snap_vox < 0 || snap_vox > XS_REACH_MAX_SNAP ||
-        (unknown_blocks != 0 && unknown_blocks != 1) || !reach_radius(radius_m, voxel_size, r2, R))
-        return -1;
+    if (snap_vox < 0 || snap_vox > XS_REACH_MAX_SNAP || (unknown_blocks != 0 && unknown_blocks != 1) || !reach_radius(radius_m, voxel_size, r2, R)) return -1;
     if (!tsdf_volume_d_ptr) return 0;
     const int mw = min_weight < 1 ? 1 : min_weight;
     if (!ClearancePrepare(R, unknown_blocks, mw)) return -1;
@@ -120,12 +119,12 @@ int KinectFusionReconstruction::Reachable(const Matrix4cf *start, float radius_m
     const int *res = res3();
     const size_t bytes = xs_reach_bytes(res);
     if (bytes == 0) return -1;
-    if (plan_.reach.size() < bytes) { plan_.reach.create(bytes); plan_.reach_key = ReachKey{}; }
+    if (plan_.reach.size() < bytes) { plan_.reach.create(bytes); reach_forget(); }
     const unsigned short *field = reinterpret_cast<const unsigned short *>(plan_.clear_field.ptr());
     ReachKey key{plan_.clear_key, r2, {-1, -1, -1}};
     // the passable words (those of the last flood, if it was over this field at this r2), and the start snapped over them
     if (!(plan_.reach_key.field == key.field) || plan_.reach_key.r2 != r2) {
-        plan_.reach_key = ReachKey{};
+        reach_forget();
         check_rc(xs_reach_passable(plan_.view_grid.ptr(), field, res, r2, plan_.reach.ptr(), st), "ReachPassable");
     }
     float p[3];
@@ -134,11 +133,19 @@ int KinectFusionReconstruction::Reachable(const Matrix4cf *start, float radius_m
     if (ReachQuery(p, 1, 1, snap_vox, &found, nullptr, key.seed) < 0) return -1;
     if (!found) key.seed[0] = key.seed[1] = key.seed[2] = -1;   // (outside the volume as a seed: contributes nothing, and nothing is reached)
     if (!(plan_.reach_key == key)) {
-        plan_.reach_key = ReachKey{};
+        reach_forget();
         check_rc(xs_reach_flood(plan_.view_grid.ptr(), field, res, r2, key.seed, 1, plan_.reach.ptr(), nullptr, st), "ReachFlood");
         plan_.reach_key = key;
     }
-    if (P == 0) return 1;
+    return 1;
+}
+
+int KinectFusionReconstruction::Reachable(const Matrix4cf *start, float radius_m, int snap_vox, int unknown_blocks, int min_weight, int P,
+                                          const Matrix4cf *camera2volume, unsigned char *reachable, unsigned short *clear2) {
+    if (shard_count > 1) return -2;
+    if (P < 0 || (P > 0 && (!camera2volume || !reachable || !clear2))) return -1;
+    const int rc = ReachPrepare(start, radius_m, snap_vox, unknown_blocks, min_weight);
+    if (rc != 1 || P == 0) return rc;
     std::vector<float> pts((size_t)P * 3);
     for (int i = 0; i < P; ++i) pack_real_pose(camera2volume[i], nullptr, &pts[(size_t)i * 3]);
     return ReachQuery(pts.data(), P, 0, 0, reachable, clear2, nullptr);
@@ -157,4 +164,105 @@ int KinectFusionReconstruction::NextReachableView(const Matrix4cf *camera2volume
     if (rc < 0) return rc;
     if (rc == 0) return -1;
     return next_reachable_view(out4xP, reachable, P, min_hits);
+}
+
+// ---- travel cost and shortest collision-free path to a candidate view ----
+// The travel field follows the flood: built over plan_.reach from the flood's own seed, rebuilt when the flood's key or the limit differ.
+bool KinectFusionReconstruction::TravelPrepare(int limit) {
+    const TravelKey key{plan_.reach_key, limit};
+    const size_t bytes = xs_travel_bytes(res3());
+    if (bytes == 0) return false;
+    if (plan_.travel.size() < bytes) { plan_.travel.create(bytes); plan_.travel_key = TravelKey{}; }
+    if (plan_.travel_ws.size() < xs_travel_workspace_bytes()) plan_.travel_ws.create(xs_travel_workspace_bytes());
+    if (plan_.travel_key == key) return true;
+    plan_.travel_key = TravelKey{};
+    check_rc(xs_travel_build(plan_.reach.ptr(), res3(), key.reach.seed, 1, limit, reinterpret_cast<unsigned short *>(plan_.travel.ptr()), plan_.travel_ws.ptr(),
+                             nullptr, current_stream()), "TravelBuild");
+    plan_.travel_key = key;
+    return true;
+}
+
+int KinectFusionReconstruction::Travel(const Matrix4cf *start, float radius_m, int snap_vox, int unknown_blocks, int min_weight, float max_travel_m, int P,
+                                       const Matrix4cf *camera2volume, unsigned char *reachable, unsigned short *clear2, unsigned short *travel3) {
+    if (shard_count > 1) return -2;   // a path is not additive over the ranks' z-slabs
+    if (P < 0 || (P > 0 && (!camera2volume || !reachable || !clear2 || !travel3)) || std::isnan(max_travel_m)) return -1;
+    const int rc = ReachPrepare(start, radius_m, snap_vox, unknown_blocks, min_weight);
+    if (rc != 1) return rc;
+    if (!TravelPrepare(travel_limit(max_travel_m, voxel_size))) return -1;
+    if (P == 0) return 1;
+    std::vector<float> pts((size_t)P * 3);
+    std::vector<int> voxel((size_t)P * 3);
+    for (int i = 0; i < P; ++i) pack_real_pose(camera2volume[i], nullptr, &pts[(size_t)i * 3]);
+    if (ReachQuery(pts.data(), P, 0, 0, reachable, clear2, voxel.data()) < 0) return -1;
+    // the answering voxels ((-1, -1, -1) where not reached: NONE) through xs_travel_query, in chunks of 4096
+    enum { CHUNK = 4096, VOXEL = 0, COST = CHUNK * 12, BYTES = COST + CHUNK * 2 };
+    if (plan_.travel_io.size() < (size_t)BYTES) plan_.travel_io.create(BYTES);
+    hipStream_t st = current_stream();
+    unsigned char *io = plan_.travel_io.ptr();
+    for (int p0 = 0; p0 < P; p0 += CHUNK) {
+        const int m = std::min(P - p0, (int)CHUNK);
+        hipSafeCall(hipMemcpyAsync(io + VOXEL, voxel.data() + 3 * (size_t)p0, (size_t)m * 12, hipMemcpyHostToDevice, st));
+        check_rc(xs_travel_query(m, reinterpret_cast<const int *>(io + VOXEL), res3(), reinterpret_cast<const unsigned short *>(plan_.travel.ptr()),
+                                 reinterpret_cast<unsigned short *>(io + COST), st), "TravelQuery");
+        hipSafeCall(hipMemcpyAsync(travel3 + p0, io + COST, (size_t)m * 2, hipMemcpyDeviceToHost, st));
+        hipSafeCall(hipStreamSynchronize(st));   // (the staging area is free again)
+    }
+    return 1;
+}
+
+int KinectFusionReconstruction::PathTo(const Matrix4cf *start, float radius_m, int snap_vox, int unknown_blocks, int min_weight, float max_travel_m,
+                                       const Matrix4cf &target, int capacity, int *voxels3, float *points3, int *needed_out) {
+    if (shard_count > 1) return -2;
+    if (capacity < 1 || std::isnan(max_travel_m)) return -1;
+    const int rc = ReachPrepare(start, radius_m, snap_vox, unknown_blocks, min_weight);
+    if (rc != 1) return rc;
+    const int limit = travel_limit(max_travel_m, voxel_size);
+    if (!TravelPrepare(limit)) return -1;
+    float p[3];
+    int voxel[3];
+    unsigned char found = 0;
+    pack_real_pose(target, nullptr, p);
+    if (ReachQuery(p, 1, 0, 0, &found, nullptr, voxel) < 0) return -1;
+    if (!found) return 0;
+    // the target, then the length, then the path's voxels in the kernel's order (target first)
+    const size_t bytes = 16 + (size_t)capacity * 12;
+    if (plan_.path_io.size() < bytes) plan_.path_io.create(bytes);
+    hipStream_t st = current_stream();
+    int *io = reinterpret_cast<int *>(plan_.path_io.ptr());
+    hipSafeCall(hipMemcpyAsync(io, voxel, 12, hipMemcpyHostToDevice, st));
+    check_rc(xs_travel_path(1, io, res3(), plan_.reach.ptr(), reinterpret_cast<const unsigned short *>(plan_.travel.ptr()), limit, capacity, io + 4, io + 3, st),
+             "TravelPath");
+    int len = 0;
+    hipSafeCall(hipMemcpyAsync(&len, io + 3, sizeof(int), hipMemcpyDeviceToHost, st));
+    hipSafeCall(hipStreamSynchronize(st));
+    if (needed_out) *needed_out = len;
+    if (len > capacity) return -4;
+    if (len < 1) return 0;   // (beyond the limit)
+    std::vector<int> path((size_t)len * 3);
+    hipSafeCall(hipMemcpyAsync(path.data(), io + 4, (size_t)len * 12, hipMemcpyDeviceToHost, st));
+    hipSafeCall(hipStreamSynchronize(st));
+    for (int s = 0; s < len; ++s)   // start first, target last
+        for (int c = 0; c < 3; ++c) {
+            const int v = path[3 * (size_t)(len - 1 - s) + (size_t)c];
+            if (voxels3) voxels3[3 * (size_t)s + (size_t)c] = v;
+            if (points3) points3[3 * (size_t)s + (size_t)c] = ((float)v + 0.5f) * voxel_size;
+        }
+    return len;
+}
+
+int KinectFusionReconstruction::NextViewByTravel(const Matrix4cf *camera2volume, int P, const xs_view_opts *opts, int min_weight, unsigned min_hits,
+                                                 unsigned *out4xP, float radius_m, int snap_vox, int unknown_blocks, float max_travel_m, float bias_m,
+                                                 unsigned short *travel3_out) {
+    if (!(bias_m >= 0.f) || !std::isfinite(bias_m)) return shard_count > 1 ? -2 : -3;
+    std::vector<unsigned> own;
+    std::vector<unsigned short> own_travel, clear2((size_t)(P > 0 ? P : 0));
+    std::vector<unsigned char> flags((size_t)(P > 0 ? P : 0));
+    if (!out4xP && P > 0) { own.resize((size_t)P * 4); out4xP = own.data(); }
+    if (!travel3_out && P > 0) { own_travel.resize((size_t)P); travel3_out = own_travel.data(); }
+    int rc = Travel(nullptr, radius_m, snap_vox, unknown_blocks, min_weight, max_travel_m, P, camera2volume, flags.data(), clear2.data(), travel3_out);
+    if (rc == 1) rc = ScoreViews(camera2volume, P, opts, min_weight, out4xP);
+    if (rc == -1) return -3;   // (-1 is "no pose qualifies" here)
+    if (rc < 0) return rc;
+    if (rc == 0) return -1;
+    return next_view_by_travel(out4xP, travel3_out, P, min_hits, travel_bias(bias_m, voxel_size));
 }

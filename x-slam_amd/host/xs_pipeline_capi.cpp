@@ -283,6 +283,26 @@ int xs_kf_next_reachable_view(void *kf, int poses, const float *c2v32xP, const x
     return ((KF *)kf)->NextReachableView(poses_of(c2v32xP, poses).data(), poses, opts, min_weight, min_hits, out4xP, radius_m, snap_vox, unknown_blocks,
                                          reachable);
 }
+int xs_kf_travel(void *kf, const float *start_c2v32_or_null, float radius_m, int snap_vox, int unknown_blocks, int min_weight, float max_travel_m, int P,
+                 const float *c2v32xP, unsigned char *reachable, unsigned short *clear2, unsigned short *travel3) {
+    if (P < 0 || (P > 0 && (!c2v32xP || !reachable || !clear2 || !travel3))) return -1;
+    const std::vector<Matrix4cf> start = poses_of(start_c2v32_or_null, start_c2v32_or_null ? 1 : 0);
+    return ((KF *)kf)->Travel(start.empty() ? nullptr : start.data(), radius_m, snap_vox, unknown_blocks, min_weight, max_travel_m, P, poses_of(c2v32xP, P).data(),
+                              reachable, clear2, travel3);
+}
+int xs_kf_path_to(void *kf, const float *start_c2v32_or_null, float radius_m, int snap_vox, int unknown_blocks, int min_weight, float max_travel_m,
+                  const float *target_c2v32, int capacity, int *voxels3, float *points3, int *needed_out) {
+    if (!target_c2v32) return -1;
+    const std::vector<Matrix4cf> start = poses_of(start_c2v32_or_null, start_c2v32_or_null ? 1 : 0);
+    return ((KF *)kf)->PathTo(start.empty() ? nullptr : start.data(), radius_m, snap_vox, unknown_blocks, min_weight, max_travel_m, poses_of(target_c2v32, 1)[0],
+                              capacity, voxels3, points3, needed_out);
+}
+int xs_kf_next_view_by_travel(void *kf, int poses, const float *c2v32xP, const xs_view_opts *opts, int min_weight, unsigned min_hits, unsigned *out4xP,
+                              float radius_m, int snap_vox, int unknown_blocks, float max_travel_m, float bias_m, unsigned short *travel3_out) {
+    if (poses < 0 || (poses > 0 && !c2v32xP)) return -3;
+    return ((KF *)kf)->NextViewByTravel(poses_of(c2v32xP, poses).data(), poses, opts, min_weight, min_hits, out4xP, radius_m, snap_vox, unknown_blocks,
+                                        max_travel_m, bias_m, travel3_out);
+}
 long long xs_kf_relocalization_index_voxels(void *kf) { return ((KF *)kf)->RelocalizationIndexVoxels(); }
 long long xs_kf_export_point_cloud(void *kf, int max_buffer, float *points_host, float *normals_host) {
     const auto pc = ((KF *)kf)->ExportPointCloud(max_buffer);

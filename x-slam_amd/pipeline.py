@@ -50,6 +50,11 @@ _SIGS = {
     "xs_kf_reachable": (C.c_int, [_vp, _f32p, C.c_float, C.c_int, C.c_int, C.c_int, C.c_int, _f32p, C.POINTER(C.c_ubyte), C.POINTER(C.c_uint16)]),
     "xs_kf_next_reachable_view": (C.c_int, [_vp, C.c_int, _f32p, C.POINTER(capi.ViewOpts), C.c_int, C.c_uint, C.POINTER(C.c_uint), C.c_float, C.c_int,
                                             C.c_int, C.POINTER(C.c_ubyte)]),
+    "xs_kf_travel": (C.c_int, [_vp, _f32p, C.c_float, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, _f32p, C.POINTER(C.c_ubyte), C.POINTER(C.c_uint16),
+                               C.POINTER(C.c_uint16)]),
+    "xs_kf_path_to": (C.c_int, [_vp, _f32p, C.c_float, C.c_int, C.c_int, C.c_int, C.c_float, _f32p, C.c_int, _i32p, _f32p, _i32p]),
+    "xs_kf_next_view_by_travel": (C.c_int, [_vp, C.c_int, _f32p, C.POINTER(capi.ViewOpts), C.c_int, C.c_uint, C.POINTER(C.c_uint), C.c_float, C.c_int,
+                                            C.c_int, C.c_float, C.c_float, C.POINTER(C.c_uint16)]),
     "xs_kf_relocalization_index_voxels": (C.c_longlong, [_vp]),
     "xs_kf_export_point_cloud": (C.c_longlong, [_vp, C.c_int, _f32p, _f32p]),
     "xs_kf_export_ply": (C.c_longlong, [_vp, C.c_int, C.c_char_p]),
@@ -459,6 +464,70 @@ class KinectFusion:
                                             flags.ctypes.data_as(C.POINTER(C.c_ubyte)))
         self._reach_call("xs_kf_next_reachable_view", rc, -3)
         return int(rc), out[:P].copy(), flags[:P].astype(bool)
+
+    def _travel_m(self, units):
+        """uint16 travel costs (thirds of a voxel edge) as float64 metres, inf for 65535."""
+        vs = float(np.float32(float(self.cfg["tsdf_voxel_size"])))
+        u = np.asarray(units, np.uint16)
+        return np.where(u == capi.TRAVEL_NONE, np.inf, u.astype(np.float64) * vs / 3.0)
+
+    def travel(self, c2vs, radius_m, start=None, snap_vox=4, unknown_blocks=True, min_weight=1, max_travel_m=None):
+        """reachable() plus how far each pose is: (reachable bool [P], clear2 uint16 [P], travel_m float64 [P]) — the length in metres of the
+        shortest path of 26-neighbour moves that cuts no corner (the <3, 4, 5> chamfer metric) from the snapped start to each pose's centre
+        voxel through the reached voxels, inf where unreachable or beyond max_travel_m (None: no limit but 65534 thirds of a voxel).
+        XsError in shard mode."""
+        m = np.ascontiguousarray(c2vs, dtype=np.float32).reshape(-1)
+        P = m.size // 32
+        assert m.size == 32 * P
+        flags, clear2, cost = np.zeros(max(P, 1), np.uint8), np.zeros(max(P, 1), np.uint16), np.zeros(max(P, 1), np.uint16)
+        s = None if start is None else np.ascontiguousarray(start, dtype=np.float32).reshape(32)
+        rc = _lib.xs_kf_travel(self.h, None if s is None else s.ctypes.data_as(_f32p), float(radius_m), int(snap_vox), int(bool(unknown_blocks)),
+                               int(min_weight), 0.0 if max_travel_m is None else float(max_travel_m), P, m.ctypes.data_as(_f32p),
+                               flags.ctypes.data_as(C.POINTER(C.c_ubyte)), clear2.ctypes.data_as(C.POINTER(C.c_uint16)),
+                               cost.ctypes.data_as(C.POINTER(C.c_uint16)))
+        self._reach_call("xs_kf_travel", rc, -1)
+        if rc != 1:
+            raise ValueError("xs_kf_travel: no volume")
+        return flags[:P].astype(bool), clear2[:P].copy(), self._travel_m(cost[:P])
+
+    def path_to(self, c2v, radius_m, start=None, snap_vox=4, unknown_blocks=True, min_weight=1, max_travel_m=None, capacity=1024):
+        """The shortest collision-free path from the snapped start to the centre voxel of pose c2v ([4, 4, 2]), start first and target last:
+        (points float32 [n, 3] — the voxel centres in volume coordinates, metres —, voxels int32 [n, 3]), or None when the target is not
+        reached (or beyond max_travel_m).  A path longer than `capacity` voxels is fetched by one more call.  XsError in shard mode."""
+        t = np.ascontiguousarray(c2v, dtype=np.float32).reshape(32)
+        s = None if start is None else np.ascontiguousarray(start, dtype=np.float32).reshape(32)
+        capacity = max(int(capacity), 1)
+        for _ in range(2):
+            voxels, points, needed = np.zeros((capacity, 3), np.int32), np.zeros((capacity, 3), np.float32), C.c_int(0)
+            rc = _lib.xs_kf_path_to(self.h, None if s is None else s.ctypes.data_as(_f32p), float(radius_m), int(snap_vox), int(bool(unknown_blocks)),
+                                    int(min_weight), 0.0 if max_travel_m is None else float(max_travel_m), t.ctypes.data_as(_f32p), capacity,
+                                    voxels.ctypes.data_as(_i32p), points.ctypes.data_as(_f32p), C.byref(needed))
+            if rc != -4:
+                break
+            capacity = int(needed.value)
+        self._reach_call("xs_kf_path_to", rc, -1)
+        if rc < 0:
+            raise capi.XsError(f"xs_kf_path_to: {rc}")
+        return None if rc == 0 else (points[:rc].copy(), voxels[:rc].copy())
+
+    def next_view_by_travel(self, candidates, radius_m, bias_m=0.5, min_hits=None, rays=(80, 60), t_near=0.2, t_far=5.0, step=None, min_weight=1,
+                            snap_vox=4, unknown_blocks=True, max_travel_m=None):
+        """Weighs what a view sees against how far away it is: among the candidates a body of radius_m can get to from the current camera
+        (within max_travel_m) with at least min_hits rays on a known surface, the one with the largest unknown / (travel + bias), bias_m
+        being the fixed cost of taking any view at all: (index, counts uint32 [P, 4], travel_m float64 [P]); index -1 when no candidate
+        qualifies.  XsError in shard mode."""
+        m = np.ascontiguousarray(candidates, dtype=np.float32).reshape(-1)
+        P = m.size // 32
+        assert m.size == 32 * P
+        if min_hits is None:
+            min_hits = int(rays[0]) * int(rays[1]) // 4
+        out, cost = np.zeros((max(P, 1), 4), np.uint32), np.zeros(max(P, 1), np.uint16)
+        opts = capi.view_opts(rays, t_near, t_far, step)
+        rc = _lib.xs_kf_next_view_by_travel(self.h, P, m.ctypes.data_as(_f32p), C.byref(opts), int(min_weight), int(min_hits),
+                                            out.ctypes.data_as(C.POINTER(C.c_uint)), float(radius_m), int(snap_vox), int(bool(unknown_blocks)),
+                                            0.0 if max_travel_m is None else float(max_travel_m), float(bias_m), cost.ctypes.data_as(C.POINTER(C.c_uint16)))
+        self._reach_call("xs_kf_next_view_by_travel", rc, -3)
+        return int(rc), out[:P].copy(), self._travel_m(cost[:P])
 
     def relocalization_index_voxels(self):
         """Band voxels in the relocalisation index as last built by relocalize_batch (0 before the first)."""
