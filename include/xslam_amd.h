@@ -570,6 +570,54 @@ int xs_travel_query(int n, const int *voxel3xN_dev, const int *res, const unsign
 int xs_travel_path(int n, const int *target3xN_dev, const int *res, const void *reach, const unsigned short *travel_dev, int limit, int capacity,
                    int *path3_dev, int *len_dev, void *stream);
 
+/* ---- frontier voxels, their clusters and one record per cluster (xs_frontier.hip) -------------------------------
+ * No counterpart in the reference.  Integer arithmetic on the grid's states throughout, no floating-point atomics; the integer atomics used
+ * (add, min, max) give results that do not depend on their order: every result is a pure function of the inputs and two runs give equal
+ * bytes.  `grid` is the observation grid as xs_view_grid_build leaves it; the volumes are not read and the grid is not written.
+ * RESOLUTIONS: those of the reach calls (every axis >= 1, Y and Z <= 65535, fewer than 2^31 bricks) with X * Y * Z < 2^32 - 1, so that a
+ * uint32 indexes every voxel and XS_FRONTIER_NONE stays free.  For any other the three size functions return 0 and every call refuses.
+ * MASK.  A voxel is FRONTIER iff its state is FREE and at least one of its six face neighbours inside the volume is UNKNOWN.  A position
+ * outside [0, res) is not UNKNOWN for this purpose (an all-FREE volume has no frontier), and the padding bits of overhanging bricks are
+ * never read as a state.  `mask` (xs_frontier_mask_bytes(res): 8 bytes per brick, 8-byte aligned device memory) holds one 64-bit word per
+ * brick of 4 x 4 x 4 voxels in the reach buffer's layout: bricks in the grid's order, voxel (lx, ly, lz) at bit lx + 4 ly + 16 lz, overhang
+ * bits clear.  xs_frontier_mask: one plain launch, a lane per brick.  No synchronisation.
+ * xs_frontier_expand: out_dev[(z * Y + y) * X + x] = 0 or 1 from the mask: tests and viewers.  No synchronisation.
+ * LABELS.  labels[(z * Y + y) * X + x] (uint32, dense; xs_frontier_label_bytes(res): 4 bytes per voxel) is XS_FRONTIER_NONE on a voxel that
+ * is no frontier voxel and otherwise the lowest linear index (z * Y + y) * X + x among the voxels of its CLUSTER.  Two frontier voxels are
+ * joined iff they differ by at most 1 on every axis (26-adjacency) and lie in the same CELL; the clusters are the connected components of
+ * that relation.  Cells are cubes of `cell` voxels aligned to the origin, cell (x / cell, y / cell, z / cell); cell = 0: one cell, the whole
+ * volume; otherwise a multiple of 8 in 8 .. 65528.
+ * xs_frontier_label: sets every voxel's label to its own index or NONE and runs rounds as plain launches: a workgroup owns a tile of
+ * 8 x 8 x 8 voxels (8 divides cell, so a tile lies in one cell), returns at once if none of its eight mask words has a bit, otherwise holds
+ * the tile's labels with a one-voxel apron in LDS (NONE outside the volume and across a cell boundary), lets every frontier voxel take the
+ * minimum over itself and its 26 neighbours until nothing in the tile changes, writes back its own labels that fell and sets the round's
+ * `changed` word with a plain store.  Labels only fall and every stored label is the index of a voxel of the same cluster; aprons are
+ * re-read from global memory every round, a stale value delays a merge by a round and never invents one, so the result does not depend on
+ * scheduling (the number of rounds may).  The host reads the changed words (in `workspace`: at least xs_frontier_workspace_bytes(res, 0)
+ * bytes of device memory, 8-byte aligned) after each batch of rounds and stops after the first round that changed nothing: THE CALL
+ * SYNCHRONISES THE STREAM.  *rounds_out (optional) receives the number of rounds up to and including that one.
+ * RECORDS.  One record of XS_FRONTIER_RECORD_WORDS = 8 uint64 per cluster, in ascending label order:
+ *   {label, count, sum of x, sum of y, sum of z, min packed as x | y << 16 | z << 32, max packed likewise, 0}
+ * over the cluster's voxels (min and max per axis: the bounding box).
+ * xs_frontier_clusters: `labels_dev` as xs_frontier_label left them for this `mask`.  *count_dev (device) and *count_host (host, optional)
+ * always receive the full number of clusters; records_dev (capacity x 8 uint64, device) is written only when that number is <= capacity,
+ * and then exactly that many records: the caller retries with a larger buffer.  `workspace`: xs_frontier_workspace_bytes(res, capacity)
+ * bytes.  The voxels whose label is their own index are compacted through an integer counter, the list is sorted on the host, and one
+ * launch over the frontier voxels finds each voxel's record by binary search and adds with integer atomics.  Needs X <= 65535 too (the
+ * packed box).  THE CALL SYNCHRONISES THE STREAM.
+ * hipErrorInvalidValue, with nothing launched and the outputs untouched: null pointers (count_host and rounds_out excepted), a resolution
+ * outside the set above, a bad cell, capacity < 1. */
+#define XS_FRONTIER_NONE 0xFFFFFFFFu
+#define XS_FRONTIER_RECORD_WORDS 8
+size_t xs_frontier_mask_bytes(const int *res);
+size_t xs_frontier_label_bytes(const int *res);
+size_t xs_frontier_workspace_bytes(const int *res, int capacity);
+int xs_frontier_mask(const void *grid, const int *res, void *mask, void *stream);
+int xs_frontier_label(const void *mask, const int *res, int cell, unsigned *labels_dev, void *workspace, int *rounds_out, void *stream);
+int xs_frontier_clusters(const void *mask, const unsigned *labels_dev, const int *res, int capacity, unsigned long long *records_dev,
+                         unsigned *count_dev, unsigned *count_host, void *workspace, void *stream);
+int xs_frontier_expand(const void *mask, const int *res, unsigned char *out_dev, void *stream);
+
 /* ---- surface extraction (export; real-valued) ------------------------------------------------ */
 size_t xs_extract_workspace_bytes(const int *res);
 /* size_t extractPoints(value_volume, weight_volume, grad_volume, volume_resolution, voxel_size,

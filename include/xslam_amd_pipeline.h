@@ -173,6 +173,27 @@ int xs_kf_path_to(void *kf, const float *start_c2v32_or_null, float radius_m, in
                   const float *target_c2v32, int capacity, int *voxels3, float *points3, int *needed_out);
 int xs_kf_next_view_by_travel(void *kf, int poses, const float *c2v32xP, const struct xs_view_opts *opts, int min_weight, unsigned min_hits, unsigned *out4xP,
                               float radius_m, int snap_vox, int unknown_blocks, float max_travel_m, float bias_m, unsigned short *travel3_out);
+/* Frontier clusters and the views proposed from them: where should the camera go next, with no candidates from
+ * the caller?  The frontier voxels of the observation grid at min_weight (FREE with an UNKNOWN face neighbour) are labelled into clusters
+ * (26-adjacency within cells of `cell` voxels: 0 for the whole volume, otherwise a multiple of 8 in 8 .. 65528; xslam_amd.h: the contract).
+ * frontiers: the records {label, count, sum x, sum y, sum z, packed min, packed max, 0} of the clusters with count >= min_size, ascending by
+ * label, into records8 (capacity x 8 uint64; may be null when capacity is 0) and their number into *count_out.  A record's centroid in
+ * metres is, per axis, ((float)((double)sum / (double)count) + 0.5f) * voxel_size.
+ * propose_views: floods as xs_kf_reachable does from the current camera (its start snapped within start_snap_vox), takes those clusters and
+ * for each the views_per_cluster (1 .. 4096) standpoints p_j = centroid + standoff_m * d_j, d_j the unit vector of the Halton pair
+ * (u, v) = (bases 2 and 3, index j + 1) with z = 1 - 2 u and phi = 2 pi v.  Each standpoint is snapped to the nearest REACHED voxel within
+ * snap_vox (0 .. 16) by xs_reach_query's rule; those that find none are dropped, and so is one whose voxel an earlier standpoint of the same
+ * cluster gave.  Each survivor yields the pose at its voxel's centre (v + 0.5f) * voxel_size whose optical axis (third column) points at the
+ * centroid and whose image-down axis is as close as orthogonality allows to the current camera's y axis (its x axis when y is within 8.1
+ * degrees of the view direction): c2v32xP_out (capacity x 32 floats, zero imaginary parts), cluster_out (capacity ints, the index into
+ * the list frontiers returns for the same cell, min_size and min_weight) and *count_out.  floorf(centre / voxel_size) is the voxel again,
+ * so xs_kf_reachable and xs_kf_travel call every proposed pose reachable.
+ * Both return 1 when they ran, 0 without a volume, -1 on bad arguments, -4 with the needed count in *count_out and nothing else written when
+ * capacity is too small, -2 in shard mode, doing nothing.  Mask, labels and records are cached and redone when the volume, min_weight or
+ * cell change.  No other call's results change. */
+int xs_kf_frontiers(void *kf, int cell, unsigned long long min_size, int min_weight, int capacity, unsigned long long *records8, int *count_out);
+int xs_kf_propose_views(void *kf, float radius_m, int start_snap_vox, int unknown_blocks, int min_weight, int cell, unsigned long long min_size,
+                        int views_per_cluster, float standoff_m, int snap_vox, int capacity, float *c2v32xP_out, int *cluster_out, int *count_out);
 /* band voxels in the relocalisation index as last built (0 before the first batch) */
 long long xs_kf_relocalization_index_voxels(void *kf);
 /* ExportPointCloud(max_buffer)  .cpp:334-372 (+ CPointCloud::exportPly, main.cpp:78-80): zero-crossing points of

@@ -82,6 +82,13 @@ _SIGS = {
     "xs_travel_build": (C.c_int, [_vp, _i32p, _i32p, C.c_int, C.c_int, _vp, _vp, _i32p, _vp]),
     "xs_travel_query": (C.c_int, [C.c_int, _vp, _i32p, _vp, _vp, _vp]),
     "xs_travel_path": (C.c_int, [C.c_int, _vp, _i32p, _vp, _vp, C.c_int, C.c_int, _vp, _vp, _vp]),
+    "xs_frontier_mask_bytes": (_sz, [_i32p]),
+    "xs_frontier_label_bytes": (_sz, [_i32p]),
+    "xs_frontier_workspace_bytes": (_sz, [_i32p, C.c_int]),
+    "xs_frontier_mask": (C.c_int, [_vp, _i32p, _vp, _vp]),
+    "xs_frontier_label": (C.c_int, [_vp, _i32p, C.c_int, _vp, _vp, _i32p, _vp]),
+    "xs_frontier_clusters": (C.c_int, [_vp, _vp, _i32p, C.c_int, _vp, _vp, C.POINTER(C.c_uint), _vp, _vp]),
+    "xs_frontier_expand": (C.c_int, [_vp, _i32p, _vp, _vp]),
     "xs_integrate_scaled_ex2": (C.c_int, [_vp, _sz, C.c_int, C.c_int, _f32p, C.c_int, _i32p, C.c_float, _f32p, _f32p, C.c_float, _vp, _vp, _vp,
                                          _sz, C.c_float, C.c_int, C.c_int, _vp, _vp, _vp, C.POINTER(IntegrateOpts), _vp]),
     "xs_integrate_classify_ex": (C.c_int, [C.c_int, C.c_int, _f32p, _i32p, C.c_float, _f32p, _f32p, C.c_float, C.c_int, C.c_int, _vp, _vp,
@@ -709,6 +716,57 @@ def travel_path(n, targets, res, reach, travel, limit, capacity, path, lengths, 
     r = _res3(res)
     check(_lib.xs_travel_path(int(n), _ptr(targets), r.ctypes.data_as(_i32p), _ptr(reach), _ptr(travel), int(limit), int(capacity), _ptr(path),
                               _ptr(lengths), _stream(stream)))
+
+
+FRONTIER_NONE, FRONTIER_RECORD_WORDS = 0xFFFFFFFF, 8   # XS_FRONTIER_NONE, XS_FRONTIER_RECORD_WORDS
+
+
+def frontier_mask_bytes(res):
+    """xs_frontier_mask_bytes (host only): the frontier mask, 8 bytes per brick of 4 x 4 x 4 voxels; 0 for an invalid resolution."""
+    return int(_lib.xs_frontier_mask_bytes(_res3(res).ctypes.data_as(_i32p)))
+
+
+def frontier_label_bytes(res):
+    """xs_frontier_label_bytes (host only): the labels, 4 bytes per voxel; 0 for an invalid resolution."""
+    return int(_lib.xs_frontier_label_bytes(_res3(res).ctypes.data_as(_i32p)))
+
+
+def frontier_workspace_bytes(res, capacity=0):
+    """xs_frontier_workspace_bytes (host only): the control words of xs_frontier_label plus what xs_frontier_clusters needs for `capacity`
+    records; 0 for an invalid resolution or a negative capacity."""
+    return int(_lib.xs_frontier_workspace_bytes(_res3(res).ctypes.data_as(_i32p), int(capacity)))
+
+
+def frontier_mask(grid, res, mask, stream=None):
+    """xs_frontier_mask: one 64-bit word per brick into `mask`: the FREE voxels of a built observation grid with an UNKNOWN face neighbour."""
+    r = _res3(res)
+    check(_lib.xs_frontier_mask(_ptr(grid), r.ctypes.data_as(_i32p), _ptr(mask), _stream(stream)))
+
+
+def frontier_label(mask, res, cell, labels, workspace, stream=None):
+    """xs_frontier_label: labels[(z Y + y) X + x] (uint32 device tensor) = the lowest linear index of the voxel's cluster (26-adjacency within
+    cells of `cell` voxels; 0: the whole volume), 0xFFFFFFFF off the frontier.  Synchronises the stream.  Returns the number of rounds."""
+    r = _res3(res)
+    rounds = C.c_int(0)
+    check(_lib.xs_frontier_label(_ptr(mask), r.ctypes.data_as(_i32p), int(cell), _ptr(labels), _ptr(workspace), C.byref(rounds), _stream(stream)))
+    return int(rounds.value)
+
+
+def frontier_clusters(mask, labels, res, capacity, records, count, workspace, stream=None):
+    """xs_frontier_clusters: one record of 8 uint64 {label, count, sum x, sum y, sum z, packed min, packed max, 0} per cluster in ascending label
+    order into `records` (capacity x 8) when the number of clusters is <= capacity; `count` (uint32 device tensor of one word) always receives
+    that number, which is also returned.  Synchronises the stream."""
+    r = _res3(res)
+    n = C.c_uint(0)
+    check(_lib.xs_frontier_clusters(_ptr(mask), _ptr(labels), r.ctypes.data_as(_i32p), int(capacity), _ptr(records), _ptr(count), C.byref(n), _ptr(workspace),
+                                    _stream(stream)))
+    return int(n.value)
+
+
+def frontier_expand(mask, res, out, stream=None):
+    """xs_frontier_expand: one byte (0 or 1) per voxel into `out` from the frontier mask."""
+    r = _res3(res)
+    check(_lib.xs_frontier_expand(_ptr(mask), r.ctypes.data_as(_i32p), _ptr(out), _stream(stream)))
 
 
 

@@ -1,5 +1,5 @@
-// xs_reach.h — what xs_reach.hip and xs_travel.hip share: the dimensions of the brick grid and the layout of the reach buffer (DESIGN.md
-// sections 4.19 and 4.20).  One 64-bit word per brick of 4 x 4 x 4 voxels, bricks in the observation grid's order ((bz BY + by) BX + bx),
+// xs_reach.h — what xs_reach.hip, xs_travel.hip and xs_frontier.hip share: the dimensions of the brick grid and the layout of the reach
+// buffer, which the frontier mask's words follow (DESIGN.md sections 4.19 to 4.21).  One 64-bit word per brick of 4 x 4 x 4 voxels, bricks in the observation grid's order ((bz BY + by) BX + bx),
 // voxel (lx, ly, lz) at bit lx + 4 ly + 16 lz, overhang bits clear: the reached words first, the passable words behind them.
 #pragma once
 #include <hip/hip_runtime.h>

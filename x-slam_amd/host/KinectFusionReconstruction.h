@@ -272,6 +272,20 @@ public:
                int capacity, int *voxels3, float *points3, int *needed_out);
     int NextViewByTravel(const Matrix4cf *camera2volume, int P, const xs_view_opts *opts, int min_weight, unsigned min_hits, unsigned *out4xP,
                          float radius_m, int snap_vox, int unknown_blocks, float max_travel_m, float bias_m, unsigned short *travel3_out);
+    // Frontier clusters and the views proposed from them: where should the camera go next, with no candidates from
+    // the caller?  Frontiers labels the frontier voxels of the observation grid at min_weight into clusters within cells of `cell` voxels
+    // (include/xslam_amd.h: the contract) and returns the records of the clusters with at least min_size voxels, in ascending label order:
+    // records8 (capacity x 8 uint64, optional when capacity is 0) and *count_out, their number.  ProposeViews floods as Reachable does from the
+    // current camera (its start snapped within start_snap_vox), takes those clusters, puts views_per_cluster standpoints around each
+    // centroid at standoff_m (view_host.hpp: frontier_standpoint), snaps each to the nearest REACHED voxel within snap_vox (dropping those
+    // that find none, and a standpoint whose voxel an earlier one of the same cluster already gave), and emits for each survivor the pose
+    // at that voxel's centre looking at the centroid (view_host.hpp: look_at; image-down hint: the current camera's y axis) with the
+    // cluster's index in Frontiers' list: c2v_out and cluster_out (capacity each) and *count_out.  Mask, labels and records are cached and
+    // redone when volume_generation, min_weight or cell differ.  Both return 1 when they ran, 0 without a volume, -1 on bad arguments, -4
+    // with the needed count in *count_out (and nothing else written) when capacity is too small, -2 in shard mode, doing nothing.
+    int Frontiers(int cell, unsigned long long min_size, int min_weight, int capacity, unsigned long long *records8, int *count_out);
+    int ProposeViews(float radius_m, int start_snap_vox, int unknown_blocks, int min_weight, int cell, unsigned long long min_size, int views_per_cluster,
+                     float standoff_m, int snap_vox, int capacity, Matrix4cf *c2v_out, int *cluster_out, int *count_out);
     long long RelocalizationIndexVoxels() const { return reloc_.band_key.generation >= 0 ? reloc_.band.count : 0; }   // the index as last built, 0 before any
     // bumped by everything that writes the volume: integrate calls, loadCheckpoint, xs_kf_volume_ptr(kf, 0, .), RebuildSignMap (the band index is rebuilt
     // when its generation differs)
@@ -337,6 +351,7 @@ private:
         bool operator==(const ReachKey &o) const { return field == o.field && r2 == o.r2 && seed[0] == o.seed[0] && seed[1] == o.seed[1] && seed[2] == o.seed[2]; }
     };
     struct TravelKey { ReachKey reach; int limit = -1; bool operator==(const TravelKey &o) const { return reach == o.reach && limit == o.limit; } };
+    struct FrontierKey { GridKey grid; int cell = -1; bool operator==(const FrontierKey &o) const { return grid == o.grid && cell == o.cell; } };
     // Relocalisation against the map (kf_relocalize.cpp): nothing the frame path touches.
     struct Reloc {
         DeviceArray<double> gn_sums;               // 29 Gauss-Newton sums (+ pad)
@@ -385,16 +400,23 @@ private:
         DeviceArray<unsigned char> travel_io;      // a cost query's voxels and answers
         DeviceArray<unsigned char> path_io;        // a path's target, length and voxels
         TravelKey travel_key;
+        DeviceArray<unsigned char> frontier_mask;  // xs_frontier_mask_bytes(resolution)
+        DeviceArray<unsigned char> frontier_labels;   // xs_frontier_label_bytes(resolution)
+        DeviceArray<unsigned char> frontier_ws;    // xs_frontier_workspace_bytes(resolution, capacity of frontier_records_d)
+        DeviceArray<unsigned long long> frontier_records_d;   // capacity x 8, and the count behind them
+        std::vector<unsigned long long> frontier_records;     // the records of every cluster, on the host
+        FrontierKey frontier_key;
     } plan_;
     bool ViewGridPrepare(int min_weight);      // (re)builds the observation grid when the volume or min_weight changed since it was built
     bool ClearancePrepare(int R, int unknown_blocks, int min_weight);   // grid and clearance field in step with the volume and the arguments
     int ReachQuery(const float *points3xN, int n, int over_passable, int snap, unsigned char *reachable, unsigned short *clear2, int *voxel);
     int ReachPrepare(const Matrix4cf *start, float radius_m, int snap_vox, int unknown_blocks, int min_weight);   // plan_.reach in step with the arguments
     bool TravelPrepare(int limit);             // the travel field in step with plan_.reach and the limit
+    bool FrontierPrepare(int cell, int min_weight);   // mask, labels and plan_.frontier_records in step with the volume and the arguments
     void reach_forget() { plan_.reach_key = ReachKey{}; plan_.travel_key = TravelKey{}; }   // the flood is not to be trusted, nor what was built over it
     // the volume object was replaced or released: whatever was derived from the old one is rebuilt on next use (the Gauss-Newton mailbox and
     // sequence numbers stay)
-    void invalidate_derived_maps() { reloc_.band_key = BandKey{}; plan_.grid_key = GridKey{}; plan_.clear_key = ClearKey{}; reach_forget(); }
+    void invalidate_derived_maps() { reloc_.band_key = BandKey{}; plan_.grid_key = GridKey{}; plan_.clear_key = ClearKey{}; plan_.frontier_key = FrontierKey{}; reach_forget(); }
     DeviceArray2D<ushort> depth_ingest_d_;     // device copy of a host frame (ProcessFrameHost)
     ushort *ingest_pinned_[2] = {nullptr, nullptr};
     hipEvent_t ingest_done_[2] = {nullptr, nullptr};

@@ -1,5 +1,5 @@
 // kf_planning.cpp — where could the camera go, and what would it see there: the observation grid and the view scores, the clearance field
-// and reachability (DESIGN.md sections 4.18, 4.19).  Each derived map is cached under the key it was built with.  None of it runs during tracking.
+// and reachability, travel cost and paths, frontier clusters and the views proposed from them (DESIGN.md sections 4.18 to 4.21).  Each derived map is cached under the key it was built with.  None of it runs during tracking.
 #include "kf_internal.hpp"
 #include "view_host.hpp"
 
@@ -265,4 +265,123 @@ int KinectFusionReconstruction::NextViewByTravel(const Matrix4cf *camera2volume,
     if (rc < 0) return rc;
     if (rc == 0) return -1;
     return next_view_by_travel(out4xP, travel3_out, P, min_hits, travel_bias(bias_m, voxel_size));
+}
+
+// ---- frontier clusters and the views proposed from them ----
+// Mask, labels and the records of every cluster (on the host) follow the grid, the grid the volume.  False when the resolution has no labels.
+bool KinectFusionReconstruction::FrontierPrepare(int cell, int min_weight) {
+    const int mw = min_weight < 1 ? 1 : min_weight;
+    const int *res = res3();
+    const size_t mask_bytes = xs_frontier_mask_bytes(res), label_bytes = xs_frontier_label_bytes(res);
+    if (mask_bytes == 0 || label_bytes == 0 || !ViewGridPrepare(mw)) return false;
+    const FrontierKey key{plan_.grid_key, cell};
+    if (plan_.frontier_mask.size() < mask_bytes) { plan_.frontier_mask.create(mask_bytes); plan_.frontier_key = FrontierKey{}; }
+    if (plan_.frontier_labels.size() < label_bytes) { plan_.frontier_labels.create(label_bytes); plan_.frontier_key = FrontierKey{}; }
+    if (plan_.frontier_key == key) return true;
+    plan_.frontier_key = FrontierKey{};
+    hipStream_t st = current_stream();
+    unsigned *labels = reinterpret_cast<unsigned *>(plan_.frontier_labels.ptr());
+    int capacity = plan_.frontier_records_d.size() > 1 ? (int)((plan_.frontier_records_d.size() - 1) / FRONTIER_RECORD_WORDS) : 4096;
+    auto room_for = [&](int cap) {   // the records with the count behind them, and the workspace that goes with that capacity
+        if (plan_.frontier_records_d.size() < (size_t)cap * FRONTIER_RECORD_WORDS + 1) plan_.frontier_records_d.create((size_t)cap * FRONTIER_RECORD_WORDS + 1);
+        const size_t ws = xs_frontier_workspace_bytes(res, cap);
+        if (plan_.frontier_ws.size() < ws) plan_.frontier_ws.create(ws);
+    };
+    room_for(capacity);
+    check_rc(xs_frontier_mask(plan_.view_grid.ptr(), res, plan_.frontier_mask.ptr(), st), "FrontierMask");
+    check_rc(xs_frontier_label(plan_.frontier_mask.ptr(), res, cell, labels, plan_.frontier_ws.ptr(), nullptr, st), "FrontierLabel");
+    unsigned count = 0;
+    for (int attempt = 0; attempt < 2; ++attempt) {   // (the second with room for the count the first returned)
+        unsigned long long *rec = plan_.frontier_records_d.ptr();
+        check_rc(xs_frontier_clusters(plan_.frontier_mask.ptr(), labels, res, capacity, rec, reinterpret_cast<unsigned *>(rec + (size_t)capacity * FRONTIER_RECORD_WORDS),
+                                      &count, plan_.frontier_ws.ptr(), st), "FrontierClusters");
+        if (count <= (unsigned)capacity) break;
+        if (count > 0x7fffffffu / 2u) return false;
+        capacity = (int)count;
+        room_for(capacity);
+    }
+    plan_.frontier_records.assign((size_t)count * FRONTIER_RECORD_WORDS, 0ull);
+    if (count) {
+        hipSafeCall(hipMemcpyAsync(plan_.frontier_records.data(), plan_.frontier_records_d.ptr(), plan_.frontier_records.size() * sizeof(unsigned long long),
+                                   hipMemcpyDeviceToHost, st));
+        hipSafeCall(hipStreamSynchronize(st));
+    }
+    plan_.frontier_key = key;
+    return true;
+}
+
+static bool frontier_cell_valid(int cell) { return cell == 0 || (cell >= 8 && cell <= 65528 && cell % 8 == 0); }
+
+int KinectFusionReconstruction::Frontiers(int cell, unsigned long long min_size, int min_weight, int capacity, unsigned long long *records8, int *count_out) {
+    if (shard_count > 1) return -2;   // a cluster is not additive over the ranks' z-slabs
+    if (!count_out || capacity < 0 || (capacity > 0 && !records8) || !frontier_cell_valid(cell)) return -1;
+    if (!tsdf_volume_d_ptr) return 0;
+    if (!FrontierPrepare(cell, min_weight)) return -1;
+    const int n = (int)(plan_.frontier_records.size() / FRONTIER_RECORD_WORDS);
+    std::vector<int> keep((size_t)n);
+    const int m = frontier_select(plan_.frontier_records.data(), n, min_size, keep.data());
+    *count_out = m;
+    if (m > capacity) return -4;
+    for (int i = 0; i < m; ++i)
+        std::memcpy(records8 + (size_t)i * FRONTIER_RECORD_WORDS, plan_.frontier_records.data() + (size_t)keep[(size_t)i] * FRONTIER_RECORD_WORDS,
+                    FRONTIER_RECORD_WORDS * sizeof(unsigned long long));
+    return 1;
+}
+
+int KinectFusionReconstruction::ProposeViews(float radius_m, int start_snap_vox, int unknown_blocks, int min_weight, int cell, unsigned long long min_size,
+                                             int views_per_cluster, float standoff_m, int snap_vox, int capacity, Matrix4cf *c2v_out, int *cluster_out,
+                                             int *count_out) {
+    if (shard_count > 1) return -2;   // neither connectivity nor a cluster is additive over the ranks' z-slabs
+    if (!count_out || capacity < 0 || (capacity > 0 && (!c2v_out || !cluster_out)) || !frontier_cell_valid(cell) || views_per_cluster < 1 ||
+        views_per_cluster > 4096 || !(standoff_m >= 0.f) || !std::isfinite(standoff_m) || snap_vox < 0 || snap_vox > XS_REACH_MAX_SNAP)
+        return -1;
+    const int rc = ReachPrepare(nullptr, radius_m, start_snap_vox, unknown_blocks, min_weight);
+    if (rc != 1) return rc;
+    if (!FrontierPrepare(cell, min_weight)) return -1;
+    const int n = (int)(plan_.frontier_records.size() / FRONTIER_RECORD_WORDS), V = views_per_cluster;
+    std::vector<int> keep((size_t)n);
+    const int m = frontier_select(plan_.frontier_records.data(), n, min_size, keep.data());
+    *count_out = 0;
+    if (m == 0) return 1;
+    // the standpoints of every kept cluster through one query over the reached words
+    std::vector<float> centroid((size_t)m * 3), pts((size_t)m * (size_t)V * 3);
+    for (int i = 0; i < m; ++i) {
+        frontier_centroid(plan_.frontier_records.data() + (size_t)keep[(size_t)i] * FRONTIER_RECORD_WORDS, voxel_size, &centroid[(size_t)i * 3]);
+        for (int j = 0; j < V; ++j) frontier_standpoint(&centroid[(size_t)i * 3], standoff_m, j, &pts[((size_t)i * (size_t)V + (size_t)j) * 3]);
+    }
+    std::vector<unsigned char> found((size_t)m * (size_t)V);
+    std::vector<int> voxel((size_t)m * (size_t)V * 3);
+    if (ReachQuery(pts.data(), m * V, 0, snap_vox, found.data(), nullptr, voxel.data()) < 0) return -1;
+    // the image-down hint: the current camera's y axis; its x axis where that is along the view
+    const Matrix4cf cam = getCamera2Volume();
+    const float down[3] = {cam.m[0][1].real(), cam.m[1][1].real(), cam.m[2][1].real()}, side[3] = {cam.m[0][0].real(), cam.m[1][0].real(), cam.m[2][0].real()};
+    std::vector<Matrix4cf> poses;
+    std::vector<int> cluster;
+    for (int i = 0; i < m; ++i)
+        for (int j = 0; j < V; ++j) {
+            const size_t q = (size_t)i * (size_t)V + (size_t)j;
+            if (!found[q]) continue;
+            bool seen = false;   // (the same answering voxel for the same cluster)
+            for (int k = 0; k < j && !seen; ++k) {
+                const size_t e = (size_t)i * (size_t)V + (size_t)k;
+                seen = found[e] && voxel[3 * e] == voxel[3 * q] && voxel[3 * e + 1] == voxel[3 * q + 1] && voxel[3 * e + 2] == voxel[3 * q + 2];
+            }
+            if (seen) continue;
+            const float pos[3] = {voxel_centre(voxel[3 * q], voxel_size), voxel_centre(voxel[3 * q + 1], voxel_size), voxel_centre(voxel[3 * q + 2], voxel_size)};
+            float R[9];
+            if (!look_at(pos, &centroid[(size_t)i * 3], down, side, R)) continue;   // (the centroid itself: no direction to look in)
+            Matrix4cf pose;
+            for (int r = 0; r < 4; ++r)
+                for (int c = 0; c < 4; ++c) pose.m[r][c] = hostComplex(r == c ? 1.f : 0.f, 0.f);
+            for (int r = 0; r < 3; ++r) {
+                for (int c = 0; c < 3; ++c) pose.m[r][c] = hostComplex(R[3 * r + c], 0.f);
+                pose.m[r][3] = hostComplex(pos[r], 0.f);
+            }
+            poses.push_back(pose);
+            cluster.push_back(i);
+        }
+    *count_out = (int)poses.size();
+    if ((int)poses.size() > capacity) return -4;
+    for (size_t p = 0; p < poses.size(); ++p) { c2v_out[p] = poses[p]; cluster_out[p] = cluster[p]; }
+    return 1;
 }

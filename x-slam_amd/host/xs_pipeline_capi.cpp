@@ -303,6 +303,19 @@ int xs_kf_next_view_by_travel(void *kf, int poses, const float *c2v32xP, const x
     return ((KF *)kf)->NextViewByTravel(poses_of(c2v32xP, poses).data(), poses, opts, min_weight, min_hits, out4xP, radius_m, snap_vox, unknown_blocks,
                                         max_travel_m, bias_m, travel3_out);
 }
+int xs_kf_frontiers(void *kf, int cell, unsigned long long min_size, int min_weight, int capacity, unsigned long long *records8, int *count_out) {
+    return ((KF *)kf)->Frontiers(cell, min_size, min_weight, capacity, records8, count_out);
+}
+int xs_kf_propose_views(void *kf, float radius_m, int start_snap_vox, int unknown_blocks, int min_weight, int cell, unsigned long long min_size,
+                        int views_per_cluster, float standoff_m, int snap_vox, int capacity, float *c2v32xP_out, int *cluster_out, int *count_out) {
+    if (capacity < 0 || (capacity > 0 && !c2v32xP_out)) return -1;
+    std::vector<Matrix4cf> m((size_t)capacity);
+    const int rc = ((KF *)kf)->ProposeViews(radius_m, start_snap_vox, unknown_blocks, min_weight, cell, min_size, views_per_cluster, standoff_m, snap_vox, capacity,
+                                            m.data(), cluster_out, count_out);
+    if (rc == 1)
+        for (int p = 0; p < *count_out; ++p) std::memcpy(c2v32xP_out + 32 * (size_t)p, &m[(size_t)p], 32 * sizeof(float));
+    return rc;
+}
 long long xs_kf_relocalization_index_voxels(void *kf) { return ((KF *)kf)->RelocalizationIndexVoxels(); }
 long long xs_kf_export_point_cloud(void *kf, int max_buffer, float *points_host, float *normals_host) {
     const auto pc = ((KF *)kf)->ExportPointCloud(max_buffer);

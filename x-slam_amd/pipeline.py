@@ -55,6 +55,9 @@ _SIGS = {
     "xs_kf_path_to": (C.c_int, [_vp, _f32p, C.c_float, C.c_int, C.c_int, C.c_int, C.c_float, _f32p, C.c_int, _i32p, _f32p, _i32p]),
     "xs_kf_next_view_by_travel": (C.c_int, [_vp, C.c_int, _f32p, C.POINTER(capi.ViewOpts), C.c_int, C.c_uint, C.POINTER(C.c_uint), C.c_float, C.c_int,
                                             C.c_int, C.c_float, C.c_float, C.POINTER(C.c_uint16)]),
+    "xs_kf_frontiers": (C.c_int, [_vp, C.c_int, C.c_ulonglong, C.c_int, C.c_int, C.POINTER(C.c_uint64), _i32p]),
+    "xs_kf_propose_views": (C.c_int, [_vp, C.c_float, C.c_int, C.c_int, C.c_int, C.c_int, C.c_ulonglong, C.c_int, C.c_float, C.c_int, C.c_int, _f32p, _i32p,
+                                      _i32p]),
     "xs_kf_relocalization_index_voxels": (C.c_longlong, [_vp]),
     "xs_kf_export_point_cloud": (C.c_longlong, [_vp, C.c_int, _f32p, _f32p]),
     "xs_kf_export_ply": (C.c_longlong, [_vp, C.c_int, C.c_char_p]),
@@ -528,6 +531,79 @@ class KinectFusion:
                                             0.0 if max_travel_m is None else float(max_travel_m), float(bias_m), cost.ctypes.data_as(C.POINTER(C.c_uint16)))
         self._reach_call("xs_kf_next_view_by_travel", rc, -3)
         return int(rc), out[:P].copy(), self._travel_m(cost[:P])
+
+    FRONTIER_DTYPE = np.dtype([("label", np.uint32), ("count", np.uint64), ("sum", np.uint64, 3), ("centroid", np.float32, 3), ("min", np.int32, 3),
+                               ("max", np.int32, 3)])
+
+    @staticmethod
+    def _frontier_call(name, rc):
+        if rc == -2:
+            raise capi.XsError(f"{name}: not available in shard mode (neither connectivity nor a cluster is additive over z-slabs)")
+        if rc == -1:
+            raise ValueError(f"{name}: bad arguments or options")
+
+    def frontiers(self, cell_vox=32, min_size=8, min_weight=1):
+        """Where known free space borders the unknown, grouped: the clusters of the frontier voxels (FREE with an UNKNOWN face neighbour in the
+        observation grid at min_weight; 26-adjacency within cells of cell_vox voxels, 0: the whole volume, otherwise a multiple of 8) that
+        have at least min_size voxels, in ascending label order.  A structured array with fields label (the lowest linear voxel index
+        (z Y + y) X + x of the cluster), count, sum (of x, y, z), centroid (float32 metres in volume coordinates: (sum / count + 0.5) voxels)
+        and the bounding box min / max (x, y, z voxels, inclusive).  XsError in shard mode."""
+        capacity, n = 1024, C.c_int(0)
+        for _ in range(2):
+            rec = np.zeros((max(capacity, 1), capi.FRONTIER_RECORD_WORDS), np.uint64)
+            rc = _lib.xs_kf_frontiers(self.h, int(cell_vox), int(min_size), int(min_weight), capacity, rec.ctypes.data_as(C.POINTER(C.c_uint64)), C.byref(n))
+            if rc != -4:
+                break
+            capacity = int(n.value)
+        self._frontier_call("xs_kf_frontiers", rc)
+        if rc != 1:
+            raise ValueError("xs_kf_frontiers: no volume" if rc == 0 else f"xs_kf_frontiers: {rc}")
+        rec = rec[:n.value]
+        out = np.zeros(len(rec), self.FRONTIER_DTYPE)
+        out["label"], out["count"], out["sum"] = rec[:, 0], rec[:, 1], rec[:, 2:5]
+        vs = np.float32(float(self.cfg["tsdf_voxel_size"]))
+        q = (rec[:, 2:5].astype(np.float64) / np.maximum(rec[:, 1:2], 1).astype(np.float64)).astype(np.float32)
+        out["centroid"] = (q + np.float32(0.5)) * vs
+        for name, col in (("min", 5), ("max", 6)):
+            out[name] = np.stack([(rec[:, col] >> np.uint64(s)) & np.uint64(0xFFFF) for s in (0, 16, 32)], axis=1).astype(np.int32)
+        return out
+
+    def propose_views(self, radius_m, views_per_cluster=6, standoff_m=1.0, cell_vox=32, min_size=8, snap_vox=4, start_snap_vox=4, unknown_blocks=True,
+                      min_weight=1):
+        """Candidate views from the map alone: for every cluster frontiers(cell_vox, min_size, min_weight) returns, views_per_cluster
+        standpoints at standoff_m around its centroid (Halton directions), each snapped to the nearest voxel within snap_vox that a body of
+        radius_m reaches from the current camera (its start snapped within start_snap_vox, as reachable() does), duplicates and
+        standpoints with no such voxel dropped: (c2vs float32 [P, 4, 4, 2] — at the voxel's centre, looking at the centroid —, cluster index
+        int32 [P] into that list).  reachable() and travel() call every proposed pose reachable.  XsError in shard mode."""
+        capacity, n = 1024, C.c_int(0)
+        for _ in range(2):
+            m, idx = np.zeros((max(capacity, 1), 4, 4, 2), np.float32), np.zeros(max(capacity, 1), np.int32)
+            rc = _lib.xs_kf_propose_views(self.h, float(radius_m), int(start_snap_vox), int(bool(unknown_blocks)), int(min_weight), int(cell_vox), int(min_size),
+                                          int(views_per_cluster), float(standoff_m), int(snap_vox), capacity, m.ctypes.data_as(_f32p), idx.ctypes.data_as(_i32p),
+                                          C.byref(n))
+            if rc != -4:
+                break
+            capacity = int(n.value)
+        self._frontier_call("xs_kf_propose_views", rc)
+        if rc != 1:
+            raise ValueError("xs_kf_propose_views: no volume" if rc == 0 else f"xs_kf_propose_views: {rc}")
+        return m[:n.value].copy(), idx[:n.value].copy()
+
+    def explore_step(self, radius_m, views_per_cluster=6, standoff_m=1.0, cell_vox=32, min_size=8, snap_vox=4, unknown_blocks=True, min_weight=1, bias_m=0.5,
+                     min_hits=None, rays=(80, 60), t_near=0.2, t_far=5.0, step=None, max_travel_m=None):
+        """Where should the camera go next, and which way?  propose_views, then next_view_by_travel over the proposed poses, then path_to the
+        chosen one (the start is snapped within snap_vox in all three).  A dict with index (into propose_views' list for the same arguments),
+        pose [4, 4, 2], cluster, counts uint32 [4] = {unknown, free, hits, frontier}, travel_m and path (path_to's (points, voxels)); None
+        when no view is proposed or none qualifies.  XsError in shard mode."""
+        cands, cluster = self.propose_views(radius_m, views_per_cluster, standoff_m, cell_vox, min_size, snap_vox, snap_vox, unknown_blocks, min_weight)
+        if len(cands) == 0:
+            return None
+        pick, counts, travel_m = self.next_view_by_travel(cands, radius_m, bias_m=bias_m, min_hits=min_hits, rays=rays, t_near=t_near, t_far=t_far, step=step,
+                                                          min_weight=min_weight, snap_vox=snap_vox, unknown_blocks=unknown_blocks, max_travel_m=max_travel_m)
+        if pick < 0:
+            return None
+        path = self.path_to(cands[pick], radius_m, snap_vox=snap_vox, unknown_blocks=unknown_blocks, min_weight=min_weight, max_travel_m=max_travel_m)
+        return dict(index=pick, pose=cands[pick].copy(), cluster=int(cluster[pick]), counts=counts[pick].copy(), travel_m=float(travel_m[pick]), path=path)
 
     def relocalization_index_voxels(self):
         """Band voxels in the relocalisation index as last built by relocalize_batch (0 before the first)."""

@@ -173,7 +173,8 @@ class ShardedKinectFusion(pl.KinectFusion):
     group, or pass `collective` (a Python callable (user, op, ptr, count)) directly.  score_views and next_best_view raise XsError on a
     shard and do nothing: occlusion along a ray is not additive over z-slabs; so do clearance_field, reachable and
     next_reachable_view: distance and connectivity are not additive either (section 4.19); and travel, path_to and next_view_by_travel: a path
-    is not additive either (section 4.20)."""
+    is not additive either (section 4.20); and frontiers, propose_views and explore_step: a cluster that crosses a slab border is not the
+    union of the slabs' clusters (section 4.21)."""
 
     def __init__(self, params, rank, world, dist=None, collective=None, torch=None, native=None):
         text = params if isinstance(params, str) else pl.yaml_text(params)
