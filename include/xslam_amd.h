@@ -680,7 +680,8 @@ size_t xs_icp_workspace_bytes(void);
 int xs_icp_workspace_init(void *workspace, void *stream);
 /* Device half of estimateCombined (ICP.h:24-31, ICP.cu:166-281 + 120-164): sums_dev receives 55
  * doubles — the 27 complex<double> sums in the reference's mbuf order, then the inlier count.
- * workspace replaces gbuf.  [y0, y1): pixel rows covered.  done_flag (optional; with sums_dev in
+ * workspace replaces gbuf.  [y0, y1): pixel rows covered, 0 <= y0 <= y1 <= rows; an empty range is a launch like any other and
+ * gives 55 zeros (it reads nothing outside the maps, y0 == y1 == rows included).  done_flag (optional; with sums_dev in
  * host-coherent pinned memory): the kernel stores done_seq there, system-scope release, after the
  * sums — the host may spin on it instead of copying + synchronising.  No synchronisation.
  * done_flag == XS_ICP_PUBLISH_PAIRS (xs_icp_accumulate, _real, _posted, _posted_real): sums_dev is host-coherent pinned memory of

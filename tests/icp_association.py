@@ -10,9 +10,10 @@ RECORD_DOUBLES = 56   # 54 sums, the inlier count, one pad / sequence word
 SUMS = 55
 
 
-def row_groups(cols, rows):
-    """G of the instance a launch over a cols x rows image runs (icp_blocks / icp_dispatch of xs_icp.hip, default settings)."""
-    tiles = -(-cols // 64) * rows
+def row_groups(cols, rows, y0=0, y1=None):
+    """G of the instance a launch over the pixel rows [y0, y1) of a cols x rows image runs (icp_blocks / icp_dispatch of xs_icp.hip,
+    default settings)."""
+    tiles = -(-cols // 64) * ((rows if y1 is None else y1) - y0)
     if 8 * 512 < tiles <= 10 * 512:
         return 36                       # 256 sixteen-wave workgroups of 18 or 19 tiles
     if -(-tiles // 8) <= 768:

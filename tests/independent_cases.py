@@ -100,6 +100,27 @@ class OracleBackend:
             self.resize_p(m0, m1, rows0, cols0, nrm)
             self.resize_p(m1, m2, rows0 // 2, cols0 // 2, nrm)
 
+    # ---- ICP reduction on pitched host buffers (tests/icp_cases.py) ----
+    def icp_p(self, Rcurr, tcurr, cv, cn, Rprev_inv, tprev, intr, pv, pn, rows, cols, dist, angle, y0=0, y1=None, real=None):
+        """The 54 sums and the inlier count of pixel rows [y0, y1): four maps of one pitch.  The oracle reads no float planes: real =
+        (vertex, normal) planes stand for complex maps with zero imaginary parts and are expanded into such, at the maps' pitch."""
+        from map_cases import Pitched
+        assert cv.pitch == cn.pitch == pv.pitch == pn.pitch
+        if real is not None:
+            cplx = []
+            for r in real:
+                b = Pitched(3 * rows, cols, np.float32, 2, cv.pitch)
+                b.image[..., 0], b.image[..., 1] = r.image, 0.0
+                cplx.append(b)
+            cv, cn = cplx
+        f = [np.ascontiguousarray(x, np.float32).reshape(-1) for x in (Rcurr, tcurr, Rprev_inv, tprev, intr)]
+        P = lambda x: x.ctypes.data_as(C.POINTER(C.c_float))
+        out = np.zeros(55, np.float64)
+        out[54] = self.o._icp_combined(P(f[0]), P(f[1]), self._a(cv), self._a(cn), P(f[2]), P(f[3]), P(f[4]), self._a(pv), self._a(pn), cv.pitch,
+                                       rows, cols, dist, angle, y0, rows if y1 is None else y1, out.ctypes.data_as(C.POINTER(C.c_double)), None, None)
+        return out
+
+
 class GpuBackend:
     """The HIP kernels through the C ABI (x-slam_amd/capi.py)."""
     def __init__(self, torch, capi, host_m3_inverse):
@@ -275,6 +296,84 @@ class GpuBackend:
         ts, ps = self._up(*bufs)
         self.c.resize_pyramid(ps[0], ps[1], vmap0.pitch, rows0, cols0, ps[2], ps[3], vmap1.pitch, ps[4], ps[5], vmap2.pitch)
         self._down(bufs[2:], ts[2:])
+
+    # ---- ICP reduction on pitched buffers (tests/icp_cases.py) ----
+    def _pinned(self, nbytes):
+        """nbytes of zeroed host-coherent pinned memory: (address, free)."""
+        hip = C.CDLL("libamdhip64.so")
+        p = C.c_void_p()
+        assert hip.hipHostMalloc(C.byref(p), C.c_size_t(nbytes), C.c_uint(0x40000000 | 0x2)) == 0
+        C.memset(p, 0, nbytes)
+        return p.value, lambda: hip.hipHostFree(p)
+
+    def icp_p(self, Rcurr, tcurr, cv, cn, Rprev_inv, tprev, intr, pv, pn, rows, cols, dist, angle, y0=0, y1=None, real=None, form="device",
+              posted=False, launches=1):
+        """The 55 doubles of one launch over pixel rows [y0, y1).  real = (vertex, normal) float planes: the _real entry points, which are
+        then given no complex current maps.  form: 'device' (sums in device memory), 'pairs' (XS_ICP_PUBLISH_PAIRS into pinned memory) or
+        'records' (xs_icp_accumulate_records + xs_icp_sum_records; the records are left in self.records).  posted: the pose comes through
+        a mailbox, posted before anything synchronises.  launches > 1: the same launch again on the same workspace, which must give the
+        same bits.  Every input buffer must come back byte-identical, guard rows and padding included."""
+        t, c = self.t, self.c
+        y1 = rows if y1 is None else y1
+        bufs = [cv, cn, pv, pn] + (list(real) if real is not None else [])
+        assert cv.pitch == cn.pitch == pv.pitch == pn.pitch and (real is None or real[0].pitch == real[1].pitch)
+        ts, ps = self._up(*bufs)
+        tail = (Rprev_inv, tprev, intr, ps[2], ps[3], cv.pitch, rows, cols, dist, angle)
+        ws = t.zeros(c.icp_workspace_bytes(), dtype=t.uint8, device="cuda")
+        frees, outs = [], []
+        try:
+            mailbox = None
+            if posted:
+                mailbox, in_dev = c.icp_mailbox_alloc()
+                frees.append(lambda: c.icp_mailbox_free(mailbox, in_dev))
+            for k in range(launches):
+                seq = 11 + k
+                if form == "records":
+                    assert not posted and real is None
+                    rec, free = self._pinned(c.icp_records_bytes())
+                    frees.append(free)
+                    c.icp_accumulate_records(Rcurr, tcurr, ps[0], ps[1], *tail, rec, seq, y0=y0, y1=y1)
+                    t.cuda.synchronize()
+                    count = c.icp_records_count(cols, y0, y1)
+                    rc, got = c.icp_sum_records(rec, count, seq, max_spins=1000)      # (the launch has completed: nothing to wait for)
+                    assert rc == 0
+                    self.records = np.ctypeslib.as_array((C.c_double * (count * 56)).from_address(rec)).reshape(count, 56).copy()
+                    outs.append(got)
+                    continue
+                if form == "pairs":
+                    sums, free = self._pinned(1024)
+                    frees.append(free)
+                    kw = dict(done_flag=c.ICP_PUBLISH_PAIRS, done_seq=seq)
+                else:
+                    sums, kw = t.full((55,), 7.0, dtype=t.float64, device="cuda"), {}
+                if posted and real is not None:
+                    c.icp_accumulate_posted_real(mailbox, seq, ps[4], ps[5], real[0].pitch, *tail, ws, sums, y0=y0, y1=y1, **kw)
+                elif posted:
+                    c.icp_accumulate_posted(mailbox, seq, ps[0], ps[1], *tail, ws, sums, y0=y0, y1=y1, **kw)
+                elif real is not None:
+                    assert form == "device"
+                    c.icp_accumulate_real(Rcurr, tcurr, ps[4], ps[5], real[0].pitch, *tail, ws, sums, y0=y0, y1=y1)
+                else:
+                    c.icp_accumulate(Rcurr, tcurr, ps[0], ps[1], *tail, ws, sums, y0=y0, y1=y1, **kw)
+                if posted:
+                    c.icp_post_pose(mailbox, Rcurr, tcurr, seq)                     # before anything waits for the launch
+                t.cuda.synchronize()
+                if form == "pairs":
+                    rc, got = c.icp_wait_pairs(sums, seq, max_spins=1000)
+                    assert rc == 0
+                    outs.append(got)
+                else:
+                    outs.append(sums.cpu().numpy())
+        finally:
+            t.cuda.synchronize()
+            for free in frees:
+                free()
+        for o in outs[1:]:
+            assert np.array_equal(o.view(np.uint64), outs[0].view(np.uint64)), "a repeated launch must give the same bits"
+        for b, d in zip(bufs, ts):
+            assert np.array_equal(d.cpu().numpy(), b.a), "the launch wrote to an input buffer"
+        return outs[0]
+
 
 def _res(prm, res):
     n = prm["tsdf_size_x"]

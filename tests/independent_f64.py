@@ -190,12 +190,51 @@ def raycast(d, h, intr, Rc2v, tc2v, Rv2w, tv2w, trunc, res, voxel_size, value, g
 
 # ------------------------------------------------------------------------------------------------
 # ICP rows and normal equations — Combined::search_newton / operator(), XKinectFusion/src/ICP.cu:196-281
+U32 = 2.0 ** -24                  # float32 unit round-off
+# Rounded float32 operations on the path to the REAL part of a complex expression (complex<float>, the reference's operation order).  A
+# running error bound: an expression whose longest path holds n rounded operations is evaluated within n * U32 of the same expression
+# with every operand replaced by its absolute value (first order; the second-order terms are 1e-7 of that).
+ICP_OPS_ROTATE = 4                # R * v, per component: a product, minus the product of the imaginary parts, two additions
+ICP_OPS_TRANSFORM = 5             # R * v + t: the translation on top
+ICP_OPS_CROSS = 3                 # a_y b_z - a_z b_y: a complex product (two roundings) and the difference
+ICP_OPS_DOT = 5                   # n . (d - s): the difference, a complex product, two additions
+ICP_OPS_PRODUCT = 2               # row_i * row_j: the product and the product of the imaginary parts taken off it
+ICP_DEVICE = 2                    # a division or square root that the device may round one ulp away from the reference's counts twice
+# The gates compare Re sqrt(sum of three complex squares): each square is two roundings, two additions follow — four relative
+# roundings of the square, two of its root — and the complex square root is five library operations (hypot, sqrt, atan2, cos, a
+# product: oc_complex.hpp / xs_complex.h), each of which may differ by an ulp between host and device: 2 + 5 * ICP_DEVICE.
+ICP_OPS_NORM = 2 + 5 * ICP_DEVICE
+
+
+def _abs_cross(a, b):
+    """|a x b| with every operation replaced by the sum of its operands' absolute values (a, b >= 0, [3, n])."""
+    return np.stack([a[1] * b[2] + a[2] * b[1], a[2] * b[0] + a[0] * b[2], a[0] * b[1] + a[1] * b[0]])
+
+
+def icp_bounds(dec, cols, y0, y1):
+    """(sum_p m_i m_j [27], sum_p (m_i dm_j + dm_i m_j) [27]) over the inliers of rows [y0, y1) from the per-pixel magnitude bounds of an
+    evaluation with margins=True, in the order of the sums."""
+    pr = np.arange(dec["ok"].size) // cols
+    sel = dec["ok"] & (pr >= y0) & (pr < y1)
+    m, dm = dec["m"][:, sel], dec["dm"][:, sel]
+    pairs = [(i, j) for i in range(6) for j in range(i, 7)]
+    return (np.array([np.dot(m[i], m[j]) for i, j in pairs]), np.array([np.dot(m[i], dm[j]) + np.dot(dm[i], m[j]) for i, j in pairs]))
+
+
 def icp_normal_equations(d, h, Rcurr, tcurr, vmap_curr, nmap_curr, Rprev_inv, tprev, intr, vmap_prev, nmap_prev, dist_thres,
-                         angle_thres, dec=None):
-    """All pixels of one pyramid level.  Maps: [3 * rows, cols, 2].  Returns (sums[27] in the kernel's order
-    i = 0..5, j = i..6 of row_i * row_j, inliers, dec)."""
+                         angle_thres, dec=None, y0=0, y1=None, margins=False):
+    """The current pixels of rows [y0, y1) of one pyramid level (association ranges over the whole model map).  Maps: [3 * rows, cols, 2].
+    Returns (sums[27] in the kernel's order i = 0..5, j = i..6 of row_i * row_j, inliers, dec).  dec (whole image, whatever the range):
+    'ok' the inliers, 'branch' the pixels each rejection test removes (in the kernel's order, each among those that reached it), and with
+    margins=True
+      'fragile'  current pixels with a valid normal of which one decision — the two roundings rint(u), rint(v) (the four image bounds are
+                 among their half-integers), cpz < 0, the distance gate, the angle gate — lies within the float32 evaluation error of its
+                 boundary (derivations at the statements below; sized for the reference's float32 evaluation, ICP_DEVICE for the device);
+      'm', 'dm'  [7, pixels]: m_i >= |row_i| formed with every operation replaced by the sum of its operands' absolute values (so the
+                 cancellation in d - s and in the cross products does not shrink it), and the same bound of the tangent d row_i / d seed."""
     fx, fy, cx, cy = (float(F32(v)) for v in intr)
     rows, cols = vmap_curr.shape[0] // 3, vmap_curr.shape[1]
+    y1 = rows if y1 is None else y1
     planes = lambda m: lin(np.asarray(m).reshape(3, rows, cols, 2), d, h).reshape(3, -1)
     vc, nc, vp, npv = planes(vmap_curr), planes(nmap_curr), planes(vmap_prev), planes(nmap_prev)
     Rc = lin(np.asarray(Rcurr).reshape(3, 3, 2), d, h)
@@ -207,25 +246,67 @@ def icp_normal_equations(d, h, Rcurr, tcurr, vmap_curr, nmap_curr, Rprev_inv, tp
         vcp = Rpi @ (vg - tp[:, None])                                   # :213
         if dec is None:
             assert d == 0.0
-            ok = ~np.isnan(nc[0])                                        # :202-204
-            ux = np.rint(vcp[0] * fx / vcp[2] + cx)                      # :216-217 __float2int_rn
-            uy = np.rint(vcp[1] * fy / vcp[2] + cy)
-            ok &= np.isfinite(ux) & np.isfinite(uy)
-            ok &= ~((ux < 0) | (uy < 0) | (ux >= cols) | (uy >= rows) | (vcp[2] < 0))   # :218-220
+            valid = ~np.isnan(nc[0])                                     # :202-204
+            fu, fv = vcp[0] * fx / vcp[2] + cx, vcp[1] * fy / vcp[2] + cy
+            ux, uy = np.rint(fu), np.rint(fv)                            # :216-217 __float2int_rn
+            fin = np.isfinite(ux) & np.isfinite(uy)
+            sides = dict(left=ux < 0, right=ux >= cols, top=uy < 0, bottom=uy >= rows, behind=vcp[2] < 0)
+            ok = valid & fin & ~np.logical_or.reduce(list(sides.values()))   # :218-220
             idx = (np.where(ok, uy, 0).astype(np.int64) * cols + np.where(ok, ux, 0).astype(np.int64))
+            inb = ok.copy()
             ok &= ~np.isnan(npv[0][idx])                                 # :222-224
-            dec = dict(idx=idx)
+            dec = dict(idx=idx, branch=dict(nan_normal=~valid, hole=inb & ~ok, **{k: valid & fin & v for k, v in sides.items()}))
         idx = dec["idx"]
         n_prev, v_prev = npv[:, idx], vp[:, idx]
         if "ok" not in dec:
+            thr_d, thr_a = float(F32(dist_thres)), float(F32(angle_thres))
             dist = np.sqrt(((v_prev - vg) ** 2).sum(0))                  # :232-234
-            ok &= ~(dist > float(F32(dist_thres)))
+            far = dist > thr_d
             ncg = Rc @ nc                                                # :235
             sine = np.sqrt((np.cross(ncg.T, n_prev.T) ** 2).sum(-1))     # :236-238
-            ok &= ~(sine >= float(F32(angle_thres)))
-            ok &= np.isfinite(dist) & np.isfinite(sine)
-            dec["ok"] = ok
-        ok = dec["ok"]
+            tilted = sine >= thr_a
+            dec["branch"].update(far=ok & far, tilted=ok & ~far & tilted)
+            dec["ok"] = ok & ~far & ~tilted & np.isfinite(dist) & np.isfinite(sine)
+            if margins:
+                A = np.abs
+                tan = lambda m, shape: A(np.asarray(m, np.float64).reshape(*shape, 2)[..., 1] / h).reshape(shape[0], -1)
+                aR, aRp = A(Rc), A(Rpi)
+                # s = Rcurr * v + t: ICP_OPS_TRANSFORM roundings on mag_g; cp = Rprev_inv * (s - tprev): one more for the difference and
+                # ICP_OPS_ROTATE for the rotation, on mag_cp
+                mag_g = aR @ A(vc) + A(tc)[:, None]
+                e_g = ICP_OPS_TRANSFORM * U32 * mag_g
+                mag_cp = aRp @ (mag_g + A(tp)[:, None])
+                e_cp = (ICP_OPS_TRANSFORM + 1 + ICP_OPS_ROTATE) * U32 * mag_cp
+                az = A(vcp[2])
+                # u = cpx * fx / cpz + cx: the errors of cpx and cpz through the quotient q, the product and the division
+                # ((1 + ICP_DEVICE) roundings of q), and the addition (one rounding of |q| + |cx|).  rint flips where u lies this
+                # close to a half-integer; -1/2 and cols - 1/2 (rows - 1/2) are the image bounds.
+                def pix_err(k, f, c0):
+                    q = A(vcp[k] * f / vcp[2])
+                    return f / az * e_cp[k] + q / az * e_cp[2] + (1 + ICP_DEVICE) * U32 * q + U32 * (q + abs(c0))
+                near_half = lambda f, e: A(f - (np.floor(f) + 0.5)) <= e
+                frag = ~fin | near_half(fu, pix_err(0, fx, cx)) | near_half(fv, pix_err(1, fy, cy))
+                frag |= az <= e_cp[2]                                    # cpz < 0
+                # |d - s|: each component of the difference carries s's error and one rounding of |d| + mag_g; the root of the sum
+                # of squares moves by at most the length of that error vector (Cauchy-Schwarz, whatever the cancellation), plus
+                # ICP_OPS_NORM roundings of the root itself
+                e_d = e_g + U32 * (A(v_prev) + mag_g)
+                frag_gate = A(dist - thr_d) <= np.sqrt((e_d ** 2).sum(0)) + ICP_OPS_NORM * U32 * dist
+                # |Rcurr n x n_prev|: ICP_OPS_ROTATE roundings on mag_n, through the cross product (n_prev is exact) plus its own
+                # ICP_OPS_CROSS roundings
+                mag_n = aR @ A(nc)
+                e_c = _abs_cross(ICP_OPS_ROTATE * U32 * mag_n, A(n_prev)) + ICP_OPS_CROSS * U32 * _abs_cross(mag_n, A(n_prev))
+                frag_gate |= A(sine - thr_a) <= np.sqrt((e_c ** 2).sum(0)) + ICP_OPS_NORM * U32 * sine
+                dec["fragile"] = valid & (frag | (ok & frag_gate))
+                # magnitude bounds of the rows: row[0:3] = s x n, row[3:6] = n, row[6] = n . (d - s); tangents by the product rule
+                dmag_g = tan(Rcurr, (3, 3)).reshape(3, 3) @ A(vc) + aR @ tan(vmap_curr, (3, rows, cols)) + tan(tcurr, (3,)).reshape(3)[:, None]
+                an, ad = A(n_prev), A(v_prev)
+                dn, dd_ = tan(nmap_prev, (3, rows, cols))[:, idx], tan(vmap_prev, (3, rows, cols))[:, idx]
+                dec["m"] = np.concatenate([_abs_cross(mag_g, an), an, (an * (ad + mag_g)).sum(0)[None]])
+                dec["dm"] = np.concatenate([_abs_cross(dmag_g, an) + _abs_cross(mag_g, dn), dn,
+                                            (dn * (ad + mag_g) + an * (dd_ + dmag_g)).sum(0)[None]])
+        pr = np.arange(rows * cols) // cols
+        ok = dec["ok"] & (pr >= y0) & (pr < y1)
         s, nn, dd = vg[:, ok], n_prev[:, ok], v_prev[:, ok]              # :239-242: n = n_prev_g, d = p_prev_g, s = p_curr_g
         row = np.empty((7, s.shape[1]))
         row[0:3] = np.cross(s.T, nn.T).T                                 # :256

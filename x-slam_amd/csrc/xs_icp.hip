@@ -861,6 +861,9 @@ static int icp_launch(const float *Rcurr18, const float *tcurr6, const float *vm
         (!host_records && (!workspace || !sums_dev)))
         return xs_set_error(hipErrorInvalidValue, who);
     if (y0 < 0 || y1 > rows || y1 < y0) return xs_set_error(hipErrorInvalidValue, "xs_icp: bad row range");
+    // an empty range at the end of the image: the one-tile-per-wave instances request the vertex of pixel (0, y0) for every lane
+    // without a tile, and row y0 == rows lies one row past the maps — the same empty launch over the last row instead
+    if (y0 == y1 && y0 == rows && rows > 0) y0 = y1 = rows - 1;
     IcpArgs a;
     if (Rcurr18) { ld_mat(Rcurr18, a.Rcurr); ld_vec(tcurr6, a.tcurr); }
     else { memset(&a.Rcurr, 0, sizeof(a.Rcurr)); memset(&a.tcurr, 0, sizeof(a.tcurr)); }
