@@ -202,6 +202,30 @@ def test_argument_checks(dev, case):
     assert bool((out[:8] != GARBAGE_I32).all()) and bool((out[8:] == GARBAGE_I32).all())
 
 
+def test_resolution_beyond_a_launch_extent(dev):
+    """(4, 65536, 4): Y does not fit a launch's grid dimension.  The calls that run over bricks take it (the grid has a size and builds: an
+    all-FREE volume gives 0x55 in every byte of the 65536 brick words); the calls that run over voxels or tiles refuse it: xs_view_grid_expand
+    with hipErrorInvalidValue (1) before any launch, and the clearance, reach, travel and frontier buffers have no size."""
+    torch, capi, _ = dev
+    res = (4, 65536, 4)
+    X, Y, Z = res
+    nbricks = 1 * (Y // 4) * 1
+    assert capi.view_grid_bytes(res) >= 16 * nbricks
+    value = torch.ones(X * Y * Z, dtype=torch.float32, device="cuda")
+    weight = torch.ones(X * Y * Z, dtype=torch.int32, device="cuda")
+    grid = torch.full((capi.view_grid_bytes(res),), 0xA5, dtype=torch.uint8, device="cuda")
+    capi.view_grid_build(value, weight, X * 4, res, grid)
+    torch.cuda.synchronize()
+    assert bool((grid[:16 * nbricks] == 0x55).all())
+    states = torch.full((X * Y * Z,), 0xEE, dtype=torch.uint8, device="cuda")
+    with pytest.raises(capi.XsError, match=r"hip error 1: xs_view_grid_expand: bad resolution"):
+        capi.view_grid_expand(grid, res, states)
+    torch.cuda.synchronize()
+    assert bool((states == 0xEE).all())
+    for sized in (capi.clearance_bytes, capi.reach_bytes, capi.travel_bytes, capi.frontier_mask_bytes, capi.frontier_label_bytes):
+        assert sized(res) == 0, sized.__name__
+
+
 # ---- orchestrator level ----------------------------------------------------------------------------------------------------------------
 def model_of_volume(kf, prm, c2vs, **kw):
     n = kf.res[0]

@@ -20,32 +20,31 @@
 //   k_reach_round      lane = brick word: grows the word to its in-brick fixpoint by masked shifts, pulls the facing bits of the six
 //                      neighbouring words, grows again, writes its own word and, if it grew, a `changed` word (a plain vector store).
 //                      Words only gain bits, a stale read of a neighbour delays a bit and never invents one, the fixpoint is unique.
+//                      The host runs the rounds through xs_grid.h's grid_run_rounds.
 //   k_reach_expand     one byte per voxel
 //   k_reach_query      lane = point: the voxel of the point, its bit, and with snap > 0 the nearest voxel of the mask in the snap cube
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include <string.h>
 #include "xs_device.h"
-#include "xs_reach.h"
+#include "xs_grid.h"
 #include "../../include/xslam_amd.h"
 
-enum { REACH_FREE = 1, REACH_OCCUPIED = 2, CLEAR_STRIP = 256, CLEAR_APRON = 256, CLEAR_WORDS = (CLEAR_STRIP + 2 * CLEAR_APRON) / 32,
-       CLEAR_NONE8 = 255, CLEAR_NONE16 = 65535, REACH_ROUNDS_PER_BATCH = 8, REACH_CONTROL_BYTES = 256 };
+enum { CLEAR_STRIP = 256, CLEAR_APRON = 256, CLEAR_WORDS = (CLEAR_STRIP + 2 * CLEAR_APRON) / 32, CLEAR_NONE8 = 255, CLEAR_NONE16 = 65535 };
 static_assert(XS_REACH_MAX_SEEDS == 64 && XS_REACH_MAX_SNAP == 16 && XS_CLEARANCE_MAX_RADIUS == 255, "the header's bounds");
 
 // ---- clearance ---------------------------------------------------------------------------------------------------------------------------
 extern "C" size_t xs_clearance_bytes(const int *res) {
-    ReachDims d;
-    return reach_dims(res, d) ? reach_voxels(d) * sizeof(uint16_t) : 0;
+    GridDims d;
+    return grid_dims_launchable(res, d) ? grid_voxels(d) * sizeof(uint16_t) : 0;
 }
 // the bytes of k_clear_x (rounded up to 256), then the uint16 of the y pass
-static size_t clear_ws_split(const ReachDims &d) { return (reach_voxels(d) + 255) / 256 * 256; }
+static size_t clear_ws_split(const GridDims &d) { return (grid_voxels(d) + 255) / 256 * 256; }
 extern "C" size_t xs_clearance_workspace_bytes(const int *res) {
-    ReachDims d;
-    return reach_dims(res, d) ? clear_ws_split(d) + reach_voxels(d) * sizeof(uint16_t) : 0;
+    GridDims d;
+    return grid_dims_launchable(res, d) ? clear_ws_split(d) + grid_voxels(d) * sizeof(uint16_t) : 0;
 }
 
-__global__ void __launch_bounds__(CLEAR_STRIP) k_clear_x(const unsigned *__restrict__ grid, ReachDims d, int R, int unknown_blocks, unsigned char *__restrict__ dist) {
+__global__ void __launch_bounds__(CLEAR_STRIP) k_clear_x(const unsigned *__restrict__ grid, GridDims d, int R, int unknown_blocks, unsigned char *__restrict__ dist) {
     __shared__ unsigned bits[4][CLEAR_WORDS];
     const int t = threadIdx.x, x0 = (int)blockIdx.x * CLEAR_STRIP, by = (int)blockIdx.y, z = (int)blockIdx.z;
     if (t < 4 * CLEAR_WORDS) bits[t / CLEAR_WORDS][t % CLEAR_WORDS] = 0u;
@@ -55,16 +54,15 @@ __global__ void __launch_bounds__(CLEAR_STRIP) k_clear_x(const unsigned *__restr
     if (t < (CLEAR_STRIP + 2 * CLEAR_APRON) / 4) {
         const int bx = (x0 - CLEAR_APRON) / 4 + t;                 // (exact: the numerator is a multiple of four, negative or not)
         if (bx >= 0 && bx < d.BX) {
-            const size_t b = ((size_t)(z >> 2) * (size_t)d.BY + (size_t)by) * (size_t)d.BX + (size_t)bx;
-            const unsigned plane = grid[4 * b + (size_t)(z & 3)];   // dword lz of the brick word: the 4 x 4 states of plane z
+            const unsigned plane = grid[4 * grid_brick_at(d, bx, by, z >> 2) + (size_t)(z & 3)];   // dword lz of the brick word: the 4 x 4 states of plane z
 #pragma unroll
             for (int ly = 0; ly < 4; ++ly) {
                 unsigned nib = 0;
 #pragma unroll
                 for (int lx = 0; lx < 4; ++lx) {
-                    const unsigned s = plane >> (2 * (lx + 4 * ly)) & 3u;
+                    const unsigned s = grid_plane_state_of(plane, lx, ly);
                     const bool inside = 4 * bx + lx < d.X;         // the padding bits of an overhanging brick are not a state
-                    if (inside && (s == REACH_OCCUPIED || (unknown_blocks && s == 0u))) nib |= 1u << lx;
+                    if (inside && (s == GRID_OCCUPIED || (unknown_blocks && s == GRID_UNKNOWN))) nib |= 1u << lx;
                 }
                 if (nib) atomicOr(&bits[ly][t >> 3], nib << (4 * (t & 7)));
             }
@@ -96,7 +94,7 @@ __global__ void __launch_bounds__(CLEAR_STRIP) k_clear_x(const unsigned *__restr
         }
         if (unknown_blocks) best = min(best, min(x + 1, d.X - x));   // the nearest position outside the volume along x
         if (best > R) best = CLEAR_NONE8;
-        dist[((size_t)z * (size_t)d.Y + (size_t)y) * (size_t)d.X + (size_t)x] = (unsigned char)best;
+        dist[grid_voxel_of(d, x, y, z)] = (unsigned char)best;
     }
 }
 
@@ -136,9 +134,9 @@ __global__ void __launch_bounds__(256) k_clear_axis(const In *__restrict__ in, u
 static int clear_tile_rows(int R) { return R <= 64 ? 64 : 128; }
 
 extern "C" int xs_clearance_build(const void *grid, const int *res, int max_radius, int unknown_blocks, void *workspace, unsigned short *field_dev, void *stream) {
-    ReachDims d;
+    GridDims d;
     if (!grid || !workspace || !field_dev) return xs_set_error(hipErrorInvalidValue, "xs_clearance_build: null pointer");
-    if (!reach_dims(res, d)) return xs_set_error(hipErrorInvalidValue, "xs_clearance_build: bad resolution");
+    if (!grid_dims_launchable(res, d)) return xs_set_error(hipErrorInvalidValue, "xs_clearance_build: bad resolution");
     if (max_radius < 1 || max_radius > XS_CLEARANCE_MAX_RADIUS) return xs_set_error(hipErrorInvalidValue, "xs_clearance_build: max_radius outside 1 .. 255");
     if (unknown_blocks != 0 && unknown_blocks != 1) return xs_set_error(hipErrorInvalidValue, "xs_clearance_build: unknown_blocks is 0 or 1");
     hipStream_t st = (hipStream_t)stream;
@@ -165,84 +163,74 @@ extern "C" int xs_clearance_build(const void *grid, const int *res, int max_radi
 }
 
 // ---- reachability ------------------------------------------------------------------------------------------------------------------------
-// The reach buffer: the reached words, the passable words, then REACH_CONTROL_BYTES of `changed` words (one per round of a batch).
+// The reach buffer: the reached words, the passable words, then GRID_CONTROL_BYTES of `changed` words (grid_run_rounds).
+static inline unsigned long long *reach_passable_of(void *reach, size_t nbricks) { return static_cast<unsigned long long *>(reach) + nbricks; }
 extern "C" size_t xs_reach_bytes(const int *res) {
-    ReachDims d;
-    return reach_dims(res, d) ? reach_bricks(d) * 16 + REACH_CONTROL_BYTES : 0;
+    GridDims d;
+    return grid_dims_launchable(res, d) ? grid_bricks(d) * 16 + GRID_CONTROL_BYTES : 0;
 }
 
-__global__ void __launch_bounds__(256) k_reach_passable(const uint4 *__restrict__ grid, const uint16_t *__restrict__ field, ReachDims d, unsigned r2,
+__global__ void __launch_bounds__(256) k_reach_passable(const uint4 *__restrict__ grid, const uint16_t *__restrict__ field, GridDims d, unsigned r2,
                                                         unsigned nbricks, unsigned long long *__restrict__ passable) {
     const unsigned b = blockIdx.x * 4u + (threadIdx.x >> 6);       // wave = brick
     if (b >= nbricks) return;
-    const int l = threadIdx.x & 63, lx = l & 3, ly = l >> 2 & 3, lz = l >> 4;
-    const int bx = (int)(b % (unsigned)d.BX), by = (int)(b / (unsigned)d.BX % (unsigned)d.BY), bz = (int)(b / ((unsigned)d.BX * (unsigned)d.BY));
-    const int x = 4 * bx + lx, y = 4 * by + ly, z = 4 * bz + lz;
+    const int l = threadIdx.x & 63;                                // lane = the voxel's bit
+    int bx, by, bz, x, y, z;
+    grid_brick_of(d, b, bx, by, bz);
+    grid_voxel_of_bit(bx, by, bz, l, x, y, z);
     bool pass = false;
-    if (x < d.X && y < d.Y && z < d.Z) {
-        const uint4 word = grid[b];
-        const unsigned plane = lz == 0 ? word.x : (lz == 1 ? word.y : (lz == 2 ? word.z : word.w));
-        const unsigned s = plane >> (2 * (lx + 4 * ly)) & 3u;
-        pass = s == REACH_FREE && (unsigned)field[((size_t)z * (size_t)d.Y + (size_t)y) * (size_t)d.X + (size_t)x] >= r2;
-    }
+    if (x < d.X && y < d.Y && z < d.Z) pass = grid_state_of(grid[b], x, y, z) == GRID_FREE && (unsigned)field[grid_voxel_of(d, x, y, z)] >= r2;
     const unsigned long long m = __ballot(pass);
     if (l == 0) passable[b] = m;
 }
 
-__global__ void k_reach_seed(ReachSeeds s, ReachDims d, const unsigned long long *__restrict__ passable, unsigned long long *__restrict__ reach) {
+__global__ void k_reach_seed(GridSeeds s, GridDims d, const unsigned long long *__restrict__ passable, unsigned long long *__restrict__ reach) {
     if (threadIdx.x != 0 || blockIdx.x != 0) return;
     for (int k = 0; k < s.n; ++k) {
         const int x = s.v[3 * k], y = s.v[3 * k + 1], z = s.v[3 * k + 2];
-        if ((unsigned)x >= (unsigned)d.X || (unsigned)y >= (unsigned)d.Y || (unsigned)z >= (unsigned)d.Z) continue;
-        const size_t b = ((size_t)(z >> 2) * (size_t)d.BY + (size_t)(y >> 2)) * (size_t)d.BX + (size_t)(x >> 2);
-        const unsigned long long bit = 1ull << ((x & 3) + 4 * (y & 3) + 16 * (z & 3));
+        if (!grid_inside(d, x, y, z)) continue;
+        const size_t b = grid_word_of(d, x, y, z);
+        const unsigned long long bit = 1ull << grid_bit_of(x, y, z);
         if (passable[b] & bit) reach[b] |= bit;
     }
 }
 
-#define REACH_X0 0x1111111111111111ull
-#define REACH_X3 0x8888888888888888ull
-#define REACH_Y0 0x000f000f000f000full
-#define REACH_Y3 0xf000f000f000f000ull
 // the word's in-brick fixpoint: the face neighbours of set bits that are passable, until nothing is added (at most 9 steps across a brick,
 // more along a winding passage inside it)
 __device__ __forceinline__ unsigned long long reach_grow(unsigned long long m, unsigned long long p) {
     for (;;) {
-        const unsigned long long g = (m | (m << 1 & ~REACH_X0) | (m >> 1 & ~REACH_X3) | (m << 4 & ~REACH_Y0) | (m >> 4 & ~REACH_Y3) | m << 16 | m >> 16) & p;
+        const unsigned long long g = (m | grid_neighbours(m)) & p;
         if (g == m) return m;
         m = g;
     }
 }
 
-__global__ void __launch_bounds__(256) k_reach_round(unsigned long long *reach, const unsigned long long *__restrict__ passable, ReachDims d, unsigned nbricks,
+__global__ void __launch_bounds__(256) k_reach_round(unsigned long long *reach, const unsigned long long *__restrict__ passable, GridDims d, unsigned nbricks,
                                                      unsigned *changed) {
     const unsigned b = blockIdx.x * 256u + threadIdx.x;
     if (b >= nbricks) return;
     const unsigned long long p = passable[b];
     if (p == 0ull) return;
-    const int bx = (int)(b % (unsigned)d.BX), by = (int)(b / (unsigned)d.BX % (unsigned)d.BY), bz = (int)(b / ((unsigned)d.BX * (unsigned)d.BY));
+    int bx, by, bz;
+    grid_brick_of(d, b, bx, by, bz);
     const unsigned sy = (unsigned)d.BX, sz = (unsigned)d.BX * (unsigned)d.BY;
     const unsigned long long old = reach[b];
-    unsigned long long m = reach_grow(old, p), in = 0ull;
-    if (bx > 0) in |= (reach[b - 1u] & REACH_X3) >> 3;
-    if (bx + 1 < d.BX) in |= (reach[b + 1u] & REACH_X0) << 3;
-    if (by > 0) in |= (reach[b - sy] & REACH_Y3) >> 12;
-    if (by + 1 < d.BY) in |= (reach[b + sy] & REACH_Y0) << 12;
-    if (bz > 0) in |= reach[b - sz] >> 48;
-    if (bz + 1 < d.BZ) in |= reach[b + sz] << 48;
+    unsigned long long m = reach_grow(old, p);
+    // (the neighbours' words as other lanes and workgroups leave them, this round or the last: see the file header)
+    const unsigned long long in = grid_neighbours_across(bx > 0 ? reach[b - 1u] : 0ull, bx + 1 < d.BX ? reach[b + 1u] : 0ull, by > 0 ? reach[b - sy] : 0ull,
+                                                         by + 1 < d.BY ? reach[b + sy] : 0ull, bz > 0 ? reach[b - sz] : 0ull, bz + 1 < d.BZ ? reach[b + sz] : 0ull);
     m = reach_grow(m | (in & p), p);
     if (m != old) { reach[b] = m; *changed = 1u; }
 }
 
-__global__ void __launch_bounds__(256) k_reach_expand(const unsigned long long *__restrict__ words, ReachDims d, unsigned char *__restrict__ out) {
-    const int x = (int)(blockIdx.x * 256u + threadIdx.x), y = (int)blockIdx.y, z = (int)blockIdx.z;
-    if (x >= d.X) return;
-    const unsigned long long w = words[((size_t)(z >> 2) * (size_t)d.BY + (size_t)(y >> 2)) * (size_t)d.BX + (size_t)(x >> 2)];
-    out[((size_t)z * (size_t)d.Y + (size_t)y) * (size_t)d.X + (size_t)x] = (unsigned char)(w >> ((x & 3) + 4 * (y & 3) + 16 * (z & 3)) & 1ull);
+__global__ void __launch_bounds__(GRID_VOXEL_THREADS) k_reach_expand(const unsigned long long *__restrict__ words, GridDims d, unsigned char *__restrict__ out) {
+    int x, y, z;
+    if (!grid_voxel_of_thread(d, x, y, z)) return;
+    out[grid_voxel_of(d, x, y, z)] = (unsigned char)grid_mask_bit(words, d, x, y, z);
 }
 
-static int reach_passable_launch(const void *grid, const unsigned short *field, const ReachDims &d, int r2, void *reach, hipStream_t st) {
-    const unsigned nbricks = (unsigned)reach_bricks(d);
+static int reach_passable_launch(const void *grid, const unsigned short *field, const GridDims &d, int r2, void *reach, hipStream_t st) {
+    const unsigned nbricks = (unsigned)grid_bricks(d);
     hipLaunchKernelGGL(k_reach_passable, dim3((nbricks + 3u) / 4u), dim3(256), 0, st, static_cast<const uint4 *>(grid), field, d, (unsigned)r2, nbricks,
                        reach_passable_of(reach, nbricks));
     XS_CHECK(hipGetLastError());
@@ -250,65 +238,46 @@ static int reach_passable_launch(const void *grid, const unsigned short *field, 
 }
 
 extern "C" int xs_reach_passable(const void *grid, const unsigned short *field_dev, const int *res, int r2, void *reach, void *stream) {
-    ReachDims d;
+    GridDims d;
     if (!grid || !field_dev || !reach) return xs_set_error(hipErrorInvalidValue, "xs_reach_passable: null pointer");
-    if (!reach_dims(res, d)) return xs_set_error(hipErrorInvalidValue, "xs_reach_passable: bad resolution");
+    if (!grid_dims_launchable(res, d)) return xs_set_error(hipErrorInvalidValue, "xs_reach_passable: bad resolution");
     if (r2 < 1 || r2 > 65025) return xs_set_error(hipErrorInvalidValue, "xs_reach_passable: r2 outside 1 .. 255^2");
     return reach_passable_launch(grid, field_dev, d, r2, reach, (hipStream_t)stream);
 }
 
 extern "C" int xs_reach_flood(const void *grid, const unsigned short *field_dev, const int *res, int r2, const int *seeds3xN, int seeds, void *reach,
                               int *rounds_out, void *stream) {
-    ReachDims d;
+    GridDims d;
     if (!grid || !field_dev || !reach || !seeds3xN) return xs_set_error(hipErrorInvalidValue, "xs_reach_flood: null pointer");
-    if (!reach_dims(res, d)) return xs_set_error(hipErrorInvalidValue, "xs_reach_flood: bad resolution");
+    if (!grid_dims_launchable(res, d)) return xs_set_error(hipErrorInvalidValue, "xs_reach_flood: bad resolution");
     if (seeds < 1 || seeds > XS_REACH_MAX_SEEDS) return xs_set_error(hipErrorInvalidValue, "xs_reach_flood: seeds outside 1 .. XS_REACH_MAX_SEEDS");
     if (r2 < 1 || r2 > 65025) return xs_set_error(hipErrorInvalidValue, "xs_reach_flood: r2 outside 1 .. 255^2");
     hipStream_t st = (hipStream_t)stream;
-    const unsigned nbricks = (unsigned)reach_bricks(d);
+    const unsigned nbricks = (unsigned)grid_bricks(d);
     unsigned long long *words = static_cast<unsigned long long *>(reach), *passable = reach_passable_of(reach, nbricks);
     unsigned *changed = reinterpret_cast<unsigned *>(passable + nbricks);
     if (int rc = reach_passable_launch(grid, field_dev, d, r2, reach, st)) return rc;
     XS_CHECK(hipMemsetAsync(words, 0, (size_t)nbricks * 8, st));
-    ReachSeeds s;
-    memset(&s, 0, sizeof(s));
-    s.n = seeds;
-    memcpy(s.v, seeds3xN, (size_t)seeds * 3 * sizeof(int));
-    hipLaunchKernelGGL(k_reach_seed, dim3(1), dim3(64), 0, st, s, d, passable, words);
+    hipLaunchKernelGGL(k_reach_seed, dim3(1), dim3(64), 0, st, grid_seeds(seeds3xN, seeds), d, passable, words);
     XS_CHECK(hipGetLastError());
-    // Rounds in batches, one `changed` word per round; the first round that changed nothing ends the flood (the rounds behind it in its
-    // batch changed nothing either).  Every changing round sets at least one of finitely many bits, so the loop ends.
-    int rounds = 0;
-    for (;;) {
-        unsigned host_changed[REACH_ROUNDS_PER_BATCH];
-        XS_CHECK(hipMemsetAsync(changed, 0, sizeof(host_changed), st));
-        for (int k = 0; k < REACH_ROUNDS_PER_BATCH; ++k) {
-            hipLaunchKernelGGL(k_reach_round, dim3((nbricks + 255u) / 256u), dim3(256), 0, st, words, passable, d, nbricks, changed + k);
-            XS_CHECK(hipGetLastError());
-        }
-        XS_CHECK(hipMemcpyAsync(host_changed, changed, sizeof(host_changed), hipMemcpyDeviceToHost, st));
-        XS_CHECK(hipStreamSynchronize(st));
-        int k = 0;
-        while (k < REACH_ROUNDS_PER_BATCH && host_changed[k]) ++k;
-        if (k < REACH_ROUNDS_PER_BATCH) { rounds += k + 1; break; }
-        rounds += REACH_ROUNDS_PER_BATCH;
-    }
-    if (rounds_out) *rounds_out = rounds;
-    return 0;
+    // every changing round sets at least one of finitely many bits
+    return grid_run_rounds(changed, st, rounds_out, [&](unsigned *changed_k) {
+        hipLaunchKernelGGL(k_reach_round, dim3((nbricks + 255u) / 256u), dim3(256), 0, st, words, passable, d, nbricks, changed_k);
+    });
 }
 
 extern "C" int xs_reach_expand(const void *reach, const int *res, int passable, unsigned char *out_dev, void *stream) {
-    ReachDims d;
+    GridDims d;
     if (!reach || !out_dev) return xs_set_error(hipErrorInvalidValue, "xs_reach_expand: null pointer");
-    if (!reach_dims(res, d)) return xs_set_error(hipErrorInvalidValue, "xs_reach_expand: bad resolution");
-    const unsigned long long *words = static_cast<const unsigned long long *>(reach) + (passable ? reach_bricks(d) : 0);
-    hipLaunchKernelGGL(k_reach_expand, dim3(((unsigned)d.X + 255u) / 256u, (unsigned)d.Y, (unsigned)d.Z), dim3(256), 0, (hipStream_t)stream, words, d, out_dev);
+    if (!grid_dims_launchable(res, d)) return xs_set_error(hipErrorInvalidValue, "xs_reach_expand: bad resolution");
+    const unsigned long long *words = static_cast<const unsigned long long *>(reach) + (passable ? grid_bricks(d) : 0);
+    hipLaunchKernelGGL(k_reach_expand, grid_voxel_blocks(d), dim3(GRID_VOXEL_THREADS), 0, (hipStream_t)stream, words, d, out_dev);
     XS_CHECK(hipGetLastError());
     return 0;
 }
 
 // ---- point query -------------------------------------------------------------------------------------------------------------------------
-__global__ void __launch_bounds__(64) k_reach_query(int n, const float *__restrict__ points, float voxel_size, ReachDims d, const unsigned long long *__restrict__ words,
+__global__ void __launch_bounds__(64) k_reach_query(int n, const float *__restrict__ points, float voxel_size, GridDims d, const unsigned long long *__restrict__ words,
                                                     const uint16_t *__restrict__ field, int snap, unsigned char *__restrict__ reachable,
                                                     uint16_t *__restrict__ clear2, int *__restrict__ voxel) {
     const int i = (int)(blockIdx.x * 64u + threadIdx.x);
@@ -321,13 +290,8 @@ __global__ void __launch_bounds__(64) k_reach_query(int n, const float *__restri
     // (a NaN compares false: outside)
     if (q0 >= 0.f && q0 < (float)d.X && q1 >= 0.f && q1 < (float)d.Y && q2 >= 0.f && q2 < (float)d.Z) {
         const int sx = (int)q0, sy = (int)q1, sz = (int)q2;
-        auto bit_of = [&](int x, int y, int z) {
-            const unsigned long long w = words[((size_t)(z >> 2) * (size_t)d.BY + (size_t)(y >> 2)) * (size_t)d.BX + (size_t)(x >> 2)];
-            return (w >> ((x & 3) + 4 * (y & 3) + 16 * (z & 3)) & 1ull) != 0ull;
-        };
-        auto field_of = [&](int x, int y, int z) { return field[((size_t)z * (size_t)d.Y + (size_t)y) * (size_t)d.X + (size_t)x]; };
-        c = field_of(sx, sy, sz);
-        if (bit_of(sx, sy, sz)) { r = 1; vx = sx; vy = sy; vz = sz; }
+        c = field[grid_voxel_of(d, sx, sy, sz)];
+        if (grid_mask_bit(words, d, sx, sy, sz)) { r = 1; vx = sx; vy = sy; vz = sz; }
         else if (snap > 0) {
             // ascending linear index, strict improvement: among equal distances the lowest index stays
             int best = 0x7fffffff;
@@ -337,10 +301,10 @@ __global__ void __launch_bounds__(64) k_reach_query(int n, const float *__restri
                     if (dyz >= best) continue;
                     for (int x = max(sx - snap, 0); x <= min(sx + snap, d.X - 1); ++x) {
                         const int dd = dyz + (x - sx) * (x - sx);
-                        if (dd < best && bit_of(x, y, z)) { best = dd; vx = x; vy = y; vz = z; }
+                        if (dd < best && grid_mask_bit(words, d, x, y, z)) { best = dd; vx = x; vy = y; vz = z; }
                     }
                 }
-            if (vx >= 0) { r = 1; c = field_of(vx, vy, vz); }
+            if (vx >= 0) { r = 1; c = field[grid_voxel_of(d, vx, vy, vz)]; }
         }
     }
     reachable[i] = r;
@@ -351,12 +315,12 @@ __global__ void __launch_bounds__(64) k_reach_query(int n, const float *__restri
 extern "C" int xs_reach_query(int n, const float *points3xN_dev, const int *res, float voxel_size, const void *reach, int over_passable,
                               const unsigned short *field_dev, int snap, unsigned char *reachable_dev, unsigned short *clear2_dev, int *voxel3xN_dev,
                               void *stream) {
-    ReachDims d;
+    GridDims d;
     if (!points3xN_dev || !reach || !field_dev || !reachable_dev || !clear2_dev) return xs_set_error(hipErrorInvalidValue, "xs_reach_query: null pointer");
-    if (!reach_dims(res, d)) return xs_set_error(hipErrorInvalidValue, "xs_reach_query: bad resolution");
+    if (!grid_dims_launchable(res, d)) return xs_set_error(hipErrorInvalidValue, "xs_reach_query: bad resolution");
     if (n < 1 || !(voxel_size > 0.f)) return xs_set_error(hipErrorInvalidValue, "xs_reach_query: n < 1 or a voxel size that is not positive");
     if (snap < 0 || snap > XS_REACH_MAX_SNAP) return xs_set_error(hipErrorInvalidValue, "xs_reach_query: snap outside 0 .. XS_REACH_MAX_SNAP");
-    const unsigned long long *words = static_cast<const unsigned long long *>(reach) + (over_passable ? reach_bricks(d) : 0);
+    const unsigned long long *words = static_cast<const unsigned long long *>(reach) + (over_passable ? grid_bricks(d) : 0);
     hipLaunchKernelGGL(k_reach_query, dim3(((unsigned)n + 63u) / 64u), dim3(64), 0, (hipStream_t)stream, n, points3xN_dev, voxel_size, d, words, field_dev, snap,
                        reachable_dev, clear2_dev, voxel3xN_dev);
     XS_CHECK(hipGetLastError());

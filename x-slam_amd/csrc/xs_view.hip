@@ -6,7 +6,8 @@
 // one 16-byte word per brick of 4 x 4 x 4 voxels, brick (bx, by, bz) at word (bz * BY + by) * BX + bx, voxel (lx, ly, lz) of it at bit
 // 2 (lx + 4 ly + 16 lz): dword lz holds the brick's plane lz.  Bricks that overhang the volume are padded with zeros, which no ray reads
 // (a sample is tested against the resolution before its brick is fetched).  Behind the bricks the buffer holds the staging area of one
-// launch's poses (xs_score_views copies them there), so one launch at a time per grid.
+// launch's poses (xs_score_views copies them there), so one launch at a time per grid.  The layout's arithmetic is xs_grid.h's, shared with
+// the kernels that read the grid (xs_reach.hip, xs_frontier.hip).
 //   k_view_grid_build    thread = brick: 16 rows of four voxels, each a 16-byte load of the values and one of the weights where the
 //                        pitch and the base are 16-byte aligned and the brick lies inside X (the exact per-voxel path otherwise), one
 //                        16-byte store.  The volume's 8 bytes per voxel are read once.
@@ -21,36 +22,28 @@
 #include <type_traits>
 #include <vector>
 #include "xs_device.h"
+#include "xs_grid.h"
 #include "../../include/xslam_amd.h"
 
 static_assert(XS_VIEW_MAX_POSES == 4096, "the header's bound");
-enum { VIEW_POSE_FLOATS = 12, VIEW_MAX_SAMPLES = 4096, VIEW_UNKNOWN = 0, VIEW_FREE = 1, VIEW_OCCUPIED = 2 };
-
-struct ViewDims { int X, Y, Z, BX, BY, BZ; };
-// false for a resolution the grid cannot index (a non-positive axis, or 2^31 bricks and more)
-static bool view_dims(const int *res, ViewDims &d) {
-    if (!res || res[0] < 1 || res[1] < 1 || res[2] < 1) return false;
-    d.X = res[0]; d.Y = res[1]; d.Z = res[2];
-    d.BX = (d.X + 3) / 4; d.BY = (d.Y + 3) / 4; d.BZ = (d.Z + 3) / 4;
-    return (unsigned long long)d.BX * (unsigned long long)d.BY * (unsigned long long)d.BZ < (1ull << 31);
-}
-static size_t view_bricks(const ViewDims &d) { return (size_t)d.BX * (size_t)d.BY * (size_t)d.BZ; }
+enum { VIEW_POSE_FLOATS = 12, VIEW_MAX_SAMPLES = 4096 };
 
 extern "C" size_t xs_view_grid_bytes(const int *res) {
-    ViewDims d;
-    if (!view_dims(res, d)) return 0;
-    return view_bricks(d) * 16 + (size_t)XS_VIEW_MAX_POSES * VIEW_POSE_FLOATS * sizeof(float);
+    GridDims d;
+    if (!grid_dims(res, d)) return 0;
+    return grid_bricks(d) * 16 + (size_t)XS_VIEW_MAX_POSES * VIEW_POSE_FLOATS * sizeof(float);
 }
 
 __device__ __forceinline__ unsigned view_state(float value, int weight, int min_weight) {
-    return weight < min_weight ? (unsigned)VIEW_UNKNOWN : (value < 0.f ? (unsigned)VIEW_OCCUPIED : (unsigned)VIEW_FREE);
+    return weight < min_weight ? (unsigned)GRID_UNKNOWN : (value < 0.f ? (unsigned)GRID_OCCUPIED : (unsigned)GRID_FREE);
 }
 
-__global__ void __launch_bounds__(256) k_view_grid_build(const float *__restrict__ value, const int *__restrict__ weight, size_t vol_step, ViewDims d,
+__global__ void __launch_bounds__(256) k_view_grid_build(const float *__restrict__ value, const int *__restrict__ weight, size_t vol_step, GridDims d,
                                                          int min_weight, int vector_rows, unsigned nbricks, uint4 *__restrict__ grid) {
     const unsigned b = blockIdx.x * 256u + threadIdx.x;
     if (b >= nbricks) return;
-    const int bx = (int)(b % (unsigned)d.BX), by = (int)(b / (unsigned)d.BX % (unsigned)d.BY), bz = (int)(b / ((unsigned)d.BX * (unsigned)d.BY));
+    int bx, by, bz;
+    grid_brick_of(d, b, bx, by, bz);
     const int x0 = 4 * bx;
     const bool whole_row = vector_rows && x0 + 4 <= d.X;   // (the row's first voxel is then 16-byte aligned: base and pitch are)
     unsigned w[4];
@@ -82,28 +75,20 @@ __global__ void __launch_bounds__(256) k_view_grid_build(const float *__restrict
     grid[b] = make_uint4(w[0], w[1], w[2], w[3]);
 }
 
-// the state of voxel (x, y, z) of the brick word (x, y, z: the voxel's own coordinates, their low two bits count)
-__device__ __forceinline__ unsigned view_state_of(const uint4 &word, int x, int y, int z) {
-    const int lz = z & 3;
-    const unsigned plane = lz == 0 ? word.x : (lz == 1 ? word.y : (lz == 2 ? word.z : word.w));
-    return plane >> (2 * ((x & 3) + 4 * (y & 3))) & 3u;
-}
-
-__global__ void __launch_bounds__(256) k_view_grid_expand(const uint4 *__restrict__ grid, ViewDims d, unsigned char *__restrict__ states) {
-    const int x = (int)(blockIdx.x * 256u + threadIdx.x), y = (int)blockIdx.y, z = (int)blockIdx.z;
-    if (x >= d.X) return;
-    const uint4 word = grid[((size_t)(z >> 2) * (size_t)d.BY + (size_t)(y >> 2)) * (size_t)d.BX + (size_t)(x >> 2)];
-    states[((size_t)z * (size_t)d.Y + (size_t)y) * (size_t)d.X + (size_t)x] = (unsigned char)view_state_of(word, x, y, z);
+__global__ void __launch_bounds__(GRID_VOXEL_THREADS) k_view_grid_expand(const uint4 *__restrict__ grid, GridDims d, unsigned char *__restrict__ states) {
+    int x, y, z;
+    if (!grid_voxel_of_thread(d, x, y, z)) return;
+    states[grid_voxel_of(d, x, y, z)] = (unsigned char)grid_state_of(grid[grid_word_of(d, x, y, z)], x, y, z);
 }
 
 extern "C" int xs_view_grid_build(const float *value, const int *weight, size_t vol_step, const int *res, int min_weight, void *grid, void *stream) {
-    ViewDims d;
+    GridDims d;
     if (!value || !weight || !grid) return xs_set_error(hipErrorInvalidValue, "xs_view_grid_build: null pointer");
-    if (!view_dims(res, d)) return xs_set_error(hipErrorInvalidValue, "xs_view_grid_build: bad resolution");
+    if (!grid_dims(res, d)) return xs_set_error(hipErrorInvalidValue, "xs_view_grid_build: bad resolution");
     if (vol_step < (size_t)d.X * sizeof(float) || vol_step % sizeof(float) != 0) return xs_set_error(hipErrorInvalidValue, "xs_view_grid_build: bad pitch");
     if (reinterpret_cast<uintptr_t>(grid) % 16 != 0) return xs_set_error(hipErrorInvalidValue, "xs_view_grid_build: the grid must be 16-byte aligned");
     const int vector_rows = vol_step % 16 == 0 && reinterpret_cast<uintptr_t>(value) % 16 == 0 && reinterpret_cast<uintptr_t>(weight) % 16 == 0;
-    const unsigned nbricks = (unsigned)view_bricks(d);
+    const unsigned nbricks = (unsigned)grid_bricks(d);
     hipLaunchKernelGGL(k_view_grid_build, dim3((nbricks + 255u) / 256u), dim3(256), 0, (hipStream_t)stream, value, weight, vol_step, d,
                        min_weight < 1 ? 1 : min_weight, vector_rows, nbricks, static_cast<uint4 *>(grid));
     XS_CHECK(hipGetLastError());
@@ -111,11 +96,10 @@ extern "C" int xs_view_grid_build(const float *value, const int *weight, size_t 
 }
 
 extern "C" int xs_view_grid_expand(const void *grid, const int *res, unsigned char *states_dev, void *stream) {
-    ViewDims d;
+    GridDims d;
     if (!grid || !states_dev) return xs_set_error(hipErrorInvalidValue, "xs_view_grid_expand: null pointer");
-    if (!view_dims(res, d) || d.Y > 65535 || d.Z > 65535) return xs_set_error(hipErrorInvalidValue, "xs_view_grid_expand: bad resolution");
-    hipLaunchKernelGGL(k_view_grid_expand, dim3(((unsigned)d.X + 255u) / 256u, (unsigned)d.Y, (unsigned)d.Z), dim3(256), 0, (hipStream_t)stream,
-                       static_cast<const uint4 *>(grid), d, states_dev);
+    if (!grid_dims_launchable(res, d)) return xs_set_error(hipErrorInvalidValue, "xs_view_grid_expand: bad resolution");
+    hipLaunchKernelGGL(k_view_grid_expand, grid_voxel_blocks(d), dim3(GRID_VOXEL_THREADS), 0, (hipStream_t)stream, static_cast<const uint4 *>(grid), d, states_dev);
     XS_CHECK(hipGetLastError());
     return 0;
 }
@@ -127,7 +111,7 @@ struct ViewArgs {
     const uint4 *grid;
     const float *poses;                          // [P][12]: R row-major, then t (camera to volume), in the grid buffer's staging area
     unsigned *out;                               // [P][4]: unknown, free, hits, frontier
-    ViewDims d;
+    GridDims d;
     int rays_x, rays_y, tiles_x, samples;
     float sx, sy;                                // float(cols) / float(rays_x), float(rows) / float(rays_y)
     float fx, fy, cx, cy;
@@ -168,17 +152,17 @@ __global__ void __launch_bounds__(64) k_score_views(const ViewArgs a) {
             const float t = a.t_near + (float)k * a.step;
             const float p0 = t0 + t * d0, p1 = t1 + t * d1, p2 = t2 + t * d2;
             const int x = __float2int_rd(p0 / a.voxel_size), y = __float2int_rd(p1 / a.voxel_size), z = __float2int_rd(p2 / a.voxel_size);
-            if ((unsigned)x >= (unsigned)a.d.X || (unsigned)y >= (unsigned)a.d.Y || (unsigned)z >= (unsigned)a.d.Z) {
+            if (!grid_inside(a.d, x, y, z)) {
                 // outside: the sample counts nothing.  Every coordinate is monotone in k, so a ray that has left the volume stays outside.
                 if (was_inside) break;
                 continue;
             }
             was_inside = true;
-            const int b = ((z >> 2) * a.d.BY + (y >> 2)) * a.d.BX + (x >> 2);
+            const int b = grid_word_of<int>(a.d, x, y, z);
             if (b != cur) { word = grid[b]; cur = b; }
-            const unsigned s = view_state_of(word, x, y, z);
-            if (s == VIEW_OCCUPIED) { hit = true; break; }
-            if (s == VIEW_FREE) { ++n_free; prev_free = true; }
+            const unsigned s = grid_state_of(word, x, y, z);
+            if (s == GRID_OCCUPIED) { hit = true; break; }
+            if (s == GRID_FREE) { ++n_free; prev_free = true; }
             else { ++n_unknown; n_frontier += prev_free ? 1u : 0u; prev_free = false; }
         }
     }
@@ -200,7 +184,7 @@ extern "C" int xs_score_views(int poses, const float *Rc2v9xP, const float *tc2v
     if (opts && opts->struct_bytes != sizeof(xs_view_opts)) return xs_set_error(hipErrorInvalidValue, "xs_score_views: opts->struct_bytes is not sizeof(xs_view_opts)");
     ViewArgs a;
     memset(&a, 0, sizeof(a));
-    if (!view_dims(res, a.d)) return xs_set_error(hipErrorInvalidValue, "xs_score_views: bad resolution");
+    if (!grid_dims(res, a.d)) return xs_set_error(hipErrorInvalidValue, "xs_score_views: bad resolution");
     if (!(voxel_size > 0.f) || rows < 1 || cols < 1) return xs_set_error(hipErrorInvalidValue, "xs_score_views: bad voxel size or image size");
     xs_view_opts o;
     memset(&o, 0, sizeof(o));
@@ -219,7 +203,7 @@ extern "C" int xs_score_views(int poses, const float *Rc2v9xP, const float *tc2v
         return xs_set_error(hipErrorInvalidValue, "xs_score_views: rays x samples does not fit a 32-bit count");
     a.grid = static_cast<const uint4 *>(grid);
     // the staging area behind the bricks (the one part of the grid buffer this call writes)
-    float *staging = reinterpret_cast<float *>(static_cast<char *>(const_cast<void *>(grid)) + view_bricks(a.d) * 16);
+    float *staging = reinterpret_cast<float *>(static_cast<char *>(const_cast<void *>(grid)) + grid_bricks(a.d) * 16);
     a.poses = staging;
     a.out = out4xP_dev;
     a.rays_x = o.rays_x; a.rays_y = o.rays_y; a.samples = samples;

@@ -44,14 +44,16 @@ int KinectFusionReconstruction::ScoreViews(const Matrix4cf *camera2volume, int P
     return 1;
 }
 
+// What a Next... call returns when the calls it is made of did not return 1.  Its own -1 is "no pose qualifies", so their -1 (bad arguments)
+// becomes -3 and their 0 (no volume) -1; -2 (sharded) stays.
+static int next_view_error(int rc) { return rc == -1 ? -3 : (rc == 0 ? -1 : rc); }
+
 int KinectFusionReconstruction::NextBestView(const Matrix4cf *camera2volume, int P, const xs_view_opts *opts, int min_weight, unsigned min_hits,
                                              unsigned *out4xP) {
     std::vector<unsigned> own;
     if (!out4xP && P > 0) { own.resize((size_t)P * 4); out4xP = own.data(); }
     const int rc = ScoreViews(camera2volume, P, opts, min_weight, out4xP);
-    if (rc == -1) return -3;   // (-1 is "no pose qualifies" here)
-    if (rc < 0) return rc;
-    if (rc == 0) return -1;
+    if (rc <= 0) return next_view_error(rc);
     return next_best_view(out4xP, P, min_hits);
 }
 
@@ -160,9 +162,7 @@ int KinectFusionReconstruction::NextReachableView(const Matrix4cf *camera2volume
     if (!reachable && P > 0) { own_flags.resize((size_t)P); reachable = own_flags.data(); }
     int rc = Reachable(nullptr, radius_m, snap_vox, unknown_blocks, min_weight, P, camera2volume, reachable, clear2.data());
     if (rc == 1) rc = ScoreViews(camera2volume, P, opts, min_weight, out4xP);
-    if (rc == -1) return -3;   // (-1 is "no pose qualifies" here)
-    if (rc < 0) return rc;
-    if (rc == 0) return -1;
+    if (rc <= 0) return next_view_error(rc);
     return next_reachable_view(out4xP, reachable, P, min_hits);
 }
 
@@ -261,9 +261,7 @@ int KinectFusionReconstruction::NextViewByTravel(const Matrix4cf *camera2volume,
     if (!travel3_out && P > 0) { own_travel.resize((size_t)P); travel3_out = own_travel.data(); }
     int rc = Travel(nullptr, radius_m, snap_vox, unknown_blocks, min_weight, max_travel_m, P, camera2volume, flags.data(), clear2.data(), travel3_out);
     if (rc == 1) rc = ScoreViews(camera2volume, P, opts, min_weight, out4xP);
-    if (rc == -1) return -3;   // (-1 is "no pose qualifies" here)
-    if (rc < 0) return rc;
-    if (rc == 0) return -1;
+    if (rc <= 0) return next_view_error(rc);
     return next_view_by_travel(out4xP, travel3_out, P, min_hits, travel_bias(bias_m, voxel_size));
 }
 
