@@ -1,5 +1,6 @@
 #!/bin/bash
-# GPU box, repository root: with the sign map, the march + crossing as ONE launch (default) against two (XS_RAY_MAP_TWO_KERNELS=1); no profiler
+# GPU box, repository root: with the sign map, the march + crossing as ONE launch (default) against two (XS_RAY_MAP_TWO_KERNELS=1); no profiler.
+# Library built with EXTRAFLAGS=-DXS_EXPERIMENTS: the switch and the k_raycast<2, *, *, true> instances it launches exist in such a build only.
 cd "$(dirname "$0")/../.."
 for mode in one two one two one two; do
   if [ $mode = two ]; then export XS_RAY_MAP_TWO_KERNELS=1; else unset XS_RAY_MAP_TWO_KERNELS; fi

@@ -208,6 +208,25 @@ def test_slab_marches_composed(g, wid, signmap):
     assert rc.assert_same_maps(bv.image(), bn.image(), cv, cn, rows, (wid, "pack + scatter")) == want_hits == int(hits_b.item())
 
 
+def test_sign_map_marches_without_the_short_division(g):
+    """Everything above runs with voxel_size prepared (xs_const_div_prepare), i.e. the march instances that take floor(p / voxel_size)
+    by the short division.  With it switched off the launchers pick the instances that divide — for the sign-map forms
+    k_raycast<0, true, false, true> and <4, true, false, true>, which nothing else launches: windows A (ragged on both axes, one idle
+    workgroup) and D (all workgroups busy, ragged lanes) through the fused sign-map launch and through three sign-map slab marches,
+    composed, against the same crops of the full frame and with the same guards as above."""
+    capi, vs = g["capi"], g["s"]["vs"]
+    assert capi.const_div_state(vs) == 3
+    was = capi.const_div_enable(0)
+    try:
+        assert capi.const_div_state(vs) == 0
+        for wid in ("A", "D"):
+            cast(g, wid, workspace=True, signmap=True)
+            test_slab_marches_composed(g, wid, True)
+    finally:
+        capi.const_div_enable(was)
+    assert capi.const_div_state(vs) == 3
+
+
 @pytest.mark.parametrize("rows,cols", rc.COMPOSE_SHAPES)
 def test_composite_kernels_on_crafted_keys(g, rows, cols):
     """mask, finish, pack and scatter against their numpy statements (raycast_cases.model_*), bit for bit, on keys of every kind and

@@ -798,15 +798,6 @@ __global__ void __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(1, 1))
     }
 }
 
-static void ld_mat(const float *p, MatS33 &m) {
-    for (int r = 0; r < 3; ++r) {
-        m.data[r].x = cfloat(p[r * 6 + 0], p[r * 6 + 1]);
-        m.data[r].y = cfloat(p[r * 6 + 2], p[r * 6 + 3]);
-        m.data[r].z = cfloat(p[r * 6 + 4], p[r * 6 + 5]);
-    }
-}
-static void ld_vec(const float *p, cfloat3 &v) { v.x = cfloat(p[0], p[1]); v.y = cfloat(p[2], p[3]); v.z = cfloat(p[4], p[5]); }
-
 enum { XS_ICP_MAX_BLOCKS = 768 };  // records a launch may write = eight-wave workgroups resident at once (three per CU: 51 KB of LDS, 79 VGPRs)
 
 extern "C" size_t xs_icp_workspace_bytes(void) { return (size_t)XS_ICP_MAX_BLOCKS * NP * sizeof(double) + 256; }
@@ -865,9 +856,9 @@ static int icp_launch(const float *Rcurr18, const float *tcurr6, const float *vm
     // without a tile, and row y0 == rows lies one row past the maps — the same empty launch over the last row instead
     if (y0 == y1 && y0 == rows && rows > 0) y0 = y1 = rows - 1;
     IcpArgs a;
-    if (Rcurr18) { ld_mat(Rcurr18, a.Rcurr); ld_vec(tcurr6, a.tcurr); }
+    if (Rcurr18) { load_mat(Rcurr18, a.Rcurr); load_vec(tcurr6, a.tcurr); }
     else { memset(&a.Rcurr, 0, sizeof(a.Rcurr)); memset(&a.tcurr, 0, sizeof(a.tcurr)); }
-    ld_mat(Rprev_inv18, a.Rprev_inv); ld_vec(tprev6, a.tprev);
+    load_mat(Rprev_inv18, a.Rprev_inv); load_vec(tprev6, a.tprev);
     a.vmap_curr = (const cfloat *)vmap_curr; a.nmap_curr = (const cfloat *)nmap_curr;
     a.vmap_g_prev = (const cfloat *)vmap_g_prev; a.nmap_g_prev = (const cfloat *)nmap_g_prev;
     a.mstep = map_step; a.intr = Intr{intr4[0], intr4[1], intr4[2], intr4[3]};
