@@ -639,6 +639,37 @@ int xs_extract_points(const float *value, size_t vol_step, const int *res, float
 int xs_extract_normals(const float *value, size_t vol_step, const int *res, float voxel_size, int zs0, int zs1, const float *points_dev,
                        size_t n, float *normals_dev, void *stream);
 
+/* ---- merging a second volume into the volume (xs_merge.hip) ----------------------------------------------------
+ * No counterpart in the reference.  Both volumes use the layout of every call here: row (Y * z + y), x contiguous, one pitch (`step`,
+ * `src_step`, bytes) shared by a volume's three arrays.  The destination pointers are at plane 0; only planes [z0, z1) are written.
+ * *written_dev (optional, device) is INCREMENTED by the number of destination voxels written.  `workspace`:
+ * xs_tsdf_merge_workspace_bytes(res, src_res) bytes of device memory (may be NULL with XS_MERGE_NO_CULL).  No synchronisation.
+ *
+ * Destination voxel (x, y, z); m = xform12, a 3 x 3 matrix in row-major order followed by 3 offsets, maps destination voxel indices to
+ * continuous source voxel indices.  Every operation is float32, in the order written:
+ *   1. g_a = ((m[3a] * float(x) + m[3a + 1] * float(y)) + m[3a + 2] * float(z)) + m[9 + a], a = 0, 1, 2.
+ *   2. The voxel is skipped unless 0 <= g_a <= float(S_a - 1) on every axis (S: the source resolution; a NaN fails).  b_a = floor(g_a),
+ *      f_a = g_a - float(b_a); the upper corner on axis a is NEEDED only when f_a > 0.
+ *   3. The needed corners are b + d with d_a = 1 only on axes with f_a > 0: 1, 2, 4 or 8 of them.  No other corner is read (at
+ *      g_a = S_a - 1 the upper corner lies outside the allocation).  ws = the smallest weight of the needed corners; the voxel is skipped
+ *      unless ws >= min_weight; then ws = min(ws, max_weight).
+ *   4. value and grad, each: interpolated along x, then y, then z, a stage being lo * (1.0f - f_a) + hi * f_a, and `lo` itself, with no
+ *      arithmetic, on an axis with f_a == 0 (-0 stays -0): the result is s.
+ *   5. wp = the destination's weight.  wp == 0: new = s.  Otherwise new = (prev * float(wp) + s * float(ws)) / float(wp + ws), for value and
+ *      grad each.  weight = min(wp + ws, max_weight).  The voxel counts as written.
+ * So an identity map into an empty volume is a copy bit for bit, a shift by whole voxels is a slice and an axis permutation is exact.
+ * The cull (a tile of destination voxels whose source index box misses the source, or touches only bricks of 4 x 4 x 4 source voxels with no
+ * weight >= min_weight, is left before any load) changes no output bit; XS_MERGE_NO_CULL switches it off: every destination voxel takes the
+ * per-voxel path.  No output depends on scheduling.
+ * hipErrorInvalidValue, with nothing launched: a null array, resolution or xform12 (or workspace, unless XS_MERGE_NO_CULL); an axis outside
+ * 1 .. 262140; a pitch that is no multiple of 4 or shorter than a row; min_weight < 1; max_weight outside [1, 1 << 24]; an entry of xform12
+ * that is not finite; an empty or reversed plane range or one outside [0, res[2]]; a source array equal to its destination counterpart. */
+#define XS_MERGE_NO_CULL 1u
+size_t xs_tsdf_merge_workspace_bytes(const int *dst_res, const int *src_res);
+int xs_tsdf_merge(float *value, int *weight, float *grad, size_t step, const int *res, int z0, int z1, const float *src_value,
+                  const int *src_weight, const float *src_grad, size_t src_step, const int *src_res, const float *xform12, int min_weight,
+                  int max_weight, unsigned flags, unsigned long long *written_dev, void *workspace, void *stream);
+
 /* ---- surface mesh (export; marching cubes with complex-step vertex derivatives) -------------------------------------------------------
  * No working counterpart in the reference (its extractMesh, ExtractPointCloud.cu:364-715, is never called).
  * Cube (x, y, z), x < X-1, y < Y-1, z in [z0, z1), is live when all 8 corners have weight >= min_weight and value < 0.99 and its corners

@@ -287,6 +287,34 @@ int xs_kf_save_checkpoint(void *kf, const char *path);
 int xs_kf_load_checkpoint(void *kf, const char *path);
 int xs_kf_save_tsdf_volume(void *kf, const char *path);
 
+/* ---- Merging a second map into the volume (xs_tsdf_merge in xslam_amd.h: the per-voxel contract) ------------
+ * T16: a real 4 x 4, row-major, taking a point of THIS map's volume frame (metres) to the OTHER map's volume frame, p_other = T p_this.
+ * The other map is resampled into this map's voxel grid and averaged into it by weight, with this instance's max_integration_weight as the
+ * cap; its resolution and voxel size may differ.  The device is drained first; afterwards the sign map, the cached planning and
+ * relocalisation maps and the previous frame's model maps (at the current pose) follow the merged volume, as after xs_kf_load_checkpoint.
+ * Poses, the frame number and the trajectory record are untouched.  *written (optional): the voxels written.
+ * merge_volume: the source as device pointers at plane 0 of its three arrays, one pitch.  merge_map: the source is another instance of this
+ * process (it is only read).  merge_checkpoint: the source is an XSTSDF2 file (xs_kf_save_checkpoint) of a whole volume, validated in
+ * full before anything is touched (magic, exact length, shard_count 1, truncation distance), uploaded to a temporary device volume.
+ * Return 1 when the merge ran, 0 without a volume, -1 on bad arguments with the state unchanged (a null or aliasing source, min_weight < 1,
+ * an entry of T that is not finite, a bad file, a truncation distance different from this map's: stored values are normalised by it, so it
+ * is refused, not rescaled), -2 in shard mode, doing nothing. */
+int xs_kf_merge_volume(void *kf, const float *src_value, const int *src_weight, const float *src_grad, size_t src_step, const int *src_res,
+                       float src_voxel_size, float src_tranc_dist, const double *T16, int min_weight, unsigned long long *written);
+int xs_kf_merge_map(void *kf, void *other_kf, const double *T16, int min_weight, unsigned long long *written);
+int xs_kf_merge_checkpoint(void *kf, const char *path, const double *T16, int min_weight, unsigned long long *written);
+/* The host's side of a merge (x-slam_amd/host/merge_host.hpp).  CPU only.
+ * merge_affine: xform12 of xs_tsdf_merge from T16 and the two voxel sizes, in float64 with one rounding to float32 at the end: the matrix
+ * block is R vs_dst / vs_src, the offset (R (0.5 vs_dst (1, 1, 1)) + t) / vs_src - 0.5.  0, or -1 (nothing written) for an input that is
+ * not finite or a voxel size that is not positive.
+ * map_transform: T16 = c2v_other c2v_this^-1 for two real, rigid camera-to-volume poses (4 x 4, row-major) of the same camera frame: the
+ * frame posed in this map, and in the other map by xs_kf_relocalize_global there, gives the T of a merge.  Returns 0.
+ * merge_tile_box: the kernel's cull.  box6 = {lo x, y, z, hi x, y, z} (inclusive) contains every source voxel that a destination voxel of
+ * the tile lo3 .. hi3 (inclusive) reads under xform12; returns 1, or 0 when no voxel of the tile falls inside the source. */
+int xs_host_merge_affine(const double *T16, double dst_voxel_size, double src_voxel_size, float *out12);
+int xs_host_map_transform(const double *c2v_this16, const double *c2v_other16, double *T16);
+int xs_host_merge_tile_box(const float *xform12, const int *lo3, const int *hi3, const int *src_res, int *box6);
+
 /* ---- The reference's own call shape (x-slam_amd/host/reference_shape.hpp) ---------------------------------------------------------
  * The per-frame sequence of Experiments/test_xkinect_fusion/main.cpp:46-60 + KinectFusionReconstruction.cpp:147-332 over nothing but the
  * reference-signature launchers (bilateralFilter, pyrDown, createVMap / createNMap, estimateCombined per iteration, integrateTsdfVolume,

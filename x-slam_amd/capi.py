@@ -166,6 +166,8 @@ _SIGS = {
     "xs_extract_workspace_bytes": (_sz, [_i32p]),
     "xs_extract_points": (C.c_int, [_vp, _sz, _i32p, C.c_float, C.c_int, C.c_int, C.c_int, _vp, _sz, _vp, C.POINTER(_sz), C.POINTER(_sz), _vp]),
     "xs_extract_normals": (C.c_int, [_vp, _sz, _i32p, C.c_float, C.c_int, C.c_int, _vp, _sz, _vp, _vp]),
+    "xs_tsdf_merge_workspace_bytes": (_sz, [_i32p, _i32p]),
+    "xs_tsdf_merge": (C.c_int, [_vp, _vp, _vp, _sz, _i32p, C.c_int, C.c_int, _vp, _vp, _vp, _sz, _i32p, _f32p, C.c_int, C.c_int, C.c_uint, _vp, _vp, _vp]),
     "xs_mesh_workspace_bytes": (_sz, [_i32p, C.POINTER(MeshOpts)]),
     "xs_extract_mesh": (C.c_int, [_vp, _vp, _vp, _sz, _i32p, C.c_float, C.POINTER(MeshOpts), _vp, _vp, _vp, _vp, _sz, _vp, _sz, _vp,
                                   C.POINTER(_sz), C.POINTER(_sz), _vp]),
@@ -829,6 +831,40 @@ def extract_normals(value, vol_step, res, voxel_size, points, n, normals, zs0=0,
     zs1 = int(r[2]) if zs1 is None else zs1
     check(_lib.xs_extract_normals(_ptr(value), vol_step, r.ctypes.data_as(_i32p), voxel_size, zs0, zs1, _ptr(points), n, _ptr(normals),
                                   _stream(stream)))
+
+
+MERGE_NO_CULL = 1   # XS_MERGE_NO_CULL
+
+
+def tsdf_merge_workspace_bytes(dst_res, src_res):
+    """xs_tsdf_merge_workspace_bytes (host only): a header and one bit per brick of 4 x 4 x 4 source voxels; 0 for an unusable resolution."""
+    return int(_lib.xs_tsdf_merge_workspace_bytes(_res3(dst_res).ctypes.data_as(_i32p), _res3(src_res).ctypes.data_as(_i32p)))
+
+
+def tsdf_merge(value, weight, grad, step, res, src_value, src_weight, src_grad, src_step, src_res, xform12, min_weight=1, max_weight=100, flags=0,
+               z0=0, z1=None, written=None, workspace=None, stream=None):
+    """xs_tsdf_merge: resamples the source volume into planes [z0, z1) of the destination's voxel grid under xform12 (destination voxel
+    indices -> continuous source voxel indices, 3 x 3 row-major then 3 offsets) and averages the two by weight.  Arrays are device tensors
+    or addresses of plane 0; `written` (uint64 / int64 device word, optional) is incremented by the number of voxels written; `workspace`:
+    tsdf_merge_workspace_bytes(res, src_res) bytes (None only with MERGE_NO_CULL).  No synchronisation."""
+    r, s = _ia(res, 3), _ia(src_res, 3)
+    m = _fa(xform12, 12)
+    z1 = int(r[2]) if z1 is None else z1
+    check(_lib.xs_tsdf_merge(_ptr(value), _ptr(weight), _ptr(grad), step, r.ctypes.data_as(_i32p), z0, z1, _ptr(src_value), _ptr(src_weight), _ptr(src_grad),
+                             src_step, s.ctypes.data_as(_i32p), m.ctypes.data_as(_f32p), int(min_weight), int(max_weight), int(flags), _ptr(written),
+                             _ptr(workspace), _stream(stream)))
+
+
+def merge_affine(T, dst_voxel_size, src_voxel_size):
+    """xs_host_merge_affine of libxslam_host.so (CPU): xform12 of tsdf_merge from a real 4 x 4 transform and the two voxel sizes."""
+    from . import pipeline
+    return pipeline.merge_affine(T, dst_voxel_size, src_voxel_size)
+
+
+def map_transform(c2v_this, c2v_other):
+    """xs_host_map_transform of libxslam_host.so (CPU): c2v_other c2v_this^-1 from the real parts."""
+    from . import pipeline
+    return pipeline.map_transform(c2v_this, c2v_other)
 
 
 MESH_OVER_CAPACITY = -2   # XS_MESH_OVER_CAPACITY

@@ -321,6 +321,21 @@ public:
     void saveTSDFVolume(const std::string &tsdf_filename);
     void saveCheckpoint(const std::string &filename);
     bool loadCheckpoint(const std::string &filename);
+    // Merging a second map into the volume (xs_tsdf_merge in include/xslam_amd.h: the contract).  The source is a
+    // whole volume in device memory in the project's layout (three arrays at plane 0, one pitch) whose resolution and voxel size may differ
+    // from this map's; T16 is a real 4 x 4, row-major, taking a point of THIS map's volume frame (metres) to the source's volume frame.
+    // The device is drained, xform12 built by merge_host.hpp's merge_affine, the kernel run with max_integration_weight, and everything
+    // derived from the volume follows as after loadCheckpoint: volume_generation, the sign map, the cached planning and relocalisation
+    // maps, the previous frame's model maps at the current pose.  Poses, frame_id and the trajectory record are untouched.  *written
+    // (optional): the voxels written.  Returns 1 when it ran, 0 without a volume, -1 on bad arguments (a null or aliasing source, a
+    // resolution or voxel size that is not positive, an entry of T that is not finite, min_weight < 1, a truncation distance different
+    // from this map's: stored values are normalised by it, so it is refused, not rescaled), -2 in shard mode, doing nothing.
+    int MergeVolume(const float *src_value, const int *src_weight, const float *src_grad, size_t src_step, const int *src_res, float src_voxel_size,
+                    float src_tranc_dist, const double *T16, int min_weight, unsigned long long *written);
+    // The same from an XSTSDF2 file (saveCheckpoint), validated in full before anything is touched: magic, exact length, a whole-volume file
+    // with shard_count 1, the truncation distance.  The file's volume goes to a temporary device volume that is freed after the merge.
+    // Any mismatch: -1 with the state unchanged.
+    int MergeCheckpoint(const std::string &filename, const double *T16, int min_weight, unsigned long long *written);
 
     // counters of the last frame (synchronise the stream)
     long long lastUpdatedVoxels();

@@ -1,6 +1,8 @@
 // kf_export.cpp — what leaves the orchestrator: point cloud and mesh with their PLY writers, the last frame's counters, the raw volume
-// and the checkpoint.  None of it runs during tracking.
+// and the checkpoint; and what enters it as a whole map: a second volume or checkpoint merged into this one.  None of it runs during tracking.
 #include "kf_internal.hpp"
+#include "merge_host.hpp"
+#include <cmath>
 #include <cstdio>
 #include <fstream>
 
@@ -212,4 +214,83 @@ bool KinectFusionReconstruction::loadCheckpoint(const std::string &filename) {
     ModelMapPyramid();
     synchronize();
     return true;
+}
+
+// ---- merging a second map ----------------------------------------------------------------------------------
+int KinectFusionReconstruction::MergeVolume(const float *src_value, const int *src_weight, const float *src_grad, size_t src_step, const int *src_res,
+                                            float src_voxel_size, float src_tranc_dist, const double *T16, int min_weight, unsigned long long *written) {
+    if (shard_count > 1) return -2;   // the source's image in a rank's z-slab needs the whole source on every rank: not built
+    if (!tsdf_volume_d_ptr) return 0;
+    if (!src_value || !src_weight || !src_grad || !src_res || !T16 || min_weight < 1) return -1;
+    for (int k = 0; k < 3; ++k)
+        if (src_res[k] < 1) return -1;
+    if (!(src_voxel_size > 0.f) || !std::isfinite(src_voxel_size) || src_tranc_dist != tsdf_volume_d_ptr->getTsdfTruncDist()) return -1;
+    DeviceArray2D<float> value = tsdf_volume_d_ptr->value(), grad = tsdf_volume_d_ptr->grad();
+    DeviceArray2D<int> weight = tsdf_volume_d_ptr->weight();
+    if (src_value == value.ptr(0) || src_weight == weight.ptr(0) || src_grad == grad.ptr(0)) return -1;
+    float xform[12];
+    if (!merge_affine(T16, (double)voxel_size, (double)src_voxel_size, xform)) return -1;
+    const size_t ws_bytes = xs_tsdf_merge_workspace_bytes(res3(), src_res);
+    if (ws_bytes == 0 || src_step % 4 != 0 || src_step < (size_t)src_res[0] * 4) return -1;
+    // the source may belong to another instance with streams of its own: drain the device, not just this instance's stream
+    synchronize();
+    hipSafeCall(hipDeviceSynchronize());
+    DeviceArray<unsigned char> ws;
+    ws.create(ws_bytes);
+    DeviceArray<unsigned long long> count;
+    count.create(1);
+    hipSafeCall(hipMemsetAsync(count.ptr(), 0, sizeof(unsigned long long), current_stream()));
+    check_rc(xs_tsdf_merge(value.ptr(0), weight.ptr(0), grad.ptr(0), value.step(), res3(), 0, res3()[2], src_value, src_weight, src_grad, src_step, src_res,
+                           xform, min_weight, max_integration_weight, 0u, count.ptr(), ws.ptr(), current_stream()), "merge");
+    ++volume_generation;
+    RebuildSignMap();    // the volume was written behind the integrate kernels' back
+    sign_map_stale_ = false;
+    invalidate_derived_maps();
+    CalculatePointCloud(vmaps_g_prev_d[0], nmaps_g_prev_d[0]);
+    ModelMapPyramid();
+    synchronize();
+    if (written) hipSafeCall(hipMemcpy(written, count.ptr(), sizeof(unsigned long long), hipMemcpyDeviceToHost));
+    return 1;
+}
+
+int KinectFusionReconstruction::MergeCheckpoint(const std::string &filename, const double *T16, int min_weight, unsigned long long *written) {
+    if (shard_count > 1) return -2;
+    if (!tsdf_volume_d_ptr) return 0;
+    if (!T16 || min_weight < 1) return -1;
+    for (int i = 0; i < 12; ++i)
+        if (!std::isfinite(T16[i])) return -1;
+    std::ifstream f(filename, std::ios::binary);
+    if (!f) return -1;
+    f.seekg(0, std::ios::end);
+    const long long file_bytes = (long long)f.tellg();
+    f.seekg(0, std::ios::beg);
+    CkptHeader h{};
+    if (file_bytes < (long long)sizeof(h)) return -1;
+    f.read(reinterpret_cast<char *>(&h), sizeof(h));
+    if (!f || std::memcmp(h.magic, "XSTSDF2", 8) != 0) return -1;
+    for (int i = 0; i < 3; ++i)
+        if (h.res[i] < 1 || h.res[i] > 65535) return -1;
+    if (h.shard_count != 1 || h.shard_rank != 0 || h.zs0 != 0 || h.zs1 != h.res[2]) return -1;   // a whole volume
+    if (!(h.voxel_size > 0.f) || !std::isfinite(h.voxel_size) || h.tranc_dist != tsdf_volume_d_ptr->getTsdfTruncDist()) return -1;
+    if (h.n_poses < 1 || h.n_poses > CKPT_MAX_POSES) return -1;
+    const int X = h.res[0];
+    const size_t rows = (size_t)h.res[1] * (size_t)h.res[2], n = rows * (size_t)X;
+    if (rows >= (size_t)1 << 31) return -1;
+    const long long expect = (long long)sizeof(h) + (long long)h.n_poses * (long long)sizeof(Matrix4cf) + 3LL * (long long)n * 4LL;
+    if (file_bytes != expect) return -1;               // truncated or trailing bytes
+    f.seekg((std::streamoff)((long long)sizeof(h) + (long long)h.n_poses * (long long)sizeof(Matrix4cf)), std::ios::beg);
+    std::vector<float> v(n), g(n);
+    std::vector<int> w(n);
+    f.read(reinterpret_cast<char *>(v.data()), (std::streamsize)(n * 4));
+    f.read(reinterpret_cast<char *>(g.data()), (std::streamsize)(n * 4));
+    f.read(reinterpret_cast<char *>(w.data()), (std::streamsize)(n * 4));
+    if (!f) return -1;
+    DeviceArray2D<float> dv, dg;   // the temporary volume: one pitch for the three arrays (the same row length and element size)
+    DeviceArray2D<int> dw;
+    dv.create((int)rows, X); dg.create((int)rows, X); dw.create((int)rows, X);
+    if (dv.step() != dg.step() || dv.step() != dw.step()) return -1;
+    restore_rows(dv, v, X, rows);
+    restore_rows(dg, g, X, rows);
+    restore_rows(dw, w, X, rows);
+    return MergeVolume(dv.ptr(0), dw.ptr(0), dg.ptr(0), dv.step(), h.res, h.voxel_size, h.tranc_dist, T16, min_weight, written);
 }

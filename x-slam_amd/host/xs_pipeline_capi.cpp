@@ -3,6 +3,7 @@
 #include "../csrc/xs_complex.h"
 #include "DoubleComplex.h"
 #include "KinectFusionReconstruction.h"
+#include "merge_host.hpp"
 #include "newton_host.hpp"
 #include <cstring>
 #include <exception>
@@ -454,5 +455,38 @@ void xs_kf_list_cover_counts(void *kf, long long *counts4) {
 int xs_kf_save_checkpoint(void *kf, const char *path) { ((KF *)kf)->saveCheckpoint(path); return 0; }
 int xs_kf_load_checkpoint(void *kf, const char *path) { return ((KF *)kf)->loadCheckpoint(path) ? 0 : -1; }
 int xs_kf_save_tsdf_volume(void *kf, const char *path) { ((KF *)kf)->saveTSDFVolume(path); return 0; }
+
+int xs_kf_merge_volume(void *kf, const float *src_value, const int *src_weight, const float *src_grad, size_t src_step, const int *src_res,
+                       float src_voxel_size, float src_tranc_dist, const double *T16, int min_weight, unsigned long long *written) {
+    return ((KF *)kf)->MergeVolume(src_value, src_weight, src_grad, src_step, src_res, src_voxel_size, src_tranc_dist, T16, min_weight, written);
+}
+int xs_kf_merge_checkpoint(void *kf, const char *path, const double *T16, int min_weight, unsigned long long *written) {
+    if (!path) return -1;
+    return ((KF *)kf)->MergeCheckpoint(path, T16, min_weight, written);
+}
+int xs_kf_merge_map(void *kf, void *other_kf, const double *T16, int min_weight, unsigned long long *written) {
+    KF *k = (KF *)kf, *o = (KF *)other_kf;
+    if (!o || o == k) return -1;
+    if (o->shard_count > 1) return -2;
+    if (!o->tsdf_volume_d_ptr) return -1;
+    o->synchronize();
+    auto v = o->tsdf_volume_d_ptr->value(), g = o->tsdf_volume_d_ptr->grad();   // (read only: the other map's sign map and indices stay as they are)
+    auto w = o->tsdf_volume_d_ptr->weight();
+    if (v.step() != g.step() || v.step() != w.step()) return -1;
+    return k->MergeVolume(v.ptr(), w.ptr(), g.ptr(), v.step(), o->volume_resolution.v, o->voxel_size, o->tsdf_volume_d_ptr->getTsdfTruncDist(), T16, min_weight,
+                          written);
+}
+int xs_host_merge_affine(const double *T16, double dst_voxel_size, double src_voxel_size, float *out12) {
+    return xs_host::merge_affine(T16, dst_voxel_size, src_voxel_size, out12) ? 0 : -1;
+}
+int xs_host_map_transform(const double *c2v_this16, const double *c2v_other16, double *T16) {
+    if (!c2v_this16 || !c2v_other16 || !T16) return -1;
+    xs_host::map_transform(c2v_this16, c2v_other16, T16);
+    return 0;
+}
+int xs_host_merge_tile_box(const float *xform12, const int *lo3, const int *hi3, const int *src_res, int *box6) {
+    if (!xform12 || !lo3 || !hi3 || !src_res || !box6) return -1;
+    return xs_host::merge_tile_box(xform12, lo3, hi3, src_res, box6) ? 1 : 0;
+}
 
 }  // extern "C"

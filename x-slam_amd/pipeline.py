@@ -94,6 +94,12 @@ _SIGS = {
     "xs_kf_save_checkpoint": (C.c_int, [_vp, C.c_char_p]),
     "xs_kf_load_checkpoint": (C.c_int, [_vp, C.c_char_p]),
     "xs_kf_save_tsdf_volume": (C.c_int, [_vp, C.c_char_p]),
+    "xs_kf_merge_volume": (C.c_int, [_vp, _vp, _vp, _vp, _sz, _i32p, C.c_float, C.c_float, _f64p, C.c_int, C.POINTER(C.c_ulonglong)]),
+    "xs_kf_merge_map": (C.c_int, [_vp, _vp, _f64p, C.c_int, C.POINTER(C.c_ulonglong)]),
+    "xs_kf_merge_checkpoint": (C.c_int, [_vp, C.c_char_p, _f64p, C.c_int, C.POINTER(C.c_ulonglong)]),
+    "xs_host_merge_affine": (C.c_int, [_f64p, C.c_double, C.c_double, _f32p]),
+    "xs_host_map_transform": (C.c_int, [_f64p, _f64p, _f64p]),
+    "xs_host_merge_tile_box": (C.c_int, [_f32p, _i32p, _i32p, _i32p, _i32p]),
     "xs_refshape_create": (_vp, [C.c_char_p]),
     "xs_refshape_destroy": (None, [_vp]),
     "xs_refshape_process_frame_host": (C.c_int, [_vp, _vp]),
@@ -168,6 +174,44 @@ def host_newton_step(s29, damping, c2v):
     m = np.ascontiguousarray(c2v, dtype=np.float32).reshape(32).copy()
     rc = _lib.xs_host_newton_step(s.ctypes.data_as(_f64p), float(damping), m.ctypes.data_as(_f32p))
     return rc == 0, m.reshape(4, 4, 2)
+
+
+def _real44(m):
+    """A real 4 x 4 float64 from a 4 x 4 (real) or 4 x 4 x 2 (re, im: the real parts) pose."""
+    a = np.asarray(m, dtype=np.float64)
+    if a.shape == (4, 4, 2):
+        a = a[..., 0]
+    return np.ascontiguousarray(a.reshape(4, 4))
+
+
+def merge_affine(T, dst_voxel_size, src_voxel_size):
+    """xform12 of capi.tsdf_merge (float32 [12]: 3 x 3 row-major, then 3 offsets) from T (real 4 x 4: a point of the destination map's volume
+    frame, in metres, to the source map's) and the two voxel sizes: float64 throughout, one rounding at the end (CPU).  ValueError for an
+    input that is not finite or a voxel size that is not positive."""
+    t = _real44(T)
+    out = np.zeros(12, np.float32)
+    if _lib.xs_host_merge_affine(t.ctypes.data_as(_f64p), float(dst_voxel_size), float(src_voxel_size), out.ctypes.data_as(_f32p)) != 0:
+        raise ValueError("merge_affine: an input is not finite, or a voxel size is not positive")
+    return out
+
+
+def map_transform(c2v_this, c2v_other):
+    """T = c2v_other c2v_this^-1 (real 4 x 4 float64) from the real parts of two camera-to-volume poses of one camera frame: the frame's pose in
+    this map and, by relocalize_global there, in the other map give the T that merge_map takes (CPU)."""
+    a, b = _real44(c2v_this), _real44(c2v_other)
+    out = np.zeros((4, 4), np.float64)
+    _lib.xs_host_map_transform(a.ctypes.data_as(_f64p), b.ctypes.data_as(_f64p), out.ctypes.data_as(_f64p))
+    return out
+
+
+def merge_tile_box(xform12, lo, hi, src_res):
+    """The merge kernel's cull box (CPU): (lo [3], hi [3]) inclusive source voxel indices that contain every source voxel a destination voxel
+    of the tile lo .. hi (inclusive) reads, or None when no voxel of the tile falls inside the source."""
+    m = np.ascontiguousarray(xform12, np.float32).reshape(12)
+    l, h, s = (np.ascontiguousarray(a, np.int32).reshape(3) for a in (lo, hi, src_res))
+    box = np.zeros(6, np.int32)
+    rc = _lib.xs_host_merge_tile_box(m.ctypes.data_as(_f32p), l.ctypes.data_as(_i32p), h.ctypes.data_as(_i32p), s.ctypes.data_as(_i32p), box.ctypes.data_as(_i32p))
+    return (box[:3].copy(), box[3:].copy()) if rc == 1 else None
 
 
 def _halton(i, base):
@@ -771,6 +815,33 @@ class KinectFusion:
 
     def save_tsdf_volume(self, path):
         _lib.xs_kf_save_tsdf_volume(self.h, path.encode())
+
+    @staticmethod
+    def _merge_call(name, rc, written):
+        if rc == -2:
+            raise capi.XsError(f"{name}: not available in shard mode")
+        if rc == -1:
+            raise ValueError(f"{name}: bad arguments (T not finite, min_weight < 1, the volume itself as source, a bad file or another truncation distance)")
+        if rc != 1:
+            raise ValueError(f"{name}: no volume" if rc == 0 else f"{name}: {rc}")
+        return int(written.value)
+
+    def merge_map(self, other, T=None, min_weight=1):
+        """Merges the map of `other` (another KinectFusion of this process; only read) into this one: its volume is resampled into this map's
+        voxel grid under T (real 4 x 4: a point of THIS map's volume frame, in metres, to the other map's; None: the identity) and averaged in by
+        weight as a new observation is, where all the corners it is interpolated from carry min_weight.  Resolutions and voxel sizes may
+        differ, the truncation distances may not.  Everything derived from the volume follows; poses and the frame number do not change.
+        Returns the number of voxels written.  XsError in shard mode, ValueError on bad arguments (the state is unchanged)."""
+        t = _real44(np.eye(4) if T is None else T)
+        n = C.c_ulonglong(0)
+        return self._merge_call("xs_kf_merge_map", _lib.xs_kf_merge_map(self.h, other.h, t.ctypes.data_as(_f64p), int(min_weight), C.byref(n)), n)
+
+    def merge_checkpoint(self, path, T=None, min_weight=1):
+        """merge_map with the other map read from a checkpoint file of a whole volume (save_checkpoint); the file is validated before anything
+        is touched and a bad one raises ValueError with the state unchanged."""
+        t = _real44(np.eye(4) if T is None else T)
+        n = C.c_ulonglong(0)
+        return self._merge_call("xs_kf_merge_checkpoint", _lib.xs_kf_merge_checkpoint(self.h, path.encode(), t.ctypes.data_as(_f64p), int(min_weight), C.byref(n)), n)
 
 
 class ReferenceCallShape:
