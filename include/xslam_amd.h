@@ -670,6 +670,41 @@ int xs_tsdf_merge(float *value, int *weight, float *grad, size_t step, const int
                   const int *src_weight, const float *src_grad, size_t src_step, const int *src_res, const float *xform12, int min_weight,
                   int max_weight, unsigned flags, unsigned long long *written_dev, void *workspace, void *stream);
 
+/* ---- aligning a second volume to the volume: Gauss-Newton terms over the band (xs_align.hip) -------------------
+ * No counterpart in the reference.  The residual of a band voxel of THIS map is "the other map, resampled at the voxel under a complex-seeded
+ * affine index map, minus this map": the sample xs_tsdf_merge would average in, at the position it would use.  `index`: the band index of THIS
+ * map (xs_tsdf_band_build); only its keys, values and count are used.  The source: value and weight arrays of the other map at plane 0, one
+ * pitch, the layout of xs_tsdf_merge; it is only read.  maps144xN: host array, per transform six seeded maps (the generators of the rigid
+ * transform, x-slam_amd/host/align_host.hpp: xs_host_align_seeded_maps) of 12 complex entries (re, im) in xform12's order.  Transform n's 29
+ * sums land at out29xN_dev + 29 n, in the layout of xs_tsdf_gauss_newton_terms.
+ *
+ * Index entry (x, y, z, gt), transform n; m_k = seed k's map, complex float32 in the arithmetic of csrc/xs_complex.h, every operation in the
+ * order written (the library is built with -ffp-contract=off):
+ *   1. g_a = ((m_k[3a] * float(x) + m_k[3a + 1] * float(y)) + m_k[3a + 2] * float(z)) + m_k[9 + a]  (complex times real, complex sums).  With
+ *      the maps of xs_host_align_seeded_maps Re g_a is merge_index's value, bit for bit, for every seed.
+ *   2. The cell comes from seed 0: the entry is dropped unless 0 <= Re g_a < float(S_a - 1) on every axis (S: the source resolution; a NaN
+ *      fails).  b_a = floor(Re g_a); for every seed f_a = g_a - float(b_a) (complex) and c_a = 1.0f - f_a.  All eight corners b + {0, 1}^3
+ *      are read on every entry that gets this far (the derivative needs the neighbours even where Re f_a = 0); no other source voxel is.
+ *   3. The entry is dropped unless all eight corner weights are >= min_weight; a dropped entry loads no value.
+ *   4. F: along x the real corner values, lo * c_0 + hi * f_0 (real times complex); then along y and along z, lo * c_a + hi * f_a (complex
+ *      times complex).
+ *   5. r_k = F - gt.  The entry is dropped if |Re r_k| > max_residual for any seed.
+ *   6. A kept entry adds, in double: Im r_j * Im r_k (j <= k, row-major) to [0, 21), Im r_k * Re r_0 to [21, 27), (Re r_0)^2 to [27], 1 to [28].
+ * Order: the entries are dealt out in chunks of 64 as for xs_tsdf_pose_hessian_band and folded in a fixed order that is a function of
+ * index->count alone: two launches on the same inputs give the same bits, and transform n's sums do not depend on `transforms`, on n or on
+ * the other transforms.  No floating-point atomics.  An index with count 0 yields zeros.
+ * Workspace: xs_tsdf_align_workspace_bytes(transforms) bytes (0 for transforms outside 1 .. XS_ALIGN_MAX_TRANSFORMS): one arrival ticket per
+ * transform in its first 256 bytes, the maps, the records.  Zero the first 256 bytes ONCE after allocation (xs_tsdf_reduce_workspace_init);
+ * every launch leaves them zero.  One launch at a time per workspace.  No synchronisation.
+ * hipErrorInvalidValue, with nothing launched: transforms outside 1 .. 32; a null pointer; an index that was not built (the checks of
+ * xs_tsdf_pose_hessian_band); a source axis outside 2 .. 262140, or rows (S_1 S_2) that do not fit an int; a pitch that is no multiple of 4
+ * or shorter than a row; min_weight < 1; max_residual not finite or <= 0; a map entry that is not finite. */
+#define XS_ALIGN_MAX_TRANSFORMS 32
+size_t xs_tsdf_align_workspace_bytes(int transforms);
+int xs_tsdf_align_terms(int transforms, const xs_band_index *index, const float *src_value, const int *src_weight, size_t src_step,
+                        const int *src_res, const float *maps144xN, int min_weight, float max_residual, void *workspace, double *out29xN_dev,
+                        void *stream);
+
 /* ---- surface mesh (export; marching cubes with complex-step vertex derivatives) -------------------------------------------------------
  * No working counterpart in the reference (its extractMesh, ExtractPointCloud.cu:364-715, is never called).
  * Cube (x, y, z), x < X-1, y < Y-1, z in [z0, z1), is live when all 8 corners have weight >= min_weight and value < 0.99 and its corners

@@ -283,6 +283,10 @@ long long xs_kf_composite_bytes(void *kf);
 void xs_kf_list_cover_counts(void *kf, long long *counts4);
 
 /* volume checkpoint (value + grad + weight + poses)   cf. saveTSDFVolume, .cpp:438-447 */
+/* The version of the volume's contents: incremented by everything that writes the volume (a frame, a merge, a loaded checkpoint,
+ * xs_kf_volume_ptr of the value array); the cached band index and planning maps are rebuilt when it has moved.  Calls that only read the
+ * map (relocalisation, export, xs_kf_align_map on either instance) leave it alone. */
+long long xs_kf_volume_generation(void *kf);
 int xs_kf_save_checkpoint(void *kf, const char *path);
 int xs_kf_load_checkpoint(void *kf, const char *path);
 int xs_kf_save_tsdf_volume(void *kf, const char *path);
@@ -314,6 +318,35 @@ int xs_kf_merge_checkpoint(void *kf, const char *path, const double *T16, int mi
 int xs_host_merge_affine(const double *T16, double dst_voxel_size, double src_voxel_size, float *out12);
 int xs_host_map_transform(const double *c2v_this16, const double *c2v_other16, double *T16);
 int xs_host_merge_tile_box(const float *xform12, const int *lo3, const int *hi3, const int *src_res, int *box6);
+
+/* ---- Aligning a second map to the volume before merging it (xs_tsdf_align_terms in xslam_amd.h: the contract) --
+ * Damped Gauss-Newton over the band index of THIS map on the residual "the other map, resampled at this map's band voxels under T, minus
+ * this map": the samples, at the positions, that a merge under T would use.  T16xN: N >= 1 starting transforms, each a real 4 x 4, row-major,
+ * as xs_kf_merge_map takes it; every start runs `iterations` damped steps ((J^T J + damping diag(J^T J)) delta = -J^T r, T <- exp(delta) T)
+ * and one final pass that only reports the loss, the starts in one launch per pass.  A voxel takes part where the other map carries
+ * min_weight on all eight corners around its sample and |residual| <= max_residual.  T16_out: the start that ended ok (at least six voxels on
+ * every pass, the final loss pass included, and a positive definite system on every step) with the highest S = count - sum r^2,
+ * relocalize_global's score (ties: the lower index).  S is a truncated-quadratic inlier score for max_residual <= 1 (every kept voxel adds
+ * 1 - r^2 >= 0); with a larger max_residual a kept voxel can subtract more than it adds, and S then ranks by fit alone among starts that
+ * all kept six voxels.  With iterations = 0 the one pass is the loss pass: a start that keeps fewer than six voxels does not end ok.
+ * report8 = {the winner's index, its count, its sum r^2, its mean loss, launches run, starts that ended ok, band voxels in the index, 0}.
+ * loss_history (optional, iterations + 1 doubles): the winner's mean loss per pass, the last entry the loss it ended at.
+ * Nothing of either map is modified; the device is drained first.  align_map: the other map is another instance of this process.
+ * align_checkpoint: an XSTSDF2 file of a whole volume, validated and uploaded as for xs_kf_merge_checkpoint.
+ * Return 1; 0 without a volume or when no start ended ok (T16_out and loss_history untouched, report8[0] = -1); -1 on bad arguments (the
+ * merge's, and N < 1, iterations < 0, damping negative or not finite, max_residual <= 0 or not finite, a source axis below 2); -2 in shard mode. */
+int xs_kf_align_map(void *kf, void *other_kf, const double *T16xN, int N, int iterations, double damping, int min_weight, float max_residual,
+                    double *T16_out, double *report8, double *loss_history);
+int xs_kf_align_checkpoint(void *kf, const char *path, const double *T16xN, int N, int iterations, double damping, int min_weight, float max_residual,
+                           double *T16_out, double *report8, double *loss_history);
+/* The host's side of an alignment pass (x-slam_amd/host/align_host.hpp).  CPU only.
+ * align_seeded_maps: out144 = six maps of 12 complex entries (re, im), xform12's order: T_k = (I + i h G_k) T through merge_affine's formula,
+ * k = three translations then three rotations, h the seed step of the Gauss-Newton kernels.  The real parts are xs_host_merge_affine's bit
+ * for bit for every k.  0, or -1 (nothing written): merge_affine's refusals.
+ * align_step: s29 the scaled sums of a pass; solves (A + damping diag A) delta = -g by Cholesky and applies T16 <- exp(delta) T16 in float64.
+ * 0 when the step was taken, -1 (T16 untouched) when count < 6 or the system is not positive definite. */
+int xs_host_align_seeded_maps(const double *T16, double vs_this, double vs_other, float *out144);
+int xs_host_align_step(const double *s29, double damping, double *T16);
 
 /* ---- The reference's own call shape (x-slam_amd/host/reference_shape.hpp) ---------------------------------------------------------
  * The per-frame sequence of Experiments/test_xkinect_fusion/main.cpp:46-60 + KinectFusionReconstruction.cpp:147-332 over nothing but the

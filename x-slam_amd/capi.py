@@ -168,6 +168,8 @@ _SIGS = {
     "xs_extract_normals": (C.c_int, [_vp, _sz, _i32p, C.c_float, C.c_int, C.c_int, _vp, _sz, _vp, _vp]),
     "xs_tsdf_merge_workspace_bytes": (_sz, [_i32p, _i32p]),
     "xs_tsdf_merge": (C.c_int, [_vp, _vp, _vp, _sz, _i32p, C.c_int, C.c_int, _vp, _vp, _vp, _sz, _i32p, _f32p, C.c_int, C.c_int, C.c_uint, _vp, _vp, _vp]),
+    "xs_tsdf_align_workspace_bytes": (_sz, [C.c_int]),
+    "xs_tsdf_align_terms": (C.c_int, [C.c_int, C.POINTER(BandIndex), _vp, _vp, _sz, _i32p, _f32p, C.c_int, C.c_float, _vp, _vp, _vp]),
     "xs_mesh_workspace_bytes": (_sz, [_i32p, C.POINTER(MeshOpts)]),
     "xs_extract_mesh": (C.c_int, [_vp, _vp, _vp, _sz, _i32p, C.c_float, C.POINTER(MeshOpts), _vp, _vp, _vp, _vp, _sz, _vp, _sz, _vp,
                                   C.POINTER(_sz), C.POINTER(_sz), _vp]),
@@ -865,6 +867,31 @@ def map_transform(c2v_this, c2v_other):
     """xs_host_map_transform of libxslam_host.so (CPU): c2v_other c2v_this^-1 from the real parts."""
     from . import pipeline
     return pipeline.map_transform(c2v_this, c2v_other)
+
+
+ALIGN_MAX_TRANSFORMS = 32   # XS_ALIGN_MAX_TRANSFORMS
+
+
+def tsdf_align_workspace_bytes(transforms):
+    """xs_tsdf_align_workspace_bytes (host only): tickets, maps and records for up to `transforms` transforms; 0 outside 1 .. 32."""
+    return int(_lib.xs_tsdf_align_workspace_bytes(int(transforms)))
+
+
+def tsdf_align_terms(index, src_value, src_weight, src_step, src_res, maps, min_weight, max_residual, workspace, out29xN, stream=None):
+    """xs_tsdf_align_terms: the 29 raw Gauss-Newton sums of N transforms over a built band index of THIS map against the value and weight
+    arrays of the other map (device tensors or addresses of plane 0); maps [N, 6, 12, 2] float32 (align_seeded_maps per transform);
+    transform n's sums land at out29xN[29 n : 29 n + 29] (float64 device tensor).  No synchronisation."""
+    m = np.ascontiguousarray(maps, dtype=np.float32).reshape(-1)
+    assert m.size % 144 == 0, m.size
+    s = _ia(src_res, 3)
+    check(_lib.xs_tsdf_align_terms(m.size // 144, C.byref(index), _ptr(src_value), _ptr(src_weight), src_step, s.ctypes.data_as(_i32p), m.ctypes.data_as(_f32p),
+                                   int(min_weight), float(max_residual), _ptr(workspace), _ptr(out29xN), _stream(stream)))
+
+
+def align_seeded_maps(T, vs_this, vs_other):
+    """xs_host_align_seeded_maps of libxslam_host.so (CPU): the six seeded maps [6, 12, 2] of tsdf_align_terms for one transform."""
+    from . import pipeline
+    return pipeline.align_seeded_maps(T, vs_this, vs_other)
 
 
 MESH_OVER_CAPACITY = -2   # XS_MESH_OVER_CAPACITY

@@ -336,6 +336,23 @@ public:
     // with shard_count 1, the truncation distance.  The file's volume goes to a temporary device volume that is freed after the merge.
     // Any mismatch: -1 with the state unchanged.
     int MergeCheckpoint(const std::string &filename, const double *T16, int min_weight, unsigned long long *written);
+    // Aligning a second map to the volume before it is merged (xs_tsdf_align_terms in include/xslam_amd.h: the
+    // contract).  The source as for MergeVolume (its grad array is not needed); T16xN: N >= 1 starting transforms, each a real 4 x 4 as
+    // MergeVolume takes it.  The device is drained, the band index of THIS map prepared, and gn_batch_loop (gn_host.hpp) run over the starts:
+    // a pass is one xs_tsdf_align_terms launch per chunk of the starts still active, a step align_host.hpp's align_step.  T16_out receives
+    // the start that ended ok — at least six voxels on every pass, the last one included, and a positive definite system on every step —
+    // with the highest S = count - sum r^2 (ties: the lower index; S is relocalize_global's truncated-quadratic score for max_residual <= 1: above
+    // that a kept voxel can subtract more than it adds); report = {its index, its count, its sum r^2,
+    // its mean loss, launches run, starts that ended ok, band voxels in the index, 0}; loss_history (optional) its loss per pass, the
+    // last entry the loss it ended at.  Nothing of either map is modified: volume_generation, poses and frame_id stay.  Returns 1; 0 without
+    // a volume or when no start ended ok (T16_out untouched, report[0] = -1); -1 on bad arguments (MergeVolume's, and N < 1, iterations < 0,
+    // a damping or max_residual that is not finite, max_residual <= 0, a source axis below 2); -2 in shard mode.
+    int AlignVolume(const float *src_value, const int *src_weight, size_t src_step, const int *src_res, float src_voxel_size, float src_tranc_dist,
+                    const double *T16xN, int N, int iterations, double damping, int min_weight, float max_residual, double *T16_out, double report[8],
+                    std::vector<double> *loss_history);
+    // The same against an XSTSDF2 file: MergeCheckpoint's validation, its temporary device volume and its free.
+    int AlignCheckpoint(const std::string &filename, const double *T16xN, int N, int iterations, double damping, int min_weight, float max_residual,
+                        double *T16_out, double report[8], std::vector<double> *loss_history);
 
     // counters of the last frame (synchronise the stream)
     long long lastUpdatedVoxels();
@@ -391,6 +408,8 @@ private:
         DeviceArray<unsigned char> score_ws;       // xs_tsdf_score_poses_workspace_bytes(XS_SCORE_MAX_POSES)
         DeviceArray<double> score_sums;            // XS_SCORE_MAX_POSES x 2
         DeviceArray2D<float> score_depth;          // ScorePoses' scaled depth
+        DeviceArray<unsigned char> align_ws;       // xs_tsdf_align_workspace_bytes(XS_ALIGN_MAX_TRANSFORMS)
+        DeviceArray<double> align_sums;            // XS_ALIGN_MAX_TRANSFORMS x 29
     } reloc_;
     const float *GaussNewtonDenseView();       // the owned planes as the dense array the Gauss-Newton kernels index (packed into gn_dense when pitched)
     void BandIndexPrepare();                   // (re)builds the band index when the volume changed since it was built

@@ -1,7 +1,10 @@
 // kf_export.cpp — what leaves the orchestrator: point cloud and mesh with their PLY writers, the last frame's counters, the raw volume
-// and the checkpoint; and what enters it as a whole map: a second volume or checkpoint merged into this one.  None of it runs during tracking.
+// and the checkpoint; and what enters it as a whole map: a second volume or checkpoint merged into this one, and aligned to it beforehand.
+// None of it runs during tracking.
 #include "kf_internal.hpp"
+#include "align_host.hpp"
 #include "merge_host.hpp"
+#include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <fstream>
@@ -253,44 +256,141 @@ int KinectFusionReconstruction::MergeVolume(const float *src_value, const int *s
     return 1;
 }
 
-int KinectFusionReconstruction::MergeCheckpoint(const std::string &filename, const double *T16, int min_weight, unsigned long long *written) {
-    if (shard_count > 1) return -2;
-    if (!tsdf_volume_d_ptr) return 0;
-    if (!T16 || min_weight < 1) return -1;
-    for (int i = 0; i < 12; ++i)
-        if (!std::isfinite(T16[i])) return -1;
+namespace {
+// An XSTSDF2 file of a whole volume, validated in full (magic, exact length, shard_count 1, the truncation distance `tranc_dist`) and uploaded
+// to a temporary device volume with one pitch for the three arrays.  False on any mismatch, with nothing allocated.
+struct CkptVolume {
+    CkptHeader h{};
+    DeviceArray2D<float> dv, dg;
+    DeviceArray2D<int> dw;
+};
+bool upload_whole_checkpoint(const std::string &filename, float tranc_dist, CkptVolume &out) {
+    CkptHeader &h = out.h;
     std::ifstream f(filename, std::ios::binary);
-    if (!f) return -1;
+    if (!f) return false;
     f.seekg(0, std::ios::end);
     const long long file_bytes = (long long)f.tellg();
     f.seekg(0, std::ios::beg);
-    CkptHeader h{};
-    if (file_bytes < (long long)sizeof(h)) return -1;
+    if (file_bytes < (long long)sizeof(h)) return false;
     f.read(reinterpret_cast<char *>(&h), sizeof(h));
-    if (!f || std::memcmp(h.magic, "XSTSDF2", 8) != 0) return -1;
+    if (!f || std::memcmp(h.magic, "XSTSDF2", 8) != 0) return false;
     for (int i = 0; i < 3; ++i)
-        if (h.res[i] < 1 || h.res[i] > 65535) return -1;
-    if (h.shard_count != 1 || h.shard_rank != 0 || h.zs0 != 0 || h.zs1 != h.res[2]) return -1;   // a whole volume
-    if (!(h.voxel_size > 0.f) || !std::isfinite(h.voxel_size) || h.tranc_dist != tsdf_volume_d_ptr->getTsdfTruncDist()) return -1;
-    if (h.n_poses < 1 || h.n_poses > CKPT_MAX_POSES) return -1;
+        if (h.res[i] < 1 || h.res[i] > 65535) return false;
+    if (h.shard_count != 1 || h.shard_rank != 0 || h.zs0 != 0 || h.zs1 != h.res[2]) return false;   // a whole volume
+    if (!(h.voxel_size > 0.f) || !std::isfinite(h.voxel_size) || h.tranc_dist != tranc_dist) return false;
+    if (h.n_poses < 1 || h.n_poses > CKPT_MAX_POSES) return false;
     const int X = h.res[0];
     const size_t rows = (size_t)h.res[1] * (size_t)h.res[2], n = rows * (size_t)X;
-    if (rows >= (size_t)1 << 31) return -1;
+    if (rows >= (size_t)1 << 31) return false;
     const long long expect = (long long)sizeof(h) + (long long)h.n_poses * (long long)sizeof(Matrix4cf) + 3LL * (long long)n * 4LL;
-    if (file_bytes != expect) return -1;               // truncated or trailing bytes
+    if (file_bytes != expect) return false;            // truncated or trailing bytes
     f.seekg((std::streamoff)((long long)sizeof(h) + (long long)h.n_poses * (long long)sizeof(Matrix4cf)), std::ios::beg);
     std::vector<float> v(n), g(n);
     std::vector<int> w(n);
     f.read(reinterpret_cast<char *>(v.data()), (std::streamsize)(n * 4));
     f.read(reinterpret_cast<char *>(g.data()), (std::streamsize)(n * 4));
     f.read(reinterpret_cast<char *>(w.data()), (std::streamsize)(n * 4));
-    if (!f) return -1;
-    DeviceArray2D<float> dv, dg;   // the temporary volume: one pitch for the three arrays (the same row length and element size)
-    DeviceArray2D<int> dw;
-    dv.create((int)rows, X); dg.create((int)rows, X); dw.create((int)rows, X);
-    if (dv.step() != dg.step() || dv.step() != dw.step()) return -1;
-    restore_rows(dv, v, X, rows);
-    restore_rows(dg, g, X, rows);
-    restore_rows(dw, w, X, rows);
-    return MergeVolume(dv.ptr(0), dw.ptr(0), dg.ptr(0), dv.step(), h.res, h.voxel_size, h.tranc_dist, T16, min_weight, written);
+    if (!f) return false;
+    out.dv.create((int)rows, X); out.dg.create((int)rows, X); out.dw.create((int)rows, X);
+    if (out.dv.step() != out.dg.step() || out.dv.step() != out.dw.step()) return false;
+    restore_rows(out.dv, v, X, rows);
+    restore_rows(out.dg, g, X, rows);
+    restore_rows(out.dw, w, X, rows);
+    return true;
+}
+}  // namespace
+
+int KinectFusionReconstruction::MergeCheckpoint(const std::string &filename, const double *T16, int min_weight, unsigned long long *written) {
+    if (shard_count > 1) return -2;
+    if (!tsdf_volume_d_ptr) return 0;
+    if (!T16 || min_weight < 1) return -1;
+    for (int i = 0; i < 12; ++i)
+        if (!std::isfinite(T16[i])) return -1;
+    CkptVolume c;
+    if (!upload_whole_checkpoint(filename, tsdf_volume_d_ptr->getTsdfTruncDist(), c)) return -1;
+    return MergeVolume(c.dv.ptr(0), c.dw.ptr(0), c.dg.ptr(0), c.dv.step(), c.h.res, c.h.voxel_size, c.h.tranc_dist, T16, min_weight, written);
+}
+
+// ---- aligning a second map -----------------------------------------------------------------------------------
+int KinectFusionReconstruction::AlignVolume(const float *src_value, const int *src_weight, size_t src_step, const int *src_res, float src_voxel_size,
+                                            float src_tranc_dist, const double *T16xN, int N, int iterations, double damping, int min_weight,
+                                            float max_residual, double *T16_out, double report[8], std::vector<double> *loss_history) {
+    if (report) { for (int i = 0; i < 8; ++i) report[i] = 0.0; report[0] = -1.0; }
+    if (shard_count > 1) return -2;   // the band index of a rank holds its own planes, the sums would need the all-reduce: not built
+    if (!tsdf_volume_d_ptr) return 0;
+    if (!src_value || !src_weight || !src_res || !T16xN || !T16_out || N < 1 || iterations < 0 || min_weight < 1) return -1;
+    if (!(max_residual > 0.f) || !std::isfinite(max_residual) || !(damping >= 0.0) || !std::isfinite(damping)) return -1;
+    for (int k = 0; k < 3; ++k)
+        if (src_res[k] < 2) return -1;
+    if (!(src_voxel_size > 0.f) || !std::isfinite(src_voxel_size) || src_tranc_dist != tsdf_volume_d_ptr->getTsdfTruncDist()) return -1;
+    if (src_value == tsdf_volume_d_ptr->value().ptr(0) || src_weight == tsdf_volume_d_ptr->weight().ptr(0)) return -1;
+    if (src_step % 4 != 0 || src_step < (size_t)src_res[0] * 4) return -1;
+    std::vector<double> T((size_t)N * 16);
+    float probe[6][24];
+    for (int n = 0; n < N; ++n) {
+        for (int i = 0; i < 16; ++i) T[(size_t)n * 16 + i] = T16xN[(size_t)n * 16 + i];
+        if (!align_seeded_maps(&T[(size_t)n * 16], (double)voxel_size, (double)src_voxel_size, probe)) return -1;
+    }
+    // the source may belong to another instance with streams of its own: drain the device, not just this instance's stream
+    synchronize();
+    hipSafeCall(hipDeviceSynchronize());
+    BandIndexPrepare();
+    ensure_reduce_workspace(reloc_.align_ws, xs_tsdf_align_workspace_bytes(XS_ALIGN_MAX_TRANSFORMS), "align workspace");
+    if (reloc_.align_sums.size() < (size_t)XS_ALIGN_MAX_TRANSFORMS * 29) reloc_.align_sums.create((size_t)XS_ALIGN_MAX_TRANSFORMS * 29);
+    std::vector<std::vector<double>> history((size_t)N);   // (always kept: the last pass's sums pick the winner)
+    std::vector<double> last((size_t)N * 29, 0.0);
+    std::vector<int> ok((size_t)N, 0);
+    std::vector<float> maps((size_t)XS_ALIGN_MAX_TRANSFORMS * 144);
+    int passes = 0;
+    gn_batch_loop(N, iterations, history.data(), ok.data(), XS_ALIGN_MAX_TRANSFORMS,
+        [&](const int *starts, int n, double *sums) {
+            for (int i = 0; i < n; ++i) {
+                float *m = &maps[(size_t)i * 144];
+                if (align_seeded_maps(&T[(size_t)starts[i] * 16], (double)voxel_size, (double)src_voxel_size, reinterpret_cast<float (*)[24]>(m))) continue;
+                // a step took T out of float32's range: a map that misses the source (every index is -1), so the start ends with count 0 and fails
+                std::fill(m, m + 144, 0.f);
+                for (int k = 0; k < 6; ++k)
+                    for (int a = 0; a < 3; ++a) m[24 * k + 2 * (9 + a)] = -1.f;
+            }
+            check_rc(xs_tsdf_align_terms(n, &reloc_.band, src_value, src_weight, src_step, src_res, maps.data(), min_weight, max_residual, reloc_.align_ws.ptr(),
+                                         reloc_.align_sums.ptr(), current_stream()), "AlignTerms");
+            fetch_sums(reloc_.align_sums.ptr(), (size_t)n * 29, sums);
+            ++passes;
+            for (int i = 0; i < n; ++i) {
+                gn_scale_sums(sums + 29 * i, sums + 29 * i);
+                std::copy(sums + 29 * i, sums + 29 * i + 29, last.begin() + (size_t)starts[i] * 29);
+            }
+        },
+        [&](int n, const double *s, int) { return align_step(s, damping, &T[(size_t)n * 16]); });
+    // the winner: the start that ended ok, with at least six voxels in its last pass too (gn_batch_loop lets the loss pass end ok whatever it
+    // counts: a start that its last step, or no step at all, left off the other map is no result), with the highest S = count - sum r^2
+    // (relocalize_global's score; ties: the lower index)
+    auto S = [&](int n) { return last[(size_t)n * 29 + 28] - last[(size_t)n * 29 + 27]; };
+    int win = -1, ended_ok = 0;
+    for (int n = 0; n < N; ++n) {
+        if (!ok[(size_t)n] || last[(size_t)n * 29 + 28] < 6) continue;
+        ++ended_ok;
+        if (win < 0 || S(n) > S(win)) win = n;
+    }
+    if (report) { report[4] = (double)passes; report[5] = (double)ended_ok; report[6] = (double)reloc_.band.count; }
+    if (win < 0) return 0;
+    const double *s = &last[(size_t)win * 29];
+    for (int i = 0; i < 16; ++i) T16_out[i] = T[(size_t)win * 16 + i];
+    if (report) { report[0] = (double)win; report[1] = s[28]; report[2] = s[27]; report[3] = s[28] > 0 ? s[27] / s[28] : 0.0; }
+    if (loss_history) *loss_history = history[(size_t)win];
+    return 1;
+}
+
+int KinectFusionReconstruction::AlignCheckpoint(const std::string &filename, const double *T16xN, int N, int iterations, double damping, int min_weight,
+                                                float max_residual, double *T16_out, double report[8], std::vector<double> *loss_history) {
+    if (report) { for (int i = 0; i < 8; ++i) report[i] = 0.0; report[0] = -1.0; }
+    if (shard_count > 1) return -2;
+    if (!tsdf_volume_d_ptr) return 0;
+    if (!T16xN || !T16_out || N < 1) return -1;
+    for (int i = 0; i < 16 * N; ++i)
+        if (i % 16 < 12 && !std::isfinite(T16xN[i])) return -1;
+    CkptVolume c;
+    if (!upload_whole_checkpoint(filename, tsdf_volume_d_ptr->getTsdfTruncDist(), c)) return -1;
+    return AlignVolume(c.dv.ptr(0), c.dw.ptr(0), c.dv.step(), c.h.res, c.h.voxel_size, c.h.tranc_dist, T16xN, N, iterations, damping, min_weight, max_residual,
+                       T16_out, report, loss_history);
 }

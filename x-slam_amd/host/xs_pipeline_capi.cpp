@@ -3,6 +3,7 @@
 #include "../csrc/xs_complex.h"
 #include "DoubleComplex.h"
 #include "KinectFusionReconstruction.h"
+#include "align_host.hpp"
 #include "merge_host.hpp"
 #include "newton_host.hpp"
 #include <cstring>
@@ -452,6 +453,7 @@ void xs_kf_list_cover_counts(void *kf, long long *counts4) {
     if (counts4) for (int i = 0; i < 4; ++i) counts4[i] = ((KF *)kf)->list_cover_counts_[i];
 }
 
+long long xs_kf_volume_generation(void *kf) { return (long long)((KF *)kf)->volume_generation; }
 int xs_kf_save_checkpoint(void *kf, const char *path) { ((KF *)kf)->saveCheckpoint(path); return 0; }
 int xs_kf_load_checkpoint(void *kf, const char *path) { return ((KF *)kf)->loadCheckpoint(path) ? 0 : -1; }
 int xs_kf_save_tsdf_volume(void *kf, const char *path) { ((KF *)kf)->saveTSDFVolume(path); return 0; }
@@ -476,6 +478,34 @@ int xs_kf_merge_map(void *kf, void *other_kf, const double *T16, int min_weight,
     return k->MergeVolume(v.ptr(), w.ptr(), g.ptr(), v.step(), o->volume_resolution.v, o->voxel_size, o->tsdf_volume_d_ptr->getTsdfTruncDist(), T16, min_weight,
                           written);
 }
+int xs_kf_align_map(void *kf, void *other_kf, const double *T16xN, int N, int iterations, double damping, int min_weight, float max_residual,
+                    double *T16_out, double *report8, double *loss_history) {
+    KF *k = (KF *)kf, *o = (KF *)other_kf;
+    if (!o || o == k) return -1;
+    if (o->shard_count > 1) return -2;
+    if (!o->tsdf_volume_d_ptr) return -1;
+    o->synchronize();
+    auto v = o->tsdf_volume_d_ptr->value();   // (read only: nothing of the other map is touched)
+    auto w = o->tsdf_volume_d_ptr->weight();
+    if (v.step() != w.step()) return -1;
+    std::vector<double> history;
+    const int rc = k->AlignVolume(v.ptr(), w.ptr(), v.step(), o->volume_resolution.v, o->voxel_size, o->tsdf_volume_d_ptr->getTsdfTruncDist(), T16xN, N, iterations,
+                                  damping, min_weight, max_residual, T16_out, report8, loss_history ? &history : nullptr);
+    if (loss_history) std::copy(history.begin(), history.end(), loss_history);   // at most iterations + 1 entries
+    return rc;
+}
+int xs_kf_align_checkpoint(void *kf, const char *path, const double *T16xN, int N, int iterations, double damping, int min_weight, float max_residual,
+                           double *T16_out, double *report8, double *loss_history) {
+    if (!path) return -1;
+    std::vector<double> history;
+    const int rc = ((KF *)kf)->AlignCheckpoint(path, T16xN, N, iterations, damping, min_weight, max_residual, T16_out, report8, loss_history ? &history : nullptr);
+    if (loss_history) std::copy(history.begin(), history.end(), loss_history);
+    return rc;
+}
+int xs_host_align_seeded_maps(const double *T16, double vs_this, double vs_other, float *out144) {
+    return xs_host::align_seeded_maps(T16, vs_this, vs_other, reinterpret_cast<float (*)[24]>(out144)) ? 0 : -1;
+}
+int xs_host_align_step(const double *s29, double damping, double *T16) { return xs_host::align_step(s29, damping, T16) ? 0 : -1; }
 int xs_host_merge_affine(const double *T16, double dst_voxel_size, double src_voxel_size, float *out12) {
     return xs_host::merge_affine(T16, dst_voxel_size, src_voxel_size, out12) ? 0 : -1;
 }

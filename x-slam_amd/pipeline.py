@@ -91,6 +91,7 @@ _SIGS = {
     "xs_kf_hint_next_frame": (None, [_vp, _vp, _sz]),
     "xs_kf_list_cover_counts": (None, [_vp, C.POINTER(C.c_longlong)]),
     "xs_kf_cumulative_counters": (None, [_vp, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]),
+    "xs_kf_volume_generation": (C.c_longlong, [_vp]),
     "xs_kf_save_checkpoint": (C.c_int, [_vp, C.c_char_p]),
     "xs_kf_load_checkpoint": (C.c_int, [_vp, C.c_char_p]),
     "xs_kf_save_tsdf_volume": (C.c_int, [_vp, C.c_char_p]),
@@ -100,6 +101,10 @@ _SIGS = {
     "xs_host_merge_affine": (C.c_int, [_f64p, C.c_double, C.c_double, _f32p]),
     "xs_host_map_transform": (C.c_int, [_f64p, _f64p, _f64p]),
     "xs_host_merge_tile_box": (C.c_int, [_f32p, _i32p, _i32p, _i32p, _i32p]),
+    "xs_kf_align_map": (C.c_int, [_vp, _vp, _f64p, C.c_int, C.c_int, C.c_double, C.c_int, C.c_float, _f64p, _f64p, _f64p]),
+    "xs_kf_align_checkpoint": (C.c_int, [_vp, C.c_char_p, _f64p, C.c_int, C.c_int, C.c_double, C.c_int, C.c_float, _f64p, _f64p, _f64p]),
+    "xs_host_align_seeded_maps": (C.c_int, [_f64p, C.c_double, C.c_double, _f32p]),
+    "xs_host_align_step": (C.c_int, [_f64p, C.c_double, _f64p]),
     "xs_refshape_create": (_vp, [C.c_char_p]),
     "xs_refshape_destroy": (None, [_vp]),
     "xs_refshape_process_frame_host": (C.c_int, [_vp, _vp]),
@@ -202,6 +207,26 @@ def map_transform(c2v_this, c2v_other):
     out = np.zeros((4, 4), np.float64)
     _lib.xs_host_map_transform(a.ctypes.data_as(_f64p), b.ctypes.data_as(_f64p), out.ctypes.data_as(_f64p))
     return out
+
+
+def align_seeded_maps(T, vs_this, vs_other):
+    """The six complex-seeded index maps of one alignment pass (float32 [6, 12, 2]: xform12's entries as (re, im)) from T (real 4 x 4, as
+    merge_affine takes it): T_k = (I + i h G_k) T through merge_affine's formula, three translations then three rotations.  The real parts
+    are merge_affine's bit for bit (CPU).  ValueError: merge_affine's refusals."""
+    t = _real44(T)
+    out = np.zeros((6, 12, 2), np.float32)
+    if _lib.xs_host_align_seeded_maps(t.ctypes.data_as(_f64p), float(vs_this), float(vs_other), out.ctypes.data_as(_f32p)) != 0:
+        raise ValueError("align_seeded_maps: an input is not finite, or a voxel size is not positive")
+    return out
+
+
+def align_step(s29, damping, T):
+    """One damped Gauss-Newton step on the 29 scaled sums of an alignment pass: (taken, T [4, 4] float64) with T <- exp(delta) T; not taken
+    (T unchanged) when count < 6 or A + damping diag(A) is not positive definite (CPU)."""
+    s = np.ascontiguousarray(s29, dtype=np.float64).reshape(29)
+    t = _real44(T).copy()
+    rc = _lib.xs_host_align_step(s.ctypes.data_as(_f64p), float(damping), t.ctypes.data_as(_f64p))
+    return rc == 0, t
 
 
 def merge_tile_box(xform12, lo, hi, src_res):
@@ -807,6 +832,10 @@ class KinectFusion:
         """After writing the value array through volume_ptr: the ray march's sign map is rebuilt from the volume."""
         _lib.xs_kf_rebuild_sign_map(self.h)
 
+    def volume_generation(self):
+        """The version of the volume's contents: moves with every write of the volume, stays under calls that only read the map."""
+        return int(_lib.xs_kf_volume_generation(self.h))
+
     def save_checkpoint(self, path):
         _lib.xs_kf_save_checkpoint(self.h, path.encode())
 
@@ -842,6 +871,38 @@ class KinectFusion:
         t = _real44(np.eye(4) if T is None else T)
         n = C.c_ulonglong(0)
         return self._merge_call("xs_kf_merge_checkpoint", _lib.xs_kf_merge_checkpoint(self.h, path.encode(), t.ctypes.data_as(_f64p), int(min_weight), C.byref(n)), n)
+
+    def _align_call(self, name, source, T0, iterations, damping, min_weight, max_residual):
+        t = np.asarray(np.eye(4) if T0 is None else T0, dtype=np.float64)
+        t = np.ascontiguousarray(t.reshape(-1, 4, 4))
+        iterations = int(iterations)
+        out, report, hist = np.zeros((4, 4), np.float64), np.zeros(8, np.float64), np.zeros(max(iterations, 0) + 1, np.float64)
+        rc = getattr(_lib, name)(self.h, source, t.ctypes.data_as(_f64p), t.shape[0], iterations, float(damping), int(min_weight), float(max_residual),
+                                 out.ctypes.data_as(_f64p), report.ctypes.data_as(_f64p), hist.ctypes.data_as(_f64p))
+        if rc == -2:
+            raise capi.XsError(f"{name}: not available in shard mode")
+        if rc == -1:
+            raise ValueError(f"{name}: bad arguments (T not finite, iterations < 0, min_weight < 1, max_residual or damping out of range, the volume itself "
+                             "as source, a bad file or another truncation distance)")
+        if rc not in (0, 1):
+            raise ValueError(f"{name}: {rc}")
+        rep = {"start": int(report[0]), "count": int(report[1]), "sum_r2": float(report[2]), "loss": float(report[3]), "passes": int(report[4]),
+               "ended_ok": int(report[5]), "band_voxels": int(report[6])}
+        return rc == 1, (out if rc == 1 else t[0].copy()), rep, (hist.copy() if rc == 1 else hist[:0].copy())
+
+    def align_map(self, other, T0=None, iterations=10, damping=1e-3, min_weight=1, max_residual=1.0):
+        """Registers the map of `other` (another KinectFusion of this process) to this one, volume to volume, before a merge: damped Gauss-Newton
+        over this map's band voxels on "the other map resampled under T minus this map", at the sample positions merge_map(other, T) will use.
+        T0: a starting guess as merge_map takes T (None: the identity), or a stack [N, 4, 4] of them, refined together; the best by
+        S = count - sum r^2 wins.  Returns (ok, T [4, 4] float64, report dict, loss history [iterations + 1]); ok False (T = the first start) when
+        no start kept six voxels on every pass and a positive definite system.  Nothing is modified.  XsError in shard mode, ValueError on bad arguments.
+        Intended use: kf.merge_map(other, kf.align_map(other, T_guess)[1])."""
+        return self._align_call("xs_kf_align_map", other.h, T0, iterations, damping, min_weight, max_residual)
+
+    def align_checkpoint(self, path, T0=None, iterations=10, damping=1e-3, min_weight=1, max_residual=1.0):
+        """align_map with the other map read from a checkpoint file of a whole volume (save_checkpoint), validated as merge_checkpoint does.
+        Intended use: kf.merge_checkpoint(path, kf.align_checkpoint(path, T_guess)[1])."""
+        return self._align_call("xs_kf_align_checkpoint", path.encode(), T0, iterations, damping, min_weight, max_residual)
 
 
 class ReferenceCallShape:
