@@ -705,6 +705,37 @@ int xs_tsdf_align_terms(int transforms, const xs_band_index *index, const float 
                         const int *src_res, const float *maps144xN, int min_weight, float max_residual, void *workspace, double *out29xN_dev,
                         void *stream);
 
+/* ---- the loss of many map-to-map transforms in one pass over the band (xs_align.hip) ---------------------------
+ * No counterpart in the reference.  The loss and voxel count of "the other map resampled under m minus this map" over the band index of THIS
+ * map, for `transforms` (1 .. XS_ALIGN_SCORE_MAX_TRANSFORMS) real index maps in one launch: what xs_tsdf_score_poses_band is to a depth frame.
+ * Real-valued: no seeds, no derivative.  The index, the source and its layout: as for xs_tsdf_align_terms.  xform12xP: host array, transform
+ * p's xform12 (xs_host_merge_affine) at + 12 p.  Transform p's two doubles land at out2xP_dev + 2 p: {sum r^2, count}.
+ *
+ * Scored entries: index entries e = stride i, i = 0 .. ceil(count / stride) - 1 (stride 1: the whole band); scored entry i belongs to chunk
+ * i / 64, lane i % 64.  Scored entry (x, y, z, gt), transform p, m = xform12xP + 12 p; every operation float32 in the order written (the
+ * library is built with -ffp-contract=off):
+ *   1. g_a = ((m[3a] * float(x) + m[3a + 1] * float(y)) + m[3a + 2] * float(z)) + m[9 + a]: xs_tsdf_merge's step 1, and with
+ *      m = xs_host_merge_affine(T) the real part of xs_tsdf_align_terms' g_a, bit for bit.
+ *   2. The entry is dropped unless 0 <= g_a < float(S_a - 1) on every axis (xs_tsdf_align_terms' cell rule; a NaN fails).  b_a = floor(g_a),
+ *      f_a = g_a - float(b_a), c_a = 1.0f - f_a.
+ *   3. The entry is dropped, without loading a value, unless all eight corner weights b + {0, 1}^3 are >= min_weight.
+ *   4. F: along x, then y, then z, each stage lo * c_a + hi * f_a (done even where f_a == 0).
+ *   5. r = F - gt.  The entry is kept only if |r| <= max_residual (a NaN drops).
+ *   6. A kept entry adds the float32 product r * r and counts 1.
+ * Order (xs_tsdf_score_poses_band's): per (chunk, transform) a six-level pairwise float tree across the wave over kept-or-zero terms,
+ * everything after that in double, in an order that is a function of index->count and stride alone: two launches on the same inputs give
+ * the same bits, and transform p's two numbers do not depend on `transforms`, on p or on the other transforms.  All terms are >= 0, so
+ * |sum - sum of the float32 terms in double| <= 8 * 2^-24 * sum.  No floating-point atomics.  An index with count 0 yields zeros.
+ * Workspace: xs_tsdf_score_transforms_workspace_bytes(transforms) bytes (0 outside 1 .. XS_ALIGN_SCORE_MAX_TRANSFORMS): one arrival ticket per
+ * tile of 64 transforms in its first 256 bytes, the maps, the records.  Zero the first 256 bytes ONCE after allocation
+ * (xs_tsdf_reduce_workspace_init); every launch leaves each ticket at zero again.  One launch at a time per workspace.  No synchronisation.
+ * hipErrorInvalidValue, with nothing launched: xs_tsdf_align_terms' refusals, transforms outside 1 .. 4096, stride < 1. */
+#define XS_ALIGN_SCORE_MAX_TRANSFORMS 4096
+size_t xs_tsdf_score_transforms_workspace_bytes(int transforms);
+int xs_tsdf_score_transforms(int transforms, const xs_band_index *index, int stride, const float *src_value, const int *src_weight,
+                             size_t src_step, const int *src_res, const float *xform12xP, int min_weight, float max_residual, void *workspace,
+                             double *out2xP_dev, void *stream);
+
 /* ---- surface mesh (export; marching cubes with complex-step vertex derivatives) -------------------------------------------------------
  * No working counterpart in the reference (its extractMesh, ExtractPointCloud.cu:364-715, is never called).
  * Cube (x, y, z), x < X-1, y < Y-1, z in [z0, z1), is live when all 8 corners have weight >= min_weight and value < 0.99 and its corners

@@ -348,6 +348,62 @@ int xs_kf_align_checkpoint(void *kf, const char *path, const double *T16xN, int 
 int xs_host_align_seeded_maps(const double *T16, double vs_this, double vs_other, float *out144);
 int xs_host_align_step(const double *s29, double damping, double *T16);
 
+/* ---- Scoring many map-to-map transforms, and alignment with no initial guess (xs_tsdf_score_transforms in
+ * xslam_amd.h: the contract) ------------------------------------------------------------------------------------------------------------
+ * score_transforms: {sum r^2, count} of "the other map resampled under T minus this map" over every stride-th entry of this map's band index
+ * for each of the P transforms T16xP + 16 p (real 4 x 4, row-major, as xs_kf_merge_map takes T), in launches of 4096; out2xP + 2 p.  The
+ * device is drained first; nothing of either map is modified.  Return 1; 0 without a volume; -1 on bad arguments (xs_kf_align_map's for the
+ * other map, min_weight and max_residual, and P < 1, stride < 1, an entry of a T that is not finite); -2 in shard mode.
+ *
+ * align_map_global: xs_kf_align_map without a guess.  The two maps' band centroids give every candidate rotation its translation; round 0
+ * scores opts->candidates transforms of xs_host_align_search_free (or the opts->user_n transforms of opts->user_T16xN, when given) and keeps
+ * the opts->keep best by S = count - sum r^2; each of opts->rounds further rounds scores floor(candidates / keep) transforms of
+ * xs_host_align_search_around about every kept one (pivot: this map's centroid; boxes refine_t and refine_r, halved per round; a kept
+ * transform is entry 0 of its own group, so the best S never falls) and keeps the best again; the kept transforms then start
+ * xs_kf_align_map's loop over the full band, whose winner and "ended ok" rule decide.
+ * report12 = {the winner's rank after the last round, its S before refinement on the strided band, its count, sum r^2 and mean loss after
+ * refinement, scoring launches run, alignment passes run, starts that ended ok, band voxels, scored entries per transform, the distance
+ * of the other map's centroid from the image of this map's under the winner, 0}.
+ * The score cannot tell a map from its image under a symmetry of the scene: a symmetric scene has several equally good answers.
+ * opts NULL: the defaults, which xs_kf_align_search_defaults writes (box_t and refine_t: this map's truncation distance).  Otherwise every
+ * field is taken as given.  Return codes: xs_kf_align_map's, including 0 with T16_out untouched when no start ends ok (or a map has no band
+ * voxel); -1 also for a wrong struct_bytes, candidates < 1, keep outside 1 .. 32, rounds < 0, stride < 1, a box that is negative or not
+ * finite, user_n < 0 or user_n > 0 without user_T16xN; -2 in shard mode.  Nothing of either map is modified. */
+typedef struct xs_align_search_opts {
+    unsigned struct_bytes;        /* sizeof(xs_align_search_opts) */
+    int candidates;               /* 2048 */
+    int keep;                     /* 8 (1 .. 32) */
+    int rounds;                   /* 2 */
+    int stride;                   /* 4 */
+    int iterations;               /* 10 */
+    int min_weight;               /* 1 */
+    int user_n;                   /* 0 */
+    double box_t;                 /* metres; the truncation distance */
+    double refine_t;              /* metres; the truncation distance */
+    double refine_r;              /* radians; 0.25 */
+    double damping;               /* 1e-3 */
+    double max_residual;          /* 1 */
+    const double *user_T16xN;     /* NULL */
+} xs_align_search_opts;
+void xs_kf_align_search_defaults(void *kf, xs_align_search_opts *opts);
+int xs_kf_score_transforms(void *kf, void *other_kf, int P, const double *T16xP, int stride, int min_weight, float max_residual, double *out2xP);
+int xs_kf_score_transforms_checkpoint(void *kf, const char *path, int P, const double *T16xP, int stride, int min_weight, float max_residual,
+                                      double *out2xP);
+int xs_kf_align_map_global(void *kf, void *other_kf, const xs_align_search_opts *opts, double *T16_out, double *report12);
+int xs_kf_align_checkpoint_global(void *kf, const char *path, const xs_align_search_opts *opts, double *T16_out, double *report12);
+/* The host's side of the search (x-slam_amd/host/align_search_host.hpp).  CPU only, float64, deterministic.
+ * align_search_free: candidate i = 0 .. n - 1 has the rotation of Shoemake's uniform-quaternion map at (halton(i + 1, 2), halton(i + 1, 3),
+ * halton(i + 1, 5)) and the translation centroid_other - R centroid_this + box_t (2 halton(i + 1, {7, 11, 13}) - 1).
+ * align_search_around: entry 0 is T16 itself; entry i >= 1, with u = 2 halton(i, {2, 3, 5, 7, 11, 13}) - 1, is T16 turned by
+ * exp(box_r u[3:6]) (axis-angle) about the image of `pivot` under T16 and shifted by box_t u[0:3].
+ * Both return 0, or -1 (nothing written) for n < 1, a null pointer, an input that is not finite or a negative box.
+ * align_search_rank: the min(keep, P) indices with the highest S = count - sum r^2, best first, ties to the lower index; returns how many.
+ * band_centroid: (sum / count + 0.5) voxel_size per axis from exact integer sums over packed keys (x | y << 21 | z << 42); 0, or -1 for no key. */
+int xs_host_align_search_free(int n, const double *centroid_this3, const double *centroid_other3, double box_t, double *T16xN);
+int xs_host_align_search_around(const double *T16, const double *pivot3, double box_t, double box_r, int n, double *T16xN);
+int xs_host_align_search_rank(const double *out2xP, int P, int keep, int *idx_out);
+int xs_host_band_centroid(const unsigned long long *keys, long long count, double voxel_size, double *out3);
+
 /* ---- The reference's own call shape (x-slam_amd/host/reference_shape.hpp) ---------------------------------------------------------
  * The per-frame sequence of Experiments/test_xkinect_fusion/main.cpp:46-60 + KinectFusionReconstruction.cpp:147-332 over nothing but the
  * reference-signature launchers (bilateralFilter, pyrDown, createVMap / createNMap, estimateCombined per iteration, integrateTsdfVolume,

@@ -170,6 +170,8 @@ _SIGS = {
     "xs_tsdf_merge": (C.c_int, [_vp, _vp, _vp, _sz, _i32p, C.c_int, C.c_int, _vp, _vp, _vp, _sz, _i32p, _f32p, C.c_int, C.c_int, C.c_uint, _vp, _vp, _vp]),
     "xs_tsdf_align_workspace_bytes": (_sz, [C.c_int]),
     "xs_tsdf_align_terms": (C.c_int, [C.c_int, C.POINTER(BandIndex), _vp, _vp, _sz, _i32p, _f32p, C.c_int, C.c_float, _vp, _vp, _vp]),
+    "xs_tsdf_score_transforms_workspace_bytes": (_sz, [C.c_int]),
+    "xs_tsdf_score_transforms": (C.c_int, [C.c_int, C.POINTER(BandIndex), C.c_int, _vp, _vp, _sz, _i32p, _f32p, C.c_int, C.c_float, _vp, _vp, _vp]),
     "xs_mesh_workspace_bytes": (_sz, [_i32p, C.POINTER(MeshOpts)]),
     "xs_extract_mesh": (C.c_int, [_vp, _vp, _vp, _sz, _i32p, C.c_float, C.POINTER(MeshOpts), _vp, _vp, _vp, _vp, _sz, _vp, _sz, _vp,
                                   C.POINTER(_sz), C.POINTER(_sz), _vp]),
@@ -886,6 +888,25 @@ def tsdf_align_terms(index, src_value, src_weight, src_step, src_res, maps, min_
     s = _ia(src_res, 3)
     check(_lib.xs_tsdf_align_terms(m.size // 144, C.byref(index), _ptr(src_value), _ptr(src_weight), src_step, s.ctypes.data_as(_i32p), m.ctypes.data_as(_f32p),
                                    int(min_weight), float(max_residual), _ptr(workspace), _ptr(out29xN), _stream(stream)))
+
+
+ALIGN_SCORE_MAX_TRANSFORMS = 4096   # XS_ALIGN_SCORE_MAX_TRANSFORMS
+
+
+def tsdf_score_transforms_workspace_bytes(transforms):
+    """xs_tsdf_score_transforms_workspace_bytes (host only): tickets, maps and records for up to `transforms` transforms; 0 outside 1 .. 4096."""
+    return int(_lib.xs_tsdf_score_transforms_workspace_bytes(int(transforms)))
+
+
+def tsdf_score_transforms(index, stride, src_value, src_weight, src_step, src_res, xforms, min_weight, max_residual, workspace, out2xP, stream=None):
+    """xs_tsdf_score_transforms: {sum r^2, count} of P real index maps xforms [P, 12] float32 (merge_affine per transform) over every stride-th
+    entry of a built band index of THIS map against the value and weight arrays of the other map (device tensors or addresses of plane 0);
+    transform p's pair lands at out2xP[2 p : 2 p + 2] (float64 device tensor).  No synchronisation."""
+    m = np.ascontiguousarray(xforms, dtype=np.float32).reshape(-1)
+    assert m.size % 12 == 0, m.size
+    s = _ia(src_res, 3)
+    check(_lib.xs_tsdf_score_transforms(m.size // 12, C.byref(index), int(stride), _ptr(src_value), _ptr(src_weight), src_step, s.ctypes.data_as(_i32p),
+                                        m.ctypes.data_as(_f32p), int(min_weight), float(max_residual), _ptr(workspace), _ptr(out2xP), _stream(stream)))
 
 
 def align_seeded_maps(T, vs_this, vs_other):

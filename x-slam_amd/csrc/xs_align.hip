@@ -13,6 +13,9 @@
 // neighbours (the dense walk deals a wave one 64-voxel run of a row after the other), so their corners share cache lines; no LDS staging.
 // Every seed runs the whole complex interpolation: per voxel the float32 results are the contract's bit for bit, and the six real parts
 // are not assumed equal (they are, to the last bits, and the voxel counts only if all six keep it).
+//
+// k_align_score, after it: the same residual without seeds, for up to 4096 transforms in one pass, which finds the
+// transform the Gauss-Newton pass above starts from when nobody supplies one.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <string.h>
@@ -166,6 +169,209 @@ extern "C" int xs_tsdf_align_terms(int transforms, const xs_band_index *index, c
     hipStream_t st = (hipStream_t)stream;
     XS_CHECK(hipMemcpyAsync(ws + ALIGN_MAPS_OFFSET, maps144xN, (size_t)transforms * ALIGN_MAP_FLOATS * sizeof(float), hipMemcpyHostToDevice, st));
     hipLaunchKernelGGL(k_align_terms, dim3(nblocks, (unsigned)transforms), dim3(64, 4), 0, st, g);
+    XS_CHECK(hipGetLastError());
+    return 0;
+}
+
+// ---- many transforms, no derivative: the loss of every map-to-map hypothesis in one pass over the index ---------
+// k_band_score_poses' scheme (xs_band.hip) with the other MAP as what is sampled: the scored entries (every stride-th of the index) are cut
+// into chunks of 64; wave w of workgroup (b, tile) takes chunks 4 b + w, + 4 nblocks, ...; lane l decodes scored entry l of the chunk once and
+// then meets the tile's transforms 64 tile .. 64 tile + 63 one after the other.  The transform index is wave-uniform (a loop counter through
+// readfirstlane): the twelve floats of an index map arrive by scalar loads and stay in scalar registers.  Per (chunk, transform): r * r where
+// the per-entry contract of include/xslam_amd.h keeps the entry, 0 where it drops it (and in the tail of the last chunk), folded across the
+// wave by wave_tree_sum_f32, the count by ballot + popcount; lane (p mod 64) adds both to the double and the unsigned it keeps for transform
+// p.  A wave none of whose lanes lies inside the source, or none of whose lanes passes the weight gate, goes on to the next transform without
+// the loads: what it leaves out is the addition of +0.0 to a sum that is never -0.0, and of 0 to a count.  Then per workgroup: the four waves
+// in wave order, one record of 64 doubles + 64 counts, an arrival ticket per tile, and the tile's last workgroup adds the records in index
+// order.  Every step's order is a function of the index's count and the stride alone.
+enum { ASCORE_TILE = 64, ASCORE_XFORMS_OFFSET = 256, ASCORE_MAX_BLOCKS = 1024, ASCORE_RECORD_BYTES = ASCORE_TILE * (sizeof(double) + sizeof(unsigned)) };
+static_assert(XS_ALIGN_SCORE_MAX_TRANSFORMS / ASCORE_TILE * sizeof(unsigned) == ASCORE_XFORMS_OFFSET, "one ticket per tile in the first 256 bytes");
+struct AlignXform { float m[12]; };
+static size_t ascore_records_offset() { return ASCORE_XFORMS_OFFSET + (size_t)XS_ALIGN_SCORE_MAX_TRANSFORMS * sizeof(AlignXform); }
+
+struct AlignScoreArgs {
+    const unsigned long long *keys;
+    const float *values;
+    long long scored;                            // ceil(count / stride): scored entry i is index entry stride * i
+    long long stride;
+    const float *svalue; const int *sweight; size_t sstep;
+    int S[3];
+    int transforms;
+    const AlignXform *xforms;                    // [transforms], in the workspace
+    int min_weight;
+    float max_residual;
+    char *records;                               // [tiles][nblocks]{64 doubles, 64 unsigned}
+    unsigned *tickets;                           // [tiles], zero between launches
+    double *out;                                 // [transforms][2]
+};
+
+__global__ void __launch_bounds__(256) k_align_score(const AlignScoreArgs g) {
+    __shared__ double s_sum[4][ASCORE_TILE];
+    __shared__ unsigned s_cnt[4][ASCORE_TILE];
+    __shared__ unsigned s_last;
+    const int lane = threadIdx.x, wave = __builtin_amdgcn_readfirstlane(threadIdx.y), tid = wave * 64 + lane;
+    const unsigned nblocks = gridDim.x, bid = blockIdx.x, tile = blockIdx.y;
+    const int p0 = (int)tile * ASCORE_TILE, np = min(ASCORE_TILE, g.transforms - p0);   // (the last tile may be partial: its other lanes keep zeros)
+    const AlignXform *__restrict__ xforms = g.xforms + p0;
+    const float top0 = (float)(g.S[0] - 1), top1 = (float)(g.S[1] - 1), top2 = (float)(g.S[2] - 1);
+    double acc = 0.0;
+    unsigned cnt = 0;
+    const long long nchunks = (g.scored + 63) / 64;
+    for (long long c = (long long)bid * 4 + wave; c < nchunks; c += 4ll * nblocks) {
+        const long long i = c * 64 + lane;
+        const bool valid = i < g.scored;         // (the last chunk's tail: masked, and it adds zeros)
+        unsigned long long key = 0;
+        float gt = 0.f;
+        if (valid) { key = g.keys[i * g.stride]; gt = g.values[i * g.stride]; }
+        const float fx = (float)(int)(key & 0x1fffff), fy = (float)(int)((key >> 21) & 0x1fffff), fz = (float)(int)(key >> 42);
+#pragma unroll 1
+        for (int j = 0; j < np; ++j) {
+            const AlignXform M = xforms[__builtin_amdgcn_readfirstlane(j)];
+            const float *m = M.m;
+            const float g0 = ((m[0] * fx + m[1] * fy) + m[2] * fz) + m[9];
+            const float g1 = ((m[3] * fx + m[4] * fy) + m[5] * fz) + m[10];
+            const float g2 = ((m[6] * fx + m[7] * fy) + m[8] * fz) + m[11];
+            const bool inside = valid && (g0 >= 0.f && g0 < top0) && (g1 >= 0.f && g1 < top1) && (g2 >= 0.f && g2 < top2);
+            if (__ballot(inside) == 0) continue;                 // the wave misses the source: the zeros it would add change no bit
+            int ws = 0, b0 = 0;
+            const int *wrow[4];
+            const float *vrow[4];
+            float f0 = 0.f, f1 = 0.f, f2 = 0.f;
+            if (inside) {
+                b0 = __float2int_rd(g0);                         // 0 <= b <= S - 2: both corners of the axis are inside the source
+                const int b1 = __float2int_rd(g1), b2 = __float2int_rd(g2);
+                f0 = g0 - (float)b0; f1 = g1 - (float)b1; f2 = g2 - (float)b2;
+#pragma unroll
+                for (int d = 0; d < 4; ++d) {                    // d: bit 0 = +y, bit 1 = +z
+                    const int row = g.S[1] * (b2 + (d >> 1)) + b1 + (d & 1);
+                    wrow[d] = row_ptr(g.sweight, g.sstep, row);
+                    vrow[d] = row_ptr(g.svalue, g.sstep, row);
+                }
+                int w[8];                                        // the eight loads in flight together
+#pragma unroll
+                for (int d = 0; d < 8; ++d) w[d] = wrow[d >> 1][b0 + (d & 1)];
+                ws = w[0];
+#pragma unroll
+                for (int d = 1; d < 8; ++d) ws = min(ws, w[d]);
+            }
+            const bool heavy = inside && ws >= g.min_weight;
+            if (__ballot(heavy) == 0) continue;                  // no lane passes the weight gate: no value is loaded
+            float rr = 0.f;
+            bool kept = false;
+            if (heavy) {
+                float v[8];                                      // corner d: bit 0 = +x, bit 1 = +y, bit 2 = +z
+#pragma unroll
+                for (int d = 0; d < 8; ++d) v[d] = vrow[d >> 1][b0 + (d & 1)];
+                const float c0 = 1.0f - f0, c1 = 1.0f - f1, c2 = 1.0f - f2;
+                const float x00 = v[0] * c0 + v[1] * f0, x10 = v[2] * c0 + v[3] * f0;
+                const float x01 = v[4] * c0 + v[5] * f0, x11 = v[6] * c0 + v[7] * f0;
+                const float y0 = x00 * c1 + x10 * f1, y1 = x01 * c1 + x11 * f1;
+                const float F = y0 * c2 + y1 * f2;
+                const float r = F - gt;
+                kept = fabsf(r) <= g.max_residual;               // (a NaN drops)
+                rr = kept ? r * r : 0.f;
+            }
+            const float s = wave_tree_sum_f32(rr);
+            const unsigned n = (unsigned)__popcll(__ballot(kept));
+            if (lane == j) { acc += (double)s; cnt += n; }
+        }
+    }
+    // the four waves in wave order, then one record per workgroup: transform lane's sum and count, stored by the lanes of wave 0
+    s_sum[wave][lane] = acc;
+    s_cnt[wave][lane] = cnt;
+    __syncthreads();
+    char *tile_records = g.records + (size_t)tile * nblocks * ASCORE_RECORD_BYTES;
+    if (tid < ASCORE_TILE) {
+        const double s = ((s_sum[0][tid] + s_sum[1][tid]) + s_sum[2][tid]) + s_sum[3][tid];
+        const unsigned n = ((s_cnt[0][tid] + s_cnt[1][tid]) + s_cnt[2][tid]) + s_cnt[3][tid];
+        char *rec = tile_records + (size_t)bid * ASCORE_RECORD_BYTES;
+        __hip_atomic_store(reinterpret_cast<double *>(rec) + tid, s, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_store(reinterpret_cast<unsigned *>(rec + ASCORE_TILE * sizeof(double)) + tid, n, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    // the hand-off of block_fold_and_finish_of (xs_gn_band.h): write-through record stores by wave 0, acknowledged, then its first lane's ticket
+    if (wave == 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    if (tid == 0) {
+        const unsigned tk = __hip_atomic_fetch_add(g.tickets + tile, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        s_last = tk == nblocks - 1 ? 1u : 0u;
+        if (s_last) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    }
+    __syncthreads();
+    if (!s_last) return;
+    // the tile's last workgroup: thread (q, l) adds transform l's records q, q + 4, ... in that order, eight loads in flight; the four row
+    // groups are then added in group order
+    {
+        const int l = tid % ASCORE_TILE, q = tid / ASCORE_TILE;
+        double s = 0.0;
+        unsigned long long n = 0;
+        auto rsum = [&](unsigned b) { return reinterpret_cast<const double *>(tile_records + (size_t)b * ASCORE_RECORD_BYTES)[l]; };
+        auto rcnt = [&](unsigned b) { return reinterpret_cast<const unsigned *>(tile_records + (size_t)b * ASCORE_RECORD_BYTES + ASCORE_TILE * sizeof(double))[l]; };
+        unsigned b = q;
+        for (; b + 4 * 7 < nblocks; b += 4 * 8) {
+            double v[8]; unsigned m[8];
+#pragma unroll
+            for (int k = 0; k < 8; ++k) { v[k] = rsum(b + 4 * k); m[k] = rcnt(b + 4 * k); }
+#pragma unroll
+            for (int k = 0; k < 8; ++k) { s += v[k]; n += m[k]; }
+        }
+        for (; b < nblocks; b += 4) { s += rsum(b); n += rcnt(b); }
+        __shared__ unsigned long long s_n[4][ASCORE_TILE];
+        s_sum[q][l] = s;   // (wave 0 read its workgroup's own sums before the ticket's barrier)
+        s_n[q][l] = n;
+        __syncthreads();
+        if (tid < np) {
+            g.out[2 * (size_t)(p0 + tid)] = ((s_sum[0][tid] + s_sum[1][tid]) + s_sum[2][tid]) + s_sum[3][tid];
+            g.out[2 * (size_t)(p0 + tid) + 1] = (double)(((s_n[0][tid] + s_n[1][tid]) + s_n[2][tid]) + s_n[3][tid]);
+        }
+        // the ticket goes back to zero for the next launch on this workspace (xs_tsdf_reduce_workspace_init zeroes it once)
+        if (tid == 0) __hip_atomic_store(g.tickets + tile, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+}
+
+extern "C" size_t xs_tsdf_score_transforms_workspace_bytes(int transforms) {
+    if (transforms < 1 || transforms > XS_ALIGN_SCORE_MAX_TRANSFORMS) return 0;
+    const size_t tiles = ((size_t)transforms + ASCORE_TILE - 1) / ASCORE_TILE;
+    return ascore_records_offset() + tiles * ASCORE_MAX_BLOCKS * ASCORE_RECORD_BYTES;
+}
+
+/* see include/xslam_amd.h */
+extern "C" int xs_tsdf_score_transforms(int transforms, const xs_band_index *index, int stride, const float *src_value, const int *src_weight,
+                                        size_t src_step, const int *src_res, const float *xform12xP, int min_weight, float max_residual,
+                                        void *workspace, double *out2xP_dev, void *stream) {
+    if (transforms < 1 || transforms > XS_ALIGN_SCORE_MAX_TRANSFORMS)
+        return xs_set_error(hipErrorInvalidValue, "xs_tsdf_score_transforms: transforms outside 1 .. XS_ALIGN_SCORE_MAX_TRANSFORMS");
+    if (stride < 1) return xs_set_error(hipErrorInvalidValue, "xs_tsdf_score_transforms: stride below 1");
+    if (!index || !src_value || !src_weight || !src_res || !xform12xP || !workspace || !out2xP_dev)
+        return xs_set_error(hipErrorInvalidValue, "xs_tsdf_score_transforms: null pointer");
+    if (index->nblocks < 1 || index->count < 0 || index->count > index->capacity || (index->count > 0 && (!index->keys || !index->values)))
+        return xs_set_error(hipErrorInvalidValue, "xs_tsdf_score_transforms: the index was not built");
+    for (int k = 0; k < 3; ++k)
+        if (src_res[k] < 2 || src_res[k] > 65535 * 4) return xs_set_error(hipErrorInvalidValue, "xs_tsdf_score_transforms: a source axis outside 2 .. 262140");
+    if ((long long)src_res[1] * (long long)src_res[2] >= (1ll << 31)) return xs_set_error(hipErrorInvalidValue, "xs_tsdf_score_transforms: the source's rows do not fit an int");
+    if (src_step % 4 != 0 || src_step < (size_t)src_res[0] * 4) return xs_set_error(hipErrorInvalidValue, "xs_tsdf_score_transforms: bad pitch");
+    if (min_weight < 1) return xs_set_error(hipErrorInvalidValue, "xs_tsdf_score_transforms: min_weight below 1");
+    if (!(max_residual > 0.f) || !isfinite(max_residual)) return xs_set_error(hipErrorInvalidValue, "xs_tsdf_score_transforms: max_residual is not finite and positive");
+    for (size_t i = 0; i < (size_t)transforms * 12; ++i)
+        if (!isfinite(xform12xP[i])) return xs_set_error(hipErrorInvalidValue, "xs_tsdf_score_transforms: a map entry is not finite");
+    AlignScoreArgs g;
+    memset(&g, 0, sizeof(g));
+    g.keys = index->keys; g.values = index->values;
+    g.stride = stride; g.scored = (index->count + stride - 1) / stride;
+    g.svalue = src_value; g.sweight = src_weight; g.sstep = src_step;
+    for (int k = 0; k < 3; ++k) g.S[k] = src_res[k];
+    g.transforms = transforms; g.min_weight = min_weight; g.max_residual = max_residual;
+    // as many workgroups per tile as give every wave a chunk, at most the record workspace's 1024: a function of the index and the stride alone
+    const long long nchunks = (g.scored + 63) / 64, want = (nchunks + 3) / 4;
+    const unsigned nblocks = (unsigned)(want < 1 ? 1 : (want > ASCORE_MAX_BLOCKS ? ASCORE_MAX_BLOCKS : want));
+    const unsigned tiles = ((unsigned)transforms + ASCORE_TILE - 1) / ASCORE_TILE;
+    char *ws = static_cast<char *>(workspace);
+    g.tickets = reinterpret_cast<unsigned *>(ws);
+    g.xforms = reinterpret_cast<const AlignXform *>(ws + ASCORE_XFORMS_OFFSET);
+    g.records = ws + ascore_records_offset();
+    g.out = out2xP_dev;
+    hipStream_t st = (hipStream_t)stream;
+    XS_CHECK(hipMemcpyAsync(ws + ASCORE_XFORMS_OFFSET, xform12xP, (size_t)transforms * sizeof(AlignXform), hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(k_align_score, dim3(nblocks, tiles), dim3(64, 4), 0, st, g);
     XS_CHECK(hipGetLastError());
     return 0;
 }

@@ -22,7 +22,6 @@
 //                                lane (p mod 64) of the wave.  The first question of a relocaliser: which of these hypotheses sees this map?
 #include <hip/hip_runtime.h>
 #include <string.h>
-#include <type_traits>
 #include <vector>
 #include "xs_gn_band.h"
 #include "../../include/xslam_amd.h"
@@ -311,19 +310,6 @@ enum { SCORE_TILE = 64, SCORE_POSES_OFFSET = 256, SCORE_MAX_BLOCKS = 1024, SCORE
 static_assert(XS_SCORE_MAX_POSES / SCORE_TILE * sizeof(unsigned) == SCORE_POSES_OFFSET, "one ticket per tile in the first 256 bytes");
 static_assert(sizeof(HessPoseF) == 12 * sizeof(float), "twelve floats per real pose");
 static size_t score_records_offset() { return SCORE_POSES_OFFSET + (size_t)XS_SCORE_MAX_POSES * sizeof(HessPoseF); }
-
-// all 64 lanes, all of them active: v[l] + v[l ^ 1], then ^ 2, 4, 8 (DPP within a row of 16), 16, 32 — a pairwise tree, the same bits in every lane
-// (float addition commutes)
-__device__ __forceinline__ float wave_tree_sum_f32(float v) {
-    auto dpp = [](float x, auto ctrl) { return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), decltype(ctrl)::value, 0xf, 0xf, false)); };
-    v += dpp(v, std::integral_constant<int, 0xb1>());    // quad_perm [1, 0, 3, 2]
-    v += dpp(v, std::integral_constant<int, 0x4e>());    // quad_perm [2, 3, 0, 1]
-    v += dpp(v, std::integral_constant<int, 0x141>());   // row_half_mirror: quad q with quad q ^ 1 (a quad's lanes are equal by now)
-    v += dpp(v, std::integral_constant<int, 0x140>());   // row_mirror: the row's halves
-    v += __shfl_xor(v, 16, 64);
-    v += __shfl_xor(v, 32, 64);
-    return v;
-}
 
 struct BandScoreArgs {
     HessArgs a;                                  // the residual's fields

@@ -2,8 +2,9 @@
 // record fold (registers -> wave -> LDS -> one record per workgroup -> the last workgroup adds the records in index order), the walk that
 // deals the band voxels (gt != 0, |gt| <= 0.95) of a slab out to the lanes, the six-pose CSFD residual of the Gauss-Newton pass, the
 // dual-complex squared residual of the Hessian kernels and the real-valued one of the loss kernels.
-// Included by exactly those two files, and by xs_align.hip for the record fold alone.
+// Included by exactly those two files, and by xs_align.hip for the record fold and the wave's float tree alone.
 #pragma once
+#include <type_traits>
 #include "xs_device.h"
 #include "xs_env.h"
 
@@ -33,6 +34,19 @@ struct HessArgs {
 };
 struct HessPoseD { MatD33 R; dcfloat3 t; };
 struct HessPoseF { float R[9]; float t[3]; };
+
+// all 64 lanes, all of them active: v[l] + v[l ^ 1], then ^ 2, 4, 8 (DPP within a row of 16), 16, 32 — a pairwise tree, the same bits in every lane
+// (float addition commutes)
+__device__ __forceinline__ float wave_tree_sum_f32(float v) {
+    auto dpp = [](float x, auto ctrl) { return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), decltype(ctrl)::value, 0xf, 0xf, false)); };
+    v += dpp(v, std::integral_constant<int, 0xb1>());    // quad_perm [1, 0, 3, 2]
+    v += dpp(v, std::integral_constant<int, 0x4e>());    // quad_perm [2, 3, 0, 1]
+    v += dpp(v, std::integral_constant<int, 0x141>());   // row_half_mirror: quad q with quad q ^ 1 (a quad's lanes are equal by now)
+    v += dpp(v, std::integral_constant<int, 0x140>());   // row_mirror: the row's halves
+    v += __shfl_xor(v, 16, 64);
+    v += __shfl_xor(v, 32, 64);
+    return v;
+}
 
 // The arrival ticket: bits 0 .. 15 count the workgroups that arrived (at most XS_TSDF_REDUCE_MAX_BLOCKS = 4096 per launch), bits 16 .. 31 those of
 // them that LEFT without summing (k_tsdf_gauss_newton<true>: told to, or their poses never came).  Every workgroup of a launch arrives exactly once,

@@ -17,6 +17,8 @@
 #include <string>
 #include <vector>
 
+struct xs_align_search_opts;   // include/xslam_amd_pipeline.h
+
 class KinectFusionReconstruction {
 public:
     typedef xs_host::Matrix3cf Matrix3frm;  // row-major complex 3x3
@@ -353,6 +355,29 @@ public:
     // The same against an XSTSDF2 file: MergeCheckpoint's validation, its temporary device volume and its free.
     int AlignCheckpoint(const std::string &filename, const double *T16xN, int N, int iterations, double damping, int min_weight, float max_residual,
                         double *T16_out, double report[8], std::vector<double> *loss_history);
+    // Many transforms against the other map in one band pass each, and alignment with no initial guess (DESIGN.md section 4.24;
+    // xs_tsdf_score_transforms in include/xslam_amd.h: the contract).  The source as for AlignVolume.
+    // ScoreTransformsVolume: the device is drained, the band index of THIS map prepared, every T16xP + 16 p put through merge_affine and
+    // scored over every stride-th band entry in launches of XS_ALIGN_SCORE_MAX_TRANSFORMS; out2xP + 2 p = {sum r^2, count}.  *launches
+    // (optional) is advanced by the launches run.  Returns 1; 0 without a volume; -1 on bad arguments (AlignVolume's for the source,
+    // min_weight and max_residual, and P < 1, stride < 1, an entry of a T that is not finite); -2 in shard mode.
+    // AlignVolumeGlobal: the search of align_search_host.hpp on top of it.  Both maps' band centroids (this map's from its index, the
+    // other's from one xs_tsdf_band_build over the source into temporary buffers), round 0 over align_search_free's candidates (or the
+    // caller's, when opts gives any), `rounds` rounds of align_search_around about each kept transform with the boxes halved per round,
+    // each scored and ranked by align_search_rank, then AlignVolume from the kept transforms over the full band: its winner and its
+    // "ended ok" decide.  opts null: the defaults (AlignSearchDefaults).  report12 = {the winner's rank after the last round, its S
+    // before refinement on the strided band, its count, sum r^2 and mean loss after refinement, scoring launches, alignment passes,
+    // starts that ended ok, band voxels, scored entries per transform, the distance of the other map's centroid from this map's under
+    // the winner, 0}.  Nothing of either map is modified.  Returns AlignVolume's codes (0 also when a map has an empty band); -1 also for
+    // candidates < 1, keep outside 1 .. 32, rounds < 0, stride < 1, a box that is negative or not finite, a wrong opts->struct_bytes.
+    int ScoreTransformsVolume(const float *src_value, const int *src_weight, size_t src_step, const int *src_res, float src_voxel_size,
+                              float src_tranc_dist, const double *T16xP, int P, int stride, int min_weight, float max_residual, double *out2xP,
+                              int *launches = nullptr);
+    int ScoreTransformsCheckpoint(const std::string &filename, const double *T16xP, int P, int stride, int min_weight, float max_residual, double *out2xP);
+    void AlignSearchDefaults(struct xs_align_search_opts *opts) const;
+    int AlignVolumeGlobal(const float *src_value, const int *src_weight, size_t src_step, const int *src_res, float src_voxel_size, float src_tranc_dist,
+                          const struct xs_align_search_opts *opts, double *T16_out, double report[12]);
+    int AlignCheckpointGlobal(const std::string &filename, const struct xs_align_search_opts *opts, double *T16_out, double report[12]);
 
     // counters of the last frame (synchronise the stream)
     long long lastUpdatedVoxels();
@@ -410,6 +435,8 @@ private:
         DeviceArray2D<float> score_depth;          // ScorePoses' scaled depth
         DeviceArray<unsigned char> align_ws;       // xs_tsdf_align_workspace_bytes(XS_ALIGN_MAX_TRANSFORMS)
         DeviceArray<double> align_sums;            // XS_ALIGN_MAX_TRANSFORMS x 29
+        DeviceArray<unsigned char> ascore_ws;      // xs_tsdf_score_transforms_workspace_bytes(XS_ALIGN_SCORE_MAX_TRANSFORMS)
+        DeviceArray<double> ascore_sums;           // XS_ALIGN_SCORE_MAX_TRANSFORMS x 2
     } reloc_;
     const float *GaussNewtonDenseView();       // the owned planes as the dense array the Gauss-Newton kernels index (packed into gn_dense when pitched)
     void BandIndexPrepare();                   // (re)builds the band index when the volume changed since it was built

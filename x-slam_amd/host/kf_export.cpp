@@ -1,9 +1,11 @@
 // kf_export.cpp — what leaves the orchestrator: point cloud and mesh with their PLY writers, the last frame's counters, the raw volume
-// and the checkpoint; and what enters it as a whole map: a second volume or checkpoint merged into this one, and aligned to it beforehand.
+// and the checkpoint; and what enters it as a whole map: a second volume or checkpoint merged into this one, and aligned to it beforehand, from a guess or from none.
 // None of it runs during tracking.
 #include "kf_internal.hpp"
 #include "align_host.hpp"
+#include "align_search_host.hpp"
 #include "merge_host.hpp"
+#include "../../include/xslam_amd_pipeline.h"   // xs_align_search_opts
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
@@ -393,4 +395,197 @@ int KinectFusionReconstruction::AlignCheckpoint(const std::string &filename, con
     if (!upload_whole_checkpoint(filename, tsdf_volume_d_ptr->getTsdfTruncDist(), c)) return -1;
     return AlignVolume(c.dv.ptr(0), c.dw.ptr(0), c.dv.step(), c.h.res, c.h.voxel_size, c.h.tranc_dist, T16xN, N, iterations, damping, min_weight, max_residual,
                        T16_out, report, loss_history);
+}
+
+// ---- many transforms against the other map, and alignment with no initial guess --------------------------------
+namespace {
+// the other map of a scoring call or a search, as AlignVolume checks its own
+bool other_map_ok(const KinectFusionReconstruction &k, const float *src_value, const int *src_weight, size_t src_step, const int *src_res, float src_voxel_size,
+                  float src_tranc_dist) {
+    if (!src_value || !src_weight || !src_res) return false;
+    for (int a = 0; a < 3; ++a)
+        if (src_res[a] < 2) return false;
+    if (!(src_voxel_size > 0.f) || !std::isfinite(src_voxel_size) || src_tranc_dist != k.tsdf_volume_d_ptr->getTsdfTruncDist()) return false;
+    if (src_value == k.tsdf_volume_d_ptr->value().ptr(0) || src_weight == k.tsdf_volume_d_ptr->weight().ptr(0)) return false;
+    return src_step % 4 == 0 && src_step >= (size_t)src_res[0] * 4;
+}
+}  // namespace
+int KinectFusionReconstruction::ScoreTransformsVolume(const float *src_value, const int *src_weight, size_t src_step, const int *src_res, float src_voxel_size,
+                                                      float src_tranc_dist, const double *T16xP, int P, int stride, int min_weight, float max_residual,
+                                                      double *out2xP, int *launches) {
+    if (shard_count > 1) return -2;   // as AlignVolume: a rank's band index holds its own planes
+    if (!tsdf_volume_d_ptr) return 0;
+    if (!T16xP || !out2xP || P < 1 || stride < 1 || min_weight < 1 || !(max_residual > 0.f) || !std::isfinite(max_residual)) return -1;
+    if (!other_map_ok(*this, src_value, src_weight, src_step, src_res, src_voxel_size, src_tranc_dist)) return -1;
+    std::vector<float> xforms((size_t)P * 12);
+    for (int p = 0; p < P; ++p)
+        if (!merge_affine(T16xP + 16 * (size_t)p, (double)voxel_size, (double)src_voxel_size, &xforms[(size_t)p * 12])) return -1;
+    // the source may belong to another instance with streams of its own: drain the device, not just this instance's stream
+    synchronize();
+    hipSafeCall(hipDeviceSynchronize());
+    BandIndexPrepare();
+    ensure_reduce_workspace(reloc_.ascore_ws, xs_tsdf_score_transforms_workspace_bytes(XS_ALIGN_SCORE_MAX_TRANSFORMS), "transform score workspace");
+    if (reloc_.ascore_sums.size() < (size_t)XS_ALIGN_SCORE_MAX_TRANSFORMS * 2) reloc_.ascore_sums.create((size_t)XS_ALIGN_SCORE_MAX_TRANSFORMS * 2);
+    for (int p0 = 0; p0 < P; p0 += XS_ALIGN_SCORE_MAX_TRANSFORMS) {
+        const int n = std::min(P - p0, (int)XS_ALIGN_SCORE_MAX_TRANSFORMS);
+        check_rc(xs_tsdf_score_transforms(n, &reloc_.band, stride, src_value, src_weight, src_step, src_res, &xforms[(size_t)p0 * 12], min_weight, max_residual,
+                                          reloc_.ascore_ws.ptr(), reloc_.ascore_sums.ptr(), current_stream()), "ScoreTransforms");
+        fetch_sums(reloc_.ascore_sums.ptr(), (size_t)n * 2, out2xP + 2 * (size_t)p0);
+        if (launches) ++*launches;
+    }
+    return 1;
+}
+
+int KinectFusionReconstruction::ScoreTransformsCheckpoint(const std::string &filename, const double *T16xP, int P, int stride, int min_weight, float max_residual,
+                                                          double *out2xP) {
+    if (shard_count > 1) return -2;
+    if (!tsdf_volume_d_ptr) return 0;
+    if (!T16xP || !out2xP || P < 1) return -1;
+    CkptVolume c;
+    if (!upload_whole_checkpoint(filename, tsdf_volume_d_ptr->getTsdfTruncDist(), c)) return -1;
+    return ScoreTransformsVolume(c.dv.ptr(0), c.dw.ptr(0), c.dv.step(), c.h.res, c.h.voxel_size, c.h.tranc_dist, T16xP, P, stride, min_weight, max_residual, out2xP);
+}
+
+void KinectFusionReconstruction::AlignSearchDefaults(xs_align_search_opts *o) const {
+    if (!o) return;
+    std::memset(o, 0, sizeof(*o));
+    o->struct_bytes = sizeof(*o);
+    o->candidates = 2048; o->keep = 8; o->rounds = 2; o->stride = 4; o->iterations = 10; o->min_weight = 1;
+    o->box_t = o->refine_t = tsdf_volume_d_ptr ? (double)tsdf_volume_d_ptr->getTsdfTruncDist() : 0.0;
+    o->refine_r = 0.25; o->damping = 1e-3; o->max_residual = 1.0;
+}
+
+namespace {
+// what the search itself refuses (AlignVolume and ScoreTransformsVolume refuse the rest)
+bool search_opts_ok(const xs_align_search_opts &o) {
+    if (o.struct_bytes != sizeof(xs_align_search_opts)) return false;
+    if (o.candidates < 1 || o.keep < 1 || o.keep > 32 || o.rounds < 0 || o.stride < 1 || o.iterations < 0 || o.min_weight < 1) return false;
+    for (double b : {o.box_t, o.refine_t, o.refine_r})
+        if (!(b >= 0.0) || !std::isfinite(b)) return false;
+    if (!(o.damping >= 0.0) || !std::isfinite(o.damping) || !(o.max_residual > 0.0) || !std::isfinite((double)(float)o.max_residual)) return false;
+    if (o.user_n < 0 || (o.user_n > 0 && !o.user_T16xN)) return false;
+    return true;
+}
+}  // namespace
+
+int KinectFusionReconstruction::AlignVolumeGlobal(const float *src_value, const int *src_weight, size_t src_step, const int *src_res, float src_voxel_size,
+                                                  float src_tranc_dist, const xs_align_search_opts *opts, double *T16_out, double report[12]) {
+    if (report) { for (int i = 0; i < 12; ++i) report[i] = 0.0; report[0] = -1.0; }
+    if (shard_count > 1) return -2;
+    if (!tsdf_volume_d_ptr) return 0;
+    xs_align_search_opts o;
+    if (opts) o = *opts; else AlignSearchDefaults(&o);
+    if (!T16_out || !search_opts_ok(o) || !other_map_ok(*this, src_value, src_weight, src_step, src_res, src_voxel_size, src_tranc_dist)) return -1;
+    const float max_residual = (float)o.max_residual;
+    // the source may belong to another instance with streams of its own: drain the device, not just this instance's stream
+    synchronize();
+    hipSafeCall(hipDeviceSynchronize());
+    BandIndexPrepare();
+    std::vector<double> cand, out2;
+    int launches = 0;
+    auto score = [&]() {
+        out2.resize(cand.size() / 16 * 2);
+        return ScoreTransformsVolume(src_value, src_weight, src_step, src_res, src_voxel_size, src_tranc_dist, cand.data(), (int)(cand.size() / 16), o.stride,
+                                     o.min_weight, max_residual, out2.data(), &launches);
+    };
+    const long long band_n = reloc_.band.count;
+    if (report) { report[8] = (double)band_n; report[9] = (double)((band_n + o.stride - 1) / o.stride); }
+    // this map's centroid from its band index, the keys downloaded once
+    double c_this[3], c_other[3];
+    {
+        std::vector<unsigned long long> keys((size_t)band_n);
+        if (band_n > 0) hipSafeCall(hipMemcpy(keys.data(), reloc_.band.keys, (size_t)band_n * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+        if (!band_centroid(keys.data(), band_n, (double)voxel_size, c_this)) return 0;
+    }
+    // the other map's from one band build over the source (count, then fill) into temporary buffers: the other instance's caches stay
+    {
+        hipStream_t st = current_stream();
+        const int X = src_res[0];
+        const size_t rows = (size_t)src_res[1] * (size_t)src_res[2];
+        DeviceArray<float> packed;
+        const float *dense = src_value;
+        if (src_step != (size_t)X * 4) {   // the band walk indexes a dense array
+            packed.create(rows * (size_t)X);
+            hipSafeCall(hipMemcpy2DAsync(packed.ptr(), (size_t)X * 4, src_value, src_step, (size_t)X * 4, rows, hipMemcpyDeviceToDevice, st));
+            dense = packed.ptr();
+        }
+        const size_t segs_bytes = xs_tsdf_band_segs_bytes(src_res, 0, src_res[2]);
+        if (segs_bytes == 0) return -1;
+        DeviceArray<long long> segs;
+        segs.create(segs_bytes / sizeof(long long));
+        DeviceArray<unsigned long long> keys_d;
+        DeviceArray<float> values_d;
+        xs_band_index idx = {};
+        idx.segs = segs.ptr();
+        int rc = xs_tsdf_band_build(dense, src_res, 0, src_res[2], &idx, st);
+        if (rc == XS_BAND_OVER_CAPACITY) {
+            keys_d.create((size_t)idx.count);
+            values_d.create((size_t)idx.count);
+            idx.keys = keys_d.ptr(); idx.values = values_d.ptr(); idx.capacity = idx.count;
+            rc = xs_tsdf_band_build(dense, src_res, 0, src_res[2], &idx, st);
+        }
+        check_rc(rc, "the other map's band");
+        std::vector<unsigned long long> keys((size_t)idx.count);
+        if (idx.count > 0) hipSafeCall(hipMemcpy(keys.data(), idx.keys, (size_t)idx.count * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+        if (!band_centroid(keys.data(), idx.count, (double)src_voxel_size, c_other)) return 0;
+    }
+    if (o.user_n > 0) cand.assign(o.user_T16xN, o.user_T16xN + 16 * (size_t)o.user_n);
+    else {
+        cand.resize((size_t)o.candidates * 16);
+        if (!align_search_free(o.candidates, c_this, c_other, o.box_t, cand.data())) return -1;
+    }
+    std::vector<double> kept, kept_S;
+    auto rank = [&]() {
+        int idx[32];
+        const int K = align_search_rank(out2.data(), (int)(out2.size() / 2), o.keep, idx);
+        kept.resize((size_t)K * 16);
+        kept_S.resize((size_t)K);
+        for (int k = 0; k < K; ++k) {
+            std::copy(&cand[(size_t)idx[k] * 16], &cand[(size_t)idx[k] * 16] + 16, &kept[(size_t)k * 16]);
+            kept_S[(size_t)k] = score_S(&out2[2 * (size_t)idx[k]]);
+        }
+    };
+    int rc = score();
+    if (rc != 1) return rc;
+    rank();
+    const int per = std::max(1, o.candidates / o.keep);
+    double bt = o.refine_t, br = o.refine_r;
+    for (int r = 1; r <= o.rounds; ++r, bt *= 0.5, br *= 0.5) {
+        const int K = (int)kept_S.size();
+        cand.resize((size_t)K * per * 16);
+        for (int k = 0; k < K; ++k)
+            if (!align_search_around(&kept[(size_t)k * 16], c_this, bt, br, per, &cand[(size_t)k * per * 16])) return -1;
+        rc = score();
+        if (rc != 1) return rc;
+        rank();
+    }
+    if (report) report[5] = (double)launches;
+    double r8[8];
+    double T[16];
+    rc = AlignVolume(src_value, src_weight, src_step, src_res, src_voxel_size, src_tranc_dist, kept.data(), (int)kept_S.size(), o.iterations, o.damping, o.min_weight,
+                     max_residual, T, r8, nullptr);
+    if (report) { report[6] = r8[4]; report[7] = r8[5]; }
+    if (rc != 1) return rc;
+    for (int i = 0; i < 16; ++i) T16_out[i] = T[i];
+    if (report) {
+        report[0] = r8[0]; report[1] = kept_S[(size_t)r8[0]];
+        report[2] = r8[1]; report[3] = r8[2]; report[4] = r8[3];
+        double d2 = 0.0;
+        for (int a = 0; a < 3; ++a) {
+            const double q = ((T[4 * a] * c_this[0] + T[4 * a + 1] * c_this[1]) + T[4 * a + 2] * c_this[2]) + T[4 * a + 3];
+            d2 += (q - c_other[a]) * (q - c_other[a]);
+        }
+        report[10] = std::sqrt(d2);
+    }
+    return 1;
+}
+
+int KinectFusionReconstruction::AlignCheckpointGlobal(const std::string &filename, const xs_align_search_opts *opts, double *T16_out, double report[12]) {
+    if (report) { for (int i = 0; i < 12; ++i) report[i] = 0.0; report[0] = -1.0; }
+    if (shard_count > 1) return -2;
+    if (!tsdf_volume_d_ptr) return 0;
+    if (!T16_out || (opts && !search_opts_ok(*opts))) return -1;
+    CkptVolume c;
+    if (!upload_whole_checkpoint(filename, tsdf_volume_d_ptr->getTsdfTruncDist(), c)) return -1;
+    return AlignVolumeGlobal(c.dv.ptr(0), c.dw.ptr(0), c.dv.step(), c.h.res, c.h.voxel_size, c.h.tranc_dist, opts, T16_out, report);
 }

@@ -4,6 +4,7 @@
 #include "DoubleComplex.h"
 #include "KinectFusionReconstruction.h"
 #include "align_host.hpp"
+#include "align_search_host.hpp"
 #include "merge_host.hpp"
 #include "newton_host.hpp"
 #include <cstring>
@@ -506,6 +507,48 @@ int xs_host_align_seeded_maps(const double *T16, double vs_this, double vs_other
     return xs_host::align_seeded_maps(T16, vs_this, vs_other, reinterpret_cast<float (*)[24]>(out144)) ? 0 : -1;
 }
 int xs_host_align_step(const double *s29, double damping, double *T16) { return xs_host::align_step(s29, damping, T16) ? 0 : -1; }
+void xs_kf_align_search_defaults(void *kf, xs_align_search_opts *opts) { ((KF *)kf)->AlignSearchDefaults(opts); }
+int xs_kf_score_transforms(void *kf, void *other_kf, int P, const double *T16xP, int stride, int min_weight, float max_residual, double *out2xP) {
+    KF *k = (KF *)kf, *o = (KF *)other_kf;
+    if (!o || o == k) return -1;
+    if (o->shard_count > 1) return -2;
+    if (!o->tsdf_volume_d_ptr) return -1;
+    o->synchronize();
+    auto v = o->tsdf_volume_d_ptr->value();   // (read only: nothing of the other map is touched)
+    auto w = o->tsdf_volume_d_ptr->weight();
+    if (v.step() != w.step()) return -1;
+    return k->ScoreTransformsVolume(v.ptr(), w.ptr(), v.step(), o->volume_resolution.v, o->voxel_size, o->tsdf_volume_d_ptr->getTsdfTruncDist(), T16xP, P, stride,
+                                    min_weight, max_residual, out2xP);
+}
+int xs_kf_score_transforms_checkpoint(void *kf, const char *path, int P, const double *T16xP, int stride, int min_weight, float max_residual, double *out2xP) {
+    if (!path) return -1;
+    return ((KF *)kf)->ScoreTransformsCheckpoint(path, T16xP, P, stride, min_weight, max_residual, out2xP);
+}
+int xs_kf_align_map_global(void *kf, void *other_kf, const xs_align_search_opts *opts, double *T16_out, double *report12) {
+    KF *k = (KF *)kf, *o = (KF *)other_kf;
+    if (!o || o == k) return -1;
+    if (o->shard_count > 1) return -2;
+    if (!o->tsdf_volume_d_ptr) return -1;
+    o->synchronize();
+    auto v = o->tsdf_volume_d_ptr->value();   // (read only: the other map's band index and caches stay as they are)
+    auto w = o->tsdf_volume_d_ptr->weight();
+    if (v.step() != w.step()) return -1;
+    return k->AlignVolumeGlobal(v.ptr(), w.ptr(), v.step(), o->volume_resolution.v, o->voxel_size, o->tsdf_volume_d_ptr->getTsdfTruncDist(), opts, T16_out, report12);
+}
+int xs_kf_align_checkpoint_global(void *kf, const char *path, const xs_align_search_opts *opts, double *T16_out, double *report12) {
+    if (!path) return -1;
+    return ((KF *)kf)->AlignCheckpointGlobal(path, opts, T16_out, report12);
+}
+int xs_host_align_search_free(int n, const double *centroid_this3, const double *centroid_other3, double box_t, double *T16xN) {
+    return xs_host::align_search_free(n, centroid_this3, centroid_other3, box_t, T16xN) ? 0 : -1;
+}
+int xs_host_align_search_around(const double *T16, const double *pivot3, double box_t, double box_r, int n, double *T16xN) {
+    return xs_host::align_search_around(T16, pivot3, box_t, box_r, n, T16xN) ? 0 : -1;
+}
+int xs_host_align_search_rank(const double *out2xP, int P, int keep, int *idx_out) { return xs_host::align_search_rank(out2xP, P, keep, idx_out); }
+int xs_host_band_centroid(const unsigned long long *keys, long long count, double voxel_size, double *out3) {
+    return xs_host::band_centroid(keys, count, voxel_size, out3) ? 0 : -1;
+}
 int xs_host_merge_affine(const double *T16, double dst_voxel_size, double src_voxel_size, float *out12) {
     return xs_host::merge_affine(T16, dst_voxel_size, src_voxel_size, out12) ? 0 : -1;
 }

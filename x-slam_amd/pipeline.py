@@ -20,6 +20,15 @@ _lib = C.CDLL(LIB_PATH)
 _vp, _sz = C.c_void_p, C.c_size_t
 _f32p, _f64p, _i32p = C.POINTER(C.c_float), C.POINTER(C.c_double), C.POINTER(C.c_int)
 COLLECTIVE_CB = C.CFUNCTYPE(None, C.c_void_p, C.c_int, C.c_void_p, C.c_long)  # (user, op, dev_ptr, count)
+
+
+class AlignSearchOpts(C.Structure):
+    """xs_align_search_opts (include/xslam_amd_pipeline.h)"""
+    _fields_ = [("struct_bytes", C.c_uint), ("candidates", C.c_int), ("keep", C.c_int), ("rounds", C.c_int), ("stride", C.c_int), ("iterations", C.c_int),
+                ("min_weight", C.c_int), ("user_n", C.c_int), ("box_t", C.c_double), ("refine_t", C.c_double), ("refine_r", C.c_double),
+                ("damping", C.c_double), ("max_residual", C.c_double), ("user_T16xN", C.POINTER(C.c_double))]
+
+
 _SIGS = {
     "xs_kf_create_sharded": (_vp, [C.c_char_p, C.c_int, C.c_int, COLLECTIVE_CB, _vp]),
     "xs_kf_shard_planes": (None, [_vp, _i32p, _i32p]),
@@ -105,6 +114,15 @@ _SIGS = {
     "xs_kf_align_checkpoint": (C.c_int, [_vp, C.c_char_p, _f64p, C.c_int, C.c_int, C.c_double, C.c_int, C.c_float, _f64p, _f64p, _f64p]),
     "xs_host_align_seeded_maps": (C.c_int, [_f64p, C.c_double, C.c_double, _f32p]),
     "xs_host_align_step": (C.c_int, [_f64p, C.c_double, _f64p]),
+    "xs_kf_align_search_defaults": (None, [_vp, C.POINTER(AlignSearchOpts)]),
+    "xs_kf_score_transforms": (C.c_int, [_vp, _vp, C.c_int, _f64p, C.c_int, C.c_int, C.c_float, _f64p]),
+    "xs_kf_score_transforms_checkpoint": (C.c_int, [_vp, C.c_char_p, C.c_int, _f64p, C.c_int, C.c_int, C.c_float, _f64p]),
+    "xs_kf_align_map_global": (C.c_int, [_vp, _vp, C.POINTER(AlignSearchOpts), _f64p, _f64p]),
+    "xs_kf_align_checkpoint_global": (C.c_int, [_vp, C.c_char_p, C.POINTER(AlignSearchOpts), _f64p, _f64p]),
+    "xs_host_align_search_free": (C.c_int, [C.c_int, _f64p, _f64p, C.c_double, _f64p]),
+    "xs_host_align_search_around": (C.c_int, [_f64p, _f64p, C.c_double, C.c_double, C.c_int, _f64p]),
+    "xs_host_align_search_rank": (C.c_int, [_f64p, C.c_int, C.c_int, _i32p]),
+    "xs_host_band_centroid": (C.c_int, [C.POINTER(C.c_uint64), C.c_longlong, C.c_double, _f64p]),
     "xs_refshape_create": (_vp, [C.c_char_p]),
     "xs_refshape_destroy": (None, [_vp]),
     "xs_refshape_process_frame_host": (C.c_int, [_vp, _vp]),
@@ -227,6 +245,47 @@ def align_step(s29, damping, T):
     t = _real44(T).copy()
     rc = _lib.xs_host_align_step(s.ctypes.data_as(_f64p), float(damping), t.ctypes.data_as(_f64p))
     return rc == 0, t
+
+
+def transform_candidates_free(n, centroid_this, centroid_other, box_t):
+    """n transforms [n, 4, 4] float64 that cover SO(3) with no guess (xs_host_align_search_free, CPU): candidate i's rotation is Shoemake's
+    uniform-quaternion map at the Halton point (i + 1; bases 2, 3, 5), its translation takes this map's centroid onto the other's, plus
+    box_t (2 halton(i + 1; 7, 11, 13) - 1) metres.  ValueError: n < 1, an input that is not finite, a negative box."""
+    a, b = (np.ascontiguousarray(c, np.float64).reshape(3) for c in (centroid_this, centroid_other))
+    out = np.zeros((max(int(n), 0), 4, 4), np.float64)
+    if _lib.xs_host_align_search_free(int(n), a.ctypes.data_as(_f64p), b.ctypes.data_as(_f64p), float(box_t), out.ctypes.data_as(_f64p)) != 0:
+        raise ValueError("transform_candidates_free: n < 1, an input that is not finite or a negative box")
+    return out
+
+
+def transform_candidates_around(T, pivot, box_t, box_r, n):
+    """n transforms [n, 4, 4] float64 about T (xs_host_align_search_around, CPU): entry 0 is T itself; entry i >= 1 turns T by
+    exp(box_r u[3:6]) about the image of `pivot` under T and shifts it by box_t u[0:3], u = 2 halton(i; 2, 3, 5, 7, 11, 13) - 1.
+    ValueError: n < 1, an input that is not finite, a negative box."""
+    t, p = _real44(T), np.ascontiguousarray(pivot, np.float64).reshape(3)
+    out = np.zeros((max(int(n), 0), 4, 4), np.float64)
+    if _lib.xs_host_align_search_around(t.ctypes.data_as(_f64p), p.ctypes.data_as(_f64p), float(box_t), float(box_r), int(n), out.ctypes.data_as(_f64p)) != 0:
+        raise ValueError("transform_candidates_around: n < 1, an input that is not finite or a negative box")
+    return out
+
+
+def transform_rank(out2xP, keep):
+    """The min(keep, P) indices of out2xP [P, 2] ({sum r^2, count}) with the highest S = count - sum r^2, best first, ties to the lower
+    index (xs_host_align_search_rank, CPU)."""
+    o = np.ascontiguousarray(out2xP, np.float64).reshape(-1, 2)
+    idx = np.zeros(max(min(int(keep), o.shape[0]), 1), np.int32)
+    n = _lib.xs_host_align_search_rank(o.ctypes.data_as(_f64p), o.shape[0], int(keep), idx.ctypes.data_as(_i32p))
+    return idx[:n].copy()
+
+
+def band_centroid(keys, voxel_size):
+    """The centroid [3] (metres) of the voxel centres of packed band keys (x | y << 21 | z << 42): exact integer sums, then (sum / count + 0.5)
+    voxel_size (xs_host_band_centroid, CPU).  ValueError for no key."""
+    k = np.ascontiguousarray(keys).view(np.uint64).reshape(-1)
+    out = np.zeros(3, np.float64)
+    if _lib.xs_host_band_centroid(k.ctypes.data_as(C.POINTER(C.c_uint64)), k.size, float(voxel_size), out.ctypes.data_as(_f64p)) != 0:
+        raise ValueError("band_centroid: no key")
+    return out
 
 
 def merge_tile_box(xform12, lo, hi, src_res):
@@ -903,6 +962,76 @@ class KinectFusion:
         """align_map with the other map read from a checkpoint file of a whole volume (save_checkpoint), validated as merge_checkpoint does.
         Intended use: kf.merge_checkpoint(path, kf.align_checkpoint(path, T_guess)[1])."""
         return self._align_call("xs_kf_align_checkpoint", path.encode(), T0, iterations, damping, min_weight, max_residual)
+
+    @staticmethod
+    def _align_rc(name, rc):
+        if rc == -2:
+            raise capi.XsError(f"{name}: not available in shard mode")
+        if rc == -1:
+            raise ValueError(f"{name}: bad arguments (T not finite, a count, stride, box, min_weight, max_residual or damping out of range, the volume "
+                             "itself as source, a bad file or another truncation distance)")
+        if rc not in (0, 1):
+            raise ValueError(f"{name}: {rc}")
+
+    def _score_transforms_call(self, name, source, Ts, stride, min_weight, max_residual):
+        t = np.ascontiguousarray(np.asarray(Ts, dtype=np.float64).reshape(-1, 4, 4))
+        out = np.zeros((t.shape[0], 2), np.float64)
+        rc = getattr(_lib, name)(self.h, source, t.shape[0], t.ctypes.data_as(_f64p), int(stride), int(min_weight), float(max_residual), out.ctypes.data_as(_f64p))
+        self._align_rc(name, rc)
+        if rc == 0:
+            raise ValueError(f"{name}: no volume")
+        return out
+
+    def score_transforms(self, other, Ts, stride=1, min_weight=1, max_residual=1.0):
+        """{sum r^2, count} [P, 2] float64 of "the map of `other` resampled under T minus this map" over every stride-th voxel of this map's
+        band, for each T of Ts [P, 4, 4] (as merge_map takes T), in one launch per 4096 transforms: the residual and the gates of align_map,
+        without derivatives.  S = count - sum r^2 ranks the transforms.  Nothing is modified.  XsError in shard mode, ValueError on bad arguments."""
+        return self._score_transforms_call("xs_kf_score_transforms", other.h, Ts, stride, min_weight, max_residual)
+
+    def score_transforms_checkpoint(self, path, Ts, stride=1, min_weight=1, max_residual=1.0):
+        """score_transforms with the other map read from a checkpoint file of a whole volume, validated as merge_checkpoint does."""
+        return self._score_transforms_call("xs_kf_score_transforms_checkpoint", path.encode(), Ts, stride, min_weight, max_residual)
+
+    def _align_global_call(self, name, source, candidates, keep, rounds, stride, box_t, refine_t, refine_r, iterations, damping, min_weight, max_residual, Ts):
+        o = AlignSearchOpts()
+        _lib.xs_kf_align_search_defaults(self.h, C.byref(o))
+        o.candidates, o.keep, o.rounds, o.stride, o.iterations, o.min_weight = int(candidates), int(keep), int(rounds), int(stride), int(iterations), int(min_weight)
+        if box_t is not None:
+            o.box_t = float(box_t)
+        if refine_t is not None:
+            o.refine_t = float(refine_t)
+        o.refine_r, o.damping, o.max_residual = float(refine_r), float(damping), float(max_residual)
+        user = None
+        if Ts is not None:
+            user = np.ascontiguousarray(np.asarray(Ts, dtype=np.float64).reshape(-1, 4, 4))
+            o.user_n, o.user_T16xN = user.shape[0], user.ctypes.data_as(_f64p)
+        out, report = np.eye(4, dtype=np.float64), np.zeros(12, np.float64)
+        rc = getattr(_lib, name)(self.h, source, C.byref(o), out.ctypes.data_as(_f64p), report.ctypes.data_as(_f64p))
+        self._align_rc(name, rc)
+        rep = {"rank": int(report[0]), "S_before": float(report[1]), "count": int(report[2]), "sum_r2": float(report[3]), "loss": float(report[4]),
+               "score_launches": int(report[5]), "passes": int(report[6]), "ended_ok": int(report[7]), "band_voxels": int(report[8]),
+               "scored_entries": int(report[9]), "centroid_distance": float(report[10])}
+        return rc == 1, out, rep
+
+    def align_map_global(self, other, candidates=2048, keep=8, rounds=2, stride=4, box_t=None, refine_t=None, refine_r=0.25, iterations=10, damping=1e-3,
+                         min_weight=1, max_residual=1.0, Ts=None):
+        """align_map with no starting guess: `candidates` transforms that cover all rotations (transform_candidates_free; translations from the
+        two maps' band centroids, jittered by box_t metres) are scored over every stride-th band voxel (score_transforms), the `keep` best by
+        S = count - sum r^2 are refined over `rounds` rounds of candidates about each (transform_candidates_around: boxes refine_t metres and
+        refine_r radians, halved per round), and the kept transforms start align_map's loop.  box_t, refine_t None: this map's truncation
+        distance.  Ts [N, 4, 4]: candidates of the caller's that replace the free ones.  Returns (ok, T [4, 4] float64, report dict); ok False
+        (T = the identity) when no start ended ok.  The score cannot tell a scene from its image under one of its own symmetries: a symmetric
+        scene has several equally good answers and any of them may be returned.  Nothing is modified.  XsError in shard mode, ValueError on
+        bad arguments.  Intended use: kf.merge_map(other, kf.align_map_global(other)[1])."""
+        return self._align_global_call("xs_kf_align_map_global", other.h, candidates, keep, rounds, stride, box_t, refine_t, refine_r, iterations, damping,
+                                       min_weight, max_residual, Ts)
+
+    def align_checkpoint_global(self, path, candidates=2048, keep=8, rounds=2, stride=4, box_t=None, refine_t=None, refine_r=0.25, iterations=10, damping=1e-3,
+                                min_weight=1, max_residual=1.0, Ts=None):
+        """align_map_global with the other map read from a checkpoint file of a whole volume (save_checkpoint), validated as merge_checkpoint
+        does.  Intended use: kf.merge_checkpoint(path, kf.align_checkpoint_global(path)[1])."""
+        return self._align_global_call("xs_kf_align_checkpoint_global", path.encode(), candidates, keep, rounds, stride, box_t, refine_t, refine_r, iterations,
+                                       damping, min_weight, max_residual, Ts)
 
 
 class ReferenceCallShape:
