@@ -670,6 +670,42 @@ int xs_tsdf_merge(float *value, int *weight, float *grad, size_t step, const int
                   const int *src_weight, const float *src_grad, size_t src_step, const int *src_res, const float *xform12, int min_weight,
                   int max_weight, unsigned flags, unsigned long long *written_dev, void *workspace, void *stream);
 
+/* ---- what differs between the volume and a second volume, as two masks (xs_diff.hip) ---------------------------
+ * No counterpart in the reference.  THIS map is (value, weight, step, res), the OTHER map (src_*); layouts, pitches and xform12 are those of
+ * the merge above, the pointers at plane 0, the whole volume always.  Neither volume is modified.  `only_this_mask` and `only_other_mask`:
+ * two different buffers of the frontier mask's size for res (8 bytes per brick of THIS map, 8-byte aligned device memory), in that
+ * mask's layout: one 64-bit word per brick of 4 x 4 x 4 voxels, brick (bx, by, bz) at (bz BY + by) BX + bx, voxel (lx, ly, lz) at bit
+ * lx + 4 ly + 16 lz, overhang bits clear: the frontier's label and cluster calls take them as they are.  The call writes EVERY word of both
+ * masks, the caller need not clear them.  counts3_dev (device): {compared, only_this, only_other} are INCREMENTED by the numbers of such
+ * voxels, with integer atomics, one add per counter and workgroup.  `workspace`: the diff's workspace size for (res, src_res) in bytes of
+ * device memory (may be NULL with XS_DIFF_NO_CULL).  No synchronisation.
+ *
+ * Destination voxel (x, y, z) of THIS map, every operation float32 in the order written:
+ *   1. The source sample: steps 1 to 3 of the merge, word for word: g_a; the voxel passes only with 0 <= g_a <= float(S_a - 1) on every axis;
+ *      b_a = floor(g_a), f_a = g_a - float(b_a); only the needed corners are read; ws = the smallest weight of the needed corners.
+ *   2. The other map is OBSERVED here iff the voxel passed the merge's step 2 and ws >= min_weight (ws is not clamped: there is no
+ *      max_weight).  This map is OBSERVED here iff its own weight wp >= min_weight.  The voxel is COMPARED iff both are observed.
+ *   3. For a compared voxel s is the merge's step 4 on the value array alone (there is no grad argument): along x, then y, then z, a stage
+ *      being lo * (1.0f - f_a) + hi * f_a and its lower operand itself on an axis with f_a == 0 (-0 stays -0).  v = this map's value.
+ *   4. only_this iff v < lo && s >= hi (matter here, firmly free there); only_other iff s < lo && v >= hi.  With lo <= hi the two exclude
+ *      each other.  (The layers above default to lo = 0, hi = 0.5: OCCUPIED in the observation grid is value < 0, and free space the
+ *      integrate step has seen holds 1.  The comparison with lo is strict, so -0.0f is not below lo = 0, as in that grid.)
+ *   5. The voxel's bit of each mask is its class; the bit of a voxel that is not compared is clear in both.
+ *   6. The counts: the number of compared voxels, and of the set bits of each mask.
+ * The cull is the merge's (a tile of 64 x 4 x 16 destination voxels whose source index box misses the source, or touches only bricks of
+ * 4 x 4 x 4 source voxels with no weight >= min_weight, stores zero words and leaves) and changes no bit; XS_DIFF_NO_CULL switches it off.
+ * A voxel with wp < min_weight reads nothing of the source.  No output depends on scheduling.
+ * hipErrorInvalidValue, with nothing launched and nothing written: what the merge refuses for these arguments (a null array, resolution
+ * or xform12, or workspace unless XS_DIFF_NO_CULL; an axis outside 1 .. 262140; a pitch that is no multiple of 4 or shorter than a row;
+ * min_weight < 1; an entry of xform12 that is not finite; a source array equal to its counterpart of this map); lo or hi not finite, or
+ * lo > hi; a null mask or counts pointer; the two masks equal, or one not 8-byte aligned; a `res` that has no frontier mask (the masks must
+ * be labelable): for it the workspace size is 0 too. */
+#define XS_DIFF_NO_CULL 1u
+size_t xs_tsdf_diff_workspace_bytes(const int *res, const int *src_res);
+int xs_tsdf_diff(const float *value, const int *weight, size_t step, const int *res, const float *src_value, const int *src_weight, size_t src_step,
+                 const int *src_res, const float *xform12, int min_weight, float lo, float hi, unsigned flags, void *only_this_mask,
+                 void *only_other_mask, unsigned long long *counts3_dev, void *workspace, void *stream);
+
 /* ---- aligning a second volume to the volume: Gauss-Newton terms over the band (xs_align.hip) -------------------
  * No counterpart in the reference.  The residual of a band voxel of THIS map is "the other map, resampled at the voxel under a complex-seeded
  * affine index map, minus this map": the sample xs_tsdf_merge would average in, at the position it would use.  `index`: the band index of THIS

@@ -404,6 +404,32 @@ int xs_host_align_search_around(const double *T16, const double *pivot3, double 
 int xs_host_align_search_rank(const double *out2xP, int P, int keep, int *idx_out);
 int xs_host_band_centroid(const unsigned long long *keys, long long count, double voxel_size, double *out3);
 
+/* ---- What differs between this map and a second map, as clusters (xs_tsdf_diff in xslam_amd.h: the contract) ----
+ * T16 and the three sources as for the merge calls above (diff_volume needs no grad array); the same source validation, and another
+ * truncation distance is refused.  THIS map is the instance's volume, the OTHER map the source resampled under T16.  A voxel is compared
+ * where both maps carry min_weight (the other on every corner its sample needs); it is ONLY_THIS where this map's value is below lo and
+ * the other's sample at least hi (matter here, firmly free there) and ONLY_OTHER the other way round (usual: lo = 0, hi = 0.5).  Each of the
+ * two masks is labelled and clustered by the frontier's calls (26-adjacency within cells of `cell` voxels: 0, or a multiple of 8 in
+ * 8 .. 65528) and the records of the clusters with count >= min_size come back in the frontier's format, ascending by label:
+ * this_records8 / other_records8 (capacity x 8 uint64 each; may be null when capacity is 0), their numbers in *this_count / *other_count.
+ * counts3 (optional): {compared, only_this, only_other} voxels.  this_dense / other_dense (optional, HOST, X * Y * Z bytes each): the masks
+ * as one byte (0 or 1) per voxel, [(z Y + y) X + x].  With the other map the earlier one, only_this is what appeared and only_other what
+ * went away.  The device is drained first.  Nothing of either map is modified: the volume generation, the sign map, the band index and the
+ * planning caches stay, the call works in buffers of its own.
+ * Return 1 when they ran, 0 without a volume, -1 on bad arguments with nothing written (the merge's, lo or hi not finite, lo > hi, a bad
+ * cell, a negative capacity, null counts, a volume the frontier calls cannot label), -2 in shard mode, -4 with both needed counts in
+ * *this_count / *other_count and nothing else written when capacity is too small for either list. */
+int xs_kf_diff_volume(void *kf, const float *src_value, const int *src_weight, size_t src_step, const int *src_res, float src_voxel_size, float src_tranc_dist,
+                      const double *T16, int min_weight, float lo, float hi, int cell, unsigned long long min_size, int capacity,
+                      unsigned long long *this_records8, int *this_count, unsigned long long *other_records8, int *other_count, unsigned long long *counts3,
+                      unsigned char *this_dense, unsigned char *other_dense);
+int xs_kf_diff_map(void *kf, void *other_kf, const double *T16, int min_weight, float lo, float hi, int cell, unsigned long long min_size, int capacity,
+                   unsigned long long *this_records8, int *this_count, unsigned long long *other_records8, int *other_count, unsigned long long *counts3,
+                   unsigned char *this_dense, unsigned char *other_dense);
+int xs_kf_diff_checkpoint(void *kf, const char *path, const double *T16, int min_weight, float lo, float hi, int cell, unsigned long long min_size, int capacity,
+                          unsigned long long *this_records8, int *this_count, unsigned long long *other_records8, int *other_count,
+                          unsigned long long *counts3, unsigned char *this_dense, unsigned char *other_dense);
+
 /* ---- The reference's own call shape (x-slam_amd/host/reference_shape.hpp) ---------------------------------------------------------
  * The per-frame sequence of Experiments/test_xkinect_fusion/main.cpp:46-60 + KinectFusionReconstruction.cpp:147-332 over nothing but the
  * reference-signature launchers (bilateralFilter, pyrDown, createVMap / createNMap, estimateCombined per iteration, integrateTsdfVolume,

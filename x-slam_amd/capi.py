@@ -167,6 +167,8 @@ _SIGS = {
     "xs_extract_points": (C.c_int, [_vp, _sz, _i32p, C.c_float, C.c_int, C.c_int, C.c_int, _vp, _sz, _vp, C.POINTER(_sz), C.POINTER(_sz), _vp]),
     "xs_extract_normals": (C.c_int, [_vp, _sz, _i32p, C.c_float, C.c_int, C.c_int, _vp, _sz, _vp, _vp]),
     "xs_tsdf_merge_workspace_bytes": (_sz, [_i32p, _i32p]),
+    "xs_tsdf_diff_workspace_bytes": (_sz, [_i32p, _i32p]),
+    "xs_tsdf_diff": (C.c_int, [_vp, _vp, _sz, _i32p, _vp, _vp, _sz, _i32p, _f32p, C.c_int, C.c_float, C.c_float, C.c_uint, _vp, _vp, _vp, _vp, _vp]),
     "xs_tsdf_merge": (C.c_int, [_vp, _vp, _vp, _sz, _i32p, C.c_int, C.c_int, _vp, _vp, _vp, _sz, _i32p, _f32p, C.c_int, C.c_int, C.c_uint, _vp, _vp, _vp]),
     "xs_tsdf_align_workspace_bytes": (_sz, [C.c_int]),
     "xs_tsdf_align_terms": (C.c_int, [C.c_int, C.POINTER(BandIndex), _vp, _vp, _sz, _i32p, _f32p, C.c_int, C.c_float, _vp, _vp, _vp]),
@@ -857,6 +859,29 @@ def tsdf_merge(value, weight, grad, step, res, src_value, src_weight, src_grad, 
     check(_lib.xs_tsdf_merge(_ptr(value), _ptr(weight), _ptr(grad), step, r.ctypes.data_as(_i32p), z0, z1, _ptr(src_value), _ptr(src_weight), _ptr(src_grad),
                              src_step, s.ctypes.data_as(_i32p), m.ctypes.data_as(_f32p), int(min_weight), int(max_weight), int(flags), _ptr(written),
                              _ptr(workspace), _stream(stream)))
+
+
+DIFF_NO_CULL = 1   # XS_DIFF_NO_CULL
+
+
+def tsdf_diff_workspace_bytes(res, src_res):
+    """xs_tsdf_diff_workspace_bytes (host only): tsdf_merge's workspace for this source; 0 for an unusable resolution or a destination that
+    has no frontier mask."""
+    return int(_lib.xs_tsdf_diff_workspace_bytes(_res3(res).ctypes.data_as(_i32p), _res3(src_res).ctypes.data_as(_i32p)))
+
+
+def tsdf_diff(value, weight, step, res, src_value, src_weight, src_step, src_res, xform12, only_this, only_other, counts, min_weight=1, lo=0.0, hi=0.5,
+              flags=0, workspace=None, stream=None):
+    """xs_tsdf_diff: compares this volume (value, weight) with the source volume resampled under xform12 as tsdf_merge samples it, where both
+    carry min_weight: only_this gets the voxels with value < lo here and >= hi there, only_other the reverse, one 64-bit word per brick in
+    the frontier mask's layout (frontier_mask_bytes(res) bytes each, every word written); counts (uint64 / int64 device tensor of 3 words) is
+    incremented by {compared, only_this, only_other}.  Arrays are device tensors or addresses of plane 0; `workspace`:
+    tsdf_diff_workspace_bytes(res, src_res) bytes (None only with DIFF_NO_CULL).  Nothing of either volume is written.  No synchronisation."""
+    r, s = _ia(res, 3), _ia(src_res, 3)
+    m = _fa(xform12, 12)
+    check(_lib.xs_tsdf_diff(_ptr(value), _ptr(weight), step, r.ctypes.data_as(_i32p), _ptr(src_value), _ptr(src_weight), src_step, s.ctypes.data_as(_i32p),
+                            m.ctypes.data_as(_f32p), int(min_weight), float(lo), float(hi), int(flags), _ptr(only_this), _ptr(only_other), _ptr(counts),
+                            _ptr(workspace), _stream(stream)))
 
 
 def merge_affine(T, dst_voxel_size, src_voxel_size):

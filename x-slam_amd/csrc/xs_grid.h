@@ -1,9 +1,9 @@
-// xs_grid.h — the one place that knows the brick grid's layout, for xs_view.hip, xs_reach.hip, xs_travel.hip and xs_frontier.hip (DESIGN.md
-// sections 4.18 to 4.21).  The volume is cut into bricks of 4 x 4 x 4 voxels, brick (bx, by, bz) at index (bz BY + by) BX + bx.  Two per-brick
+// xs_grid.h — the one place that knows the brick grid's layout, for xs_view.hip, xs_reach.hip, xs_travel.hip, xs_frontier.hip and xs_diff.hip
+// (DESIGN.md sections 4.18 to 4.21 and 4.25).  The volume is cut into bricks of 4 x 4 x 4 voxels, brick (bx, by, bz) at index (bz BY + by) BX + bx.  Two per-brick
 // formats follow that order:
 //   the OBSERVATION GRID  one 16-byte word per brick, two bits of state per voxel, voxel (lx, ly, lz) at bit 2 (lx + 4 ly) of dword lz (dword lz
 //                         holds the brick's plane lz); bricks that overhang the volume are padded with zeros, which are not a state
-//   a MASK                one 64-bit word per brick (the reached and the passable words of the reach buffer, the frontier mask), voxel
+//   a MASK                one 64-bit word per brick (the reached and the passable words of the reach buffer, the frontier mask, the two masks of a diff), voxel
 //                         (lx, ly, lz) at bit lx + 4 ly + 16 lz, overhang bits clear
 // and dense per-voxel arrays (the clearance field, the travel field, the labels) are indexed (z Y + y) X + x.  Also here: the launch shapes
 // over voxels and over tiles of 8 x 8 x 8, and the host's loop of rounds to a fixpoint.

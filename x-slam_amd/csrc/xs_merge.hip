@@ -12,30 +12,16 @@
 // text the host's self-test runs) misses the source leaves before any load, and so does a tile whose box touches only bricks of 4 x 4 x 4
 // source voxels without a weight >= min_weight (one bit per brick, built by k_merge_bricks into the workspace).  Both tests are conservative
 // and change no output bit; XS_MERGE_NO_CULL switches them off.
-#include "xs_device.h"
-#include "../../include/xslam_amd.h"
-#include "../host/merge_host.hpp"
+#include "xs_merge_sample.h"
 #include <math.h>
 
 using namespace xs;
-using xs_host::merge_index;
-using xs_host::merge_tile_box;
-
-enum { MERGE_TZ = 16,                // planes a workgroup walks: a tile is 64 x 4 x 16 voxels (at 4 planes the tiles that leave at the cull,
-                                     // one dependent load and a barrier each, cost more than the voxels that stay: profiles/merge_probe.txt)
-       MERGE_BRICK_CAP = 2048,       // a tile whose box holds more bricks than this is not tested against the brick bits
-       MERGE_HEADER_BYTES = 256 };   // the workspace's first bytes, kept free for control words
 
 struct MergeArgs {
     float *value; int *weight; float *grad; size_t step;
     int X, Y, Z, z0, z1;
-    const float *svalue; const int *sweight; const float *sgrad; size_t sstep;
-    int S[3];
-    float m[12];
-    int min_weight, max_weight;
-    unsigned cull;
-    const unsigned *bricks;          // bit b of the brick grid, brick (bx, by, bz) at b = (bz BY + by) BX + bx
-    int BX, BY, BZ;
+    MergeSource src;                 // (xs_merge_sample.h: the sampler, the brick bits and the cull, shared with xs_diff.hip)
+    int max_weight;
     unsigned long long *written;
 };
 
@@ -73,47 +59,10 @@ __global__ void __launch_bounds__(256) k_merge_bricks(const int *sweight, size_t
 namespace {
 // the per-voxel contract of include/xslam_amd.h; true when the voxel was written
 __device__ __forceinline__ bool merge_voxel(const MergeArgs &a, int x, int y, int z) {
-    int b[3];
-    float f[3];
-    bool need[3];
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        const float g = merge_index(a.m, k, x, y, z);
-        if (!(g >= 0.f && g <= (float)(a.S[k] - 1))) return false;
-        b[k] = __float2int_rd(g);
-        f[k] = g - (float)b[k];
-        need[k] = f[k] > 0.f;            // then g < S - 1 and b + 1 is inside the source
-    }
-    const int needmask = (need[0] ? 1 : 0) | (need[1] ? 2 : 0) | (need[2] ? 4 : 0);
-    // corner d (bit 0: +x, bit 1: +y, bit 2: +z) is read only where every axis it steps along is needed
-    int ws = 0x7fffffff;
-#pragma unroll
-    for (int d = 0; d < 8; ++d)
-        if ((d & ~needmask) == 0) ws = min(ws, row_ptr(a.sweight, a.sstep, a.S[1] * (b[2] + (d >> 2)) + b[1] + (d >> 1 & 1))[b[0] + (d & 1)]);
-    if (ws < a.min_weight) return false;
+    int ws;
+    float sv, sq;
+    if (!merge_sample<true>(a.src, x, y, z, ws, sv, sq)) return false;
     ws = min(ws, a.max_weight);
-    float v[8], q[8];
-#pragma unroll
-    for (int d = 0; d < 8; ++d) {
-        v[d] = 0.f; q[d] = 0.f;
-        if ((d & ~needmask) == 0) {
-            const int row = a.S[1] * (b[2] + (d >> 2)) + b[1] + (d >> 1 & 1);
-            v[d] = row_ptr(a.svalue, a.sstep, row)[b[0] + (d & 1)];
-            q[d] = row_ptr(a.sgrad, a.sstep, row)[b[0] + (d & 1)];
-        }
-    }
-    // x, then y, then z; an axis with fraction 0 passes its lower operand through untouched (-0 stays -0)
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        const int stride = 1 << k;
-        const float fk = f[k], gk = 1.0f - fk;
-#pragma unroll
-        for (int d = 0; d < 8; d += 2 * stride) {
-            v[d] = need[k] ? v[d] * gk + v[d + stride] * fk : v[d];
-            q[d] = need[k] ? q[d] * gk + q[d + stride] * fk : q[d];
-        }
-    }
-    const float sv = v[0], sq = q[0];
     int *wrow = row_ptr(a.weight, a.step, a.Y * z + y);
     float *vrow = row_ptr(a.value, a.step, a.Y * z + y), *grow = row_ptr(a.grad, a.step, a.Y * z + y);
     const int wp = wrow[x];
@@ -135,22 +84,9 @@ __global__ void __launch_bounds__(256) k_merge(const MergeArgs a) {
     const int x0 = (int)blockIdx.x * 64, y0 = (int)blockIdx.y * 4;
     const int zt0 = a.z0 + (int)blockIdx.z * MERGE_TZ, zt1 = min(zt0 + MERGE_TZ, a.z1);
     __shared__ unsigned s_count[4];
-    if (a.cull) {   // (every branch here is uniform over the workgroup)
+    if (a.src.cull) {   // (uniform over the workgroup)
         const int lo[3] = {x0, y0, zt0}, hi[3] = {min(x0 + 63, a.X - 1), min(y0 + 3, a.Y - 1), zt1 - 1};
-        int box[6];
-        if (!merge_tile_box(a.m, lo, hi, a.S, box)) return;
-        const int bx0 = box[0] >> 2, by0 = box[1] >> 2, bz0 = box[2] >> 2;
-        const int nx = (box[3] >> 2) - bx0 + 1, ny = (box[4] >> 2) - by0 + 1, nz = (box[5] >> 2) - bz0 + 1;
-        const long long n = (long long)nx * ny * nz;
-        if (n <= MERGE_BRICK_CAP) {
-            int any = 0;
-            for (int i = wave * 64 + lane; i < (int)n; i += 256) {
-                const int ix = i % nx, iy = i / nx % ny, iz = i / (nx * ny);
-                const size_t bi = ((size_t)(bz0 + iz) * (size_t)a.BY + (size_t)(by0 + iy)) * (size_t)a.BX + (size_t)(bx0 + ix);
-                any |= (int)(a.bricks[bi >> 5] >> (bi & 31) & 1u);
-            }
-            if (!__syncthreads_or(any)) return;
-        }
+        if (merge_tile_culled(a.src, lo, hi)) return;
     }
     const int x = x0 + lane, y = y0 + wave;
     const bool inside = x < a.X && y < a.Y;
@@ -168,23 +104,29 @@ __global__ void __launch_bounds__(256) k_merge(const MergeArgs a) {
     }
 }
 
-namespace {
-// false for a resolution the launches cannot index: an axis outside 1 .. 65535 x 4, rows that do not fit an int
-bool merge_res_ok(const int *r) {
-    for (int k = 0; k < 3; ++k)
-        if (r[k] < 1 || r[k] > 65535 * 4) return false;
-    return (long long)r[1] * (long long)r[2] < (1ll << 31);
+// see xs_merge_sample.h
+int xs::merge_source_prepare(MergeSource &s, const float *src_value, const int *src_weight, const float *src_grad, size_t src_step, const int *src_res,
+                             const float *xform12, int min_weight, bool cull, void *workspace, hipStream_t st) {
+    s.value = src_value; s.weight = src_weight; s.grad = src_grad; s.step = src_step;
+    for (int k = 0; k < 3; ++k) s.S[k] = src_res[k];
+    for (int i = 0; i < 12; ++i) s.m[i] = xform12[i];
+    s.min_weight = min_weight; s.cull = cull ? 1u : 0u;
+    s.BX = div_up(src_res[0], 4); s.BY = div_up(src_res[1], 4); s.BZ = div_up(src_res[2], 4);
+    s.bricks = nullptr;
+    if (cull) {
+        unsigned *bricks = (unsigned *)((char *)workspace + MERGE_HEADER_BYTES);
+        s.bricks = bricks;
+        XS_CHECK(hipMemsetAsync(bricks, 0, merge_brick_words(src_res) * sizeof(unsigned), st));
+        hipLaunchKernelGGL(k_merge_bricks, dim3(div_up(s.S[0], 64), s.BY, s.BZ), dim3(64, 4), 0, st, src_weight, src_step, s.S[0], s.S[1], s.S[2], min_weight,
+                           s.BX, s.BY, bricks);
+    }
+    return 0;
 }
-size_t merge_brick_words(const int *r) {
-    const size_t bricks = (size_t)div_up(r[0], 4) * (size_t)div_up(r[1], 4) * (size_t)div_up(r[2], 4);
-    return (bricks + 31) / 32;
-}
-}  // namespace
 
 /* the workspace of xs_tsdf_merge: a header and one bit per brick of 4 x 4 x 4 source voxels; 0 for a null or unusable resolution */
 extern "C" size_t xs_tsdf_merge_workspace_bytes(const int *dst_res, const int *src_res) {
     if (!dst_res || !src_res || !merge_res_ok(dst_res) || !merge_res_ok(src_res)) return 0;
-    return MERGE_HEADER_BYTES + ((merge_brick_words(src_res) * sizeof(unsigned) + 255) / 256) * 256;
+    return merge_workspace_bytes(src_res);
 }
 
 /* see include/xslam_amd.h */
@@ -207,20 +149,10 @@ extern "C" int xs_tsdf_merge(float *value, int *weight, float *grad, size_t step
     MergeArgs a;
     a.value = value; a.weight = weight; a.grad = grad; a.step = step;
     a.X = res[0]; a.Y = res[1]; a.Z = res[2]; a.z0 = z0; a.z1 = z1;
-    a.svalue = src_value; a.sweight = src_weight; a.sgrad = src_grad; a.sstep = src_step;
-    for (int k = 0; k < 3; ++k) a.S[k] = src_res[k];
-    for (int i = 0; i < 12; ++i) a.m[i] = xform12[i];
-    a.min_weight = min_weight; a.max_weight = max_weight; a.cull = cull ? 1u : 0u;
-    a.BX = div_up(src_res[0], 4); a.BY = div_up(src_res[1], 4); a.BZ = div_up(src_res[2], 4);
-    a.bricks = cull ? (const unsigned *)((const char *)workspace + MERGE_HEADER_BYTES) : nullptr;
+    a.max_weight = max_weight;
     a.written = written_dev;
     hipStream_t st = (hipStream_t)stream;
-    if (cull) {
-        unsigned *bricks = (unsigned *)((char *)workspace + MERGE_HEADER_BYTES);
-        XS_CHECK(hipMemsetAsync(bricks, 0, merge_brick_words(src_res) * sizeof(unsigned), st));
-        hipLaunchKernelGGL(k_merge_bricks, dim3(div_up(a.S[0], 64), a.BY, a.BZ), dim3(64, 4), 0, st, src_weight, src_step, a.S[0], a.S[1], a.S[2], min_weight,
-                           a.BX, a.BY, bricks);
-    }
+    if (int rc = merge_source_prepare(a.src, src_value, src_weight, src_grad, src_step, src_res, xform12, min_weight, cull, workspace, st)) return rc;
     hipLaunchKernelGGL(k_merge, dim3(div_up(a.X, 64), div_up(a.Y, 4), div_up(z1 - z0, MERGE_TZ)), dim3(64, 4), 0, st, a);
     XS_CHECK(hipGetLastError());
     return 0;

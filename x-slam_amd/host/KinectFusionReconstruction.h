@@ -378,6 +378,24 @@ public:
     int AlignVolumeGlobal(const float *src_value, const int *src_weight, size_t src_step, const int *src_res, float src_voxel_size, float src_tranc_dist,
                           const struct xs_align_search_opts *opts, double *T16_out, double report[12]);
     int AlignCheckpointGlobal(const std::string &filename, const struct xs_align_search_opts *opts, double *T16_out, double report[12]);
+    // What differs between this map and a second map, as clusters (xs_tsdf_diff in include/xslam_amd.h: the contract).
+    // The source and T16 as for MergeVolume (its grad array is not needed).  The device is drained, xform12 built by merge_affine, the two
+    // masks written by xs_tsdf_diff (only_this: this map has matter where the other is firmly free; only_other: the reverse), each labelled
+    // and clustered by the frontier's calls within cells of `cell` voxels (the frontier's rule), and the clusters with count >= min_size
+    // (frontier_select) returned in the frontier's record format: this_records8 / other_records8 (capacity x 8 uint64 each; may be null when
+    // capacity is 0) with *this_count / *other_count.  counts3 (optional) = {compared, only_this, only_other} voxels; this_dense /
+    // other_dense (optional, host, X * Y * Z bytes each) the masks expanded to a byte per voxel.  Every buffer is the call's own: nothing of
+    // either map is modified, volume_generation, the sign map, the band index and the planning caches stay.  Returns 1; 0 without a volume;
+    // -1 on bad arguments (MergeVolume's, lo or hi not finite or lo > hi, a bad cell, a negative capacity, a volume the frontier calls cannot
+    // label); -2 in shard mode; -4 when a list does not fit capacity, with both needed counts returned and nothing else written.
+    int DiffVolume(const float *src_value, const int *src_weight, size_t src_step, const int *src_res, float src_voxel_size, float src_tranc_dist,
+                   const double *T16, int min_weight, float lo, float hi, int cell, unsigned long long min_size, int capacity,
+                   unsigned long long *this_records8, int *this_count, unsigned long long *other_records8, int *other_count, unsigned long long counts3[3],
+                   unsigned char *this_dense, unsigned char *other_dense);
+    // The same against an XSTSDF2 file: MergeCheckpoint's validation, its temporary device volume and its free.
+    int DiffCheckpoint(const std::string &filename, const double *T16, int min_weight, float lo, float hi, int cell, unsigned long long min_size, int capacity,
+                       unsigned long long *this_records8, int *this_count, unsigned long long *other_records8, int *other_count, unsigned long long counts3[3],
+                       unsigned char *this_dense, unsigned char *other_dense);
 
     // counters of the last frame (synchronise the stream)
     long long lastUpdatedVoxels();

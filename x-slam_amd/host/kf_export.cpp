@@ -1,14 +1,17 @@
 // kf_export.cpp — what leaves the orchestrator: point cloud and mesh with their PLY writers, the last frame's counters, the raw volume
-// and the checkpoint; and what enters it as a whole map: a second volume or checkpoint merged into this one, and aligned to it beforehand, from a guess or from none.
+// and the checkpoint; and what enters it as a whole map: a second volume or checkpoint merged into this one, and aligned to it beforehand, from a guess or from none,
+// or compared with it voxel by voxel into clusters of change.
 // None of it runs during tracking.
 #include "kf_internal.hpp"
 #include "align_host.hpp"
 #include "align_search_host.hpp"
 #include "merge_host.hpp"
+#include "view_host.hpp"   // the frontier's record format, cell rule and frontier_select
 #include "../../include/xslam_amd_pipeline.h"   // xs_align_search_opts
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
+#include <cstring>
 #include <fstream>
 
 using namespace xs_host;
@@ -588,4 +591,106 @@ int KinectFusionReconstruction::AlignCheckpointGlobal(const std::string &filenam
     CkptVolume c;
     if (!upload_whole_checkpoint(filename, tsdf_volume_d_ptr->getTsdfTruncDist(), c)) return -1;
     return AlignVolumeGlobal(c.dv.ptr(0), c.dw.ptr(0), c.dv.step(), c.h.res, c.h.voxel_size, c.h.tranc_dist, opts, T16_out, report);
+}
+
+// ---- what differs between this map and a second map ------------------------------------------------------------
+int KinectFusionReconstruction::DiffVolume(const float *src_value, const int *src_weight, size_t src_step, const int *src_res, float src_voxel_size,
+                                           float src_tranc_dist, const double *T16, int min_weight, float lo, float hi, int cell, unsigned long long min_size,
+                                           int capacity, unsigned long long *this_records8, int *this_count, unsigned long long *other_records8,
+                                           int *other_count, unsigned long long counts3[3], unsigned char *this_dense, unsigned char *other_dense) {
+    if (shard_count > 1) return -2;   // the source's image in a rank's z-slab needs the whole source on every rank, and a cluster is not additive over slabs
+    if (!this_count || !other_count || capacity < 0 || (capacity > 0 && (!this_records8 || !other_records8)) || !frontier_cell_valid(cell)) return -1;
+    if (!tsdf_volume_d_ptr) return 0;
+    if (!src_value || !src_weight || !src_res || !T16 || min_weight < 1) return -1;
+    if (!std::isfinite(lo) || !std::isfinite(hi) || lo > hi) return -1;
+    for (int k = 0; k < 3; ++k)
+        if (src_res[k] < 1) return -1;
+    if (!(src_voxel_size > 0.f) || !std::isfinite(src_voxel_size) || src_tranc_dist != tsdf_volume_d_ptr->getTsdfTruncDist()) return -1;
+    DeviceArray2D<float> value = tsdf_volume_d_ptr->value();
+    DeviceArray2D<int> weight = tsdf_volume_d_ptr->weight();
+    if (src_value == value.ptr(0) || src_weight == weight.ptr(0)) return -1;
+    float xform[12];
+    if (!merge_affine(T16, (double)voxel_size, (double)src_voxel_size, xform)) return -1;
+    const int *res = res3();
+    const size_t ws_bytes = xs_tsdf_diff_workspace_bytes(res, src_res), mask_bytes = xs_frontier_mask_bytes(res), label_bytes = xs_frontier_label_bytes(res);
+    if (ws_bytes == 0 || mask_bytes == 0 || label_bytes == 0 || res[0] > 65535 || src_step % 4 != 0 || src_step < (size_t)src_res[0] * 4) return -1;
+    // the source may belong to another instance with streams of its own: drain the device, not just this instance's stream
+    synchronize();
+    hipSafeCall(hipDeviceSynchronize());
+    // buffers of the call's own: the frontier cache, and everything else derived from the volume, stays as it is
+    hipStream_t st = current_stream();
+    DeviceArray<unsigned char> ws, masks, labels, frontier_ws, dense;
+    DeviceArray<unsigned long long> counts, records_d;
+    ws.create(ws_bytes);
+    masks.create(2 * mask_bytes);
+    labels.create(label_bytes);
+    counts.create(3);
+    void *mask[2] = {masks.ptr(), masks.ptr() + mask_bytes};
+    hipSafeCall(hipMemsetAsync(counts.ptr(), 0, 3 * sizeof(unsigned long long), st));
+    check_rc(xs_tsdf_diff(value.ptr(0), weight.ptr(0), value.step(), res, src_value, src_weight, src_step, src_res, xform, min_weight, lo, hi, 0u, mask[0], mask[1],
+                          counts.ptr(), ws.ptr(), st), "diff");
+    std::vector<unsigned long long> records[2];
+    std::vector<int> keep[2];
+    int kept[2] = {0, 0};
+    int cap = 4096;
+    auto room_for = [&](int c) {   // the records with the count behind them, and the workspace that goes with that capacity
+        records_d.create((size_t)c * FRONTIER_RECORD_WORDS + 1);
+        frontier_ws.create(xs_frontier_workspace_bytes(res, c));
+    };
+    room_for(cap);
+    for (int k = 0; k < 2; ++k) {
+        unsigned *lab = reinterpret_cast<unsigned *>(labels.ptr());
+        check_rc(xs_frontier_label(mask[k], res, cell, lab, frontier_ws.ptr(), nullptr, st), "DiffLabel");
+        unsigned count = 0;
+        for (int attempt = 0; attempt < 2; ++attempt) {   // (the second with room for the count the first returned)
+            unsigned long long *rec = records_d.ptr();
+            check_rc(xs_frontier_clusters(mask[k], lab, res, cap, rec, reinterpret_cast<unsigned *>(rec + (size_t)cap * FRONTIER_RECORD_WORDS), &count,
+                                          frontier_ws.ptr(), st), "DiffClusters");
+            if (count <= (unsigned)cap) break;
+            if (count > 0x7fffffffu / 2u) return -1;
+            cap = (int)count;
+            room_for(cap);
+        }
+        records[k].assign((size_t)count * FRONTIER_RECORD_WORDS, 0ull);
+        if (count) {
+            hipSafeCall(hipMemcpyAsync(records[k].data(), records_d.ptr(), records[k].size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+            hipSafeCall(hipStreamSynchronize(st));
+        }
+        keep[k].resize((size_t)count);
+        kept[k] = frontier_select(records[k].data(), (int)count, min_size, keep[k].data());
+    }
+    *this_count = kept[0];
+    *other_count = kept[1];
+    if (kept[0] > capacity || kept[1] > capacity) return -4;
+    unsigned long long *out[2] = {this_records8, other_records8};
+    for (int k = 0; k < 2; ++k)
+        for (int i = 0; i < kept[k]; ++i)
+            std::memcpy(out[k] + (size_t)i * FRONTIER_RECORD_WORDS, records[k].data() + (size_t)keep[k][(size_t)i] * FRONTIER_RECORD_WORDS,
+                        FRONTIER_RECORD_WORDS * sizeof(unsigned long long));
+    if (counts3) hipSafeCall(hipMemcpy(counts3, counts.ptr(), 3 * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+    unsigned char *host_dense[2] = {this_dense, other_dense};
+    for (int k = 0; k < 2; ++k) {
+        if (!host_dense[k]) continue;
+        const size_t voxels = (size_t)res[0] * (size_t)res[1] * (size_t)res[2];
+        dense.create(voxels);
+        check_rc(xs_frontier_expand(mask[k], res, dense.ptr(), st), "DiffExpand");
+        hipSafeCall(hipMemcpyAsync(host_dense[k], dense.ptr(), voxels, hipMemcpyDeviceToHost, st));
+        hipSafeCall(hipStreamSynchronize(st));
+    }
+    return 1;
+}
+
+int KinectFusionReconstruction::DiffCheckpoint(const std::string &filename, const double *T16, int min_weight, float lo, float hi, int cell,
+                                               unsigned long long min_size, int capacity, unsigned long long *this_records8, int *this_count,
+                                               unsigned long long *other_records8, int *other_count, unsigned long long counts3[3], unsigned char *this_dense,
+                                               unsigned char *other_dense) {
+    if (shard_count > 1) return -2;
+    if (!tsdf_volume_d_ptr) return 0;
+    if (!T16 || min_weight < 1) return -1;
+    for (int i = 0; i < 12; ++i)
+        if (!std::isfinite(T16[i])) return -1;
+    CkptVolume c;
+    if (!upload_whole_checkpoint(filename, tsdf_volume_d_ptr->getTsdfTruncDist(), c)) return -1;
+    return DiffVolume(c.dv.ptr(0), c.dw.ptr(0), c.dv.step(), c.h.res, c.h.voxel_size, c.h.tranc_dist, T16, min_weight, lo, hi, cell, min_size, capacity,
+                      this_records8, this_count, other_records8, other_count, counts3, this_dense, other_dense);
 }

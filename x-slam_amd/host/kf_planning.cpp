@@ -308,8 +308,6 @@ bool KinectFusionReconstruction::FrontierPrepare(int cell, int min_weight) {
     return true;
 }
 
-static bool frontier_cell_valid(int cell) { return cell == 0 || (cell >= 8 && cell <= 65528 && cell % 8 == 0); }
-
 int KinectFusionReconstruction::Frontiers(int cell, unsigned long long min_size, int min_weight, int capacity, unsigned long long *records8, int *count_out) {
     if (shard_count > 1) return -2;   // a cluster is not additive over the ranks' z-slabs
     if (!count_out || capacity < 0 || (capacity > 0 && !records8) || !frontier_cell_valid(cell)) return -1;

@@ -1,7 +1,7 @@
 // merge_host.hpp — the host's side of merging a second TSDF map into the volume: the affine map from this volume's
 // voxel indices to the other volume's continuous voxel indices, the rigid transform between two maps from one camera frame posed in both, and the
 // source index box of a destination tile that the kernel's cull uses.  No device call and no HIP header: the orchestrator uses it in front of
-// the launch, csrc/xs_merge.hip compiles merge_tile_box for the device from this same text, and tests/cxx/merge_selftest.cpp runs all of it
+// the launch, csrc/xs_merge_sample.h (xs_merge.hip, xs_diff.hip) compiles merge_tile_box for the device from this same text, and tests/cxx/merge_selftest.cpp runs all of it
 // under the sanitizers without a GPU.
 #pragma once
 #include <cmath>

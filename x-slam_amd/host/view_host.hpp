@@ -169,4 +169,7 @@ inline int frontier_select(const unsigned long long *records, int n, unsigned lo
     return m;
 }
 
+// The cells of the labelling: 0 (one cell, the whole volume) or a multiple of 8 in 8 .. 65528.
+inline bool frontier_cell_valid(int cell) { return cell == 0 || (cell >= 8 && cell <= 65528 && cell % 8 == 0); }
+
 }  // namespace xs_host

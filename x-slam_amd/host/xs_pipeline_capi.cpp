@@ -539,6 +539,34 @@ int xs_kf_align_checkpoint_global(void *kf, const char *path, const xs_align_sea
     if (!path) return -1;
     return ((KF *)kf)->AlignCheckpointGlobal(path, opts, T16_out, report12);
 }
+int xs_kf_diff_volume(void *kf, const float *src_value, const int *src_weight, size_t src_step, const int *src_res, float src_voxel_size, float src_tranc_dist,
+                      const double *T16, int min_weight, float lo, float hi, int cell, unsigned long long min_size, int capacity,
+                      unsigned long long *this_records8, int *this_count, unsigned long long *other_records8, int *other_count, unsigned long long *counts3,
+                      unsigned char *this_dense, unsigned char *other_dense) {
+    return ((KF *)kf)->DiffVolume(src_value, src_weight, src_step, src_res, src_voxel_size, src_tranc_dist, T16, min_weight, lo, hi, cell, min_size, capacity,
+                                  this_records8, this_count, other_records8, other_count, counts3, this_dense, other_dense);
+}
+int xs_kf_diff_map(void *kf, void *other_kf, const double *T16, int min_weight, float lo, float hi, int cell, unsigned long long min_size, int capacity,
+                   unsigned long long *this_records8, int *this_count, unsigned long long *other_records8, int *other_count, unsigned long long *counts3,
+                   unsigned char *this_dense, unsigned char *other_dense) {
+    KF *k = (KF *)kf, *o = (KF *)other_kf;
+    if (!o || o == k) return -1;
+    if (o->shard_count > 1) return -2;
+    if (!o->tsdf_volume_d_ptr) return -1;
+    o->synchronize();
+    auto v = o->tsdf_volume_d_ptr->value();   // (read only: nothing of the other map is touched)
+    auto w = o->tsdf_volume_d_ptr->weight();
+    if (v.step() != w.step()) return -1;
+    return k->DiffVolume(v.ptr(), w.ptr(), v.step(), o->volume_resolution.v, o->voxel_size, o->tsdf_volume_d_ptr->getTsdfTruncDist(), T16, min_weight, lo, hi, cell,
+                         min_size, capacity, this_records8, this_count, other_records8, other_count, counts3, this_dense, other_dense);
+}
+int xs_kf_diff_checkpoint(void *kf, const char *path, const double *T16, int min_weight, float lo, float hi, int cell, unsigned long long min_size, int capacity,
+                          unsigned long long *this_records8, int *this_count, unsigned long long *other_records8, int *other_count,
+                          unsigned long long *counts3, unsigned char *this_dense, unsigned char *other_dense) {
+    if (!path) return -1;
+    return ((KF *)kf)->DiffCheckpoint(path, T16, min_weight, lo, hi, cell, min_size, capacity, this_records8, this_count, other_records8, other_count, counts3,
+                                      this_dense, other_dense);
+}
 int xs_host_align_search_free(int n, const double *centroid_this3, const double *centroid_other3, double box_t, double *T16xN) {
     return xs_host::align_search_free(n, centroid_this3, centroid_other3, box_t, T16xN) ? 0 : -1;
 }

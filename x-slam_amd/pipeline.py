@@ -29,6 +29,10 @@ class AlignSearchOpts(C.Structure):
                 ("damping", C.c_double), ("max_residual", C.c_double), ("user_T16xN", C.POINTER(C.c_double))]
 
 
+# what the three diff calls share behind T16: min_weight, lo, hi, cell, min_size, capacity, two record buffers with their counts, counts3, two dense masks
+_DIFF_TAIL = [C.c_int, C.c_float, C.c_float, C.c_int, C.c_ulonglong, C.c_int, C.POINTER(C.c_uint64), _i32p, C.POINTER(C.c_uint64), _i32p,
+              C.POINTER(C.c_ulonglong), C.POINTER(C.c_ubyte), C.POINTER(C.c_ubyte)]
+
 _SIGS = {
     "xs_kf_create_sharded": (_vp, [C.c_char_p, C.c_int, C.c_int, COLLECTIVE_CB, _vp]),
     "xs_kf_shard_planes": (None, [_vp, _i32p, _i32p]),
@@ -107,6 +111,9 @@ _SIGS = {
     "xs_kf_merge_volume": (C.c_int, [_vp, _vp, _vp, _vp, _sz, _i32p, C.c_float, C.c_float, _f64p, C.c_int, C.POINTER(C.c_ulonglong)]),
     "xs_kf_merge_map": (C.c_int, [_vp, _vp, _f64p, C.c_int, C.POINTER(C.c_ulonglong)]),
     "xs_kf_merge_checkpoint": (C.c_int, [_vp, C.c_char_p, _f64p, C.c_int, C.POINTER(C.c_ulonglong)]),
+    "xs_kf_diff_volume": (C.c_int, [_vp, _vp, _vp, _sz, _i32p, C.c_float, C.c_float, _f64p] + _DIFF_TAIL),
+    "xs_kf_diff_map": (C.c_int, [_vp, _vp, _f64p] + _DIFF_TAIL),
+    "xs_kf_diff_checkpoint": (C.c_int, [_vp, C.c_char_p, _f64p] + _DIFF_TAIL),
     "xs_host_merge_affine": (C.c_int, [_f64p, C.c_double, C.c_double, _f32p]),
     "xs_host_map_transform": (C.c_int, [_f64p, _f64p, _f64p]),
     "xs_host_merge_tile_box": (C.c_int, [_f32p, _i32p, _i32p, _i32p, _i32p]),
@@ -353,6 +360,12 @@ def set_stream(stream):
 
 class Mesh(collections.namedtuple("Mesh", "vertices vertex_im normals triangles edge_keys")):
     """A triangle mesh of the TSDF (KinectFusion.export_mesh): numpy arrays, vertices in ascending edge key."""
+
+
+class MapDiff(collections.namedtuple("MapDiff", "counts only_this only_other masks")):
+    """What differs between two maps (KinectFusion.diff_map): counts, a dict of compared, only_this and only_other voxels; only_this and
+    only_other, the clusters of each class as structured arrays of KinectFusion.FRONTIER_DTYPE; masks, the pair (only_this, only_other) of
+    uint8 [Z, Y, X] or None."""
 
 
 class KinectFusion:
@@ -686,7 +699,11 @@ class KinectFusion:
         self._frontier_call("xs_kf_frontiers", rc)
         if rc != 1:
             raise ValueError("xs_kf_frontiers: no volume" if rc == 0 else f"xs_kf_frontiers: {rc}")
-        rec = rec[:n.value]
+        return self._cluster_records(rec[:n.value])
+
+    def _cluster_records(self, rec):
+        """Records of 8 uint64 in the frontier's format [n, 8] as a structured array of FRONTIER_DTYPE: label, count, sum, the centroid in
+        metres and the bounding box."""
         out = np.zeros(len(rec), self.FRONTIER_DTYPE)
         out["label"], out["count"], out["sum"] = rec[:, 0], rec[:, 1], rec[:, 2:5]
         vs = np.float32(float(self.cfg["tsdf_voxel_size"]))
@@ -930,6 +947,49 @@ class KinectFusion:
         t = _real44(np.eye(4) if T is None else T)
         n = C.c_ulonglong(0)
         return self._merge_call("xs_kf_merge_checkpoint", _lib.xs_kf_merge_checkpoint(self.h, path.encode(), t.ctypes.data_as(_f64p), int(min_weight), C.byref(n)), n)
+
+    def _diff_call(self, name, source, T, min_weight, lo, hi, cell_vox, min_size, masks, capacity):
+        t = _real44(np.eye(4) if T is None else T)
+        u64p = C.POINTER(C.c_uint64)
+        dense = [np.zeros((self.res[2], self.res[1], self.res[0]), np.uint8) for _ in range(2)] if masks else None
+        dp = [d.ctypes.data_as(C.POINTER(C.c_ubyte)) for d in dense] if masks else [None, None]
+        counts, n_this, n_other = np.zeros(3, np.uint64), C.c_int(0), C.c_int(0)
+        for _ in range(2):   # (the second with room for the counts the first returned)
+            recs = [np.zeros((max(capacity, 1), capi.FRONTIER_RECORD_WORDS), np.uint64) for _ in range(2)]
+            rc = getattr(_lib, name)(self.h, *source, t.ctypes.data_as(_f64p), int(min_weight), float(lo), float(hi), int(cell_vox), int(min_size), capacity,
+                                     recs[0].ctypes.data_as(u64p), C.byref(n_this), recs[1].ctypes.data_as(u64p), C.byref(n_other),
+                                     counts.ctypes.data_as(C.POINTER(C.c_ulonglong)), dp[0], dp[1])
+            if rc != -4:
+                break
+            capacity = max(int(n_this.value), int(n_other.value))
+        if rc == -2:
+            raise capi.XsError(f"{name}: not available in shard mode")
+        if rc == -1:
+            raise ValueError(f"{name}: bad arguments (T, lo or hi not finite, lo > hi, min_weight < 1, a bad cell, the volume itself as source, a bad file or "
+                             "another truncation distance)")
+        if rc != 1:
+            raise ValueError(f"{name}: no volume" if rc == 0 else f"{name}: {rc}")
+        return MapDiff(dict(compared=int(counts[0]), only_this=int(counts[1]), only_other=int(counts[2])), self._cluster_records(recs[0][:n_this.value]),
+                       self._cluster_records(recs[1][:n_other.value]), tuple(dense) if masks else None)
+
+    def diff_map(self, other, T=None, min_weight=1, lo=0.0, hi=0.5, cell_vox=0, min_size=8, masks=False, capacity=1024):
+        """What differs between this map and the map of `other` (another KinectFusion of this process), with nothing averaged: THIS map is
+        self, the OTHER map is `other` resampled into this map's voxel grid under T as merge_map does it (real 4 x 4: a point of this map's
+        volume frame, in metres, to the other map's; None: the identity).  A voxel is compared where both maps carry min_weight; it is
+        only_this where this map's value is below lo and the other's at least hi (matter here, firmly free there) and only_other the other
+        way round.  With `other` the earlier map, only_this is what appeared and only_other what went away.  Returns a MapDiff: counts (a
+        dict of compared, only_this and only_other voxels), only_this and only_other (the clusters of each class with at least min_size voxels,
+        26-adjacency within cells of cell_vox voxels, 0: the whole volume, as frontiers() returns them) and masks (the pair of uint8 [Z, Y, X],
+        with masks=True).  capacity: the first guess at the number of clusters per class; a longer list is fetched by a second run.  Nothing
+        of either map is modified.  XsError in shard mode, ValueError on bad arguments.
+        Intended use: kf.diff_map(other, kf.align_map_global(other)[1])."""
+        return self._diff_call("xs_kf_diff_map", (other.h,), T, min_weight, lo, hi, cell_vox, min_size, masks, int(capacity))
+
+    def diff_checkpoint(self, path, T=None, min_weight=1, lo=0.0, hi=0.5, cell_vox=0, min_size=8, masks=False, capacity=1024):
+        """diff_map with the other map read from a checkpoint file of a whole volume (save_checkpoint), validated as merge_checkpoint does: with
+        yesterday's checkpoint as the other map, only_this is what appeared since and only_other what went away.
+        Intended use: kf.diff_checkpoint(path, kf.align_checkpoint_global(path)[1])."""
+        return self._diff_call("xs_kf_diff_checkpoint", (path.encode(),), T, min_weight, lo, hi, cell_vox, min_size, masks, int(capacity))
 
     def _align_call(self, name, source, T0, iterations, damping, min_weight, max_residual):
         t = np.asarray(np.eye(4) if T0 is None else T0, dtype=np.float64)
