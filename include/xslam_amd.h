@@ -706,6 +706,46 @@ int xs_tsdf_diff(const float *value, const int *weight, size_t step, const int *
                  const int *src_res, const float *xform12, int min_weight, float lo, float hi, unsigned flags, void *only_this_mask,
                  void *only_other_mask, unsigned long long *counts3_dev, void *workspace, void *stream);
 
+/* ---- the volume as bricks of 8 x 8 x 8 voxels, one word or 512 per array (xs_pack.hip) ---------------------------
+ * No counterpart in the reference.  The kernels behind the brick-sparse checkpoint XSTSDF3 ("Checkpoint formats").  The arrays
+ * are given at the FIRST STORED PLANE, in the layout of every call here (row Y * z + y, x contiguous) with one pitch `step` (bytes) shared by the
+ * three; `planes` is the number of stored planes (res[2] for a whole volume), res[2] itself is only range-checked.  Byte offsets row * step are
+ * computed in 64 bits.  None of the calls synchronises.
+ *
+ * Bricks: nbx, nby, nbz = ceil(res[0] / 8), ceil(res[1] / 8), ceil(planes / 8); brick (bx, by, bz) has index (bz nby + by) nbx + bx and holds
+ * voxels 8 b + (i, j, k), i, j, k in 0 .. 7, those inside X x Y x planes being its in-volume voxels; (8 bx, 8 by, 8 bz), its first voxel, always
+ * is.  All comparisons are on 32-bit WORDS, never on floats: +0.0 differs from -0.0, two NaNs with different payloads differ, one NaN pattern
+ * equals itself.
+ *   class:   bit 0 (value), bit 1 (weight), bit 2 (grad): set iff some in-volume word of that array differs from the array's word at the
+ *            brick's first voxel (the array is DENSE in the brick); clear: the array is UNIFORM there.
+ *   words:   a uniform array takes 1 word of the payload (the first voxel's), a dense array 512: the word of local voxel (i, j, k) at
+ *            i + 8 j + 64 k, positions outside the volume holding the first voxel's word.  Within a brick: value, weight, grad.
+ *   offsets: offsets[b] = the sum of the words of bricks 0 .. b - 1 (uint64), offsets[nbricks] the payload's length in words.
+ * So class bytes, offsets and payload are a pure function of the volume's bits, and no output depends on scheduling (the sums are integer).
+ *
+ * The brick count for (res, planes), 0 where the calls below would refuse them; and the workspace of classify and of the offsets call, in bytes
+ * of device memory (0 likewise). */
+size_t xs_tsdf_pack_bricks(const int *res, int planes);
+size_t xs_tsdf_pack_workspace_bytes(const int *res, int planes);
+/* Fills cls_dev[nbricks] (each byte written once, no atomics) and offsets_dev[nbricks + 1] from the volume, which is only read. */
+int xs_tsdf_pack_classify(const float *value, const int *weight, const float *grad, size_t step, const int *res, int planes,
+                          unsigned char *cls_dev, unsigned long long *offsets_dev, void *workspace, void *stream);
+/* The offsets alone, from class bytes that came from elsewhere (a file): bits 3 .. 7 of a class byte are ignored here, a reader validates them
+ * beforehand.  workspace: the workspace size of any (res, planes) with this brick count.  Refuses a null pointer and nbricks outside [1, 2^31). */
+int xs_tsdf_pack_offsets(const unsigned char *cls_dev, size_t nbricks, unsigned long long *offsets_dev, void *workspace, void *stream);
+/* Writes the payload words of bricks [brick0, brick1) to payload_dev[0 .. offsets[brick1] - offsets[brick0]): the volume is only read.  The range
+ * exists so that a host can stream a volume of any size through a buffer of fixed size: a brick takes at most 1536 words. */
+int xs_tsdf_pack_gather(const float *value, const int *weight, const float *grad, size_t step, const int *res, int planes,
+                        const unsigned char *cls_dev, const unsigned long long *offsets_dev, size_t brick0, size_t brick1, unsigned *payload_dev,
+                        void *stream);
+/* The inverse: writes every in-volume voxel of bricks [brick0, brick1) from payload_dev (laid out as the gather of the same range leaves it) and
+ * nothing else: no pitch padding, no row outside those bricks.
+ * hipErrorInvalidValue, with nothing launched, from classify, gather and unpack alike: a null pointer; res[0], res[1], res[2] or planes outside
+ * 1 .. 262140, res[1] * planes of 2^31 and more, or 2^31 bricks and more; a pitch that is no multiple of 4 or shorter than a row; an empty or
+ * reversed brick range or one outside [0, nbricks]. */
+int xs_tsdf_unpack(float *value, int *weight, float *grad, size_t step, const int *res, int planes, const unsigned char *cls_dev,
+                   const unsigned long long *offsets_dev, size_t brick0, size_t brick1, const unsigned *payload_dev, void *stream);
+
 /* ---- aligning a second volume to the volume: Gauss-Newton terms over the band (xs_align.hip) -------------------
  * No counterpart in the reference.  The residual of a band voxel of THIS map is "the other map, resampled at the voxel under a complex-seeded
  * affine index map, minus this map": the sample xs_tsdf_merge would average in, at the position it would use.  `index`: the band index of THIS

@@ -290,6 +290,23 @@ long long xs_kf_volume_generation(void *kf);
 int xs_kf_save_checkpoint(void *kf, const char *path);
 int xs_kf_load_checkpoint(void *kf, const char *path);
 int xs_kf_save_tsdf_volume(void *kf, const char *path);
+/* The brick-sparse checkpoint XSTSDF3 ("Checkpoint formats"), lossless.  The save above writes the dense
+ * XSTSDF2 as before; this one classifies and compacts the volume on the device and streams it through one pinned staging buffer, never holding
+ * the whole volume on the host.  A rank of a sharded run saves its own planes.  The load above and every *_checkpoint call take either format:
+ * they look at the magic.  stats12 (optional): bricks, the bricks of classes 0 .. 7, payload words, file bytes, gather chunks.
+ * Return 0; -1 without a volume or when the file cannot be written. */
+int xs_kf_save_checkpoint_sparse(void *kf, const char *path, unsigned long long *stats12);
+/* The staging buffer of sparse saves and loads, in 32-bit words: sets it when words >= 1536 (one brick at its largest; 0 leaves it alone) and
+ * returns the value in effect, by default 16 Mi words = 64 MiB; -1 for a value between.  Pinned host memory and the device buffer of a chunk are
+ * bounded by it whatever the volume's size. */
+long long xs_kf_checkpoint_staging_words(void *kf, unsigned long long words);
+/* What a checkpoint file of either format holds, without a GPU and without reading a payload: the header, and for XSTSDF3 the class bytes, under
+ * the format's full validation (XSTSDF2: geometry, pose count, exact length; XSTSDF3: pack_validate of x-slam_amd/host/pack_host.hpp).
+ * out32: 0 format version (2 or 3); 1 valid (1 / 0); 2 .. 4 res; 5 voxel size; 6 truncation distance; 7 frame_id; 8 n_poses; 9, 10 zs0, zs1;
+ * 11, 12 shard rank and count; 13 brick edge; 14 .. 16 nbx, nby, nbz; 17 nbricks; 18 .. 25 bricks of classes 0 .. 7; 26 payload words (XSTSDF2:
+ * 3 words per voxel); 27 file bytes; 28 the validation's code (0 valid; the PackError of pack_host.hpp); 29 .. 31 zero.  Fields a failed validation did not reach are
+ * zero.  Return 0 when the file opened and carries one of the two magics (valid or not: out32[1] says), -1 otherwise or for a null argument. */
+int xs_host_checkpoint_info(const char *path, double *out32);
 
 /* ---- Merging a second map into the volume (xs_tsdf_merge in xslam_amd.h: the per-voxel contract) ------------
  * T16: a real 4 x 4, row-major, taking a point of THIS map's volume frame (metres) to the OTHER map's volume frame, p_other = T p_this.

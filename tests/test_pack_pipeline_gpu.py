@@ -1,0 +1,245 @@
+"""GPU: the brick-sparse checkpoint at the orchestrator's level (KinectFusion.save_checkpoint(path, sparse=True), load_checkpoint and the
+*_checkpoint calls on such a file) at 64^3 on the synthetic scene S1, six frames, as tests/test_merge_pipeline_gpu.py
+does.  The file is held to the Python reader and model of tests/pack_cases.py; everything a dense checkpoint gives, the sparse one gives bit for bit."""
+import ctypes as C
+import importlib
+import os
+import struct
+import threading
+
+import numpy as np
+import pytest
+
+import merge_cases as mc
+import pack_cases as pc
+from helpers import synth
+
+pytestmark = pytest.mark.gpu
+N, FRAMES = 64, 6
+
+
+@pytest.fixture(scope="module")
+def dev():
+    import torch
+    assert torch.cuda.is_available()
+    return torch, importlib.import_module("x-slam_amd.capi"), importlib.import_module("x-slam_amd.pipeline")
+
+
+@pytest.fixture(scope="module")
+def scene(dev, tmp_path_factory):
+    """A after six frames (never modified by a test), its dense and its sparse checkpoint, the frames, the parameters."""
+    torch, capi, pl = dev
+    prm = synth.s1_params(N)
+    frames = [torch.from_numpy(synth.s1_frame(k).view(np.int16)).cuda() for k in range(FRAMES + 2)]
+    a = pl.KinectFusion(prm)
+    for k in range(FRAMES):
+        assert a.process_frame(frames[k]) == 1
+    a.synchronize()
+    d = tmp_path_factory.mktemp("pack")
+    dense, sparse = str(d / "a_dense.ckpt"), str(d / "a_sparse.ckpt")
+    assert a.save_checkpoint(dense) is None
+    stats = a.save_checkpoint(sparse, sparse=True)
+    yield dict(a=a, prm=prm, frames=frames, volume=tuple(x.copy() for x in a.volume()), dense=dense, sparse=sparse, stats=stats, dir=d)
+    a.close()
+
+
+def same_volume(x, y):
+    return mc.same_bits(x[0], y[0]) and np.array_equal(x[1], y[1]) and mc.same_bits(x[2], y[2])
+
+
+def cube_words(vol):
+    return tuple(pc.words(a).reshape(N, N, N) for a in vol)
+
+
+def test_the_sparse_file_is_the_models(dev, scene, tmp_path):
+    """The Python reader decodes the file to A's volume bit for bit; class bytes, offsets and payload are the model's; the poses are the dense file's
+    bytes; header, stats and length follow the formula; a second save, and a save through a staging buffer of one brick's size, give the same
+    bytes; the file is below a quarter of the dense one (the oracle's condition of tests/test_pack_cases_cpu.py, no performance number)."""
+    torch, capi, pl = dev
+    a, stats = scene["a"], scene["stats"]
+    blob, dense = open(scene["sparse"], "rb").read(), open(scene["dense"], "rb").read()
+    r = pc.read_xstsdf3(blob)
+    vol = cube_words(scene["volume"])
+    assert all(np.array_equal(x, y) for x, y in zip(r["volume"], vol))
+    cls, offsets = pc.classify(*vol)
+    assert np.array_equal(r["cls"], cls) and np.array_equal(r["offsets"], offsets)
+    n_poses = a.num_poses()
+    assert r["poses"] == dense[52:52 + 128 * n_poses] and r["n_poses"] == n_poses and len(dense) == 52 + 128 * n_poses + 12 * N ** 3
+    assert blob == pc.write_xstsdf3(*vol, voxel_size=r["voxel_size"], tranc_dist=r["tranc_dist"], frame_id=a.frame_id, poses=r["poses"])
+    assert r["res"] == (N, N, N) and r["planes"] == (0, N) and r["shard"] == (0, 1) and r["frame_id"] == a.frame_id == FRAMES
+    assert r["tranc_dist"] == a.tranc_dist() and r["voxel_size"] == float(np.float32(scene["prm"]["tsdf_voxel_size"]))
+    assert blob[:52] == b"XSTSDF3\0" + dense[8:52]
+    assert stats == dict(bricks=512, classes=np.bincount(cls, minlength=8).tolist(), payload_words=int(offsets[-1]), file_bytes=len(blob), chunks=1)
+    assert len(blob) == 88 + 128 * n_poses + 512 + 4 * int(offsets[-1])
+    info = pl.checkpoint_info(scene["sparse"])
+    assert info["valid"] and info["version"] == 3 and info["classes"] == stats["classes"] and info["payload_words"] == stats["payload_words"]
+    assert pl.checkpoint_info(scene["dense"])["valid"] and pl.checkpoint_info(scene["dense"])["version"] == 2
+    print(f"sparse / dense = {len(blob) / len(dense):.4f}; bricks per class {stats['classes']}")
+    assert len(blob) < 0.25 * len(dense)
+    assert stats["classes"][0] >= 1 and stats["classes"][7] >= 1
+    again = str(tmp_path / "again.ckpt")
+    assert a.save_checkpoint(again, sparse=True) == stats and open(again, "rb").read() == blob
+    # through the smallest staging buffer: many chunks, the same file; and a load through it
+    assert a.checkpoint_staging_words() == 16 << 20
+    with pytest.raises(ValueError):
+        a.checkpoint_staging_words(1535)
+    assert a.checkpoint_staging_words(1536) == 1536
+    small = a.save_checkpoint(again, sparse=True)
+    assert small["chunks"] == len(pc.chunk_ends(offsets, 1536)) > 40 and dict(small, chunks=1) == stats and open(again, "rb").read() == blob
+    assert a.checkpoint_staging_words(16 << 20) == 16 << 20
+    b = pl.KinectFusion(scene["prm"])
+    b.checkpoint_staging_words(2000)
+    assert b.load_checkpoint(scene["sparse"]) and same_volume(b.volume(), scene["volume"])
+    b.close()
+    assert same_volume(a.volume(), scene["volume"])
+
+
+def test_load_sparse_is_load_dense(dev, scene):
+    """Into two fresh instances: equal volume, frame_id, pose record and current pose; the next frame gives the same pose bits and volumes; equal
+    point clouds (the sign map was rebuilt from the unpacked volume)."""
+    torch, capi, pl = dev
+    prm, frames = scene["prm"], scene["frames"]
+    s, d = pl.KinectFusion(prm), pl.KinectFusion(prm)
+    assert s.load_checkpoint(scene["sparse"]) and d.load_checkpoint(scene["dense"])
+    assert same_volume(s.volume(), scene["volume"]) and same_volume(d.volume(), scene["volume"])
+    assert s.frame_id == d.frame_id == FRAMES and s.num_poses() == d.num_poses() == scene["a"].num_poses()
+    for i in range(s.num_poses()):
+        assert np.array_equal(s.world2camera(i).view(np.uint32), d.world2camera(i).view(np.uint32))
+    assert np.array_equal(s.world2camera().view(np.uint32), scene["a"].world2camera().view(np.uint32))
+    ps, pd = s.export_point_cloud(), d.export_point_cloud()
+    assert len(ps[0]) > 100 and mc.same_bits(ps[0], pd[0]) and np.array_equal(ps[1].view(np.uint32), pd[1].view(np.uint32))
+    for k in (FRAMES, FRAMES + 1):
+        assert s.process_frame(frames[k]) == 1 and d.process_frame(frames[k]) == 1
+        assert np.array_equal(s.world2camera().view(np.uint32), d.world2camera().view(np.uint32))
+        assert same_volume(s.volume(), d.volume())
+    assert not same_volume(s.volume(), scene["volume"])
+    s.close()
+    d.close()
+
+
+def test_the_map_calls_take_the_sparse_file(dev, scene):
+    """merge_checkpoint, diff_checkpoint with masks, align_checkpoint and score_transforms_checkpoint return on the sparse file what they return on
+    the dense file, compared as bits."""
+    torch, capi, pl = dev
+    prm, frames = scene["prm"], scene["frames"]
+    T = np.eye(4)
+    T[:3, :3] = mc.rotation((0.2, 1.0, 0.1), np.radians(4.0))
+    T[:3, 3] = (0.05, -0.02, 0.03)
+    out = {}
+    for kind in ("dense", "sparse"):
+        path = scene[kind]
+        c = pl.KinectFusion(prm)
+        for k in range(3):
+            assert c.process_frame(frames[k]) == 1
+        diff = c.diff_checkpoint(path, T, masks=True)
+        ok, Ta, report, hist = c.align_checkpoint(path, T, iterations=3)
+        Ts = np.stack([np.eye(4), T, Ta])
+        scores = c.score_transforms_checkpoint(path, Ts, stride=2)
+        written = c.merge_checkpoint(path, T, min_weight=2)
+        out[kind] = dict(diff=diff, align=(ok, Ta, report, hist), scores=scores, written=written, volume=c.volume())
+        c.close()
+    d, s = out["dense"], out["sparse"]
+    assert s["written"] == d["written"] > 1000 and same_volume(s["volume"], d["volume"])
+    assert s["diff"].counts == d["diff"].counts and d["diff"].counts["compared"] > 1000
+    assert s["diff"].only_this.tobytes() == d["diff"].only_this.tobytes() and s["diff"].only_other.tobytes() == d["diff"].only_other.tobytes()
+    assert all(np.array_equal(x, y) for x, y in zip(s["diff"].masks, d["diff"].masks))
+    assert s["align"][0] == d["align"][0] and np.array_equal(np.asarray(s["align"][1]).view(np.uint64), np.asarray(d["align"][1]).view(np.uint64))
+    assert s["align"][2] == d["align"][2] and d["align"][2]["count"] > 100
+    assert np.array_equal(np.asarray(s["align"][3], np.float64).view(np.uint64), np.asarray(d["align"][3], np.float64).view(np.uint64))
+    assert np.array_equal(np.asarray(s["scores"], np.float64).view(np.uint64), np.asarray(d["scores"], np.float64).view(np.uint64))
+
+
+def test_bad_files_change_nothing(dev, scene, tmp_path):
+    """Each bad file of the CPU list, and a sparse file of another resolution or another truncation distance: load_checkpoint returns False,
+    merge_checkpoint raises ValueError, xs_kf_merge_checkpoint returns -1, and the volume, the frame number and the poses keep their bits."""
+    torch, capi, pl = dev
+    prm, frames = scene["prm"], scene["frames"]
+    blob = open(scene["sparse"], "rb").read()
+    bad, dense_blob = pc.bad_files(blob)
+    assert pc.read_xstsdf3(blob)["n_poses"] >= 1
+    other_res = pl.KinectFusion(synth.s1_params(32))
+    other_td = pl.KinectFusion(dict(prm, thres_range=prm["thres_range"] + 1))
+    for name, kf in (("res32", other_res), ("tranc", other_td)):
+        assert kf.process_frame(frames[0]) == 1
+        p = str(tmp_path / (name + ".ckpt"))
+        kf.save_checkpoint(p, sparse=True)
+        assert pl.checkpoint_info(p)["valid"]
+        bad[name] = open(p, "rb").read()
+        kf.close()
+    bad["magic"] = b"XSTSDF1\0" + blob[8:]
+    bad["sharded"] = blob[:44] + struct.pack("<ii", 0, 2) + blob[52:]
+    c = pl.KinectFusion(prm)
+    for k in range(2):
+        assert c.process_frame(frames[k]) == 1
+    before = tuple(x.copy() for x in c.volume())
+    state = (c.frame_id, c.num_poses(), c.world2camera().copy(), c.volume_generation())
+    eye = np.eye(4)
+    for name, data in bad.items():
+        p = str(tmp_path / (name + ".bad"))
+        open(p, "wb").write(data)
+        if name != "res32":          # (a valid whole-volume file of another resolution is a legitimate source of a merge: only the load refuses it)
+            n = C.c_ulonglong(7)
+            assert pl._lib.xs_kf_merge_checkpoint(c.h, p.encode(), eye.ctypes.data_as(pl._f64p), 1, C.byref(n)) == -1, name
+            with pytest.raises(ValueError):
+                c.merge_checkpoint(p)
+        assert not c.load_checkpoint(p), name
+        assert same_volume(c.volume(), before), name
+    assert (c.frame_id, c.num_poses(), c.volume_generation()) == (state[0], state[1], state[3]) and np.array_equal(c.world2camera(), state[2])
+    assert c.process_frame(frames[2]) == 1
+    c.close()
+
+
+def test_two_ranks_save_and_restore_their_planes(dev, scene, tmp_path):
+    """Two ranks as threads on one GPU: each rank's sparse file decodes to its own planes and restores them bit for bit after another frame has
+    changed them; the map calls still refuse in shard mode (XsError, -2) whichever format the file has."""
+    torch, capi, pl = dev
+    sh = importlib.import_module("x-slam_amd.sharded")
+    frames = scene["frames"]
+    world = 2
+    prm = dict(scene["prm"], icp_shard_rows=False)
+    lw = sh.LocalWorld(torch, world)
+    shards = [sh.ShardedKinectFusion(prm, r, world, collective=lw.collective_for(r)) for r in range(world)]
+    errors, done = [], [False] * world
+
+    def work(r):
+        try:
+            k = shards[r]
+            for f in range(2):
+                assert k.process_frame(frames[f]) == 1
+            saved = tuple(x.copy() for x in k.volume())
+            p = str(tmp_path / f"rank{r}.ckpt")
+            stats = k.save_checkpoint(p, sparse=True)
+            z0, z1 = k.stored
+            rd = pc.read_xstsdf3(open(p, "rb").read())
+            assert rd["planes"] == (z0, z1) and rd["shard"] == (r, world) and rd["res"] == (N, N, N) and rd["brick_grid"] == pc.grid((N, N, z1 - z0))
+            assert all(np.array_equal(x.reshape(-1), pc.words(y)) for x, y in zip(rd["volume"], saved))
+            assert stats["file_bytes"] == os.path.getsize(p) and stats["bricks"] == pc.nbricks((N, N, z1 - z0))
+            assert k.process_frame(frames[2]) == 1
+            assert not same_volume(k.volume(), saved)
+            assert k.load_checkpoint(p)                    # (the restore re-raycasts the model maps: a collective, every rank takes part)
+            assert same_volume(k.volume(), saved) and k.frame_id == 2
+            refused = 0
+            for call in (lambda: k.merge_checkpoint(scene["sparse"]), lambda: k.diff_checkpoint(scene["sparse"]), lambda: k.align_checkpoint(scene["sparse"]),
+                         lambda: k.score_transforms_checkpoint(scene["sparse"], np.eye(4)[None])):
+                try:
+                    call()
+                except capi.XsError:
+                    refused += 1
+            assert refused == 4
+            n = C.c_ulonglong(0)
+            assert pl._lib.xs_kf_merge_checkpoint(k.h, scene["sparse"].encode(), np.eye(4).ctypes.data_as(pl._f64p), 1, C.byref(n)) == -2
+            assert same_volume(k.volume(), saved)
+            assert k.process_frame(frames[2]) == 1
+            done[r] = True
+        except BaseException as e:  # noqa: BLE001
+            errors.append(e)
+            lw.barrier.abort()
+
+    th = [threading.Thread(target=work, args=(r,)) for r in range(world)]
+    [t.start() for t in th]
+    [t.join() for t in th]
+    assert not errors, errors
+    assert done == [True] * world
+    assert np.array_equal(shards[0].world2camera(), shards[1].world2camera())
+    for s in shards:
+        s.close()

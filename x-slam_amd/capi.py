@@ -169,6 +169,12 @@ _SIGS = {
     "xs_tsdf_merge_workspace_bytes": (_sz, [_i32p, _i32p]),
     "xs_tsdf_diff_workspace_bytes": (_sz, [_i32p, _i32p]),
     "xs_tsdf_diff": (C.c_int, [_vp, _vp, _sz, _i32p, _vp, _vp, _sz, _i32p, _f32p, C.c_int, C.c_float, C.c_float, C.c_uint, _vp, _vp, _vp, _vp, _vp]),
+    "xs_tsdf_pack_bricks": (_sz, [_i32p, C.c_int]),
+    "xs_tsdf_pack_workspace_bytes": (_sz, [_i32p, C.c_int]),
+    "xs_tsdf_pack_classify": (C.c_int, [_vp, _vp, _vp, _sz, _i32p, C.c_int, _vp, _vp, _vp, _vp]),
+    "xs_tsdf_pack_offsets": (C.c_int, [_vp, _sz, _vp, _vp, _vp]),
+    "xs_tsdf_pack_gather": (C.c_int, [_vp, _vp, _vp, _sz, _i32p, C.c_int, _vp, _vp, _sz, _sz, _vp, _vp]),
+    "xs_tsdf_unpack": (C.c_int, [_vp, _vp, _vp, _sz, _i32p, C.c_int, _vp, _vp, _sz, _sz, _vp, _vp]),
     "xs_tsdf_merge": (C.c_int, [_vp, _vp, _vp, _sz, _i32p, C.c_int, C.c_int, _vp, _vp, _vp, _sz, _i32p, _f32p, C.c_int, C.c_int, C.c_uint, _vp, _vp, _vp]),
     "xs_tsdf_align_workspace_bytes": (_sz, [C.c_int]),
     "xs_tsdf_align_terms": (C.c_int, [C.c_int, C.POINTER(BandIndex), _vp, _vp, _sz, _i32p, _f32p, C.c_int, C.c_float, _vp, _vp, _vp]),
@@ -859,6 +865,46 @@ def tsdf_merge(value, weight, grad, step, res, src_value, src_weight, src_grad, 
     check(_lib.xs_tsdf_merge(_ptr(value), _ptr(weight), _ptr(grad), step, r.ctypes.data_as(_i32p), z0, z1, _ptr(src_value), _ptr(src_weight), _ptr(src_grad),
                              src_step, s.ctypes.data_as(_i32p), m.ctypes.data_as(_f32p), int(min_weight), int(max_weight), int(flags), _ptr(written),
                              _ptr(workspace), _stream(stream)))
+
+
+def tsdf_pack_bricks(res, planes=None):
+    """xs_tsdf_pack_bricks (host only): the bricks of 8 x 8 x 8 voxels of `planes` stored planes (None: res[2]); 0 for what the pack calls refuse."""
+    r = _ia(res, 3)
+    return int(_lib.xs_tsdf_pack_bricks(r.ctypes.data_as(_i32p), int(r[2]) if planes is None else int(planes)))
+
+
+def tsdf_pack_workspace_bytes(res, planes=None):
+    """xs_tsdf_pack_workspace_bytes (host only): the workspace of tsdf_pack_classify and tsdf_pack_offsets; 0 as tsdf_pack_bricks."""
+    r = _ia(res, 3)
+    return int(_lib.xs_tsdf_pack_workspace_bytes(r.ctypes.data_as(_i32p), int(r[2]) if planes is None else int(planes)))
+
+
+def tsdf_pack_classify(value, weight, grad, step, res, cls, offsets, workspace, planes=None, stream=None):
+    """xs_tsdf_pack_classify: cls [nbricks] uint8 (bit 0 / 1 / 2: the value / weight / grad words of the brick are not all equal to the word at
+    its first voxel) and offsets [nbricks + 1] uint64 (the exclusive sum of the words per brick: 1 or 512 per array) of the volume given at its
+    first stored plane.  Arrays are device tensors or addresses.  No synchronisation."""
+    r = _ia(res, 3)
+    check(_lib.xs_tsdf_pack_classify(_ptr(value), _ptr(weight), _ptr(grad), step, r.ctypes.data_as(_i32p), int(r[2]) if planes is None else int(planes),
+                                     _ptr(cls), _ptr(offsets), _ptr(workspace), _stream(stream)))
+
+
+def tsdf_pack_offsets(cls, nbricks, offsets, workspace, stream=None):
+    """xs_tsdf_pack_offsets: the offsets alone from class bytes on the device.  No synchronisation."""
+    check(_lib.xs_tsdf_pack_offsets(_ptr(cls), int(nbricks), _ptr(offsets), _ptr(workspace), _stream(stream)))
+
+
+def tsdf_pack_gather(value, weight, grad, step, res, cls, offsets, brick0, brick1, payload, planes=None, stream=None):
+    """xs_tsdf_pack_gather: the payload words of bricks [brick0, brick1) to payload[0 ..] (uint32 / int32 device words).  No synchronisation."""
+    r = _ia(res, 3)
+    check(_lib.xs_tsdf_pack_gather(_ptr(value), _ptr(weight), _ptr(grad), step, r.ctypes.data_as(_i32p), int(r[2]) if planes is None else int(planes),
+                                   _ptr(cls), _ptr(offsets), int(brick0), int(brick1), _ptr(payload), _stream(stream)))
+
+
+def tsdf_unpack(value, weight, grad, step, res, cls, offsets, brick0, brick1, payload, planes=None, stream=None):
+    """xs_tsdf_unpack: the inverse of tsdf_pack_gather: writes every in-volume voxel of bricks [brick0, brick1) and nothing else.  No synchronisation."""
+    r = _ia(res, 3)
+    check(_lib.xs_tsdf_unpack(_ptr(value), _ptr(weight), _ptr(grad), step, r.ctypes.data_as(_i32p), int(r[2]) if planes is None else int(planes),
+                              _ptr(cls), _ptr(offsets), int(brick0), int(brick1), _ptr(payload), _stream(stream)))
 
 
 DIFF_NO_CULL = 1   # XS_DIFF_NO_CULL

@@ -322,7 +322,15 @@ public:
     // KinectFusionReconstruction.cpp:438-447)
     void saveTSDFVolume(const std::string &tsdf_filename);
     void saveCheckpoint(const std::string &filename);
-    bool loadCheckpoint(const std::string &filename);
+    bool loadCheckpoint(const std::string &filename);   // either format: it looks at the magic
+    // The brick-sparse checkpoint XSTSDF3 (pack_host.hpp: the format), lossless: the volume is classified and compacted on the
+    // device (xs_tsdf_pack_classify, xs_tsdf_pack_gather) and leaves through one pinned staging buffer of checkpoint_staging_words words, chunk by chunk;
+    // the host never holds the whole volume.  A rank of a sharded run saves its own planes, as saveCheckpoint does.  stats12 (optional): bricks, the
+    // bricks of classes 0 .. 7, payload words, file bytes, gather chunks.  False when the file cannot be written (or there is no volume).
+    bool saveCheckpointSparse(const std::string &filename, unsigned long long *stats12);
+    // The staging buffer of sparse saves and loads in 32-bit words: 16 Mi words (64 MiB) unless set; at least one brick's 1536.  It bounds the pinned
+    // host buffer and the device buffer of a chunk whatever the volume's size (a volume whose payload is smaller allocates only that).
+    unsigned long long checkpoint_staging_words = 16ull << 20;
     // Merging a second map into the volume (xs_tsdf_merge in include/xslam_amd.h: the contract).  The source is a
     // whole volume in device memory in the project's layout (three arrays at plane 0, one pitch) whose resolution and voxel size may differ
     // from this map's; T16 is a real 4 x 4, row-major, taking a point of THIS map's volume frame (metres) to the source's volume frame.

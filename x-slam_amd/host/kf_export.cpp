@@ -6,6 +6,7 @@
 #include "align_host.hpp"
 #include "align_search_host.hpp"
 #include "merge_host.hpp"
+#include "pack_host.hpp"
 #include "view_host.hpp"   // the frontier's record format, cell rule and frontier_select
 #include "../../include/xslam_amd_pipeline.h"   // xs_align_search_opts
 #include <algorithm>
@@ -155,7 +156,138 @@ template <class T>
 void restore_rows(DeviceArray2D<T> dst, const std::vector<T> &src, int cols, size_t rows) {
     hipSafeCall(hipMemcpy2D(dst.ptr(), dst.step(), src.data(), (size_t)cols * sizeof(T), (size_t)cols * sizeof(T), rows, hipMemcpyHostToDevice));
 }
+
+// ---- the brick-sparse checkpoint, version 3 (pack_host.hpp: the format and its validation) ----
+static_assert(sizeof(CkptHeader) == sizeof(CkptPrefix) && sizeof(Matrix4cf) == PACK_POSE_BYTES, "XSTSDF3 shares XSTSDF2's header fields and pose record");
+// the one staging buffer of a sparse save or load, pinned so that the copies run at the link's rate
+struct PinnedWords {
+    unsigned *p = nullptr;
+    explicit PinnedWords(size_t words) { hipSafeCall(hipHostMalloc((void **)&p, words * sizeof(unsigned), hipHostMallocDefault)); }
+    ~PinnedWords() { if (p) (void)hipHostFree(p); }
+    PinnedWords(const PinnedWords &) = delete;
+    PinnedWords &operator=(const PinnedWords &) = delete;
+};
+// a chunk holds at most the staging buffer's words, at least one brick's, and no more than there is
+uint64_t chunk_words_for(unsigned long long staging_words, uint64_t payload_words) {
+    return std::max<uint64_t>(PACK_MAX_BRICK_WORDS, std::min<uint64_t>(staging_words, payload_words));
+}
+// An XSTSDF3 file read whole into host memory and validated in full; nothing on the device is touched or allocated.
+struct SparseFile {
+    PackHeader h{};
+    std::vector<char> bytes;           // the file
+    std::vector<uint64_t> offsets;     // nbricks + 1
+    const char *poses() const { return bytes.data() + sizeof(PackHeader); }
+    const unsigned char *cls() const { return reinterpret_cast<const unsigned char *>(poses() + (size_t)h.p.n_poses * PACK_POSE_BYTES); }
+    const char *payload() const { return reinterpret_cast<const char *>(cls()) + pack_class_bytes_padded(h.nbricks); }
+};
+bool read_sparse_file(std::ifstream &f, long long file_bytes, SparseFile &s) {
+    if (file_bytes < (long long)sizeof(PackHeader)) return false;
+    f.seekg(0, std::ios::beg);
+    f.read(reinterpret_cast<char *>(&s.h), sizeof(s.h));
+    uint64_t head = 0;
+    if (!f || pack_validate_header(s.h, &head) != PACK_OK) return false;
+    if ((uint64_t)file_bytes != head + 4 * s.h.payload_words) return false;   // (before the file's size is allocated: the size is then what the header says)
+    s.bytes.resize((size_t)file_bytes);
+    f.seekg(0, std::ios::beg);
+    f.read(s.bytes.data(), (std::streamsize)file_bytes);
+    if (!f || pack_validate(s.h, s.cls(), (uint64_t)file_bytes, nullptr) != PACK_OK) return false;
+    s.offsets.resize((size_t)s.h.nbricks + 1);
+    pack_offsets(s.cls(), s.h.nbricks, s.offsets.data());
+    return true;
+}
+// The validated file's volume into three device arrays of one pitch, at their first stored plane: class bytes up, offsets by the device's scan,
+// then chunk by chunk through the pinned buffer and the unpack kernel.  Every in-volume voxel is written; the stream is drained on return.
+void unpack_sparse(const SparseFile &s, float *value, int *weight, float *grad, size_t step, unsigned long long staging_words) {
+    hipStream_t st = current_stream();
+    const int *res = s.h.p.res, planes = s.h.p.zs1 - s.h.p.zs0;
+    const uint64_t nbricks = s.h.nbricks, padded = pack_class_bytes_padded(nbricks);
+    DeviceArray<unsigned char> cls_d, ws;
+    DeviceArray<unsigned long long> off_d;
+    DeviceArray<unsigned> pay_d;
+    cls_d.create(padded);
+    off_d.create(nbricks + 1);
+    ws.create(xs_tsdf_pack_workspace_bytes(res, planes));
+    const uint64_t chunk_words = chunk_words_for(staging_words, s.h.payload_words);
+    pay_d.create(chunk_words);
+    PinnedWords pin(chunk_words);
+    hipSafeCall(hipMemcpyAsync(cls_d.ptr(), s.cls(), padded, hipMemcpyHostToDevice, st));
+    check_rc(xs_tsdf_pack_offsets(cls_d.ptr(), nbricks, off_d.ptr(), ws.ptr(), st), "pack offsets");
+    for (uint64_t b0 = 0, b1; b0 < nbricks; b0 = b1) {
+        b1 = pack_chunk_end(s.offsets.data(), nbricks, b0, chunk_words);
+        const size_t n = (size_t)(s.offsets[b1] - s.offsets[b0]);
+        std::memcpy(pin.p, s.payload() + 4 * s.offsets[b0], 4 * n);
+        hipSafeCall(hipMemcpyAsync(pay_d.ptr(), pin.p, 4 * n, hipMemcpyHostToDevice, st));
+        check_rc(xs_tsdf_unpack(value, weight, grad, step, res, planes, cls_d.ptr(), off_d.ptr(), b0, b1, pay_d.ptr(), st), "unpack");
+        hipSafeCall(hipStreamSynchronize(st));   // (the pinned buffer is filled again)
+    }
+}
 }  // namespace
+
+bool KinectFusionReconstruction::saveCheckpointSparse(const std::string &filename, unsigned long long *stats12) {
+    if (stats12) std::fill(stats12, stats12 + 12, 0ull);
+    if (!tsdf_volume_d_ptr) return false;
+    DeviceArray2D<float> dv = tsdf_volume_d_ptr->value(), dg = tsdf_volume_d_ptr->grad();
+    DeviceArray2D<int> dw = tsdf_volume_d_ptr->weight();
+    if (dv.step() != dg.step() || dv.step() != dw.step()) return false;   // (TsdfVolume allocates the three arrays alike)
+    const int *res = res3(), planes = zs1 - zs0;
+    PackHeader h{};
+    int nb[3];
+    const uint64_t nbricks = pack_brick_grid(res[0], res[1], planes, nb);
+    if (nbricks == 0 || xs_tsdf_pack_bricks(res, planes) != nbricks) return false;
+    const uint64_t padded = pack_class_bytes_padded(nbricks);
+    synchronize();
+    hipStream_t st = current_stream();
+    DeviceArray<unsigned char> cls_d, ws;
+    DeviceArray<unsigned long long> off_d;
+    cls_d.create(padded);
+    off_d.create(nbricks + 1);
+    ws.create(xs_tsdf_pack_workspace_bytes(res, planes));
+    hipSafeCall(hipMemsetAsync(cls_d.ptr(), 0, padded, st));   // (the padding)
+    check_rc(xs_tsdf_pack_classify(dv.ptr(0), dw.ptr(0), dg.ptr(0), dv.step(), res, planes, cls_d.ptr(), off_d.ptr(), ws.ptr(), st), "pack classify");
+    std::vector<unsigned char> cls(padded);
+    unsigned long long payload_words = 0;
+    hipSafeCall(hipMemcpyAsync(cls.data(), cls_d.ptr(), padded, hipMemcpyDeviceToHost, st));
+    hipSafeCall(hipMemcpyAsync(&payload_words, off_d.ptr() + nbricks, sizeof(payload_words), hipMemcpyDeviceToHost, st));
+    hipSafeCall(hipStreamSynchronize(st));
+    std::vector<uint64_t> offsets(nbricks + 1);
+    pack_offsets(cls.data(), nbricks, offsets.data());
+    if (offsets[nbricks] != payload_words) check_rc(-1, "pack classify: the device's offsets disagree with its class bytes");
+    std::snprintf(h.p.magic, sizeof(h.p.magic), "XSTSDF3");
+    for (int i = 0; i < 3; ++i) h.p.res[i] = volume_resolution[i];
+    h.p.voxel_size = voxel_size; h.p.tranc_dist = tsdf_volume_d_ptr->getTsdfTruncDist(); h.p.frame_id = frame_id;
+    h.p.n_poses = (int)world2camera_record.size();
+    h.p.zs0 = zs0; h.p.zs1 = zs1; h.p.shard_rank = shard_rank; h.p.shard_count = shard_count;
+    h.brick_edge = PACK_BRICK_EDGE; h.nbx = nb[0]; h.nby = nb[1]; h.nbz = nb[2]; h.reserved = 0;
+    h.nbricks = nbricks; h.payload_words = payload_words;
+    std::ofstream f(filename, std::ios::binary);
+    if (!f) return false;
+    f.write(reinterpret_cast<const char *>(&h), sizeof(h));
+    f.write(reinterpret_cast<const char *>(world2camera_record.data()), (std::streamsize)((size_t)h.p.n_poses * sizeof(Matrix4cf)));
+    f.write(reinterpret_cast<const char *>(cls.data()), (std::streamsize)padded);
+    const uint64_t chunk_words = chunk_words_for(checkpoint_staging_words, payload_words);
+    DeviceArray<unsigned> pay_d;
+    pay_d.create(chunk_words);
+    PinnedWords pin(chunk_words);
+    unsigned long long chunks = 0;
+    for (uint64_t b0 = 0, b1; b0 < nbricks; b0 = b1, ++chunks) {
+        b1 = pack_chunk_end(offsets.data(), nbricks, b0, chunk_words);
+        const size_t n = (size_t)(offsets[b1] - offsets[b0]);
+        check_rc(xs_tsdf_pack_gather(dv.ptr(0), dw.ptr(0), dg.ptr(0), dv.step(), res, planes, cls_d.ptr(), off_d.ptr(), b0, b1, pay_d.ptr(), st), "pack gather");
+        hipSafeCall(hipMemcpyAsync(pin.p, pay_d.ptr(), 4 * n, hipMemcpyDeviceToHost, st));
+        hipSafeCall(hipStreamSynchronize(st));
+        f.write(reinterpret_cast<const char *>(pin.p), (std::streamsize)(4 * n));
+    }
+    f.flush();
+    if (!f) return false;
+    if (stats12) {
+        stats12[0] = nbricks;
+        for (uint64_t b = 0; b < nbricks; ++b) ++stats12[1 + cls[b]];
+        stats12[9] = payload_words;
+        stats12[10] = sizeof(h) + (uint64_t)h.p.n_poses * sizeof(Matrix4cf) + padded + 4 * payload_words;
+        stats12[11] = chunks;
+    }
+    return true;
+}
 void KinectFusionReconstruction::saveCheckpoint(const std::string &filename) {
     std::vector<float> v, g;
     std::vector<int> w;
@@ -186,7 +318,43 @@ bool KinectFusionReconstruction::loadCheckpoint(const std::string &filename) {
     CkptHeader h{};
     if (file_bytes < (long long)sizeof(h)) return false;
     f.read(reinterpret_cast<char *>(&h), sizeof(h));
-    if (!f || std::memcmp(h.magic, "XSTSDF2", 8) != 0) return false;
+    if (!f) return false;
+    // what follows the restored volume, whichever format it came in
+    auto commit = [&](std::vector<Matrix4cf> &poses, int file_frame_id) {
+        ++volume_generation;
+        RebuildSignMap();    // the volume was written behind the integrate kernels' back
+        world2camera_record.swap(poses);
+        world2camera = world2camera_record.back();
+        frame_id = file_frame_id;
+        // previous-frame maps are derived state: regenerate them from the restored volume and pose (in a sharded run every
+        // rank must load its own file before the next frame: the raycast composite is a collective)
+        CalculatePointCloud(vmaps_g_prev_d[0], nmaps_g_prev_d[0]);
+        ModelMapPyramid();
+        synchronize();
+    };
+    if (std::memcmp(h.magic, "XSTSDF3", 8) == 0) {
+        // the brick-sparse format: the same geometry and shard checks against this instance, and pack_validate's on the file itself, which is read
+        // whole into host memory before anything is touched
+        SparseFile s;
+        if (!read_sparse_file(f, file_bytes, s)) return false;
+        const CkptPrefix &p = s.h.p;
+        for (int i = 0; i < 3; ++i) if (p.res[i] != volume_resolution[i]) return false;
+        if (p.voxel_size != voxel_size || p.tranc_dist != tsdf_volume_d_ptr->getTsdfTruncDist()) return false;
+        if (p.zs0 != zs0 || p.zs1 != zs1 || p.shard_rank != shard_rank || p.shard_count != shard_count || p.frame_id < 0) return false;
+        DeviceArray2D<float> dv = tsdf_volume_d_ptr->value(), dg = tsdf_volume_d_ptr->grad();
+        DeviceArray2D<int> dw = tsdf_volume_d_ptr->weight();
+        const size_t rows = (size_t)p.res[1] * (size_t)(p.zs1 - p.zs0);
+        if ((size_t)dv.rows() != rows || dv.cols() != p.res[0] || (size_t)dg.rows() != rows || (size_t)dw.rows() != rows) return false;
+        if (dv.step() != dg.step() || dv.step() != dw.step()) return false;
+        std::vector<Matrix4cf> poses((size_t)p.n_poses);
+        std::memcpy(static_cast<void *>(poses.data()), s.poses(), poses.size() * sizeof(Matrix4cf));
+        // validated: commit
+        synchronize();
+        unpack_sparse(s, dv.ptr(0), dw.ptr(0), dg.ptr(0), dv.step(), checkpoint_staging_words);
+        commit(poses, p.frame_id);
+        return true;
+    }
+    if (std::memcmp(h.magic, "XSTSDF2", 8) != 0) return false;
     for (int i = 0; i < 3; ++i) if (h.res[i] != volume_resolution[i]) return false;
     if (h.voxel_size != voxel_size || h.tranc_dist != tsdf_volume_d_ptr->getTsdfTruncDist()) return false;
     if (h.zs0 != zs0 || h.zs1 != zs1 || h.shard_rank != shard_rank || h.shard_count != shard_count) return false;
@@ -211,16 +379,7 @@ bool KinectFusionReconstruction::loadCheckpoint(const std::string &filename) {
     restore_rows(dv, v, X, rows);
     restore_rows(dg, g, X, rows);
     restore_rows(dw, w, X, rows);
-    ++volume_generation;
-    RebuildSignMap();    // the volume was written behind the integrate kernels' back
-    world2camera_record.swap(poses);
-    world2camera = world2camera_record.back();
-    frame_id = h.frame_id;
-    // previous-frame maps are derived state: regenerate them from the restored volume and pose (in a sharded run every
-    // rank must load its own file before the next frame: the raycast composite is a collective)
-    CalculatePointCloud(vmaps_g_prev_d[0], nmaps_g_prev_d[0]);
-    ModelMapPyramid();
-    synchronize();
+    commit(poses, h.frame_id);
     return true;
 }
 
@@ -262,14 +421,15 @@ int KinectFusionReconstruction::MergeVolume(const float *src_value, const int *s
 }
 
 namespace {
-// An XSTSDF2 file of a whole volume, validated in full (magic, exact length, shard_count 1, the truncation distance `tranc_dist`) and uploaded
+// A checkpoint file of a whole volume in either format (XSTSDF2: dense; XSTSDF3: brick-sparse, pack_validate on top), validated in full (magic, exact length,
+// shard_count 1, the truncation distance `tranc_dist`) and uploaded, the dense file as it is, the sparse one compact and expanded by the unpack kernel,
 // to a temporary device volume with one pitch for the three arrays.  False on any mismatch, with nothing allocated.
 struct CkptVolume {
     CkptHeader h{};
     DeviceArray2D<float> dv, dg;
     DeviceArray2D<int> dw;
 };
-bool upload_whole_checkpoint(const std::string &filename, float tranc_dist, CkptVolume &out) {
+bool upload_whole_checkpoint(const std::string &filename, float tranc_dist, unsigned long long staging_words, CkptVolume &out) {
     CkptHeader &h = out.h;
     std::ifstream f(filename, std::ios::binary);
     if (!f) return false;
@@ -278,7 +438,9 @@ bool upload_whole_checkpoint(const std::string &filename, float tranc_dist, Ckpt
     f.seekg(0, std::ios::beg);
     if (file_bytes < (long long)sizeof(h)) return false;
     f.read(reinterpret_cast<char *>(&h), sizeof(h));
-    if (!f || std::memcmp(h.magic, "XSTSDF2", 8) != 0) return false;
+    if (!f) return false;
+    const bool sparse = std::memcmp(h.magic, "XSTSDF3", 8) == 0;
+    if (!sparse && std::memcmp(h.magic, "XSTSDF2", 8) != 0) return false;
     for (int i = 0; i < 3; ++i)
         if (h.res[i] < 1 || h.res[i] > 65535) return false;
     if (h.shard_count != 1 || h.shard_rank != 0 || h.zs0 != 0 || h.zs1 != h.res[2]) return false;   // a whole volume
@@ -287,6 +449,14 @@ bool upload_whole_checkpoint(const std::string &filename, float tranc_dist, Ckpt
     const int X = h.res[0];
     const size_t rows = (size_t)h.res[1] * (size_t)h.res[2], n = rows * (size_t)X;
     if (rows >= (size_t)1 << 31) return false;
+    if (sparse) {   // the compact file up, the temporary volume filled by the unpack kernel (the header's first 52 bytes are the fields checked above)
+        SparseFile s;
+        if (!read_sparse_file(f, file_bytes, s)) return false;
+        out.dv.create((int)rows, X); out.dg.create((int)rows, X); out.dw.create((int)rows, X);
+        if (out.dv.step() != out.dg.step() || out.dv.step() != out.dw.step()) return false;
+        unpack_sparse(s, out.dv.ptr(0), out.dw.ptr(0), out.dg.ptr(0), out.dv.step(), staging_words);
+        return true;
+    }
     const long long expect = (long long)sizeof(h) + (long long)h.n_poses * (long long)sizeof(Matrix4cf) + 3LL * (long long)n * 4LL;
     if (file_bytes != expect) return false;            // truncated or trailing bytes
     f.seekg((std::streamoff)((long long)sizeof(h) + (long long)h.n_poses * (long long)sizeof(Matrix4cf)), std::ios::beg);
@@ -312,7 +482,7 @@ int KinectFusionReconstruction::MergeCheckpoint(const std::string &filename, con
     for (int i = 0; i < 12; ++i)
         if (!std::isfinite(T16[i])) return -1;
     CkptVolume c;
-    if (!upload_whole_checkpoint(filename, tsdf_volume_d_ptr->getTsdfTruncDist(), c)) return -1;
+    if (!upload_whole_checkpoint(filename, tsdf_volume_d_ptr->getTsdfTruncDist(), checkpoint_staging_words, c)) return -1;
     return MergeVolume(c.dv.ptr(0), c.dw.ptr(0), c.dg.ptr(0), c.dv.step(), c.h.res, c.h.voxel_size, c.h.tranc_dist, T16, min_weight, written);
 }
 
@@ -395,7 +565,7 @@ int KinectFusionReconstruction::AlignCheckpoint(const std::string &filename, con
     for (int i = 0; i < 16 * N; ++i)
         if (i % 16 < 12 && !std::isfinite(T16xN[i])) return -1;
     CkptVolume c;
-    if (!upload_whole_checkpoint(filename, tsdf_volume_d_ptr->getTsdfTruncDist(), c)) return -1;
+    if (!upload_whole_checkpoint(filename, tsdf_volume_d_ptr->getTsdfTruncDist(), checkpoint_staging_words, c)) return -1;
     return AlignVolume(c.dv.ptr(0), c.dw.ptr(0), c.dv.step(), c.h.res, c.h.voxel_size, c.h.tranc_dist, T16xN, N, iterations, damping, min_weight, max_residual,
                        T16_out, report, loss_history);
 }
@@ -445,7 +615,7 @@ int KinectFusionReconstruction::ScoreTransformsCheckpoint(const std::string &fil
     if (!tsdf_volume_d_ptr) return 0;
     if (!T16xP || !out2xP || P < 1) return -1;
     CkptVolume c;
-    if (!upload_whole_checkpoint(filename, tsdf_volume_d_ptr->getTsdfTruncDist(), c)) return -1;
+    if (!upload_whole_checkpoint(filename, tsdf_volume_d_ptr->getTsdfTruncDist(), checkpoint_staging_words, c)) return -1;
     return ScoreTransformsVolume(c.dv.ptr(0), c.dw.ptr(0), c.dv.step(), c.h.res, c.h.voxel_size, c.h.tranc_dist, T16xP, P, stride, min_weight, max_residual, out2xP);
 }
 
@@ -589,7 +759,7 @@ int KinectFusionReconstruction::AlignCheckpointGlobal(const std::string &filenam
     if (!tsdf_volume_d_ptr) return 0;
     if (!T16_out || (opts && !search_opts_ok(*opts))) return -1;
     CkptVolume c;
-    if (!upload_whole_checkpoint(filename, tsdf_volume_d_ptr->getTsdfTruncDist(), c)) return -1;
+    if (!upload_whole_checkpoint(filename, tsdf_volume_d_ptr->getTsdfTruncDist(), checkpoint_staging_words, c)) return -1;
     return AlignVolumeGlobal(c.dv.ptr(0), c.dw.ptr(0), c.dv.step(), c.h.res, c.h.voxel_size, c.h.tranc_dist, opts, T16_out, report);
 }
 
@@ -690,7 +860,7 @@ int KinectFusionReconstruction::DiffCheckpoint(const std::string &filename, cons
     for (int i = 0; i < 12; ++i)
         if (!std::isfinite(T16[i])) return -1;
     CkptVolume c;
-    if (!upload_whole_checkpoint(filename, tsdf_volume_d_ptr->getTsdfTruncDist(), c)) return -1;
+    if (!upload_whole_checkpoint(filename, tsdf_volume_d_ptr->getTsdfTruncDist(), checkpoint_staging_words, c)) return -1;
     return DiffVolume(c.dv.ptr(0), c.dw.ptr(0), c.dv.step(), c.h.res, c.h.voxel_size, c.h.tranc_dist, T16, min_weight, lo, hi, cell, min_size, capacity,
                       this_records8, this_count, other_records8, other_count, counts3, this_dense, other_dense);
 }

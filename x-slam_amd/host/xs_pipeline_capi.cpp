@@ -7,9 +7,12 @@
 #include "align_search_host.hpp"
 #include "merge_host.hpp"
 #include "newton_host.hpp"
+#include "pack_host.hpp"
 #include <cstring>
 #include <exception>
+#include <fstream>
 #include <memory>
+#include <vector>
 
 typedef KinectFusionReconstruction KF;
 using xs_host::Matrix4cf;
@@ -458,6 +461,70 @@ long long xs_kf_volume_generation(void *kf) { return (long long)((KF *)kf)->volu
 int xs_kf_save_checkpoint(void *kf, const char *path) { ((KF *)kf)->saveCheckpoint(path); return 0; }
 int xs_kf_load_checkpoint(void *kf, const char *path) { return ((KF *)kf)->loadCheckpoint(path) ? 0 : -1; }
 int xs_kf_save_tsdf_volume(void *kf, const char *path) { ((KF *)kf)->saveTSDFVolume(path); return 0; }
+int xs_kf_save_checkpoint_sparse(void *kf, const char *path, unsigned long long *stats12) {
+    if (!kf || !path) return -1;
+    return ((KF *)kf)->saveCheckpointSparse(path, stats12) ? 0 : -1;
+}
+long long xs_kf_checkpoint_staging_words(void *kf, unsigned long long words) {
+    if (!kf || (words != 0 && words < xs_host::PACK_MAX_BRICK_WORDS) || words > (1ull << 40)) return -1;
+    if (words) ((KF *)kf)->checkpoint_staging_words = words;
+    return (long long)((KF *)kf)->checkpoint_staging_words;
+}
+int xs_host_checkpoint_info(const char *path, double *out32) {
+    using namespace xs_host;
+    if (!path || !out32) return -1;
+    for (int i = 0; i < 32; ++i) out32[i] = 0.0;
+    std::ifstream f(path, std::ios::binary);
+    if (!f) return -1;
+    f.seekg(0, std::ios::end);
+    const long long file_bytes = (long long)f.tellg();
+    f.seekg(0, std::ios::beg);
+    PackHeader h{};
+    if (file_bytes < (long long)sizeof(CkptPrefix)) return -1;
+    f.read(reinterpret_cast<char *>(&h.p), sizeof(h.p));
+    if (!f) return -1;
+    const bool v3 = pack_magic_is(h.p.magic, "XSTSDF3"), v2 = pack_magic_is(h.p.magic, "XSTSDF2");
+    if (!v2 && !v3) return -1;
+    const CkptPrefix &p = h.p;
+    out32[0] = v3 ? 3.0 : 2.0;
+    for (int i = 0; i < 3; ++i) out32[2 + i] = p.res[i];
+    out32[5] = p.voxel_size; out32[6] = p.tranc_dist; out32[7] = p.frame_id; out32[8] = p.n_poses; out32[9] = p.zs0; out32[10] = p.zs1;
+    out32[11] = p.shard_rank; out32[12] = p.shard_count;
+    out32[27] = (double)file_bytes;
+    PackError e = PACK_OK;
+    if (v2) {   // what loadCheckpoint asks of the file itself
+        if (p.res[2] < 1 || p.zs0 < 0 || p.zs1 <= p.zs0 || p.zs1 > p.res[2] || pack_brick_grid(p.res[0], p.res[1], p.zs1 - p.zs0, nullptr) == 0) e = PACK_BAD_GEOMETRY;
+        else if (p.n_poses < 1 || p.n_poses > PACK_MAX_POSES) e = PACK_BAD_POSES;
+        else {
+            const unsigned long long words = 3ull * (unsigned long long)p.res[0] * (unsigned long long)p.res[1] * (unsigned long long)(p.zs1 - p.zs0);
+            out32[26] = (double)words;
+            if ((unsigned long long)file_bytes != sizeof(CkptPrefix) + (unsigned long long)p.n_poses * PACK_POSE_BYTES + 4ull * words) e = PACK_BAD_LENGTH;
+        }
+    } else {
+        if (file_bytes < (long long)sizeof(PackHeader)) e = PACK_BAD_LENGTH;
+        else {
+            f.read(reinterpret_cast<char *>(&h) + sizeof(h.p), sizeof(h) - sizeof(h.p));
+            out32[13] = h.brick_edge; out32[14] = h.nbx; out32[15] = h.nby; out32[16] = h.nbz;
+            out32[17] = (double)h.nbricks; out32[26] = (double)h.payload_words;
+            uint64_t head = 0;
+            e = f ? pack_validate_header(h, &head) : PACK_BAD_LENGTH;
+            if (e == PACK_OK) {
+                if ((uint64_t)file_bytes < head) e = PACK_BAD_LENGTH;
+                else {
+                    std::vector<unsigned char> cls((size_t)pack_class_bytes_padded(h.nbricks));
+                    f.seekg((std::streamoff)(sizeof(PackHeader) + (uint64_t)p.n_poses * PACK_POSE_BYTES), std::ios::beg);
+                    f.read(reinterpret_cast<char *>(cls.data()), (std::streamsize)cls.size());
+                    uint64_t hist[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+                    e = f ? pack_validate(h, cls.data(), (uint64_t)file_bytes, hist) : PACK_BAD_LENGTH;
+                    for (int c = 0; c < 8; ++c) out32[18 + c] = (double)hist[c];
+                }
+            }
+        }
+    }
+    out32[1] = e == PACK_OK ? 1.0 : 0.0;
+    out32[28] = (double)e;
+    return 0;
+}
 
 int xs_kf_merge_volume(void *kf, const float *src_value, const int *src_weight, const float *src_grad, size_t src_step, const int *src_res,
                        float src_voxel_size, float src_tranc_dist, const double *T16, int min_weight, unsigned long long *written) {

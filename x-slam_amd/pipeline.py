@@ -108,6 +108,9 @@ _SIGS = {
     "xs_kf_save_checkpoint": (C.c_int, [_vp, C.c_char_p]),
     "xs_kf_load_checkpoint": (C.c_int, [_vp, C.c_char_p]),
     "xs_kf_save_tsdf_volume": (C.c_int, [_vp, C.c_char_p]),
+    "xs_kf_save_checkpoint_sparse": (C.c_int, [_vp, C.c_char_p, C.POINTER(C.c_ulonglong)]),
+    "xs_kf_checkpoint_staging_words": (C.c_longlong, [_vp, C.c_ulonglong]),
+    "xs_host_checkpoint_info": (C.c_int, [C.c_char_p, _f64p]),
     "xs_kf_merge_volume": (C.c_int, [_vp, _vp, _vp, _vp, _sz, _i32p, C.c_float, C.c_float, _f64p, C.c_int, C.POINTER(C.c_ulonglong)]),
     "xs_kf_merge_map": (C.c_int, [_vp, _vp, _f64p, C.c_int, C.POINTER(C.c_ulonglong)]),
     "xs_kf_merge_checkpoint": (C.c_int, [_vp, C.c_char_p, _f64p, C.c_int, C.POINTER(C.c_ulonglong)]),
@@ -303,6 +306,26 @@ def merge_tile_box(xform12, lo, hi, src_res):
     box = np.zeros(6, np.int32)
     rc = _lib.xs_host_merge_tile_box(m.ctypes.data_as(_f32p), l.ctypes.data_as(_i32p), h.ctypes.data_as(_i32p), s.ctypes.data_as(_i32p), box.ctypes.data_as(_i32p))
     return (box[:3].copy(), box[3:].copy()) if rc == 1 else None
+
+
+CHECKPOINT_ERRORS = ("ok", "magic", "geometry", "brick_edge", "reserved", "brick_grid", "poses", "class_byte", "payload_words", "length")
+
+
+def checkpoint_info(path):
+    """What a checkpoint file of either format holds (CPU; no payload is read): a dict with version (2: dense XSTSDF2, 3: brick-sparse XSTSDF3),
+    valid (the format's full validation: header fields, every class byte, the sum of the words per class, the exact file length), error (one of
+    CHECKPOINT_ERRORS), res, voxel_size, tranc_dist, frame_id, n_poses, planes (zs0, zs1), shard (rank, count), file_bytes, payload_words and,
+    for version 3, brick_edge, brick_grid, bricks and classes (bricks per class 0 .. 7).  ValueError for a file that is neither."""
+    o = np.zeros(32, np.float64)
+    if _lib.xs_host_checkpoint_info(str(path).encode(), o.ctypes.data_as(_f64p)) != 0:
+        raise ValueError(f"checkpoint_info: {path} is not a checkpoint file")
+    i = lambda k: int(o[k])
+    info = dict(version=i(0), valid=bool(o[1]), error=CHECKPOINT_ERRORS[i(28)], res=(i(2), i(3), i(4)), voxel_size=float(np.float32(o[5])),
+                tranc_dist=float(np.float32(o[6])), frame_id=i(7), n_poses=i(8), planes=(i(9), i(10)), shard=(i(11), i(12)), file_bytes=i(27),
+                payload_words=i(26))
+    if info["version"] == 3:
+        info.update(brick_edge=i(13), brick_grid=(i(14), i(15), i(16)), bricks=i(17), classes=[i(18 + c) for c in range(8)])
+    return info
 
 
 def _halton(i, base):
@@ -912,10 +935,29 @@ class KinectFusion:
         """The version of the volume's contents: moves with every write of the volume, stays under calls that only read the map."""
         return int(_lib.xs_kf_volume_generation(self.h))
 
-    def save_checkpoint(self, path):
-        _lib.xs_kf_save_checkpoint(self.h, path.encode())
+    def save_checkpoint(self, path, sparse=False):
+        """The volume and the pose record to a file.  sparse=False: the dense XSTSDF2 dump, 12 bytes per voxel.  sparse=True: the brick-sparse
+        XSTSDF3 (lossless; classified and compacted on the GPU, streamed through one pinned staging buffer), and the save's statistics as a dict:
+        bricks, classes (bricks per class 0 .. 7), payload_words, file_bytes, chunks.  load_checkpoint and every *_checkpoint method take
+        either file.  A rank of a sharded run saves its own planes in either format."""
+        if not sparse:
+            _lib.xs_kf_save_checkpoint(self.h, path.encode())
+            return None
+        s = (C.c_ulonglong * 12)()
+        if _lib.xs_kf_save_checkpoint_sparse(self.h, path.encode(), s) != 0:
+            raise OSError(f"save_checkpoint: cannot write {path}")
+        return dict(bricks=int(s[0]), classes=[int(s[1 + c]) for c in range(8)], payload_words=int(s[9]), file_bytes=int(s[10]), chunks=int(s[11]))
+
+    def checkpoint_staging_words(self, words=0):
+        """The staging buffer of sparse saves and loads in 32-bit words (default 16 Mi = 64 MiB): set when words >= 1536, returned either way."""
+        n = int(_lib.xs_kf_checkpoint_staging_words(self.h, int(words)))
+        if n < 0:
+            raise ValueError("checkpoint_staging_words: at least 1536 words (one brick at its largest)")
+        return n
 
     def load_checkpoint(self, path):
+        """Restores the volume, the pose record and the frame number from a checkpoint of either format (the magic decides), written by an
+        instance of the same geometry (and, in shard mode, the same rank).  False, with the state unchanged, for any other file."""
         return _lib.xs_kf_load_checkpoint(self.h, path.encode()) == 0
 
     def save_tsdf_volume(self, path):
@@ -942,7 +984,7 @@ class KinectFusion:
         return self._merge_call("xs_kf_merge_map", _lib.xs_kf_merge_map(self.h, other.h, t.ctypes.data_as(_f64p), int(min_weight), C.byref(n)), n)
 
     def merge_checkpoint(self, path, T=None, min_weight=1):
-        """merge_map with the other map read from a checkpoint file of a whole volume (save_checkpoint); the file is validated before anything
+        """merge_map with the other map read from a checkpoint file of a whole volume (save_checkpoint, dense or sparse: either format is accepted); the file is validated before anything
         is touched and a bad one raises ValueError with the state unchanged."""
         t = _real44(np.eye(4) if T is None else T)
         n = C.c_ulonglong(0)
@@ -986,7 +1028,7 @@ class KinectFusion:
         return self._diff_call("xs_kf_diff_map", (other.h,), T, min_weight, lo, hi, cell_vox, min_size, masks, int(capacity))
 
     def diff_checkpoint(self, path, T=None, min_weight=1, lo=0.0, hi=0.5, cell_vox=0, min_size=8, masks=False, capacity=1024):
-        """diff_map with the other map read from a checkpoint file of a whole volume (save_checkpoint), validated as merge_checkpoint does: with
+        """diff_map with the other map read from a checkpoint file of a whole volume (save_checkpoint, dense or sparse: either format is accepted), validated as merge_checkpoint does: with
         yesterday's checkpoint as the other map, only_this is what appeared since and only_other what went away.
         Intended use: kf.diff_checkpoint(path, kf.align_checkpoint_global(path)[1])."""
         return self._diff_call("xs_kf_diff_checkpoint", (path.encode(),), T, min_weight, lo, hi, cell_vox, min_size, masks, int(capacity))
@@ -1019,7 +1061,7 @@ class KinectFusion:
         return self._align_call("xs_kf_align_map", other.h, T0, iterations, damping, min_weight, max_residual)
 
     def align_checkpoint(self, path, T0=None, iterations=10, damping=1e-3, min_weight=1, max_residual=1.0):
-        """align_map with the other map read from a checkpoint file of a whole volume (save_checkpoint), validated as merge_checkpoint does.
+        """align_map with the other map read from a checkpoint file of a whole volume (save_checkpoint, dense or sparse: either format is accepted), validated as merge_checkpoint does.
         Intended use: kf.merge_checkpoint(path, kf.align_checkpoint(path, T_guess)[1])."""
         return self._align_call("xs_kf_align_checkpoint", path.encode(), T0, iterations, damping, min_weight, max_residual)
 
@@ -1049,7 +1091,7 @@ class KinectFusion:
         return self._score_transforms_call("xs_kf_score_transforms", other.h, Ts, stride, min_weight, max_residual)
 
     def score_transforms_checkpoint(self, path, Ts, stride=1, min_weight=1, max_residual=1.0):
-        """score_transforms with the other map read from a checkpoint file of a whole volume, validated as merge_checkpoint does."""
+        """score_transforms with the other map read from a checkpoint file of a whole volume (either format is accepted), validated as merge_checkpoint does."""
         return self._score_transforms_call("xs_kf_score_transforms_checkpoint", path.encode(), Ts, stride, min_weight, max_residual)
 
     def _align_global_call(self, name, source, candidates, keep, rounds, stride, box_t, refine_t, refine_r, iterations, damping, min_weight, max_residual, Ts):
@@ -1088,7 +1130,7 @@ class KinectFusion:
 
     def align_checkpoint_global(self, path, candidates=2048, keep=8, rounds=2, stride=4, box_t=None, refine_t=None, refine_r=0.25, iterations=10, damping=1e-3,
                                 min_weight=1, max_residual=1.0, Ts=None):
-        """align_map_global with the other map read from a checkpoint file of a whole volume (save_checkpoint), validated as merge_checkpoint
+        """align_map_global with the other map read from a checkpoint file of a whole volume (save_checkpoint, dense or sparse: either format is accepted), validated as merge_checkpoint
         does.  Intended use: kf.merge_checkpoint(path, kf.align_checkpoint_global(path)[1])."""
         return self._align_global_call("xs_kf_align_checkpoint_global", path.encode(), candidates, keep, rounds, stride, box_t, refine_t, refine_r, iterations,
                                        damping, min_weight, max_residual, Ts)
