@@ -1,5 +1,5 @@
 // merge_selftest.cpp — x-slam_amd/host/merge_host.hpp under the host sanitizers, no GPU: merge_affine against the closed forms, map_transform's
-// round trip, and merge_tile_box (the text the merge kernel compiles for the device) against the per-voxel indices of whole tiles.
+// round trip, second_map_ok's table, and merge_tile_box (the text the merge kernel compiles for the device) against the per-voxel indices of whole tiles.
 // Built and run by tests/test_merge_cases_cpu.py with -fsanitize=address,undefined -fno-sanitize-recover=all -ffp-contract=off.
 #include "merge_host.hpp"
 #include <cstdint>
@@ -186,7 +186,55 @@ static void test_tile_box() {
     CHECK(!merge_tile_box(neg, lo, hi, S, box));
 }
 
+// second_map_ok: one case per rule and per parameter combination.  The accepted map first; every other row changes one thing about it.
+static void test_second_map() {
+    static float this_value[4], this_grad[4], value[4], grad[4];
+    static int this_weight[4], weight[4];
+    const float td = 0.03f;
+    const SecondMap good{value, weight, grad, 40, {10, 3, 2}, 0.01f, td};   // a pitch of exactly 4 X
+    auto ok = [&](const SecondMap &m, int min_axis, bool need_grad) { return second_map_ok(m, min_axis, need_grad, td, this_value, this_weight, this_grad); };
+    auto with = [&](void (*change)(SecondMap &)) { SecondMap m = good; change(m); return m; };
+    struct Row { SecondMap m; int min_axis; bool need_grad, want; const char *what; };
+    const Row rows[] = {
+        {good, 1, true, true, "the map, for a merge"},
+        {good, 2, false, true, "the map, for an alignment"},
+        {with([](SecondMap &m) { m.value = nullptr; }), 1, false, false, "no value array"},
+        {with([](SecondMap &m) { m.weight = nullptr; }), 1, false, false, "no weight array"},
+        {with([](SecondMap &m) { m.grad = nullptr; }), 1, true, false, "no grad array where it is needed"},
+        {with([](SecondMap &m) { m.grad = nullptr; }), 1, false, true, "no grad array where it is not"},
+        {with([](SecondMap &m) { m.res[0] = 0; m.step = 4; }), 1, false, false, "an axis of 0 (x)"},
+        {with([](SecondMap &m) { m.res[1] = 0; }), 1, false, false, "an axis of 0 (y)"},
+        {with([](SecondMap &m) { m.res[2] = 0; }), 1, false, false, "an axis of 0 (z)"},
+        {with([](SecondMap &m) { m.res[2] = -3; }), 1, false, false, "a negative axis"},
+        {with([](SecondMap &m) { m.res[2] = 1; }), 1, false, true, "an axis of 1, minimum 1"},
+        {with([](SecondMap &m) { m.res[2] = 1; }), 2, false, false, "an axis of 1, minimum 2"},
+        {with([](SecondMap &m) { m.res[0] = 1; m.step = 4; }), 2, false, false, "an x axis of 1, minimum 2"},
+        {with([](SecondMap &m) { m.res[0] = 1; m.step = 4; }), 1, true, true, "a volume of one column"},
+        {with([](SecondMap &m) { m.voxel_size = 0.f; }), 1, false, false, "a voxel size of 0"},
+        {with([](SecondMap &m) { m.voxel_size = -0.01f; }), 1, false, false, "a negative voxel size"},
+        {with([](SecondMap &m) { m.voxel_size = std::numeric_limits<float>::quiet_NaN(); }), 1, false, false, "a voxel size that is NaN"},
+        {with([](SecondMap &m) { m.voxel_size = std::numeric_limits<float>::infinity(); }), 1, false, false, "an infinite voxel size"},
+        {with([](SecondMap &m) { m.voxel_size = 7.f; }), 2, true, true, "another voxel size"},
+        {with([](SecondMap &m) { m.tranc_dist = std::nextafter(m.tranc_dist, 1.f); }), 1, false, false, "a truncation distance one ulp above"},
+        {with([](SecondMap &m) { m.tranc_dist = std::nextafter(m.tranc_dist, 0.f); }), 2, false, false, "a truncation distance one ulp below"},
+        {with([](SecondMap &m) { m.value = this_value; }), 1, false, false, "this map's value array"},
+        {with([](SecondMap &m) { m.weight = this_weight; }), 2, false, false, "this map's weight array"},
+        {with([](SecondMap &m) { m.grad = this_grad; }), 1, true, false, "this map's grad array, for a merge"},
+        {with([](SecondMap &m) { m.grad = this_grad; }), 1, false, true, "this map's grad array where grad is not read"},
+        {with([](SecondMap &m) { m.step = 36; }), 1, false, false, "a pitch below 4 X"},
+        {with([](SecondMap &m) { m.step = 0; }), 1, false, false, "no pitch"},
+        {with([](SecondMap &m) { m.step = 42; }), 1, false, false, "a pitch that is no multiple of 4"},
+        {with([](SecondMap &m) { m.step = 256; }), 2, true, true, "a padded pitch"},
+    };
+    for (const Row &r : rows) {
+        const bool got = ok(r.m, r.min_axis, r.need_grad);
+        if (got != r.want) { std::printf("FAILED second_map_ok: %s\n", r.what); ++failures; }
+    }
+    CHECK(!second_map_ok(SecondMap{}, 1, false, 0.f, this_value, this_weight, this_grad));   // the empty descriptor
+}
+
 int main() {
+    test_second_map();
     test_affine();
     test_transform();
     test_tile_box();

@@ -1,5 +1,5 @@
 // pack_selftest.cpp — x-slam_amd/host/pack_host.hpp under the host sanitizers, no GPU: the header's layout, the words per class, the brick grid and
-// its refusals, the validation of a header with its class bytes rule by rule, the offsets, the partition of the bricks into chunks (no gap, no
+// its refusals, the validation of a header with its class bytes rule by rule, the dense format's file rules, the offsets, the partition of the bricks into chunks (no gap, no
 // chunk above the staging words, none that one more brick would fit into), and the 64-bit sums at the brick counts of a 1024^3 volume and beyond.
 // Built and run by tests/test_pack_cases_cpu.py with -fsanitize=address,undefined -fno-sanitize-recover=all -ffp-contract=off.
 #include "pack_host.hpp"
@@ -118,6 +118,45 @@ static void test_validation() {
     CHECK(hr.nbricks == 18 && hr.nbz == 3 && pack_validate(hr, rk.data(), file_bytes_of(hr), nullptr) == PACK_OK);
 }
 
+// pack_validate_dense: the accepted XSTSDF2 file, and one case per PackError it can return
+static void test_dense_validation() {
+    PackHeader h3 = header_for(17, 9, 64, 24, 41, {});
+    CkptPrefix good = h3.p;   // a rank's planes of a 17 x 9 x 64 volume, two poses
+    good.magic[6] = '2';
+    const uint64_t words = 3ull * 17 * 9 * 17, bytes = 52 + 2 * 128 + 4 * words;
+    auto with = [&](void (*change)(CkptPrefix &)) { CkptPrefix p = good; change(p); return p; };
+    struct Row { CkptPrefix p; uint64_t file_bytes; PackError want; const char *what; };
+    const Row rows[] = {
+        {good, bytes, PACK_OK, "the file"},
+        {h3.p, bytes, PACK_BAD_MAGIC, "the sparse format's magic"},
+        {with([](CkptPrefix &p) { p.magic[7] = 'x'; }), bytes, PACK_BAD_MAGIC, "a magic without its NUL"},
+        {with([](CkptPrefix &p) { p.res[2] = 0; }), bytes, PACK_BAD_GEOMETRY, "no planes in the volume"},
+        {with([](CkptPrefix &p) { p.zs0 = -1; }), bytes, PACK_BAD_GEOMETRY, "a first plane below 0"},
+        {with([](CkptPrefix &p) { p.zs1 = p.zs0; }), bytes, PACK_BAD_GEOMETRY, "no stored plane"},
+        {with([](CkptPrefix &p) { p.zs1 = 65; }), bytes, PACK_BAD_GEOMETRY, "planes past the resolution"},
+        {with([](CkptPrefix &p) { p.res[0] = 0; }), bytes, PACK_BAD_GEOMETRY, "an axis the brick grid refuses"},
+        {with([](CkptPrefix &p) { p.res[1] = PACK_MAX_AXIS + 1; }), bytes, PACK_BAD_GEOMETRY, "an axis above the brick grid's bound"},
+        {with([](CkptPrefix &p) { p.n_poses = 0; }), bytes, PACK_BAD_POSES, "no pose"},
+        {with([](CkptPrefix &p) { p.n_poses = PACK_MAX_POSES + 1; }), bytes, PACK_BAD_POSES, "more poses than the bound"},
+        {good, bytes - 4, PACK_BAD_LENGTH, "a truncated file"},
+        {good, bytes + 1, PACK_BAD_LENGTH, "trailing bytes"},
+        {with([](CkptPrefix &p) { p.n_poses = 3; }), bytes, PACK_BAD_LENGTH, "a pose the length does not hold"},
+    };
+    for (const Row &r : rows) {
+        uint64_t w = 77;
+        const PackError got = pack_validate_dense(r.p, r.file_bytes, &w);
+        if (got != r.want) { std::printf("FAILED pack_validate_dense: %s: %d\n", r.what, (int)got); ++failures; }
+        // the words are reported once geometry and pose count hold, whatever the length
+        CHECK(w == ((got == PACK_OK || got == PACK_BAD_LENGTH) ? words : 77));
+        CHECK(pack_validate_dense(r.p, r.file_bytes, nullptr) == got);
+    }
+    // a whole 1024^3 volume: the length passes 2^33 bytes
+    h3 = header_for(1024, 1024, 1024, 0, 1024, {});
+    h3.p.magic[6] = '2';
+    uint64_t w = 0;
+    CHECK(pack_validate_dense(h3.p, 52 + 256 + 12884901888ull, &w) == PACK_OK && w == 3221225472ull);
+}
+
 static void check_partition(const std::vector<uint64_t> &offsets, uint64_t staging) {
     const uint64_t n = offsets.size() - 1;
     uint64_t b0 = 0, chunks = 0;
@@ -164,6 +203,7 @@ int main() {
     test_layout_and_words();
     test_grid();
     test_validation();
+    test_dense_validation();
     test_offsets_and_partition();
     if (failures) { std::printf("%d checks FAILED\n", failures); return 1; }
     std::printf("all checks held\n");

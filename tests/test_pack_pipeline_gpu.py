@@ -118,8 +118,8 @@ def test_load_sparse_is_load_dense(dev, scene):
 
 
 def test_the_map_calls_take_the_sparse_file(dev, scene):
-    """merge_checkpoint, diff_checkpoint with masks, align_checkpoint and score_transforms_checkpoint return on the sparse file what they return on
-    the dense file, compared as bits."""
+    """merge_checkpoint, diff_checkpoint with masks, align_checkpoint, score_transforms_checkpoint and align_checkpoint_global (over the caller's
+    candidates, so that the search is short) return on the sparse file what they return on the dense file, compared as bits."""
     torch, capi, pl = dev
     prm, frames = scene["prm"], scene["frames"]
     T = np.eye(4)
@@ -135,8 +135,9 @@ def test_the_map_calls_take_the_sparse_file(dev, scene):
         ok, Ta, report, hist = c.align_checkpoint(path, T, iterations=3)
         Ts = np.stack([np.eye(4), T, Ta])
         scores = c.score_transforms_checkpoint(path, Ts, stride=2)
+        search = c.align_checkpoint_global(path, Ts=Ts, keep=2, rounds=1, stride=2, iterations=3)
         written = c.merge_checkpoint(path, T, min_weight=2)
-        out[kind] = dict(diff=diff, align=(ok, Ta, report, hist), scores=scores, written=written, volume=c.volume())
+        out[kind] = dict(diff=diff, align=(ok, Ta, report, hist), scores=scores, search=search, written=written, volume=c.volume())
         c.close()
     d, s = out["dense"], out["sparse"]
     assert s["written"] == d["written"] > 1000 and same_volume(s["volume"], d["volume"])
@@ -147,6 +148,8 @@ def test_the_map_calls_take_the_sparse_file(dev, scene):
     assert s["align"][2] == d["align"][2] and d["align"][2]["count"] > 100
     assert np.array_equal(np.asarray(s["align"][3], np.float64).view(np.uint64), np.asarray(d["align"][3], np.float64).view(np.uint64))
     assert np.array_equal(np.asarray(s["scores"], np.float64).view(np.uint64), np.asarray(d["scores"], np.float64).view(np.uint64))
+    assert s["search"][0] == d["search"][0] and np.array_equal(s["search"][1].view(np.uint64), d["search"][1].view(np.uint64))
+    assert s["search"][2] == d["search"][2] and d["search"][2]["band_voxels"] > 100
 
 
 def test_bad_files_change_nothing(dev, scene, tmp_path):
@@ -186,6 +189,49 @@ def test_bad_files_change_nothing(dev, scene, tmp_path):
         assert same_volume(c.volume(), before), name
     assert (c.frame_id, c.num_poses(), c.volume_generation()) == (state[0], state[1], state[3]) and np.array_equal(c.world2camera(), state[2])
     assert c.process_frame(frames[2]) == 1
+    c.close()
+
+
+def test_every_map_call_refuses_a_bad_file_alike(dev, scene, tmp_path):
+    """The five *_checkpoint calls open the file through one opener: against a truncated file, a file of a sharded run and a file of another
+    truncation distance (one ulp), each method raises ValueError and each xs_kf_*_checkpoint returns -1, and the volume, the frame number, the
+    pose count and volume_generation keep their bits."""
+    torch, capi, pl = dev
+    prm, frames = scene["prm"], scene["frames"]
+    blob = open(scene["sparse"], "rb").read()
+    td = np.frombuffer(blob[24:28], np.float32)[0]
+    bad = {"truncated": blob[:-4], "sharded": blob[:44] + struct.pack("<ii", 0, 2) + blob[52:],
+           "tranc": blob[:24] + np.nextafter(td, np.float32(1)).tobytes() + blob[28:]}
+    assert pl.checkpoint_info(scene["sparse"])["tranc_dist"] == float(td) == scene["a"].tranc_dist()
+    c = pl.KinectFusion(prm)
+    for k in range(2):
+        assert c.process_frame(frames[k]) == 1
+    before = tuple(x.copy() for x in c.volume())
+    state = (c.frame_id, c.num_poses(), c.volume_generation())
+    eye = np.eye(4)
+
+    def f64(a):
+        return a.ctypes.data_as(pl._f64p)
+
+    for name, data in bad.items():
+        p = str(tmp_path / (name + ".bad"))
+        open(p, "wb").write(data)
+        for call in (lambda: c.merge_checkpoint(p), lambda: c.diff_checkpoint(p), lambda: c.align_checkpoint(p),
+                     lambda: c.score_transforms_checkpoint(p, eye[None]), lambda: c.align_checkpoint_global(p, Ts=eye[None], keep=1, rounds=0)):
+            with pytest.raises(ValueError):
+                call()
+        n, out, rep, hist, out2 = C.c_ulonglong(7), np.zeros(16), np.zeros(12), np.zeros(4), np.zeros(2)
+        counts, n_this, n_other = np.zeros(3, np.uint64), C.c_int(0), C.c_int(0)
+        opts = pl.AlignSearchOpts()
+        pl._lib.xs_kf_align_search_defaults(c.h, C.byref(opts))
+        assert pl._lib.xs_kf_merge_checkpoint(c.h, p.encode(), f64(eye), 1, C.byref(n)) == -1, name
+        assert pl._lib.xs_kf_diff_checkpoint(c.h, p.encode(), f64(eye), 1, 0.0, 0.5, 0, 8, 0, None, C.byref(n_this), None, C.byref(n_other),
+                                             counts.ctypes.data_as(C.POINTER(C.c_ulonglong)), None, None) == -1, name
+        assert pl._lib.xs_kf_align_checkpoint(c.h, p.encode(), f64(eye), 1, 3, 1e-3, 1, 1.0, f64(out), f64(rep), f64(hist)) == -1, name
+        assert pl._lib.xs_kf_score_transforms_checkpoint(c.h, p.encode(), 1, f64(eye), 1, 1, 1.0, f64(out2)) == -1, name
+        assert pl._lib.xs_kf_align_checkpoint_global(c.h, p.encode(), C.byref(opts), f64(out), f64(rep)) == -1, name
+        assert n.value == 7 and not out.any() and same_volume(c.volume(), before), name
+    assert (c.frame_id, c.num_poses(), c.volume_generation()) == state
     c.close()
 
 

@@ -12,6 +12,7 @@
 #pragma once
 #include "TsdfVolume.h"
 #include "flat_yaml.hpp"
+#include "merge_host.hpp"   // SecondMap
 #include "../csrc/xs_host_wait.h"
 #include <chrono>
 #include <string>
@@ -331,44 +332,51 @@ public:
     // The staging buffer of sparse saves and loads in 32-bit words: 16 Mi words (64 MiB) unless set; at least one brick's 1536.  It bounds the pinned
     // host buffer and the device buffer of a chunk whatever the volume's size (a volume whose payload is smaller allocates only that).
     unsigned long long checkpoint_staging_words = 16ull << 20;
-    // Merging a second map into the volume (xs_tsdf_merge in include/xslam_amd.h: the contract).  The source is a
-    // whole volume in device memory in the project's layout (three arrays at plane 0, one pitch) whose resolution and voxel size may differ
-    // from this map's; T16 is a real 4 x 4, row-major, taking a point of THIS map's volume frame (metres) to the source's volume frame.
+    // ---- the calls that take a second map (kf_second_map.cpp) ----
+    // The second map is a SecondMap (merge_host.hpp): a whole volume in device memory in the project's layout (the arrays at plane 0, one pitch)
+    // whose resolution and voxel size may differ from this map's; it is only read.  Every operation below refuses it with -1 when
+    // second_map_ok does: a null or aliasing array, an axis below the operation's minimum, a voxel size that is not finite and positive, a pitch
+    // that holds no row, or a truncation distance different from this map's (stored values are normalised by it, so it is refused, not
+    // rescaled).  Every operation returns -2 in shard mode before anything else, then 0 without a volume, then -1 on bad arguments, doing
+    // nothing; 1 when it ran.  A T16 is a real 4 x 4, row-major, taking a point of THIS map's volume frame (metres) to the second map's volume
+    // frame; an entry of its rows 0 .. 2 that is not finite is a bad argument.  Two ways to obtain the map besides the caller's own pointers:
+    // OtherInstanceMap: the volume of another instance of this process, which is synchronised and only read (grad only with_grad: a merge).
+    // 1; -1 for null or this instance itself, -2 for a sharded instance, -1 for one without a volume or with arrays of unequal pitch.
+    int OtherInstanceMap(KinectFusionReconstruction *other, bool with_grad, xs_host::SecondMap &out) const;
+    // OpenCheckpointMap: a checkpoint file of a whole volume in either format (saveCheckpoint, saveCheckpointSparse), read and validated in
+    // full before anything is allocated — the format's rules (pack_host.hpp), axes 1 .. 65535, shard_count 1, every plane, this map's
+    // truncation distance — then written into a temporary device volume that `out` owns and out.map views; it is freed with `out`.
+    // 1; -2 in shard mode, 0 without a volume, -1 for any other file; nothing of this instance is touched.
+    struct CheckpointMap {
+        DeviceArray2D<float> dv, dg;
+        DeviceArray2D<int> dw;
+        xs_host::SecondMap map;
+    };
+    int OpenCheckpointMap(const std::string &filename, CheckpointMap &out);
+    // Merging (xs_tsdf_merge in include/xslam_amd.h: the contract).  The map's grad array is needed; axes >= 1.
     // The device is drained, xform12 built by merge_host.hpp's merge_affine, the kernel run with max_integration_weight, and everything
     // derived from the volume follows as after loadCheckpoint: volume_generation, the sign map, the cached planning and relocalisation
     // maps, the previous frame's model maps at the current pose.  Poses, frame_id and the trajectory record are untouched.  *written
-    // (optional): the voxels written.  Returns 1 when it ran, 0 without a volume, -1 on bad arguments (a null or aliasing source, a
-    // resolution or voxel size that is not positive, an entry of T that is not finite, min_weight < 1, a truncation distance different
-    // from this map's: stored values are normalised by it, so it is refused, not rescaled), -2 in shard mode, doing nothing.
-    int MergeVolume(const float *src_value, const int *src_weight, const float *src_grad, size_t src_step, const int *src_res, float src_voxel_size,
-                    float src_tranc_dist, const double *T16, int min_weight, unsigned long long *written);
-    // The same from an XSTSDF2 file (saveCheckpoint), validated in full before anything is touched: magic, exact length, a whole-volume file
-    // with shard_count 1, the truncation distance.  The file's volume goes to a temporary device volume that is freed after the merge.
-    // Any mismatch: -1 with the state unchanged.
-    int MergeCheckpoint(const std::string &filename, const double *T16, int min_weight, unsigned long long *written);
+    // (optional): the voxels written.  -1 also for min_weight < 1.
+    int MergeVolume(const xs_host::SecondMap &src, const double *T16, int min_weight, unsigned long long *written);
     // Aligning a second map to the volume before it is merged (xs_tsdf_align_terms in include/xslam_amd.h: the
-    // contract).  The source as for MergeVolume (its grad array is not needed); T16xN: N >= 1 starting transforms, each a real 4 x 4 as
-    // MergeVolume takes it.  The device is drained, the band index of THIS map prepared, and gn_batch_loop (gn_host.hpp) run over the starts:
+    // contract).  Axes >= 2.  T16xN: N >= 1 starting transforms.
+    // The device is drained, the band index of THIS map prepared, and gn_batch_loop (gn_host.hpp) run over the starts:
     // a pass is one xs_tsdf_align_terms launch per chunk of the starts still active, a step align_host.hpp's align_step.  T16_out receives
     // the start that ended ok — at least six voxels on every pass, the last one included, and a positive definite system on every step —
     // with the highest S = count - sum r^2 (ties: the lower index; S is relocalize_global's truncated-quadratic score for max_residual <= 1: above
     // that a kept voxel can subtract more than it adds); report = {its index, its count, its sum r^2,
     // its mean loss, launches run, starts that ended ok, band voxels in the index, 0}; loss_history (optional) its loss per pass, the
-    // last entry the loss it ended at.  Nothing of either map is modified: volume_generation, poses and frame_id stay.  Returns 1; 0 without
-    // a volume or when no start ended ok (T16_out untouched, report[0] = -1); -1 on bad arguments (MergeVolume's, and N < 1, iterations < 0,
-    // a damping or max_residual that is not finite, max_residual <= 0, a source axis below 2); -2 in shard mode.
-    int AlignVolume(const float *src_value, const int *src_weight, size_t src_step, const int *src_res, float src_voxel_size, float src_tranc_dist,
-                    const double *T16xN, int N, int iterations, double damping, int min_weight, float max_residual, double *T16_out, double report[8],
-                    std::vector<double> *loss_history);
-    // The same against an XSTSDF2 file: MergeCheckpoint's validation, its temporary device volume and its free.
-    int AlignCheckpoint(const std::string &filename, const double *T16xN, int N, int iterations, double damping, int min_weight, float max_residual,
-                        double *T16_out, double report[8], std::vector<double> *loss_history);
+    // last entry the loss it ended at.  Nothing of either map is modified: volume_generation, poses and frame_id stay.  0 also when no start
+    // ended ok (T16_out untouched, report[0] = -1); -1 also for N < 1, iterations < 0, min_weight < 1, a damping or max_residual that is not
+    // finite, max_residual <= 0.
+    int AlignVolume(const xs_host::SecondMap &src, const double *T16xN, int N, int iterations, double damping, int min_weight, float max_residual,
+                    double *T16_out, double report[8], std::vector<double> *loss_history);
     // Many transforms against the other map in one band pass each, and alignment with no initial guess (DESIGN.md section 4.24;
-    // xs_tsdf_score_transforms in include/xslam_amd.h: the contract).  The source as for AlignVolume.
+    // xs_tsdf_score_transforms in include/xslam_amd.h: the contract).  Axes >= 2.
     // ScoreTransformsVolume: the device is drained, the band index of THIS map prepared, every T16xP + 16 p put through merge_affine and
     // scored over every stride-th band entry in launches of XS_ALIGN_SCORE_MAX_TRANSFORMS; out2xP + 2 p = {sum r^2, count}.  *launches
-    // (optional) is advanced by the launches run.  Returns 1; 0 without a volume; -1 on bad arguments (AlignVolume's for the source,
-    // min_weight and max_residual, and P < 1, stride < 1, an entry of a T that is not finite); -2 in shard mode.
+    // (optional) is advanced by the launches run.  -1 also for AlignVolume's min_weight and max_residual, P < 1, stride < 1.
     // AlignVolumeGlobal: the search of align_search_host.hpp on top of it.  Both maps' band centroids (this map's from its index, the
     // other's from one xs_tsdf_band_build over the source into temporary buffers), round 0 over align_search_free's candidates (or the
     // caller's, when opts gives any), `rounds` rounds of align_search_around about each kept transform with the boxes halved per round,
@@ -378,32 +386,23 @@ public:
     // starts that ended ok, band voxels, scored entries per transform, the distance of the other map's centroid from this map's under
     // the winner, 0}.  Nothing of either map is modified.  Returns AlignVolume's codes (0 also when a map has an empty band); -1 also for
     // candidates < 1, keep outside 1 .. 32, rounds < 0, stride < 1, a box that is negative or not finite, a wrong opts->struct_bytes.
-    int ScoreTransformsVolume(const float *src_value, const int *src_weight, size_t src_step, const int *src_res, float src_voxel_size,
-                              float src_tranc_dist, const double *T16xP, int P, int stride, int min_weight, float max_residual, double *out2xP,
+    int ScoreTransformsVolume(const xs_host::SecondMap &src, const double *T16xP, int P, int stride, int min_weight, float max_residual, double *out2xP,
                               int *launches = nullptr);
-    int ScoreTransformsCheckpoint(const std::string &filename, const double *T16xP, int P, int stride, int min_weight, float max_residual, double *out2xP);
     void AlignSearchDefaults(struct xs_align_search_opts *opts) const;
-    int AlignVolumeGlobal(const float *src_value, const int *src_weight, size_t src_step, const int *src_res, float src_voxel_size, float src_tranc_dist,
-                          const struct xs_align_search_opts *opts, double *T16_out, double report[12]);
-    int AlignCheckpointGlobal(const std::string &filename, const struct xs_align_search_opts *opts, double *T16_out, double report[12]);
+    int AlignVolumeGlobal(const xs_host::SecondMap &src, const struct xs_align_search_opts *opts, double *T16_out, double report[12]);
     // What differs between this map and a second map, as clusters (xs_tsdf_diff in include/xslam_amd.h: the contract).
-    // The source and T16 as for MergeVolume (its grad array is not needed).  The device is drained, xform12 built by merge_affine, the two
+    // Axes >= 1.  The output arguments are checked before the volume.  The device is drained, xform12 built by merge_affine, the two
     // masks written by xs_tsdf_diff (only_this: this map has matter where the other is firmly free; only_other: the reverse), each labelled
     // and clustered by the frontier's calls within cells of `cell` voxels (the frontier's rule), and the clusters with count >= min_size
     // (frontier_select) returned in the frontier's record format: this_records8 / other_records8 (capacity x 8 uint64 each; may be null when
     // capacity is 0) with *this_count / *other_count.  counts3 (optional) = {compared, only_this, only_other} voxels; this_dense /
     // other_dense (optional, host, X * Y * Z bytes each) the masks expanded to a byte per voxel.  Every buffer is the call's own: nothing of
-    // either map is modified, volume_generation, the sign map, the band index and the planning caches stay.  Returns 1; 0 without a volume;
-    // -1 on bad arguments (MergeVolume's, lo or hi not finite or lo > hi, a bad cell, a negative capacity, a volume the frontier calls cannot
-    // label); -2 in shard mode; -4 when a list does not fit capacity, with both needed counts returned and nothing else written.
-    int DiffVolume(const float *src_value, const int *src_weight, size_t src_step, const int *src_res, float src_voxel_size, float src_tranc_dist,
-                   const double *T16, int min_weight, float lo, float hi, int cell, unsigned long long min_size, int capacity,
+    // either map is modified, volume_generation, the sign map, the band index and the planning caches stay.  -1 also for min_weight < 1, lo or
+    // hi not finite or lo > hi, a bad cell, a negative capacity, a volume the frontier calls cannot label; -4 when a list does not fit
+    // capacity, with both needed counts returned and nothing else written.
+    int DiffVolume(const xs_host::SecondMap &src, const double *T16, int min_weight, float lo, float hi, int cell, unsigned long long min_size, int capacity,
                    unsigned long long *this_records8, int *this_count, unsigned long long *other_records8, int *other_count, unsigned long long counts3[3],
                    unsigned char *this_dense, unsigned char *other_dense);
-    // The same against an XSTSDF2 file: MergeCheckpoint's validation, its temporary device volume and its free.
-    int DiffCheckpoint(const std::string &filename, const double *T16, int min_weight, float lo, float hi, int cell, unsigned long long min_size, int capacity,
-                       unsigned long long *this_records8, int *this_count, unsigned long long *other_records8, int *other_count, unsigned long long counts3[3],
-                       unsigned char *this_dense, unsigned char *other_dense);
 
     // counters of the last frame (synchronise the stream)
     long long lastUpdatedVoxels();
@@ -503,6 +502,8 @@ private:
     void reach_forget() { plan_.reach_key = ReachKey{}; plan_.travel_key = TravelKey{}; }   // the flood is not to be trusted, nor what was built over it
     // the volume object was replaced or released: whatever was derived from the old one is rebuilt on next use (the Gauss-Newton mailbox and
     // sequence numbers stay)
+    bool takes_second_map(const xs_host::SecondMap &m, int min_axis, bool need_grad) const;   // second_map_ok against this volume
+    void drain_device();   // what every call that takes a second map does before its first launch
     void invalidate_derived_maps() { reloc_.band_key = BandKey{}; plan_.grid_key = GridKey{}; plan_.clear_key = ClearKey{}; plan_.frontier_key = FrontierKey{}; reach_forget(); }
     DeviceArray2D<ushort> depth_ingest_d_;     // device copy of a host frame (ProcessFrameHost)
     ushort *ingest_pinned_[2] = {nullptr, nullptr};

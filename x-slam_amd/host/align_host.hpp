@@ -7,6 +7,13 @@
 
 namespace xs_host {
 
+// the report of an alignment call that has no result (yet): zeros, and -1 where the winner's index goes
+inline void align_report_clear(double *report, int n) {
+    if (!report) return;
+    for (int i = 0; i < n; ++i) report[i] = 0.0;
+    report[0] = -1.0;
+}
+
 // The six seeded maps of one pass: T_k = (I + i h G_k) T, k = 0 .. 5 (G_k: unit translation along axis k, or the hat matrix of axis k - 3:
 // gn_seeded_poses' order), each put through merge_affine's formula.  out[k]: the 12 entries of xform12 as (re, im) pairs.  The real part of T_k
 // is T itself, so the 12 real parts are merge_affine(T) bit for bit for every k; the seed goes into the imaginary parts alone: Im T_k = h G_k T

@@ -1,8 +1,11 @@
 // kf_internal.hpp — what more than one translation unit of the orchestrator needs and no caller of the class does
-// (KinectFusionReconstruction.cpp: lifecycle and frame path; kf_relocalize.cpp; kf_planning.cpp; kf_export.cpp).
+// (KinectFusionReconstruction.cpp: lifecycle and frame path; kf_relocalize.cpp; kf_planning.cpp; kf_export.cpp: point cloud, mesh, counters, raw
+// volume; kf_checkpoint.cpp: saving, reading and restoring checkpoints; kf_second_map.cpp: the calls that take a second map).
 #pragma once
 #include "KinectFusionReconstruction.h"
+#include "pack_host.hpp"
 #include <algorithm>
+#include <cstdint>
 #include <cstdlib>
 #include <cstring>
 #include <iostream>
@@ -26,3 +29,30 @@ inline void pack_real_pose(const xs_host::Matrix4cf &pose, float R9[9], float t3
         t3[r] = pose.m[r][3].real();
     }
 }
+
+// An XSTSDF3 file read whole into host memory and validated in full (pack_validate).
+struct SparseFile {
+    xs_host::PackHeader h{};
+    std::vector<char> bytes;           // the file
+    std::vector<uint64_t> offsets;     // nbricks + 1
+    const char *poses() const { return bytes.data() + sizeof(xs_host::PackHeader); }
+    const unsigned char *cls() const { return reinterpret_cast<const unsigned char *>(poses() + (size_t)h.p.n_poses * xs_host::PACK_POSE_BYTES); }
+    const char *payload() const { return reinterpret_cast<const char *>(cls()) + xs_host::pack_class_bytes_padded(h.nbricks); }
+};
+// A checkpoint file of either format (the magic decides) in host memory, validated at the format's level: pack_validate_dense or pack_validate
+// (pack_host.hpp).  Nothing on the device is touched or allocated by read; what the file must be for its reader (this instance's geometry for
+// loadCheckpoint, a whole volume for OpenCheckpointMap) is the reader's to check, on prefix().
+struct CheckpointFile {
+    bool read(const std::string &filename);   // false for a file that cannot be read or breaks its format's rules
+    const xs_host::CkptPrefix &prefix() const { return sparse.h.p; }
+    std::vector<xs_host::Matrix4cf> poses;
+    // The file's volume into three device arrays of one pitch of `step` bytes, at their first stored plane: every in-volume voxel is written and the
+    // copies have completed on return.  staging_words: the pinned buffer of a sparse file's chunks.
+    void write_to(float *value, int *weight, float *grad, size_t step, unsigned long long staging_words) const;
+
+private:
+    bool is_sparse = false;
+    SparseFile sparse;                 // (a dense file uses its prefix alone)
+    std::vector<float> value, grad;    // a dense file's arrays
+    std::vector<int> weight;
+};

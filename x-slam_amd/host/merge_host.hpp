@@ -1,7 +1,7 @@
 // merge_host.hpp — the host's side of merging a second TSDF map into the volume: the affine map from this volume's
-// voxel indices to the other volume's continuous voxel indices, the rigid transform between two maps from one camera frame posed in both, and the
-// source index box of a destination tile that the kernel's cull uses.  No device call and no HIP header: the orchestrator uses it in front of
-// the launch, csrc/xs_merge_sample.h (xs_merge.hip, xs_diff.hip) compiles merge_tile_box for the device from this same text, and tests/cxx/merge_selftest.cpp runs all of it
+// voxel indices to the other volume's continuous voxel indices, the rigid transform between two maps from one camera frame posed in both, the
+// source index box of a destination tile that the kernel's cull uses, and the descriptor of a second map with the one rule that accepts it.
+// No device call and no HIP header: the orchestrator uses it in front of the launch, csrc/xs_merge_sample.h (xs_merge.hip, xs_diff.hip) compiles merge_tile_box for the device from this same text, and tests/cxx/merge_selftest.cpp runs all of it
 // under the sanitizers without a GPU.
 #pragma once
 #include <cmath>
@@ -52,6 +52,33 @@ inline void map_transform(const double *c2v_this16, const double *c2v_other16, d
             for (int k = 0; k < 4; ++k) s += (r < 3 ? c2v_other16[4 * r + k] : (k == 3 ? 1.0 : 0.0)) * inv[4 * k + c];
             T16[4 * r + c] = s;
         }
+}
+
+// The second map of a map-level call (merge, align, score, search, diff): a whole volume in device memory in the project's layout, the arrays at
+// plane 0 with one pitch of `step` bytes; its resolution and voxel size may differ from this map's.  It is only read.  It comes from
+// the caller's pointers, from another instance of the process or from a checkpoint file of a whole volume in either format
+// (KinectFusionReconstruction.h: OtherInstanceMap, OpenCheckpointMap).
+struct SecondMap {
+    const float *value = nullptr;
+    const int *weight = nullptr;
+    const float *grad = nullptr;   // only a merge reads it
+    size_t step = 0;
+    int res[3] = {0, 0, 0};
+    float voxel_size = 0.f, tranc_dist = 0.f;
+};
+
+// Whether an operation takes the map: no null array (grad only where it is needed), every axis at least min_axis (1 where the map is sampled, 2
+// where its differences are), a finite positive voxel size, this map's truncation distance exactly (stored values are normalised by it, so
+// another is refused, not rescaled), no array that is this map's own, and a pitch that is a multiple of 4 holding a row.  Every refusal is the
+// caller's -1.
+inline bool second_map_ok(const SecondMap &m, int min_axis, bool need_grad, float this_tranc_dist, const float *this_value, const int *this_weight,
+                          const float *this_grad) {
+    if (!m.value || !m.weight || (need_grad && !m.grad)) return false;
+    for (int a = 0; a < 3; ++a)
+        if (m.res[a] < min_axis) return false;
+    if (!(m.voxel_size > 0.f) || !std::isfinite(m.voxel_size) || m.tranc_dist != this_tranc_dist) return false;
+    if (m.value == this_value || m.weight == this_weight || (need_grad && m.grad == this_grad)) return false;
+    return m.step % 4 == 0 && m.step >= (size_t)m.res[0] * 4;
 }
 
 // One axis of the per-voxel contract's step 1, float32 in the order written (both builds compile with -ffp-contract=off).

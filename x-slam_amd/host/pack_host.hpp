@@ -1,8 +1,9 @@
 // pack_host.hpp — the host's side of the brick-sparse volume checkpoint XSTSDF3 (INTEGRATION.md "Checkpoint formats"):
 // the file header, the words a brick of a given class takes in the payload, the validation of a header with its class bytes against the file's
-// length, the exclusive sum of the words per brick, and the partition of the bricks into chunks that fit a staging buffer.  No device call and no
-// HIP header: kf_export.cpp uses it around the kernels of csrc/xs_pack.hip, xs_pipeline_capi.cpp for xs_host_checkpoint_info, xs_pack.hip itself for
-// the brick grid, and tests/cxx/pack_selftest.cpp runs all of it under the sanitizers without a GPU.
+// length, the exclusive sum of the words per brick, the partition of the bricks into chunks that fit a staging buffer, and the file rules of the
+// dense XSTSDF2.  No device call and no HIP header: kf_checkpoint.cpp uses it around the kernels of csrc/xs_pack.hip and in its reader,
+// xs_pipeline_capi.cpp for xs_host_checkpoint_info, xs_pack.hip itself for the brick grid, and tests/cxx/pack_selftest.cpp runs all of it under the
+// sanitizers without a GPU.
 //
 // The file, little endian:  PackHeader (88 bytes) | n_poses x 128 bytes (Matrix4cf, as XSTSDF2) | nbricks class bytes, zero-padded to a multiple of 4 |
 // payload_words 32-bit words.  Brick (bx, by, bz) of 8 x 8 x 8 voxels, bz counted from the first stored plane, has index (bz nby + by) nbx + bx.
@@ -99,6 +100,19 @@ inline PackError pack_validate(const PackHeader &h, const unsigned char *cls, ui
     if (hist8) for (int c = 0; c < 8; ++c) hist8[c] = hist[c];
     if (words != h.payload_words) return PACK_BAD_PAYLOAD_WORDS;
     if (file_bytes != head + 4 * words) return PACK_BAD_LENGTH;   // truncated or trailing bytes
+    return PACK_OK;
+}
+
+// The dense XSTSDF2 file (prefix | n_poses x 128 bytes | value, grad, weight of the stored planes as dense rows): the magic, the planes within the
+// resolution, a brick grid pack_brick_grid accepts (the bounds both formats share), the pose count and the exact length.  *words (optional): the
+// 32-bit words of the three arrays, written once geometry and pose count hold.
+inline PackError pack_validate_dense(const CkptPrefix &p, uint64_t file_bytes, uint64_t *words) {
+    if (!pack_magic_is(p.magic, "XSTSDF2")) return PACK_BAD_MAGIC;
+    if (p.res[2] < 1 || p.zs0 < 0 || p.zs1 <= p.zs0 || p.zs1 > p.res[2] || pack_brick_grid(p.res[0], p.res[1], p.zs1 - p.zs0, nullptr) == 0) return PACK_BAD_GEOMETRY;
+    if (p.n_poses < 1 || p.n_poses > PACK_MAX_POSES) return PACK_BAD_POSES;
+    const uint64_t w = 3ull * (uint64_t)p.res[0] * (uint64_t)p.res[1] * (uint64_t)(p.zs1 - p.zs0);
+    if (words) *words = w;
+    if (file_bytes != sizeof(CkptPrefix) + (uint64_t)p.n_poses * PACK_POSE_BYTES + 4 * w) return PACK_BAD_LENGTH;   // truncated or trailing bytes
     return PACK_OK;
 }
 

@@ -492,14 +492,10 @@ int xs_host_checkpoint_info(const char *path, double *out32) {
     out32[11] = p.shard_rank; out32[12] = p.shard_count;
     out32[27] = (double)file_bytes;
     PackError e = PACK_OK;
-    if (v2) {   // what loadCheckpoint asks of the file itself
-        if (p.res[2] < 1 || p.zs0 < 0 || p.zs1 <= p.zs0 || p.zs1 > p.res[2] || pack_brick_grid(p.res[0], p.res[1], p.zs1 - p.zs0, nullptr) == 0) e = PACK_BAD_GEOMETRY;
-        else if (p.n_poses < 1 || p.n_poses > PACK_MAX_POSES) e = PACK_BAD_POSES;
-        else {
-            const unsigned long long words = 3ull * (unsigned long long)p.res[0] * (unsigned long long)p.res[1] * (unsigned long long)(p.zs1 - p.zs0);
-            out32[26] = (double)words;
-            if ((unsigned long long)file_bytes != sizeof(CkptPrefix) + (unsigned long long)p.n_poses * PACK_POSE_BYTES + 4ull * words) e = PACK_BAD_LENGTH;
-        }
+    if (v2) {
+        uint64_t words = 0;
+        e = pack_validate_dense(p, (uint64_t)file_bytes, &words);
+        out32[26] = (double)words;
     } else {
         if (file_bytes < (long long)sizeof(PackHeader)) e = PACK_BAD_LENGTH;
         else {
@@ -526,49 +522,47 @@ int xs_host_checkpoint_info(const char *path, double *out32) {
     return 0;
 }
 
+// ---- the calls that take a second map: from the caller's pointers (*_volume), from another instance (*_map) or from a file (*_checkpoint) ----
+static xs_host::SecondMap second_map(const float *value, const int *weight, const float *grad, size_t step, const int *res, float voxel_size, float tranc_dist) {
+    xs_host::SecondMap m{value, weight, grad, step, {0, 0, 0}, voxel_size, tranc_dist};   // (a null res stays 0 x 0 x 0, which every operation refuses)
+    for (int a = 0; res && a < 3; ++a) m.res[a] = res[a];
+    return m;
+}
 int xs_kf_merge_volume(void *kf, const float *src_value, const int *src_weight, const float *src_grad, size_t src_step, const int *src_res,
                        float src_voxel_size, float src_tranc_dist, const double *T16, int min_weight, unsigned long long *written) {
-    return ((KF *)kf)->MergeVolume(src_value, src_weight, src_grad, src_step, src_res, src_voxel_size, src_tranc_dist, T16, min_weight, written);
+    return ((KF *)kf)->MergeVolume(second_map(src_value, src_weight, src_grad, src_step, src_res, src_voxel_size, src_tranc_dist), T16, min_weight, written);
 }
 int xs_kf_merge_checkpoint(void *kf, const char *path, const double *T16, int min_weight, unsigned long long *written) {
     if (!path) return -1;
-    return ((KF *)kf)->MergeCheckpoint(path, T16, min_weight, written);
+    KF::CheckpointMap c;
+    const int rc = ((KF *)kf)->OpenCheckpointMap(path, c);
+    return rc != 1 ? rc : ((KF *)kf)->MergeVolume(c.map, T16, min_weight, written);
 }
 int xs_kf_merge_map(void *kf, void *other_kf, const double *T16, int min_weight, unsigned long long *written) {
-    KF *k = (KF *)kf, *o = (KF *)other_kf;
-    if (!o || o == k) return -1;
-    if (o->shard_count > 1) return -2;
-    if (!o->tsdf_volume_d_ptr) return -1;
-    o->synchronize();
-    auto v = o->tsdf_volume_d_ptr->value(), g = o->tsdf_volume_d_ptr->grad();   // (read only: the other map's sign map and indices stay as they are)
-    auto w = o->tsdf_volume_d_ptr->weight();
-    if (v.step() != g.step() || v.step() != w.step()) return -1;
-    return k->MergeVolume(v.ptr(), w.ptr(), g.ptr(), v.step(), o->volume_resolution.v, o->voxel_size, o->tsdf_volume_d_ptr->getTsdfTruncDist(), T16, min_weight,
-                          written);
+    xs_host::SecondMap m;
+    const int rc = ((KF *)kf)->OtherInstanceMap((KF *)other_kf, true, m);
+    return rc != 1 ? rc : ((KF *)kf)->MergeVolume(m, T16, min_weight, written);
+}
+static int align_call(KF *k, const xs_host::SecondMap &m, const double *T16xN, int N, int iterations, double damping, int min_weight, float max_residual,
+                      double *T16_out, double *report8, double *loss_history) {
+    std::vector<double> history;
+    const int rc = k->AlignVolume(m, T16xN, N, iterations, damping, min_weight, max_residual, T16_out, report8, loss_history ? &history : nullptr);
+    if (loss_history) std::copy(history.begin(), history.end(), loss_history);   // at most iterations + 1 entries
+    return rc;
 }
 int xs_kf_align_map(void *kf, void *other_kf, const double *T16xN, int N, int iterations, double damping, int min_weight, float max_residual,
                     double *T16_out, double *report8, double *loss_history) {
-    KF *k = (KF *)kf, *o = (KF *)other_kf;
-    if (!o || o == k) return -1;
-    if (o->shard_count > 1) return -2;
-    if (!o->tsdf_volume_d_ptr) return -1;
-    o->synchronize();
-    auto v = o->tsdf_volume_d_ptr->value();   // (read only: nothing of the other map is touched)
-    auto w = o->tsdf_volume_d_ptr->weight();
-    if (v.step() != w.step()) return -1;
-    std::vector<double> history;
-    const int rc = k->AlignVolume(v.ptr(), w.ptr(), v.step(), o->volume_resolution.v, o->voxel_size, o->tsdf_volume_d_ptr->getTsdfTruncDist(), T16xN, N, iterations,
-                                  damping, min_weight, max_residual, T16_out, report8, loss_history ? &history : nullptr);
-    if (loss_history) std::copy(history.begin(), history.end(), loss_history);   // at most iterations + 1 entries
-    return rc;
+    xs_host::SecondMap m;
+    const int rc = ((KF *)kf)->OtherInstanceMap((KF *)other_kf, false, m);
+    return rc != 1 ? rc : align_call((KF *)kf, m, T16xN, N, iterations, damping, min_weight, max_residual, T16_out, report8, loss_history);
 }
 int xs_kf_align_checkpoint(void *kf, const char *path, const double *T16xN, int N, int iterations, double damping, int min_weight, float max_residual,
                            double *T16_out, double *report8, double *loss_history) {
     if (!path) return -1;
-    std::vector<double> history;
-    const int rc = ((KF *)kf)->AlignCheckpoint(path, T16xN, N, iterations, damping, min_weight, max_residual, T16_out, report8, loss_history ? &history : nullptr);
-    if (loss_history) std::copy(history.begin(), history.end(), loss_history);
-    return rc;
+    xs_host::align_report_clear(report8, 8);
+    KF::CheckpointMap c;
+    const int rc = ((KF *)kf)->OpenCheckpointMap(path, c);
+    return rc != 1 ? rc : align_call((KF *)kf, c.map, T16xN, N, iterations, damping, min_weight, max_residual, T16_out, report8, loss_history);
 }
 int xs_host_align_seeded_maps(const double *T16, double vs_this, double vs_other, float *out144) {
     return xs_host::align_seeded_maps(T16, vs_this, vs_other, reinterpret_cast<float (*)[24]>(out144)) ? 0 : -1;
@@ -576,63 +570,51 @@ int xs_host_align_seeded_maps(const double *T16, double vs_this, double vs_other
 int xs_host_align_step(const double *s29, double damping, double *T16) { return xs_host::align_step(s29, damping, T16) ? 0 : -1; }
 void xs_kf_align_search_defaults(void *kf, xs_align_search_opts *opts) { ((KF *)kf)->AlignSearchDefaults(opts); }
 int xs_kf_score_transforms(void *kf, void *other_kf, int P, const double *T16xP, int stride, int min_weight, float max_residual, double *out2xP) {
-    KF *k = (KF *)kf, *o = (KF *)other_kf;
-    if (!o || o == k) return -1;
-    if (o->shard_count > 1) return -2;
-    if (!o->tsdf_volume_d_ptr) return -1;
-    o->synchronize();
-    auto v = o->tsdf_volume_d_ptr->value();   // (read only: nothing of the other map is touched)
-    auto w = o->tsdf_volume_d_ptr->weight();
-    if (v.step() != w.step()) return -1;
-    return k->ScoreTransformsVolume(v.ptr(), w.ptr(), v.step(), o->volume_resolution.v, o->voxel_size, o->tsdf_volume_d_ptr->getTsdfTruncDist(), T16xP, P, stride,
-                                    min_weight, max_residual, out2xP);
+    xs_host::SecondMap m;
+    const int rc = ((KF *)kf)->OtherInstanceMap((KF *)other_kf, false, m);
+    return rc != 1 ? rc : ((KF *)kf)->ScoreTransformsVolume(m, T16xP, P, stride, min_weight, max_residual, out2xP);
 }
 int xs_kf_score_transforms_checkpoint(void *kf, const char *path, int P, const double *T16xP, int stride, int min_weight, float max_residual, double *out2xP) {
     if (!path) return -1;
-    return ((KF *)kf)->ScoreTransformsCheckpoint(path, T16xP, P, stride, min_weight, max_residual, out2xP);
+    KF::CheckpointMap c;
+    const int rc = ((KF *)kf)->OpenCheckpointMap(path, c);
+    return rc != 1 ? rc : ((KF *)kf)->ScoreTransformsVolume(c.map, T16xP, P, stride, min_weight, max_residual, out2xP);
 }
 int xs_kf_align_map_global(void *kf, void *other_kf, const xs_align_search_opts *opts, double *T16_out, double *report12) {
-    KF *k = (KF *)kf, *o = (KF *)other_kf;
-    if (!o || o == k) return -1;
-    if (o->shard_count > 1) return -2;
-    if (!o->tsdf_volume_d_ptr) return -1;
-    o->synchronize();
-    auto v = o->tsdf_volume_d_ptr->value();   // (read only: the other map's band index and caches stay as they are)
-    auto w = o->tsdf_volume_d_ptr->weight();
-    if (v.step() != w.step()) return -1;
-    return k->AlignVolumeGlobal(v.ptr(), w.ptr(), v.step(), o->volume_resolution.v, o->voxel_size, o->tsdf_volume_d_ptr->getTsdfTruncDist(), opts, T16_out, report12);
+    xs_host::SecondMap m;
+    const int rc = ((KF *)kf)->OtherInstanceMap((KF *)other_kf, false, m);
+    return rc != 1 ? rc : ((KF *)kf)->AlignVolumeGlobal(m, opts, T16_out, report12);
 }
 int xs_kf_align_checkpoint_global(void *kf, const char *path, const xs_align_search_opts *opts, double *T16_out, double *report12) {
     if (!path) return -1;
-    return ((KF *)kf)->AlignCheckpointGlobal(path, opts, T16_out, report12);
+    xs_host::align_report_clear(report12, 12);
+    KF::CheckpointMap c;
+    const int rc = ((KF *)kf)->OpenCheckpointMap(path, c);
+    return rc != 1 ? rc : ((KF *)kf)->AlignVolumeGlobal(c.map, opts, T16_out, report12);
 }
 int xs_kf_diff_volume(void *kf, const float *src_value, const int *src_weight, size_t src_step, const int *src_res, float src_voxel_size, float src_tranc_dist,
                       const double *T16, int min_weight, float lo, float hi, int cell, unsigned long long min_size, int capacity,
                       unsigned long long *this_records8, int *this_count, unsigned long long *other_records8, int *other_count, unsigned long long *counts3,
                       unsigned char *this_dense, unsigned char *other_dense) {
-    return ((KF *)kf)->DiffVolume(src_value, src_weight, src_step, src_res, src_voxel_size, src_tranc_dist, T16, min_weight, lo, hi, cell, min_size, capacity,
-                                  this_records8, this_count, other_records8, other_count, counts3, this_dense, other_dense);
+    return ((KF *)kf)->DiffVolume(second_map(src_value, src_weight, nullptr, src_step, src_res, src_voxel_size, src_tranc_dist), T16, min_weight, lo, hi, cell,
+                                  min_size, capacity, this_records8, this_count, other_records8, other_count, counts3, this_dense, other_dense);
 }
 int xs_kf_diff_map(void *kf, void *other_kf, const double *T16, int min_weight, float lo, float hi, int cell, unsigned long long min_size, int capacity,
                    unsigned long long *this_records8, int *this_count, unsigned long long *other_records8, int *other_count, unsigned long long *counts3,
                    unsigned char *this_dense, unsigned char *other_dense) {
-    KF *k = (KF *)kf, *o = (KF *)other_kf;
-    if (!o || o == k) return -1;
-    if (o->shard_count > 1) return -2;
-    if (!o->tsdf_volume_d_ptr) return -1;
-    o->synchronize();
-    auto v = o->tsdf_volume_d_ptr->value();   // (read only: nothing of the other map is touched)
-    auto w = o->tsdf_volume_d_ptr->weight();
-    if (v.step() != w.step()) return -1;
-    return k->DiffVolume(v.ptr(), w.ptr(), v.step(), o->volume_resolution.v, o->voxel_size, o->tsdf_volume_d_ptr->getTsdfTruncDist(), T16, min_weight, lo, hi, cell,
-                         min_size, capacity, this_records8, this_count, other_records8, other_count, counts3, this_dense, other_dense);
+    xs_host::SecondMap m;
+    const int rc = ((KF *)kf)->OtherInstanceMap((KF *)other_kf, false, m);
+    return rc != 1 ? rc : ((KF *)kf)->DiffVolume(m, T16, min_weight, lo, hi, cell, min_size, capacity, this_records8, this_count, other_records8, other_count,
+                                                 counts3, this_dense, other_dense);
 }
 int xs_kf_diff_checkpoint(void *kf, const char *path, const double *T16, int min_weight, float lo, float hi, int cell, unsigned long long min_size, int capacity,
                           unsigned long long *this_records8, int *this_count, unsigned long long *other_records8, int *other_count,
                           unsigned long long *counts3, unsigned char *this_dense, unsigned char *other_dense) {
     if (!path) return -1;
-    return ((KF *)kf)->DiffCheckpoint(path, T16, min_weight, lo, hi, cell, min_size, capacity, this_records8, this_count, other_records8, other_count, counts3,
-                                      this_dense, other_dense);
+    KF::CheckpointMap c;
+    const int rc = ((KF *)kf)->OpenCheckpointMap(path, c);
+    return rc != 1 ? rc : ((KF *)kf)->DiffVolume(c.map, T16, min_weight, lo, hi, cell, min_size, capacity, this_records8, this_count, other_records8, other_count,
+                                                 counts3, this_dense, other_dense);
 }
 int xs_host_align_search_free(int n, const double *centroid_this3, const double *centroid_other3, double box_t, double *T16xN) {
     return xs_host::align_search_free(n, centroid_this3, centroid_other3, box_t, T16xN) ? 0 : -1;

@@ -964,14 +964,21 @@ class KinectFusion:
         _lib.xs_kf_save_tsdf_volume(self.h, path.encode())
 
     @staticmethod
-    def _merge_call(name, rc, written):
+    def _map_call(name, rc, bad, zero_ok=False):
+        """The return code of a call that takes a second map: XsError in shard mode, ValueError on bad arguments (`bad` names the call's own) and,
+        unless zero_ok (the align calls: no result), without a volume."""
         if rc == -2:
             raise capi.XsError(f"{name}: not available in shard mode")
         if rc == -1:
-            raise ValueError(f"{name}: bad arguments (T not finite, min_weight < 1, the volume itself as source, a bad file or another truncation distance)")
-        if rc != 1:
+            raise ValueError(f"{name}: bad arguments ({bad}, the volume itself as source, a bad file or another truncation distance)")
+        if rc != 1 and not (zero_ok and rc == 0):
             raise ValueError(f"{name}: no volume" if rc == 0 else f"{name}: {rc}")
-        return int(written.value)
+
+    def _merge_call(self, name, source, T, min_weight):
+        t = _real44(np.eye(4) if T is None else T)
+        n = C.c_ulonglong(0)
+        self._map_call(name, getattr(_lib, name)(self.h, source, t.ctypes.data_as(_f64p), int(min_weight), C.byref(n)), "T not finite, min_weight < 1")
+        return int(n.value)
 
     def merge_map(self, other, T=None, min_weight=1):
         """Merges the map of `other` (another KinectFusion of this process; only read) into this one: its volume is resampled into this map's
@@ -979,16 +986,12 @@ class KinectFusion:
         weight as a new observation is, where all the corners it is interpolated from carry min_weight.  Resolutions and voxel sizes may
         differ, the truncation distances may not.  Everything derived from the volume follows; poses and the frame number do not change.
         Returns the number of voxels written.  XsError in shard mode, ValueError on bad arguments (the state is unchanged)."""
-        t = _real44(np.eye(4) if T is None else T)
-        n = C.c_ulonglong(0)
-        return self._merge_call("xs_kf_merge_map", _lib.xs_kf_merge_map(self.h, other.h, t.ctypes.data_as(_f64p), int(min_weight), C.byref(n)), n)
+        return self._merge_call("xs_kf_merge_map", other.h, T, min_weight)
 
     def merge_checkpoint(self, path, T=None, min_weight=1):
         """merge_map with the other map read from a checkpoint file of a whole volume (save_checkpoint, dense or sparse: either format is accepted); the file is validated before anything
         is touched and a bad one raises ValueError with the state unchanged."""
-        t = _real44(np.eye(4) if T is None else T)
-        n = C.c_ulonglong(0)
-        return self._merge_call("xs_kf_merge_checkpoint", _lib.xs_kf_merge_checkpoint(self.h, path.encode(), t.ctypes.data_as(_f64p), int(min_weight), C.byref(n)), n)
+        return self._merge_call("xs_kf_merge_checkpoint", path.encode(), T, min_weight)
 
     def _diff_call(self, name, source, T, min_weight, lo, hi, cell_vox, min_size, masks, capacity):
         t = _real44(np.eye(4) if T is None else T)
@@ -1004,13 +1007,7 @@ class KinectFusion:
             if rc != -4:
                 break
             capacity = max(int(n_this.value), int(n_other.value))
-        if rc == -2:
-            raise capi.XsError(f"{name}: not available in shard mode")
-        if rc == -1:
-            raise ValueError(f"{name}: bad arguments (T, lo or hi not finite, lo > hi, min_weight < 1, a bad cell, the volume itself as source, a bad file or "
-                             "another truncation distance)")
-        if rc != 1:
-            raise ValueError(f"{name}: no volume" if rc == 0 else f"{name}: {rc}")
+        self._map_call(name, rc, "T, lo or hi not finite, lo > hi, min_weight < 1, a bad cell")
         return MapDiff(dict(compared=int(counts[0]), only_this=int(counts[1]), only_other=int(counts[2])), self._cluster_records(recs[0][:n_this.value]),
                        self._cluster_records(recs[1][:n_other.value]), tuple(dense) if masks else None)
 
@@ -1040,13 +1037,7 @@ class KinectFusion:
         out, report, hist = np.zeros((4, 4), np.float64), np.zeros(8, np.float64), np.zeros(max(iterations, 0) + 1, np.float64)
         rc = getattr(_lib, name)(self.h, source, t.ctypes.data_as(_f64p), t.shape[0], iterations, float(damping), int(min_weight), float(max_residual),
                                  out.ctypes.data_as(_f64p), report.ctypes.data_as(_f64p), hist.ctypes.data_as(_f64p))
-        if rc == -2:
-            raise capi.XsError(f"{name}: not available in shard mode")
-        if rc == -1:
-            raise ValueError(f"{name}: bad arguments (T not finite, iterations < 0, min_weight < 1, max_residual or damping out of range, the volume itself "
-                             "as source, a bad file or another truncation distance)")
-        if rc not in (0, 1):
-            raise ValueError(f"{name}: {rc}")
+        self._map_call(name, rc, "T not finite, iterations < 0, min_weight < 1, max_residual or damping out of range", zero_ok=True)
         rep = {"start": int(report[0]), "count": int(report[1]), "sum_r2": float(report[2]), "loss": float(report[3]), "passes": int(report[4]),
                "ended_ok": int(report[5]), "band_voxels": int(report[6])}
         return rc == 1, (out if rc == 1 else t[0].copy()), rep, (hist.copy() if rc == 1 else hist[:0].copy())
@@ -1065,23 +1056,13 @@ class KinectFusion:
         Intended use: kf.merge_checkpoint(path, kf.align_checkpoint(path, T_guess)[1])."""
         return self._align_call("xs_kf_align_checkpoint", path.encode(), T0, iterations, damping, min_weight, max_residual)
 
-    @staticmethod
-    def _align_rc(name, rc):
-        if rc == -2:
-            raise capi.XsError(f"{name}: not available in shard mode")
-        if rc == -1:
-            raise ValueError(f"{name}: bad arguments (T not finite, a count, stride, box, min_weight, max_residual or damping out of range, the volume "
-                             "itself as source, a bad file or another truncation distance)")
-        if rc not in (0, 1):
-            raise ValueError(f"{name}: {rc}")
+    _BAD_SEARCH = "T not finite, a count, stride, box, min_weight, max_residual or damping out of range"
 
     def _score_transforms_call(self, name, source, Ts, stride, min_weight, max_residual):
         t = np.ascontiguousarray(np.asarray(Ts, dtype=np.float64).reshape(-1, 4, 4))
         out = np.zeros((t.shape[0], 2), np.float64)
         rc = getattr(_lib, name)(self.h, source, t.shape[0], t.ctypes.data_as(_f64p), int(stride), int(min_weight), float(max_residual), out.ctypes.data_as(_f64p))
-        self._align_rc(name, rc)
-        if rc == 0:
-            raise ValueError(f"{name}: no volume")
+        self._map_call(name, rc, self._BAD_SEARCH)
         return out
 
     def score_transforms(self, other, Ts, stride=1, min_weight=1, max_residual=1.0):
@@ -1109,7 +1090,7 @@ class KinectFusion:
             o.user_n, o.user_T16xN = user.shape[0], user.ctypes.data_as(_f64p)
         out, report = np.eye(4, dtype=np.float64), np.zeros(12, np.float64)
         rc = getattr(_lib, name)(self.h, source, C.byref(o), out.ctypes.data_as(_f64p), report.ctypes.data_as(_f64p))
-        self._align_rc(name, rc)
+        self._map_call(name, rc, self._BAD_SEARCH, zero_ok=True)
         rep = {"rank": int(report[0]), "S_before": float(report[1]), "count": int(report[2]), "sum_r2": float(report[3]), "loss": float(report[4]),
                "score_launches": int(report[5]), "passes": int(report[6]), "ended_ok": int(report[7]), "band_voxels": int(report[8]),
                "scored_entries": int(report[9]), "centroid_distance": float(report[10])}
