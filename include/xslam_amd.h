@@ -670,6 +670,54 @@ int xs_tsdf_merge(float *value, int *weight, float *grad, size_t step, const int
                   const int *src_weight, const float *src_grad, size_t src_step, const int *src_res, const float *xform12, int min_weight,
                   int max_weight, unsigned flags, unsigned long long *written_dev, void *workspace, void *stream);
 
+/* ---- taking fused frames out of the volume and fusing frames with a sign (xs_integrate.hip) ---------------------
+ * No counterpart in the reference.  One pass over planes [z0, z1) applies up to XS_REINTEGRATE_MAX_OPS observations to every voxel, each
+ * with a sign.  The volume arguments are xs_integrate_scaled's: value / weight / grad at the first stored plane z0 (the whole volume: plane 0,
+ * z0 = 0, z1 = res[2]), one pitch `vol_step` (bytes), z over global plane indices; only planes [z0, z1) are touched.  Every op's image is
+ * rows x cols floats with the pitch `scaled_step`, as xs_scale_depth writes it (no valid depth beyond 5 m); ops may share one image.  The op
+ * table is read on the host during the call and travels in the kernel's arguments: no copy to the device, no synchronisation.
+ * counts4_dev (device): {removed, added, emptied, orphaned} are INCREMENTED by the numbers below, with integer atomics, one add per counter
+ * and workgroup.
+ *
+ * The observation obs(op) at a voxel is, by definition, what xs_integrate_scaled writes into a ZEROED volume with the op's image and pose and
+ * this call's intr4, voxel_size, tranc_dist and threshold: the voxel is SEEN iff that call writes it, and t = (value, grad) written there.
+ * The kernel computes it with the integrate kernels' own per-voxel functions in their operation order (threshold > 0: the bilinear instance).
+ * Per voxel the ops are applied in list order, each on the state the previous one left; float32, in the order written; the complex state
+ * (value, grad) is divided by a real divisor component by component; w is the weight:
+ *   sign = +1, seen:          new = (prev * float(w) + 1.0f * t) / float(w + 1); w = min(w + 1, max_weight): the integrate kernels' running
+ *                             mean, exactly.  Counts as ADDED.
+ *   sign = -1, seen, w >= 2:  new = (prev * float(w) - 1.0f * t) / float(w - 1); w = w - 1; then the real part (value) is clamped to [-1, 1] —
+ *                             a mean of observations lies there, only rounding or the removal of something never added leaves it; the
+ *                             imaginary part (grad) is not clamped.  Counts as REMOVED.
+ *   sign = -1, seen, w == 1:  value, grad and weight become 0, the state xs_init_volume leaves.  Counts as REMOVED and as EMPTIED.
+ *   sign = -1, seen, w <= 0:  nothing changes.  Counts as ORPHANED.
+ *   not seen:                 nothing changes.
+ * A voxel no op changes keeps its bits (a word is stored only if an op changed it); rows outside [z0, z1) and a row's padding are never
+ * written.  The cull (a row of 64 x 1 x 8 voxels that an op's view frustum, padded as the integrate kernels pad it and closed at the far
+ * limit of a 5 m depth, cannot see skips that op; a tile of 64 x 4 x 8 voxels no op can see is left before any load) changes no bit;
+ * XS_REINTEGRATE_NO_CULL switches it off.  No output depends on scheduling.
+ *
+ * What removal cannot undo: once a voxel's weight has been clamped at max_weight its value is a moving average, no longer the mean of the
+ * frames fused there, and taking an old frame out of it is an approximation (the frame's share has decayed, the call subtracts a full one).
+ * The call cannot know this and does not refuse.  Removing an observation that was never added, or with another pose, image or parameter
+ * than it was added with, is arithmetic on the same rules, not an inverse.
+ *
+ * hipErrorInvalidValue, with nothing launched and nothing written: `ops` outside 1 .. XS_REINTEGRATE_MAX_OPS; a sign other than +1 or -1; a
+ * null ops_host, image, intr4, res, array or counts4_dev; a pose entry that is not finite; what xs_integrate_scaled refuses for the shared
+ * arguments (a pitch that is no multiple of 4 or shorter than a row, planes outside the volume); an empty or reversed plane range; an axis
+ * outside 1 .. 262140; max_weight outside [1, 1 << 24]; voxel_size or tranc_dist not positive and finite. */
+#define XS_REINTEGRATE_MAX_OPS 8
+#define XS_REINTEGRATE_NO_CULL 1u
+typedef struct xs_reintegrate_op {
+    int sign;                   /* -1: take the observation out, +1: put it in */
+    const float *depth_scaled;  /* device, rows x cols, the image xs_scale_depth gives; ops may share one */
+    float Rv2c18[18], tv2c6[6]; /* the complex pose, as xs_integrate_scaled takes it */
+} xs_reintegrate_op;
+int xs_tsdf_reintegrate(int ops, const xs_reintegrate_op *ops_host, size_t scaled_step, int rows, int cols, const float *intr4,
+                        int max_weight, const int *res, float voxel_size, float tranc_dist, float threshold,
+                        float *value, int *weight, float *grad, size_t vol_step, int z0, int z1,
+                        unsigned long long *counts4_dev, unsigned flags, void *stream);
+
 /* ---- what differs between the volume and a second volume, as two masks (xs_diff.hip) ---------------------------
  * No counterpart in the reference.  THIS map is (value, weight, step, res), the OTHER map (src_*); layouts, pitches and xform12 are those of
  * the merge above, the pointers at plane 0, the whole volume always.  Neither volume is modified.  `only_this_mask` and `only_other_mask`:

@@ -324,6 +324,22 @@ int xs_kf_merge_volume(void *kf, const float *src_value, const int *src_weight, 
                        float src_voxel_size, float src_tranc_dist, const double *T16, int min_weight, unsigned long long *written);
 int xs_kf_merge_map(void *kf, void *other_kf, const double *T16, int min_weight, unsigned long long *written);
 int xs_kf_merge_checkpoint(void *kf, const char *path, const double *T16, int min_weight, unsigned long long *written);
+/* ---- Taking fused frames out of the volume and fusing them again at corrected poses (xs_tsdf_reintegrate in
+ * xslam_amd.h: the per-voxel contract) --------------------------------------------------------------------------------------------------------
+ * n entries.  Entry i: the depth frame depth_dev[i] (u16 millimetres on the device, rows of step_bytes; entries may share a frame), mode[i] bit 0:
+ * take it out of the volume at camera2volume c2v_old32xN + 32 i, bit 1: put it in at c2v_new32xN + 32 i (1: remove, 2: add, 3: move; both poses
+ * [4, 4, 2] with their seeds; the array of a mode no entry asks for may be NULL).  frame_index (optional, n ints): an entry >= 0 replaces that
+ * frame's stored world2camera by the pose that gives c2v_new (the entry must add), < 0 leaves the record alone.  The device is drained, every
+ * distinct frame scaled once into a buffer of the call's own, the observations applied in entry order (an entry's removal before its addition)
+ * in launches of at most XS_REINTEGRATE_MAX_OPS, with this instance's max_integration_weight and biInterpolate_threshold; afterwards the
+ * volume's version is bumped and the sign map, the cached planning and relocalisation maps and the previous frame's model maps (at the current
+ * pose) follow the edited volume, as after a merge: the next xs_kf_process_frame tracks against it.  The frame number and the number of poses
+ * are untouched.  counts4 (optional) = {removed, added, emptied, orphaned} voxels over all observations.  A frame taken out of voxels whose
+ * weight had reached max_integration_weight is removed only approximately (xslam_amd.h).
+ * Return 1 when it ran, 0 without a volume, -1 on bad arguments with the state unchanged (n < 1, a null frame or array, a mode outside 1 .. 3, a
+ * pose entry that is not finite, a frame index past the record or on an entry that does not add), -2 in shard mode, doing nothing. */
+int xs_kf_reintegrate(void *kf, int n, const uint16_t *const *depth_dev, size_t step_bytes, const float *c2v_old32xN, const float *c2v_new32xN,
+                      const int *mode, const int *frame_index, unsigned long long *counts4);
 /* The host's side of a merge (x-slam_amd/host/merge_host.hpp).  CPU only.
  * merge_affine: xform12 of xs_tsdf_merge from T16 and the two voxel sizes, in float64 with one rounding to float32 at the end: the matrix
  * block is R vs_dst / vs_src, the offset (R (0.5 vs_dst (1, 1, 1)) + t) / vs_src - 0.5.  0, or -1 (nothing written) for an input that is

@@ -59,6 +59,11 @@ class BandIndex(C.Structure):
                 ("nblocks", C.c_int), ("res", C.c_int * 3), ("z0", C.c_int), ("z1", C.c_int)]
 
 
+class ReintegrateOp(C.Structure):
+    """xs_reintegrate_op (include/xslam_amd.h): one signed observation of tsdf_reintegrate."""
+    _fields_ = [("sign", C.c_int), ("depth_scaled", C.c_void_p), ("Rv2c18", C.c_float * 18), ("tv2c6", C.c_float * 6)]
+
+
 class ViewOpts(C.Structure):
     """xs_view_opts (include/xslam_amd.h)."""
     _fields_ = [("struct_bytes", C.c_uint), ("rays_x", C.c_int), ("rays_y", C.c_int), ("t_near", C.c_float), ("t_far", C.c_float), ("step", C.c_float)]
@@ -176,6 +181,8 @@ _SIGS = {
     "xs_tsdf_pack_gather": (C.c_int, [_vp, _vp, _vp, _sz, _i32p, C.c_int, _vp, _vp, _sz, _sz, _vp, _vp]),
     "xs_tsdf_unpack": (C.c_int, [_vp, _vp, _vp, _sz, _i32p, C.c_int, _vp, _vp, _sz, _sz, _vp, _vp]),
     "xs_tsdf_merge": (C.c_int, [_vp, _vp, _vp, _sz, _i32p, C.c_int, C.c_int, _vp, _vp, _vp, _sz, _i32p, _f32p, C.c_int, C.c_int, C.c_uint, _vp, _vp, _vp]),
+    "xs_tsdf_reintegrate": (C.c_int, [C.c_int, C.POINTER(ReintegrateOp), _sz, C.c_int, C.c_int, _f32p, C.c_int, _i32p, C.c_float, C.c_float, C.c_float, _vp, _vp, _vp,
+                                      _sz, C.c_int, C.c_int, _vp, C.c_uint, _vp]),
     "xs_tsdf_align_workspace_bytes": (_sz, [C.c_int]),
     "xs_tsdf_align_terms": (C.c_int, [C.c_int, C.POINTER(BandIndex), _vp, _vp, _sz, _i32p, _f32p, C.c_int, C.c_float, _vp, _vp, _vp]),
     "xs_tsdf_score_transforms_workspace_bytes": (_sz, [C.c_int]),
@@ -865,6 +872,29 @@ def tsdf_merge(value, weight, grad, step, res, src_value, src_weight, src_grad, 
     check(_lib.xs_tsdf_merge(_ptr(value), _ptr(weight), _ptr(grad), step, r.ctypes.data_as(_i32p), z0, z1, _ptr(src_value), _ptr(src_weight), _ptr(src_grad),
                              src_step, s.ctypes.data_as(_i32p), m.ctypes.data_as(_f32p), int(min_weight), int(max_weight), int(flags), _ptr(written),
                              _ptr(workspace), _stream(stream)))
+
+
+REINTEGRATE_MAX_OPS = 8      # XS_REINTEGRATE_MAX_OPS
+REINTEGRATE_NO_CULL = 1      # XS_REINTEGRATE_NO_CULL
+
+
+def tsdf_reintegrate(ops, scaled_step, rows, cols, intr, max_weight, res, voxel_size, tranc_dist, value, weight, grad, vol_step, counts, threshold=0.0,
+                     z0=0, z1=None, flags=0, stream=None):
+    """xs_tsdf_reintegrate: applies the observations `ops` = [(sign, depth_scaled, Rv2c, tv2c), ...] (at most REINTEGRATE_MAX_OPS; sign -1 takes the
+    observation out of the running mean, +1 puts it in; depth_scaled: a device tensor or address, the image scale_depth gives, shared pitch
+    scaled_step) to planes [z0, z1) in one pass, in list order per voxel.  value / weight / grad: device tensors or addresses of the first stored
+    plane z0, as integrate_scaled takes them; counts (uint64 / int64 device tensor of 4 words) is incremented by {removed, added, emptied,
+    orphaned}.  The table travels in the kernel's arguments.  No synchronisation."""
+    r = _ia(res, 3)
+    k = _fa(intr, 4)
+    table = (ReintegrateOp * max(len(ops), 1))()
+    for o, (sign, depth, R, t) in zip(table, ops):
+        o.sign, o.depth_scaled = int(sign), _ptr(depth)
+        o.Rv2c18[:] = _fa(R, 18).tolist()
+        o.tv2c6[:] = _fa(t, 6).tolist()
+    z1 = int(r[2]) if z1 is None else z1
+    check(_lib.xs_tsdf_reintegrate(len(ops), table, scaled_step, rows, cols, k.ctypes.data_as(_f32p), int(max_weight), r.ctypes.data_as(_i32p), voxel_size,
+                                   tranc_dist, threshold, _ptr(value), _ptr(weight), _ptr(grad), vol_step, z0, z1, _ptr(counts), int(flags), _stream(stream)))
 
 
 def tsdf_pack_bricks(res, planes=None):

@@ -359,6 +359,18 @@ public:
     // maps, the previous frame's model maps at the current pose.  Poses, frame_id and the trajectory record are untouched.  *written
     // (optional): the voxels written.  -1 also for min_weight < 1.
     int MergeVolume(const xs_host::SecondMap &src, const double *T16, int min_weight, unsigned long long *written);
+    // Taking fused frames out of the volume and fusing them again at corrected poses (kf_reintegrate.cpp; DESIGN.md section 4.27;
+    // xs_tsdf_reintegrate in include/xslam_amd.h: the contract).  Entry i: the depth frame depths[i] (u16, device), mode[i] bit 0: take it out at
+    // c2v_old[i], bit 1: put it in at c2v_new[i] (camera2volume, seeds included; the pointer of a mode that is not asked for may be null);
+    // frame_index (optional) per entry: >= 0 replaces that frame's world2camera_record entry by the pose that gives c2v_new[i] (and world2camera
+    // with the last entry), < 0 leaves the record alone.  The device is drained, each distinct image scaled into a buffer of the call's own, the
+    // ops issued in entry order (an entry's removal before its addition) in launches of at most XS_REINTEGRATE_MAX_OPS with
+    // max_integration_weight and biInterpolate_threshold, and everything derived from the volume follows as after MergeVolume.  frame_id and the
+    // number of poses are untouched.  counts4 (optional) = {removed, added, emptied, orphaned} voxels over all ops.  Returns 1, 0 without a
+    // volume, -1 on bad arguments (n < 1, a null frame, a mode outside 1 .. 3, a missing pose or one that is not finite, a frame index past
+    // the record) with the state unchanged, -2 in shard mode.
+    int ReintegrateFrames(int n, const DeviceArray2D<ushort> *depths, const Matrix4cf *c2v_old, const Matrix4cf *c2v_new, const int *mode,
+                          const int *frame_index, unsigned long long counts4[4]);
     // Aligning a second map to the volume before it is merged (xs_tsdf_align_terms in include/xslam_amd.h: the
     // contract).  Axes >= 2.  T16xN: N >= 1 starting transforms.
     // The device is drained, the band index of THIS map prepared, and gn_batch_loop (gn_host.hpp) run over the starts:

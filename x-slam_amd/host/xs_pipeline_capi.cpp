@@ -543,6 +543,15 @@ int xs_kf_merge_map(void *kf, void *other_kf, const double *T16, int min_weight,
     const int rc = ((KF *)kf)->OtherInstanceMap((KF *)other_kf, true, m);
     return rc != 1 ? rc : ((KF *)kf)->MergeVolume(m, T16, min_weight, written);
 }
+int xs_kf_reintegrate(void *kf, int n, const uint16_t *const *depth_dev, size_t step_bytes, const float *c2v_old32xN, const float *c2v_new32xN,
+                      const int *mode, const int *frame_index, unsigned long long *counts4) {
+    KF *k = (KF *)kf;
+    if (n < 1 || !depth_dev || !mode) return -1;
+    std::vector<DeviceArray2D<ushort>> depths;
+    for (int i = 0; i < n; ++i) depths.push_back(wrap_depth(k, depth_dev[i], step_bytes));
+    const std::vector<Matrix4cf> olds = poses_of(c2v_old32xN, c2v_old32xN ? n : 0), news = poses_of(c2v_new32xN, c2v_new32xN ? n : 0);
+    return k->ReintegrateFrames(n, depths.data(), olds.empty() ? nullptr : olds.data(), news.empty() ? nullptr : news.data(), mode, frame_index, counts4);
+}
 static int align_call(KF *k, const xs_host::SecondMap &m, const double *T16xN, int N, int iterations, double damping, int min_weight, float max_residual,
                       double *T16_out, double *report8, double *loss_history) {
     std::vector<double> history;

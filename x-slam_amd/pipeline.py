@@ -111,6 +111,7 @@ _SIGS = {
     "xs_kf_save_checkpoint_sparse": (C.c_int, [_vp, C.c_char_p, C.POINTER(C.c_ulonglong)]),
     "xs_kf_checkpoint_staging_words": (C.c_longlong, [_vp, C.c_ulonglong]),
     "xs_host_checkpoint_info": (C.c_int, [C.c_char_p, _f64p]),
+    "xs_kf_reintegrate": (C.c_int, [_vp, C.c_int, C.POINTER(_vp), _sz, _f32p, _f32p, _i32p, _i32p, C.POINTER(C.c_ulonglong)]),
     "xs_kf_merge_volume": (C.c_int, [_vp, _vp, _vp, _vp, _sz, _i32p, C.c_float, C.c_float, _f64p, C.c_int, C.POINTER(C.c_ulonglong)]),
     "xs_kf_merge_map": (C.c_int, [_vp, _vp, _f64p, C.c_int, C.POINTER(C.c_ulonglong)]),
     "xs_kf_merge_checkpoint": (C.c_int, [_vp, C.c_char_p, _f64p, C.c_int, C.POINTER(C.c_ulonglong)]),
@@ -992,6 +993,64 @@ class KinectFusion:
         """merge_map with the other map read from a checkpoint file of a whole volume (save_checkpoint, dense or sparse: either format is accepted); the file is validated before anything
         is touched and a bad one raises ValueError with the state unchanged."""
         return self._merge_call("xs_kf_merge_checkpoint", path.encode(), T, min_weight)
+
+    def _reintegrate_call(self, depths, c2v_olds, c2v_news, modes, frames):
+        n = len(depths)
+        if n < 1 or len(modes) != n:
+            raise ValueError("reintegrate: at least one frame, one mode per frame")
+        P = (_vp * n)(*[d if isinstance(d, int) else d.data_ptr() for d in depths])
+
+        def poses(c):
+            if c is None:
+                return None, None
+            a = np.ascontiguousarray(c, dtype=np.float32).reshape(-1)
+            if a.size != 32 * n:
+                raise ValueError("reintegrate: one camera2volume [4, 4, 2] per frame")
+            return a, a.ctypes.data_as(_f32p)
+
+        olds, po = poses(c2v_olds)
+        news, pn = poses(c2v_news)
+        mode = np.ascontiguousarray(modes, np.int32)
+        idx = None if frames is None else np.ascontiguousarray([-1 if f is None else int(f) for f in frames], np.int32)
+        if idx is not None and idx.size != n:
+            raise ValueError("reintegrate: one frame index (or None) per frame")
+        counts = (C.c_ulonglong * 4)()
+        rc = _lib.xs_kf_reintegrate(self.h, n, P, self.width * 2, po, pn, mode.ctypes.data_as(_i32p), None if idx is None else idx.ctypes.data_as(_i32p), counts)
+        if rc == -2:
+            raise capi.XsError("reintegrate: not available in shard mode")
+        if rc != 1:
+            raise ValueError("reintegrate: no volume" if rc == 0 else "reintegrate: bad arguments (a pose that is not finite, a frame index past the record)")
+        return dict(removed=int(counts[0]), added=int(counts[1]), emptied=int(counts[2]), orphaned=int(counts[3]))
+
+    def deintegrate(self, depth_dev, c2v):
+        """Takes the depth frame (torch CUDA tensor [H, W], u16 millimetres) fused at camera2volume c2v [4, 4, 2] out of the volume again: every
+        voxel the frame wrote loses that observation from its running mean and one unit of weight; a voxel it alone had written is empty
+        again.  Exact up to rounding while no weight had reached max_integration_weight (include/xslam_amd.h: what removal cannot undo).
+        Everything derived from the volume follows, as after merge_map; poses and the frame number do not change.  Returns the counts
+        dict(removed, added, emptied, orphaned) in voxels; orphaned: the frame would have written there but nothing was left to take.
+        XsError in shard mode, ValueError on bad arguments (the state is unchanged)."""
+        return self._reintegrate_call([depth_dev], [c2v], None, [1], None)
+
+    def reintegrate(self, depth_dev, c2v_old, c2v_new, frame=None):
+        """deintegrate at c2v_old and fuse the same frame again at c2v_new, in one pass over the volume.  frame: the index of that frame in the
+        pose record (world2camera(frame)), which then receives the pose that gives c2v_new.  Returns the counts."""
+        return self._reintegrate_call([depth_dev], [c2v_old], [c2v_new], [3], None if frame is None else [frame])
+
+    def reintegrate_batch(self, depths, c2v_olds, c2v_news, frames=None):
+        """reintegrate for several frames: the observations are applied in list order, up to eight per pass over the volume, and the derived
+        state is rebuilt once.  The volume equals the one the single calls in the same order leave, bit for bit.  Returns the summed counts."""
+        return self._reintegrate_call(list(depths), c2v_olds, c2v_news, [3] * len(depths), frames)
+
+    def refine_frame(self, depth_dev, c2v, iterations=5, damping=1e-3, frame=None):
+        """Refines the pose of a frame that is already fused: takes it out at c2v, runs relocalize against the map without it starting at c2v —
+        a map that still holds the frame pulls the refinement towards where the frame already is — and puts it back at the refined pose, or at
+        c2v again if the refinement failed.  Returns (ok, refined c2v [4, 4, 2], loss history, counts of both edits summed)."""
+        c2v = np.ascontiguousarray(c2v, dtype=np.float32).reshape(4, 4, 2)
+        out = self.deintegrate(depth_dev, c2v)
+        ok, refined, hist = self.relocalize(depth_dev, c2v, iterations=iterations, damping=damping)
+        ok = bool(ok) and bool(np.isfinite(refined).all())
+        back = self._reintegrate_call([depth_dev], None, [refined if ok else c2v], [2], None if frame is None or not ok else [frame])
+        return ok, (refined if ok else c2v), hist, {k: out[k] + back[k] for k in out}
 
     def _diff_call(self, name, source, T, min_weight, lo, hi, cell_vox, min_size, masks, capacity):
         t = _real44(np.eye(4) if T is None else T)
