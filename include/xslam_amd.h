@@ -860,6 +860,77 @@ int xs_tsdf_score_transforms(int transforms, const xs_band_index *index, int str
                              size_t src_step, const int *src_res, const float *xform12xP, int min_weight, float max_residual, void *workspace,
                              double *out2xP_dev, void *stream);
 
+/* ---- depth, normal and shaded views of a map, many views in one launch (xs_render.hip) ------------------------
+ * No counterpart in the reference, whose only ray caster is the tracker's (xs_raycast above: complex arithmetic, normalised rays, one
+ * view, the tracking buffers).  This one is real arithmetic at any intrinsics and image size, and its depth is measured along the camera's
+ * z: the image is what a depth sensor at that pose would report.  The volume (value, weight, one pitch vol_step in bytes, rows in
+ * (z * Y + y) order, the pointers at plane 0) is only read; byte offsets row * vol_step are computed in 64 bits.
+ *
+ * xs_render_workspace_bytes: the workspace for `res` in bytes of device memory (256-byte aligned): a header, the staging area of one
+ * launch's poses, and the BRICK MASK, one bit per brick of 8 x 8 x 8 voxels.  0 for a null or unusable resolution.  Host only.
+ * xs_render_mask_build: bit bx & 31 of word (bz BY + by) WX + (bx >> 5), with BX, BY, BZ = ceil(res / 8) and WX = ceil(BX / 32), is set iff
+ * brick (bx, by, bz) holds a voxel with value < 0 && weight >= min_weight (min_weight below 1 means 1); the other bits of a row's last
+ * word are clear.  One read of the two arrays, one writer per word, no atomics.  The call then records (res, min_weight) in the header.  The
+ * mask describes the volume as it was when the call ran: rebuild it after the volume changes.  No synchronisation.
+ *
+ * xs_render_views: `views` (1 .. XS_RENDER_MAX_VIEWS) real camera-to-volume poses, host arrays Rc2v9xP + 9 p (row-major) / tc2v3xP + 3 p,
+ * copied into the workspace's staging area (one launch at a time per workspace), each rendering a rows x cols image (1 .. 4096 each) of a
+ * camera with intrinsics intr4 = {fx, fy, cx, cy}, all in one launch.  Every float operation below is one IEEE float32 operation in the
+ * order written (the library is built -ffp-contract=off; divides and square roots correctly rounded), there are no floating-point
+ * atomics: a float32 model on the host reproduces every output bit, two launches give the same bits, and view p's output does not
+ * depend on `views`, on p or on the other views.  opts (NULL: all defaults): t_near, t_far = 0, 0 means 0.2, 5.0; step = 0 means
+ * voxel_size; min_weight below 1 means 1; shade_mode 0 (headlight) is the only mode.
+ *   pixel (x, y):  dx = (float(x) - cx) / fx,  dy = (float(y) - cy) / fy,  d[c] = (R[c][0] * dx + R[c][1] * dy) + R[c][2]  (not normalised:
+ *                  t is depth along the camera's z; the unprojection xs_create_vmap applies to a depth image)
+ *   sample k = 0 .. n - 1:  t_k = t_near + float(k) * step (no running sum), n = the number of k with t_k < t_far;  p[c] = tc2v[c] + t_k * d[c];
+ *                  q[c] = p[c] / voxel_size; the voxel is floor(q[c]) and lies inside iff 0 <= q[c] < float(res[c]) on every axis (a NaN
+ *                  is outside).  The sample's state s_k is NONE where the voxel is outside or its weight < min_weight, otherwise its value.
+ *   march, k = 0 .. n - 2, the first k at which s_k and s_k+1 are both values and
+ *                  s_k < 0 && s_k+1 > 0:  the ray ends as BACKFACE;
+ *                  s_k > 0 && s_k+1 < 0:  the ray is REFINED and ends, as HIT or as REJECTED.
+ *                  A NONE sample, and a value of 0.0f or -0.0f, never ends a ray.  A ray nothing ends is NONE.
+ *   F(P), the trilinear value at a point P (metres):  g[c] = P[c] / voxel_size - 0.5f; REFUSED unless 0 <= g[c] <= float(res[c] - 1) on
+ *                  every axis; b[c] = floor(g[c]), f[c] = g[c] - float(b[c]); only the corners b + e with e[c] = 1 on axes with f[c] > 0
+ *                  are read; REFUSED if the smallest weight among them < min_weight; the values are interpolated along x, then y, then
+ *                  z, a stage being lo * (1.0f - f[c]) + hi * f[c], and its lower operand itself on an axis with f[c] == 0 (the
+ *                  sampling rule of xs_tsdf_merge, steps 2 to 4, on the value array).
+ *   refinement:    F0 = F(p(t_k)), F1 = F(p(t_k+1)), with p(t)[c] = tc2v[c] + t * d[c].  REJECTED if F0 or F1 is refused, or
+ *                  !(F0 >= 0 && F1 <= 0), or F1 - F0 == 0.  Otherwise HIT with ts = t_k - step * (F0 / (F1 - F0)).
+ * Outputs, each optional (NULL: not wanted; another output's bits do not depend on it), dense and view-major:
+ *   depth_f32 [P][rows][cols]     ts; 0.0f where the ray is no HIT.
+ *   depth_u16 [P][rows][cols]     r = rint(ts * 1000.0f) where 1 <= r <= 65535, else 0: millimetres, as xs_scale_depth takes them.
+ *   normal    [P][3][rows][cols]  in the volume frame, pointing into free space:  Q = p(ts), h = 0.5f * voxel_size,
+ *                                 G[c] = F(Q + h e_c) - F(Q - h e_c) (only coordinate c changes), gg = (G[0] * G[0] + G[1] * G[1]) + G[2] * G[2],
+ *                                 N[c] = G[c] / sqrt(gg).  The NaN 0x7fffffff in all three where the ray is no HIT, one of the six
+ *                                 samples is refused, or !(gg > 0).
+ *   shade     [P][rows][cols]     uint8, headlight:  nd = (N[0] * d[0] + N[1] * d[1]) + N[2] * d[2],  dd = (d[0] * d[0] + d[1] * d[1]) + d[2] * d[2],
+ *                                 rint(255.0f * min(1.0f, |nd| / sqrt(dd))); 0 where the ray is no HIT or has no normal.
+ *   counts4xP [P][4]              uint32 {hit, backface, rejected, none} of the view's rows * cols rays; zeroed by the call on the
+ *                                 stream, then integer atomics, one per counter and workgroup.
+ * The cull (opts->cull != 0): a sample whose brick's mask bit is clear cannot be the negative side of either event, so it is read only
+ * when its neighbour sample turns out to be a negative value.  It changes no bit of any output.  It needs a mask built in this workspace
+ * for this res with a min_weight not above the call's: the call reads the header back on the stream and waits for it (the one
+ * synchronisation; without the cull there is none).
+ * hipErrorInvalidValue, with nothing launched and every output untouched: views outside 1 .. XS_RENDER_MAX_VIEWS; rows or cols outside
+ * 1 .. 4096; a null pose, intrinsics, resolution, volume or workspace pointer; every output null; a pose or intrinsic entry that is not
+ * finite; fx or fy equal to 0; voxel_size not positive and finite; a pitch that is no multiple of 4 or shorter than a row; step < 0 or
+ * not finite; a range that is not finite or has t_far <= t_near; more than 4096 samples; an axis outside 1 .. 262140 or rows that do not
+ * fit an int (the merge's rule); opts->struct_bytes not sizeof(xs_render_opts); a shade_mode other than 0; the cull without such a mask. */
+#define XS_RENDER_MAX_VIEWS 64
+typedef struct xs_render_opts {
+    unsigned struct_bytes;     /* sizeof(xs_render_opts) */
+    float t_near, t_far;       /* depth range along the camera's z; 0, 0 = 0.2, 5.0 */
+    float step;                /* depth increment per sample; 0 = voxel_size */
+    int min_weight;            /* a voxel with a smaller weight is unseen; below 1 = 1 */
+    int cull;                  /* not 0: consult the workspace's brick mask */
+    int shade_mode;            /* 0: headlight */
+} xs_render_opts;
+size_t xs_render_workspace_bytes(const int *res);
+int xs_render_mask_build(const float *value, const int *weight, size_t vol_step, const int *res, int min_weight, void *workspace, void *stream);
+int xs_render_views(int views, const float *Rc2v9xP, const float *tc2v3xP, const float *intr4, int rows, int cols, const float *value,
+                    const int *weight, size_t vol_step, const int *res, float voxel_size, const xs_render_opts *opts, void *workspace,
+                    float *depth_f32, uint16_t *depth_u16, float *normal, unsigned char *shade, unsigned *counts4xP, void *stream);
+
 /* ---- surface mesh (export; marching cubes with complex-step vertex derivatives) -------------------------------------------------------
  * No working counterpart in the reference (its extractMesh, ExtractPointCloud.cu:364-715, is never called).
  * Cube (x, y, z), x < X-1, y < Y-1, z in [z0, z1), is live when all 8 corners have weight >= min_weight and value < 0.99 and its corners

@@ -463,6 +463,32 @@ int xs_kf_diff_checkpoint(void *kf, const char *path, const double *T16, int min
                           unsigned long long *this_records8, int *this_count, unsigned long long *other_records8, int *other_count,
                           unsigned long long *counts3, unsigned char *this_dense, unsigned char *other_dense);
 
+/* Depth, normal and shaded views of a map from poses the caller picks (xs_render_views in xslam_amd.h: the contract).
+ * `views` >= 1 camera2volume matrices c2v, 4 x 4 row-major: 16 floats each with complex_poses = 0, or 32 with complex_poses = 1 ((re, im) pairs as
+ * xs_kf_get_camera2volume gives them; the real part is used).  Each renders a rows x cols image of a camera with intrinsics intr4 = {fx, fy, cx,
+ * cy} (NULL: the configuration's; rows, cols = 0, 0: its image size) in launches of XS_RENDER_MAX_VIEWS views.  opts: an xs_render_opts of
+ * xslam_amd.h, or NULL for the defaults (depths 0.2 .. 5.0 in steps of a voxel, min_weight 1, the cull on).  The outputs, each optional (NULL:
+ * not wanted), view-major: depth float [views][rows][cols] in metres along the camera's z, 0 without a hit; depth_u16 the same in millimetres,
+ * what xs_kf_process_frame and xs_kf_relocalize take; normal float [views][3][rows][cols] in the volume frame, NaN without one; shade uint8
+ * [views][rows][cols]; counts4 unsigned [views][4] = {hit, backface, rejected, none}.  on_device = 0: host arrays; 1: device arrays, written
+ * in place.  The device is drained before and the stream after: the outputs are complete on return.  Nothing of any map is modified.
+ * render_views renders this instance's map; the brick mask of the cull is cached and follows the volume like the observation grid.
+ * render_volume, render_map and render_checkpoint render a second map (the caller's arrays; another instance; a checkpoint of a whole volume in
+ * either format), as the merge obtains it, with its own resolution and voxel size.
+ * Return 1, 0 without a volume, -1 on bad arguments (views < 1, a null c2v, every output null, what xs_render_views refuses, a second map the
+ * merge would refuse) with nothing written, -2 in shard mode. */
+struct xs_render_opts;
+int xs_kf_render_views(void *kf, int views, const float *c2v, int complex_poses, const float *intr4, int rows, int cols, const struct xs_render_opts *opts,
+                       float *depth, uint16_t *depth_u16, float *normal, unsigned char *shade, unsigned *counts4, int on_device);
+int xs_kf_render_volume(void *kf, const float *src_value, const int *src_weight, size_t src_step, const int *src_res, float src_voxel_size, float src_tranc_dist,
+                        int views, const float *c2v, int complex_poses, const float *intr4, int rows, int cols, const struct xs_render_opts *opts, float *depth,
+                        uint16_t *depth_u16, float *normal, unsigned char *shade, unsigned *counts4, int on_device);
+int xs_kf_render_map(void *kf, void *other_kf, int views, const float *c2v, int complex_poses, const float *intr4, int rows, int cols,
+                     const struct xs_render_opts *opts, float *depth, uint16_t *depth_u16, float *normal, unsigned char *shade, unsigned *counts4, int on_device);
+int xs_kf_render_checkpoint(void *kf, const char *path, int views, const float *c2v, int complex_poses, const float *intr4, int rows, int cols,
+                            const struct xs_render_opts *opts, float *depth, uint16_t *depth_u16, float *normal, unsigned char *shade, unsigned *counts4,
+                            int on_device);
+
 /* ---- The reference's own call shape (x-slam_amd/host/reference_shape.hpp) ---------------------------------------------------------
  * The per-frame sequence of Experiments/test_xkinect_fusion/main.cpp:46-60 + KinectFusionReconstruction.cpp:147-332 over nothing but the
  * reference-signature launchers (bilateralFilter, pyrDown, createVMap / createNMap, estimateCombined per iteration, integrateTsdfVolume,

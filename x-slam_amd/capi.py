@@ -69,7 +69,17 @@ class ViewOpts(C.Structure):
     _fields_ = [("struct_bytes", C.c_uint), ("rays_x", C.c_int), ("rays_y", C.c_int), ("t_near", C.c_float), ("t_far", C.c_float), ("step", C.c_float)]
 
 
+class RenderOpts(C.Structure):
+    """xs_render_opts (include/xslam_amd.h)."""
+    _fields_ = [("struct_bytes", C.c_uint), ("t_near", C.c_float), ("t_far", C.c_float), ("step", C.c_float), ("min_weight", C.c_int), ("cull", C.c_int),
+                ("shade_mode", C.c_int)]
+
+
 _SIGS = {
+    "xs_render_workspace_bytes": (_sz, [_i32p]),
+    "xs_render_mask_build": (C.c_int, [_vp, _vp, _sz, _i32p, C.c_int, _vp, _vp]),
+    "xs_render_views": (C.c_int, [C.c_int, _f32p, _f32p, _f32p, C.c_int, C.c_int, _vp, _vp, _sz, _i32p, C.c_float, C.POINTER(RenderOpts), _vp, _vp, _vp, _vp,
+                                  _vp, _vp, _vp]),
     "xs_view_grid_bytes": (_sz, [_i32p]),
     "xs_view_grid_build": (C.c_int, [_vp, _vp, _sz, _i32p, C.c_int, _vp, _vp]),
     "xs_view_grid_expand": (C.c_int, [_vp, _i32p, _vp, _vp]),
@@ -635,6 +645,51 @@ def score_views(Rc2vxP, tc2vxP, intr, rows, cols, res, voxel_size, grid, out4xP,
     k, R, t, r = _fa(intr, 4), _fa(R, 9 * P), _fa(tc2vxP, 3 * P), _ia(res, 3)
     check(_lib.xs_score_views(P, R.ctypes.data_as(_f32p), t.ctypes.data_as(_f32p), k.ctypes.data_as(_f32p), rows, cols, r.ctypes.data_as(_i32p),
                               voxel_size, _ptr(grid), C.byref(opts) if opts is not None else None, _ptr(out4xP), _stream(stream)))
+
+
+RENDER_MAX_VIEWS = 64   # XS_RENDER_MAX_VIEWS
+RENDER_HEADER_BYTES, RENDER_STAGING_BYTES = 256, 64 * 12 * 4   # the workspace in front of the mask words (host/render_host.hpp)
+
+
+def render_opts(t_near=0.0, t_far=0.0, step=None, min_weight=1, cull=True, shade_mode=0):
+    """An xs_render_opts; zeros (step None) are the library's defaults: depths 0.2 .. 5.0, a voxel per step."""
+    o = RenderOpts()
+    o.struct_bytes = C.sizeof(RenderOpts)
+    o.t_near, o.t_far, o.step = float(t_near), float(t_far), 0.0 if step is None else float(step)
+    o.min_weight, o.cull, o.shade_mode = int(min_weight), int(bool(cull)), int(shade_mode)
+    return o
+
+
+def render_workspace_bytes(res):
+    """xs_render_workspace_bytes (host only): header, pose staging area and brick mask for a resolution; 0 for an unusable one."""
+    return int(_lib.xs_render_workspace_bytes(_res3(res).ctypes.data_as(_i32p)))
+
+
+def render_mask_build(value, weight, vol_step, res, workspace, min_weight=1, stream=None):
+    """xs_render_mask_build: one bit per brick of 8 x 8 x 8 voxels (any value < 0 with weight >= min_weight) into the workspace, and its header."""
+    r = _ia(res, 3)
+    check(_lib.xs_render_mask_build(_ptr(value), _ptr(weight), vol_step, r.ctypes.data_as(_i32p), int(min_weight), _ptr(workspace), _stream(stream)))
+
+
+def render_views(Rc2vxP, tc2vxP, intr, rows, cols, value, weight, vol_step, res, voxel_size, workspace, opts=None, depth=None, depth_u16=None, normal=None,
+                 shade=None, counts=None, views=None, stream=None):
+    """xs_render_views: P real camera-to-volume poses Rc2vxP [P, 3, 3], tc2vxP [P, 3] render rows x cols images of the volume in one launch into
+    the device tensors that are given: depth float32 [P, rows, cols], depth_u16 uint16 [P, rows, cols], normal float32 [P, 3, rows, cols], shade
+    uint8 [P, rows, cols], counts uint32 [P, 4] = {hit, backface, rejected, none}.  opts: render_opts(...) or None.  A None among the host
+    arrays goes through as a null pointer (`views` then says how many were meant).  Waits for the stream once when opts.cull is set."""
+    def fp(x):
+        if x is None:
+            return None, None
+        a = np.ascontiguousarray(x, dtype=np.float32).reshape(-1)
+        return a, a.ctypes.data_as(_f32p)
+    R, Rp = fp(Rc2vxP)
+    t, tp = fp(tc2vxP)
+    k, kp = fp(intr)
+    r = None if res is None else _ia(res, 3)
+    P = int(views) if views is not None else R.size // 9
+    check(_lib.xs_render_views(P, Rp, tp, kp, int(rows), int(cols), _ptr(value), _ptr(weight), vol_step, None if r is None else r.ctypes.data_as(_i32p),
+                               voxel_size, C.byref(opts) if opts is not None else None, _ptr(workspace), _ptr(depth), _ptr(depth_u16), _ptr(normal),
+                               _ptr(shade), _ptr(counts), _stream(stream)))
 
 
 CLEARANCE_MAX_RADIUS, REACH_MAX_SEEDS, REACH_MAX_SNAP = 255, 64, 16   # XS_CLEARANCE_MAX_RADIUS, XS_REACH_MAX_SEEDS, XS_REACH_MAX_SNAP

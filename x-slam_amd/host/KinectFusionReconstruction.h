@@ -416,6 +416,23 @@ public:
                    unsigned long long *this_records8, int *this_count, unsigned long long *other_records8, int *other_count, unsigned long long counts3[3],
                    unsigned char *this_dense, unsigned char *other_dense);
 
+    // Depth, normal and shaded views of a map from poses the caller picks (kf_render.cpp; xs_render_views in
+    // include/xslam_amd.h: the contract).  c2v: P camera2volume matrices, 4 x 4 row-major with `stride` floats per entry (1: real, 2: (re, im)
+    // pairs, the real part used).  intr4 null: the configuration's level-0 intrinsics; rows, cols 0, 0: its image size.  opts null: the
+    // defaults with the cull on.  The outputs are view-major arrays as the contract lays them out, each optional (null: not wanted), on the
+    // host, or with on_device != 0 in device memory, where the call leaves them without copying.  The device is drained, the views rendered in
+    // launches of XS_RENDER_MAX_VIEWS, and the stream drained again: the outputs are complete on return.
+    // RenderViews renders THIS map.  Its brick mask lives in a workspace that is cached under (volume_generation, min_weight) the way the
+    // observation grid is, and dropped with it whenever the volume is edited.  RenderSecondMap renders another map (axes >= 1), with a
+    // workspace of the call's own whose mask is built per call; nothing of this instance is touched.
+    // Both return 1, -2 in shard mode (a ray's first crossing is not additive over the ranks' z-slabs), 0 without a volume, -1 on bad
+    // arguments (P < 1, a null c2v, a stride other than 1 or 2, every output null, whatever xs_render_views refuses).
+    struct RenderOutputs { float *depth = nullptr; uint16_t *depth_u16 = nullptr; float *normal = nullptr; unsigned char *shade = nullptr; unsigned *counts = nullptr; };
+    int RenderViews(const float *c2v, int stride, int P, const float *intr4, int rows, int cols, const xs_render_opts *opts, const RenderOutputs &out,
+                    int on_device);
+    int RenderSecondMap(const xs_host::SecondMap &src, const float *c2v, int stride, int P, const float *intr4, int rows, int cols, const xs_render_opts *opts,
+                        const RenderOutputs &out, int on_device);
+
     // counters of the last frame (synchronise the stream)
     long long lastUpdatedVoxels();
     long long lastRaycastHits();
@@ -504,6 +521,8 @@ private:
         DeviceArray<unsigned long long> frontier_records_d;   // capacity x 8, and the count behind them
         std::vector<unsigned long long> frontier_records;     // the records of every cluster, on the host
         FrontierKey frontier_key;
+        DeviceArray<unsigned char> render_ws;      // xs_render_workspace_bytes(resolution): header, a launch's poses, the brick mask
+        GridKey render_key;                        // what the mask in it was built at
     } plan_;
     bool ViewGridPrepare(int min_weight);      // (re)builds the observation grid when the volume or min_weight changed since it was built
     bool ClearancePrepare(int R, int unknown_blocks, int min_weight);   // grid and clearance field in step with the volume and the arguments
@@ -516,7 +535,10 @@ private:
     // sequence numbers stay)
     bool takes_second_map(const xs_host::SecondMap &m, int min_axis, bool need_grad) const;   // second_map_ok against this volume
     void drain_device();   // what every call that takes a second map does before its first launch
-    void invalidate_derived_maps() { reloc_.band_key = BandKey{}; plan_.grid_key = GridKey{}; plan_.clear_key = ClearKey{}; plan_.frontier_key = FrontierKey{}; reach_forget(); }
+    void invalidate_derived_maps() { reloc_.band_key = BandKey{}; plan_.grid_key = GridKey{}; plan_.clear_key = ClearKey{}; plan_.frontier_key = FrontierKey{}; plan_.render_key = GridKey{}; reach_forget(); }
+    // the views of one volume through xs_render_views, in chunks; `ws` holds a mask built for (res, the options' min_weight) unless the cull is off
+    int RenderVolume(const float *value, const int *weight, size_t step, const int *res, float vs, void *ws, const float *c2v, int stride, int P, const float *intr4,
+                     int rows, int cols, const xs_render_opts &opts, const RenderOutputs &out, int on_device);
     DeviceArray2D<ushort> depth_ingest_d_;     // device copy of a host frame (ProcessFrameHost)
     ushort *ingest_pinned_[2] = {nullptr, nullptr};
     hipEvent_t ingest_done_[2] = {nullptr, nullptr};

@@ -625,6 +625,36 @@ int xs_kf_diff_checkpoint(void *kf, const char *path, const double *T16, int min
     return rc != 1 ? rc : ((KF *)kf)->DiffVolume(c.map, T16, min_weight, lo, hi, cell, min_size, capacity, this_records8, this_count, other_records8, other_count,
                                                  counts3, this_dense, other_dense);
 }
+static KF::RenderOutputs render_outputs(float *depth, uint16_t *depth_u16, float *normal, unsigned char *shade, unsigned *counts4) {
+    KF::RenderOutputs o;
+    o.depth = depth; o.depth_u16 = depth_u16; o.normal = normal; o.shade = shade; o.counts = counts4;
+    return o;
+}
+int xs_kf_render_views(void *kf, int views, const float *c2v, int complex_poses, const float *intr4, int rows, int cols, const xs_render_opts *opts, float *depth,
+                       uint16_t *depth_u16, float *normal, unsigned char *shade, unsigned *counts4, int on_device) {
+    return ((KF *)kf)->RenderViews(c2v, complex_poses ? 2 : 1, views, intr4, rows, cols, opts, render_outputs(depth, depth_u16, normal, shade, counts4), on_device);
+}
+int xs_kf_render_volume(void *kf, const float *src_value, const int *src_weight, size_t src_step, const int *src_res, float src_voxel_size, float src_tranc_dist,
+                        int views, const float *c2v, int complex_poses, const float *intr4, int rows, int cols, const xs_render_opts *opts, float *depth,
+                        uint16_t *depth_u16, float *normal, unsigned char *shade, unsigned *counts4, int on_device) {
+    return ((KF *)kf)->RenderSecondMap(second_map(src_value, src_weight, nullptr, src_step, src_res, src_voxel_size, src_tranc_dist), c2v, complex_poses ? 2 : 1, views,
+                                       intr4, rows, cols, opts, render_outputs(depth, depth_u16, normal, shade, counts4), on_device);
+}
+int xs_kf_render_map(void *kf, void *other_kf, int views, const float *c2v, int complex_poses, const float *intr4, int rows, int cols, const xs_render_opts *opts,
+                     float *depth, uint16_t *depth_u16, float *normal, unsigned char *shade, unsigned *counts4, int on_device) {
+    xs_host::SecondMap m;
+    const int rc = ((KF *)kf)->OtherInstanceMap((KF *)other_kf, false, m);
+    return rc != 1 ? rc : ((KF *)kf)->RenderSecondMap(m, c2v, complex_poses ? 2 : 1, views, intr4, rows, cols, opts,
+                                                      render_outputs(depth, depth_u16, normal, shade, counts4), on_device);
+}
+int xs_kf_render_checkpoint(void *kf, const char *path, int views, const float *c2v, int complex_poses, const float *intr4, int rows, int cols,
+                            const xs_render_opts *opts, float *depth, uint16_t *depth_u16, float *normal, unsigned char *shade, unsigned *counts4, int on_device) {
+    if (!path) return -1;
+    KF::CheckpointMap c;
+    const int rc = ((KF *)kf)->OpenCheckpointMap(path, c);
+    return rc != 1 ? rc : ((KF *)kf)->RenderSecondMap(c.map, c2v, complex_poses ? 2 : 1, views, intr4, rows, cols, opts,
+                                                      render_outputs(depth, depth_u16, normal, shade, counts4), on_device);
+}
 int xs_host_align_search_free(int n, const double *centroid_this3, const double *centroid_other3, double box_t, double *T16xN) {
     return xs_host::align_search_free(n, centroid_this3, centroid_other3, box_t, T16xN) ? 0 : -1;
 }

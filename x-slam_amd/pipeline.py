@@ -33,7 +33,14 @@ class AlignSearchOpts(C.Structure):
 _DIFF_TAIL = [C.c_int, C.c_float, C.c_float, C.c_int, C.c_ulonglong, C.c_int, C.POINTER(C.c_uint64), _i32p, C.POINTER(C.c_uint64), _i32p,
               C.POINTER(C.c_ulonglong), C.POINTER(C.c_ubyte), C.POINTER(C.c_ubyte)]
 
+# what the four render calls share behind their source: views, c2v, complex_poses, intr4, rows, cols, opts, five outputs, on_device
+_RENDER_TAIL = [C.c_int, _f32p, C.c_int, _f32p, C.c_int, C.c_int, C.POINTER(capi.RenderOpts), _vp, _vp, _vp, _vp, _vp, C.c_int]
+
 _SIGS = {
+    "xs_kf_render_views": (C.c_int, [_vp] + _RENDER_TAIL),
+    "xs_kf_render_volume": (C.c_int, [_vp, _vp, _vp, _sz, _i32p, C.c_float, C.c_float] + _RENDER_TAIL),
+    "xs_kf_render_map": (C.c_int, [_vp, _vp] + _RENDER_TAIL),
+    "xs_kf_render_checkpoint": (C.c_int, [_vp, C.c_char_p] + _RENDER_TAIL),
     "xs_kf_create_sharded": (_vp, [C.c_char_p, C.c_int, C.c_int, COLLECTIVE_CB, _vp]),
     "xs_kf_shard_planes": (None, [_vp, _i32p, _i32p]),
     "xs_host_double_complex_table": (C.c_int, [C.c_int, C.c_long, _f32p, _f32p, _f32p]),
@@ -390,6 +397,23 @@ class MapDiff(collections.namedtuple("MapDiff", "counts only_this only_other mas
     """What differs between two maps (KinectFusion.diff_map): counts, a dict of compared, only_this and only_other voxels; only_this and
     only_other, the clusters of each class as structured arrays of KinectFusion.FRONTIER_DTYPE; masks, the pair (only_this, only_other) of
     uint8 [Z, Y, X] or None."""
+
+
+class RenderedViews(collections.namedtuple("RenderedViews", "depth depth_u16 normal shade counts")):
+    """What KinectFusion.render_views returns for P views of rows x cols pixels: depth float32 [P, rows, cols] (metres along the camera's z, 0 without
+    a hit), depth_u16 uint16 [P, rows, cols] (millimetres, what process_frame and relocalize take), normal float32 [P, 3, rows, cols] (volume
+    frame, pointing into free space, NaN without one), shade uint8 [P, rows, cols] (headlight shading, 0 without a normal) and counts uint32
+    [P, 4] = {hit, backface, rejected, none} rays.  An output that was not asked for is None."""
+
+
+def save_view_pgm(path, shade):
+    """One rendered image (uint8 [rows, cols], e.g. RenderedViews.shade[p]) as a binary P5 file."""
+    a = shade.cpu().numpy() if hasattr(shade, "cpu") else np.asarray(shade)
+    if a.ndim != 2 or a.dtype != np.uint8:
+        raise ValueError("save_view_pgm: a uint8 image [rows, cols] is needed")
+    with open(path, "wb") as f:
+        f.write(b"P5\n%d %d\n255\n" % (a.shape[1], a.shape[0]))
+        f.write(np.ascontiguousarray(a).tobytes())
 
 
 class KinectFusion:
@@ -1051,6 +1075,61 @@ class KinectFusion:
         ok = bool(ok) and bool(np.isfinite(refined).all())
         back = self._reintegrate_call([depth_dev], None, [refined if ok else c2v], [2], None if frame is None or not ok else [frame])
         return ok, (refined if ok else c2v), hist, {k: out[k] + back[k] for k in out}
+
+    def _render_call(self, name, source, c2vs, intr, size, t_near, t_far, step, min_weight, outputs, cull, device):
+        m = np.ascontiguousarray(c2vs, dtype=np.float32)
+        if m.ndim == 2 or (m.ndim == 3 and m.shape[-1] == 2):
+            m = m[None]
+        if m.shape[1:] not in ((4, 4), (4, 4, 2)) or m.shape[0] < 1:
+            raise ValueError(f"{name}: c2vs must be [P, 4, 4] or [P, 4, 4, 2]")
+        P, is_complex = m.shape[0], int(m.ndim == 4)
+        m = m.reshape(-1)
+        k = None if intr is None else np.ascontiguousarray(intr, dtype=np.float32).reshape(4)
+        rows, cols = (self.height, self.width) if size is None else (int(size[0]), int(size[1]))
+        wanted = set(outputs)
+        if not wanted or not wanted <= {"depth", "depth_u16", "normal", "shade", "counts"}:
+            raise ValueError(f"{name}: outputs must name some of depth, depth_u16, normal, shade, counts")
+        shapes = dict(depth=((P, rows, cols), np.float32), depth_u16=((P, rows, cols), np.uint16), normal=((P, 3, rows, cols), np.float32),
+                      shade=((P, rows, cols), np.uint8), counts=((P, 4), np.uint32))
+        out, ptr = {}, {}
+        if device:
+            import torch
+            dt = {np.float32: torch.float32, np.uint16: getattr(torch, "uint16", torch.int16), np.uint8: torch.uint8, np.uint32: torch.int32}
+            for n in wanted:
+                out[n] = torch.empty(shapes[n][0], dtype=dt[shapes[n][1]], device="cuda")
+                ptr[n] = out[n].data_ptr()
+        else:
+            for n in wanted:
+                out[n] = np.zeros(*shapes[n])
+                ptr[n] = out[n].ctypes.data
+        opts = capi.render_opts(t_near, t_far, step, min_weight, cull)
+        rc = getattr(_lib, name)(self.h, *source, P, m.ctypes.data_as(_f32p), is_complex, None if k is None else k.ctypes.data_as(_f32p), rows, cols,
+                                 C.byref(opts), ptr.get("depth"), ptr.get("depth_u16"), ptr.get("normal"), ptr.get("shade"), ptr.get("counts"), int(bool(device)))
+        self._map_call(name, rc, "poses, intrinsics or size out of range or not finite, t_far <= t_near, more than 4096 samples, a map that cannot be rendered")
+        return RenderedViews(*(out.get(n) for n in RenderedViews._fields))
+
+    def render_views(self, c2vs, intr=None, size=None, t_near=0.2, t_far=5.0, step=None, min_weight=1, outputs=("depth", "normal", "shade"), cull=True,
+                     device=False):
+        """Views of the map from P poses the caller picks, c2vs [P, 4, 4] or [P, 4, 4, 2] camera-to-volume (real parts; camera2volume() gives one),
+        64 views per launch: a RenderedViews of the `outputs` asked for (depth, depth_u16, normal, shade, counts), numpy arrays, or torch tensors
+        on the GPU with device=True.  intr (fx, fy, cx, cy) and size (rows, cols) default to the configuration's camera; depths t_near .. t_far
+        along the camera's z in increments of `step` (None: a voxel); a voxel with a weight below min_weight is unseen.  cull=False reads every
+        sample instead of consulting the brick mask: the same bits, slower.  depth_u16 is what a depth sensor at that pose would deliver, so it
+        can stand in for a frame: relocalize(views.depth_u16[p], c2v) with device=True.  counts says how the rays ended; a crossing whose two
+        trilinear values do not bracket zero is rejected, which a step of two or three voxels makes rarer than a step of one (DESIGN.md section
+        4.28).  XsError in shard mode, ValueError on bad arguments."""
+        return self._render_call("xs_kf_render_views", (), c2vs, intr, size, t_near, t_far, step, min_weight, outputs, cull, device)
+
+    def render_map(self, other, c2vs, **kw):
+        """render_views of the map of `other` (another KinectFusion of this process, which is only read); the poses are in ITS volume frame, the
+        default camera is this instance's."""
+        kw = {**dict(intr=None, size=None, t_near=0.2, t_far=5.0, step=None, min_weight=1, outputs=("depth", "normal", "shade"), cull=True, device=False), **kw}
+        return self._render_call("xs_kf_render_map", (other.h,), c2vs, **kw)
+
+    def render_checkpoint(self, path, c2vs, **kw):
+        """render_views of the map in a checkpoint file of a whole volume (save_checkpoint, dense or sparse), validated as merge_checkpoint does."""
+        kw = {**dict(intr=None, size=None, t_near=0.2, t_far=5.0, step=None, min_weight=1, outputs=("depth", "normal", "shade"), cull=True, device=False), **kw}
+        return self._render_call("xs_kf_render_checkpoint", (path.encode(),), c2vs, **kw)
 
     def _diff_call(self, name, source, T, min_weight, lo, hi, cell_vox, min_size, masks, capacity):
         t = _real44(np.eye(4) if T is None else T)
