@@ -931,6 +931,53 @@ int xs_render_views(int views, const float *Rc2v9xP, const float *tc2v3xP, const
                     const int *weight, size_t vol_step, const int *res, float voxel_size, const xs_render_opts *opts, void *workspace,
                     float *depth_f32, uint16_t *depth_u16, float *normal, unsigned char *shade, unsigned *counts4xP, void *stream);
 
+/* ---- the map sampled at the caller's points, and at a depth frame's pixels (xs_sample.hip) ---------------------
+ * No counterpart in the reference.  What is the signed distance here, which way does it grow, has this place been seen: F(P) of
+ * xs_render_views above (the same device function, xs_trilinear.h) applied to points the caller supplies, one lane per point, all in one
+ * launch.  The volume is given as xs_render_views takes it, plus an optional `grad` array with the same pitch; it is only read; byte
+ * offsets row * vol_step are computed in 64 bits.  Every float operation below is one IEEE float32 operation in the order written (the
+ * library is built -ffp-contract=off), there are no floating-point atomics, no synchronisation and no workspace: a float32 model on the
+ * host reproduces every output bit, two launches give equal bytes, and point i's outputs depend on nothing but point i, the volume and
+ * the options (not on n, not on i).  opts (NULL: all defaults): min_weight below 1 means 1.
+ *
+ * xs_tsdf_sample_points: n points (1 .. 2^30), a device array points3xN_dev + 3 i of float32 metres (4-byte aligned).  xform12 (host,
+ * optional): row-major R, then t.
+ *   with a transform:  P[c] = ((R[c][0] * p[0] + R[c][1] * p[1]) + R[c][2] * p[2]) + t[c];   without one:  P = p, the point's bits as they are.
+ * xs_tsdf_sample_depth: the points of a depth image's pixels: u16 millimetres, pitched (depth_step bytes per row), rows x cols (1 .. 4096
+ * each), a camera with intrinsics intr4 = {fx, fy, cx, cy} at the real camera-to-volume pose Rc2v9 (row-major), tc2v3 (host arrays).
+ *   pixel (x, y), D = depth[y][x]:  NO_DEPTH if D < 200 || D > 5000 (xs_scale_depth's rule); otherwise z = float(D) / 1000.f,
+ *                  dx = (float(x) - cx) / fx,  dy = (float(y) - cy) / fy,  d[c] = (R[c][0] * dx + R[c][1] * dy) + R[c][2],
+ *                  P[c] = tc2v[c] + z * d[c]:  xs_render_views' p(t) at t = z.
+ * Outputs, each optional (NULL: not wanted; another output's bits do not depend on it); per point [N] / [N][3], per pixel dense
+ * [rows][cols] / [3][rows][cols]:
+ *   status    uint8    0 OUTSIDE: F(P) refused by its range test (a NaN or an infinite coordinate is outside);  1 UNSEEN: refused because the
+ *                      smallest weight among the needed corners < min_weight;  2 OK;  3 NO_DEPTH (the depth call only).
+ *   value     float32  F(P) exactly as xs_render_views defines it: voxel centres at (i + 0.5) voxel_size, only the corners on axes with
+ *                      f > 0 read.  The NaN 0x7fffffff where the status is not OK.  In units of the truncation distance, like the volume.
+ *   dvalue    float32  the same interpolation (the same corners, fractions and order) applied to the grad array; 0x7fffffff where not OK.
+ *   gradient  float32  G[c] / voxel_size,  G[c] = F(P + h e_c) - F(P - h e_c) (only coordinate c changes),  h = 0.5f * voxel_size:
+ *                      xs_render_views' G, in value per metre.  It is the derivative of the continuous interpolant averaged over one
+ *                      voxel, continuous across cell faces; its direction is the render's normal.  0x7fffffff in all three where the
+ *                      centre is not OK or any of the six samples is refused.
+ *   counts4   unsigned long long [4] = {outside, unseen, ok, no_depth}; zeroed by the call on the stream, then integer atomics, one per
+ *                      counter and workgroup.
+ * hipErrorInvalidValue, with nothing launched and every output untouched: n outside 1 .. 2^30; rows or cols outside 1 .. 4096; a null
+ * points, depth, pose, intrinsics, resolution or volume pointer; every output null; dvalue wanted without grad; an output pointer equal to
+ * the points (depth) pointer; a transform, pose or intrinsic entry that is not finite; fx or fy equal to 0; voxel_size not positive and
+ * finite; xs_render_views' pitch and resolution rules; opts->struct_bytes not sizeof(xs_sample_opts); a depth pitch shorter than a row or
+ * odd. */
+typedef struct xs_sample_opts {
+    unsigned struct_bytes;     /* sizeof(xs_sample_opts) */
+    int min_weight;            /* a voxel with a smaller weight is unseen; below 1 = 1 */
+} xs_sample_opts;
+int xs_tsdf_sample_points(long long n, const float *points3xN_dev, const float *xform12, const float *value, const int *weight, const float *grad,
+                          size_t vol_step, const int *res, float voxel_size, const xs_sample_opts *opts, unsigned char *status, float *value_out,
+                          float *dvalue, float *gradient3xN, unsigned long long *counts4, void *stream);
+int xs_tsdf_sample_depth(const uint16_t *depth_dev, size_t depth_step, int rows, int cols, const float *intr4, const float *Rc2v9, const float *tc2v3,
+                         const float *value, const int *weight, const float *grad, size_t vol_step, const int *res, float voxel_size,
+                         const xs_sample_opts *opts, unsigned char *status, float *value_out, float *dvalue, float *gradient3,
+                         unsigned long long *counts4, void *stream);
+
 /* ---- surface mesh (export; marching cubes with complex-step vertex derivatives) -------------------------------------------------------
  * No working counterpart in the reference (its extractMesh, ExtractPointCloud.cu:364-715, is never called).
  * Cube (x, y, z), x < X-1, y < Y-1, z in [z0, z1), is live when all 8 corners have weight >= min_weight and value < 0.99 and its corners

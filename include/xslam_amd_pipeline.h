@@ -489,6 +489,37 @@ int xs_kf_render_checkpoint(void *kf, const char *path, int views, const float *
                             const struct xs_render_opts *opts, float *depth, uint16_t *depth_u16, float *normal, unsigned char *shade, unsigned *counts4,
                             int on_device);
 
+/* The map asked at points the caller supplies, and at the pixels of a depth frame (xs_tsdf_sample_points and
+ * xs_tsdf_sample_depth in xslam_amd.h: the contract).  points: n x 3 floats in metres, 1 <= n <= 2^30, in a frame that T16 (a real 4 x 4,
+ * row-major; NULL: none, the points' bits are used as they are) takes to the sampled map's volume frame.  A voxel with a weight below
+ * min_weight (below 1: 1) is unseen.  The outputs, each optional (NULL: not wanted): status uint8 [n] (0 outside, 1 unseen, 2 ok, 3 no
+ * depth); value float [n], the trilinear value in units of the truncation distance, NaN where the status is not ok; dvalue float [n], the
+ * grad array interpolated the same way; gradient float [n][3] in value per metre; counts4 unsigned long long [4] = {outside, unseen, ok,
+ * no_depth}.  on_device bit 0: the points (the depth image) are device memory; bit 1: the outputs are, and are written in place.  The device
+ * is drained before and the stream after: the outputs are complete on return.  Nothing of any map or cache is modified.
+ * sample_points asks this instance's map; sample_volume, sample_map and sample_checkpoint a second map (the caller's arrays, src_grad only
+ * where dvalue is wanted; another instance; a checkpoint of a whole volume in either format), as the render calls obtain it.
+ * frame_residuals asks this map at the points of a depth image (u16 millimetres, depth_step bytes per row, 0: packed) seen from the
+ * camera2volume c2v (16 floats, or 32 with complex_poses = 1: the real parts) with intrinsics intr4 (NULL: the configuration's; rows, cols =
+ * 0, 0: its image size): the outputs are images [rows][cols], the gradient [3][rows][cols], and value is the frame's signed residual
+ * against the map at that pose.
+ * Return 1, 0 without a volume, -1 on bad arguments (what the kernels' calls refuse, a T16 entry that is not finite, a second map the
+ * merge would refuse) with nothing written, -2 in shard mode (a point's eight corners may straddle two ranks' slabs).
+ * xs_host_sample_compose: T16 = T_a2v16 T_p2a16 for points given in a frame P whose pose in frame A is T_p2a, A's in the volume T_a2v
+ * (affine, float64; host only); 0, -1 for a null pointer. */
+int xs_kf_sample_points(void *kf, long long n, const float *points, const double *T16, int min_weight, unsigned char *status, float *value, float *dvalue,
+                        float *gradient, unsigned long long *counts4, int on_device);
+int xs_kf_sample_volume(void *kf, const float *src_value, const int *src_weight, const float *src_grad, size_t src_step, const int *src_res, float src_voxel_size,
+                        float src_tranc_dist, long long n, const float *points, const double *T16, int min_weight, unsigned char *status, float *value,
+                        float *dvalue, float *gradient, unsigned long long *counts4, int on_device);
+int xs_kf_sample_map(void *kf, void *other_kf, long long n, const float *points, const double *T16, int min_weight, unsigned char *status, float *value,
+                     float *dvalue, float *gradient, unsigned long long *counts4, int on_device);
+int xs_kf_sample_checkpoint(void *kf, const char *path, long long n, const float *points, const double *T16, int min_weight, unsigned char *status, float *value,
+                            float *dvalue, float *gradient, unsigned long long *counts4, int on_device);
+int xs_kf_frame_residuals(void *kf, const unsigned short *depth, size_t depth_step, const float *c2v, int complex_poses, const float *intr4, int rows, int cols,
+                          int min_weight, unsigned char *status, float *value, float *dvalue, float *gradient, unsigned long long *counts4, int on_device);
+int xs_host_sample_compose(const double *T_a2v16, const double *T_p2a16, double *T16);
+
 /* ---- The reference's own call shape (x-slam_amd/host/reference_shape.hpp) ---------------------------------------------------------
  * The per-frame sequence of Experiments/test_xkinect_fusion/main.cpp:46-60 + KinectFusionReconstruction.cpp:147-332 over nothing but the
  * reference-signature launchers (bilateralFilter, pyrDown, createVMap / createNMap, estimateCombined per iteration, integrateTsdfVolume,

@@ -75,7 +75,15 @@ class RenderOpts(C.Structure):
                 ("shade_mode", C.c_int)]
 
 
+class SampleOpts(C.Structure):
+    """xs_sample_opts (include/xslam_amd.h)."""
+    _fields_ = [("struct_bytes", C.c_uint), ("min_weight", C.c_int)]
+
+
 _SIGS = {
+    "xs_tsdf_sample_points": (C.c_int, [C.c_longlong, _vp, _f32p, _vp, _vp, _vp, _sz, _i32p, C.c_float, C.POINTER(SampleOpts), _vp, _vp, _vp, _vp, _vp, _vp]),
+    "xs_tsdf_sample_depth": (C.c_int, [_vp, _sz, C.c_int, C.c_int, _f32p, _f32p, _f32p, _vp, _vp, _vp, _sz, _i32p, C.c_float, C.POINTER(SampleOpts), _vp, _vp, _vp,
+                                       _vp, _vp, _vp]),
     "xs_render_workspace_bytes": (_sz, [_i32p]),
     "xs_render_mask_build": (C.c_int, [_vp, _vp, _sz, _i32p, C.c_int, _vp, _vp]),
     "xs_render_views": (C.c_int, [C.c_int, _f32p, _f32p, _f32p, C.c_int, C.c_int, _vp, _vp, _sz, _i32p, C.c_float, C.POINTER(RenderOpts), _vp, _vp, _vp, _vp,
@@ -690,6 +698,52 @@ def render_views(Rc2vxP, tc2vxP, intr, rows, cols, value, weight, vol_step, res,
     check(_lib.xs_render_views(P, Rp, tp, kp, int(rows), int(cols), _ptr(value), _ptr(weight), vol_step, None if r is None else r.ctypes.data_as(_i32p),
                                voxel_size, C.byref(opts) if opts is not None else None, _ptr(workspace), _ptr(depth), _ptr(depth_u16), _ptr(normal),
                                _ptr(shade), _ptr(counts), _stream(stream)))
+
+
+SAMPLE_OUTSIDE, SAMPLE_UNSEEN, SAMPLE_OK, SAMPLE_NO_DEPTH = 0, 1, 2, 3   # the status byte of the sample calls, and the index into their counts
+SAMPLE_MAX_POINTS = 1 << 30
+
+
+def sample_opts(min_weight=1):
+    """An xs_sample_opts."""
+    o = SampleOpts()
+    o.struct_bytes = C.sizeof(SampleOpts)
+    o.min_weight = int(min_weight)
+    return o
+
+
+def _f32_or_null(x):
+    if x is None:
+        return None, None
+    a = np.ascontiguousarray(x, dtype=np.float32).reshape(-1)
+    return a, a.ctypes.data_as(_f32p)
+
+
+def sample_points(n, points, value, weight, vol_step, res, voxel_size, xform12=None, grad=None, opts=None, status=None, value_out=None, dvalue=None,
+                  gradient=None, counts=None, stream=None):
+    """xs_tsdf_sample_points: n points (device float32 [n, 3], metres; xform12 = row-major R then t takes them to the volume frame, None: as they
+    are) sampled in the volume in one launch into the device tensors that are given: status uint8 [n] (SAMPLE_*), value_out float32 [n], dvalue
+    float32 [n] (the grad array interpolated alike), gradient float32 [n, 3] (value per metre), counts uint64 [4] = {outside, unseen, ok,
+    no_depth}.  opts: sample_opts(...) or None.  A None among the host arrays goes through as a null pointer."""
+    m, mp = _f32_or_null(xform12)
+    r = None if res is None else _ia(res, 3)
+    check(_lib.xs_tsdf_sample_points(int(n), _ptr(points), mp, _ptr(value), _ptr(weight), _ptr(grad), vol_step, None if r is None else r.ctypes.data_as(_i32p),
+                                     voxel_size, C.byref(opts) if opts is not None else None, _ptr(status), _ptr(value_out), _ptr(dvalue), _ptr(gradient),
+                                     _ptr(counts), _stream(stream)))
+
+
+def sample_depth(depth, depth_step, rows, cols, intr, Rc2v, tc2v, value, weight, vol_step, res, voxel_size, grad=None, opts=None, status=None, value_out=None,
+                 dvalue=None, gradient=None, counts=None, stream=None):
+    """xs_tsdf_sample_depth: sample_points at the points of a depth image's pixels (device u16 millimetres, depth_step bytes per row) seen from the
+    real camera-to-volume pose Rc2v [3, 3], tc2v [3] with intrinsics intr (fx, fy, cx, cy): status and the floats are images [rows, cols], gradient
+    [3, rows, cols]; a pixel with a depth outside 200 .. 5000 is SAMPLE_NO_DEPTH."""
+    k, kp = _f32_or_null(intr)
+    R, Rp = _f32_or_null(Rc2v)
+    t, tp = _f32_or_null(tc2v)
+    r = None if res is None else _ia(res, 3)
+    check(_lib.xs_tsdf_sample_depth(_ptr(depth), depth_step, int(rows), int(cols), kp, Rp, tp, _ptr(value), _ptr(weight), _ptr(grad), vol_step,
+                                    None if r is None else r.ctypes.data_as(_i32p), voxel_size, C.byref(opts) if opts is not None else None, _ptr(status),
+                                    _ptr(value_out), _ptr(dvalue), _ptr(gradient), _ptr(counts), _stream(stream)))
 
 
 CLEARANCE_MAX_RADIUS, REACH_MAX_SEEDS, REACH_MAX_SNAP = 255, 64, 16   # XS_CLEARANCE_MAX_RADIUS, XS_REACH_MAX_SEEDS, XS_REACH_MAX_SNAP

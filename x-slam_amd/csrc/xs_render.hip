@@ -12,14 +12,15 @@
 //                        registers; with the cull a sample in a brick without a negative voxel is not read unless its neighbour turns out
 //                        negative (the mask word is read through L2 and kept in a register while the ray stays in the same 32 bricks).  The
 //                        crossing is refined after the loop, by every lane of the wave that found one at once, then the six samples of
-//                        the normal.  The trilinear sample restates xs_merge_sample.h's rule on the value array (DESIGN.md says why it is
-//                        not shared).  Four class counts per wave by ballot and popcount, one integer atomic each.
+//                        the normal.  The trilinear sample is xs_trilinear.h's, shared with xs_sample.hip (xs_merge_sample.h keeps its
+//                        own: DESIGN.md says why).  Four class counts per wave by ballot and popcount, one integer atomic each.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdio.h>
 #include <string.h>
 #include <vector>
 #include "xs_merge_sample.h"   // merge_res_ok
+#include "xs_trilinear.h"
 #include "../host/render_host.hpp"
 
 using namespace xs;
@@ -105,42 +106,11 @@ __device__ __forceinline__ int render_state(const RenderArgs &a, int x, int y, i
     return ST_VALUE;
 }
 
-// F(P) of the contract: xs_merge_sample.h's merge_sample<false> from its index g onwards, on the value array.  False where it is refused.
+// F(P) of the contract (xs_trilinear.h, shared with xs_sample.hip) on the value array.  False where it is refused.
 __device__ __forceinline__ bool render_trilinear(const RenderArgs &a, float p0, float p1, float p2, float &out) {
-    const float p[3] = {p0, p1, p2};
-    const int S[3] = {a.X, a.Y, a.Z};
-    int b[3];
-    float f[3];
-    bool need[3];
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        const float g = p[k] / a.voxel_size - 0.5f;
-        if (!(g >= 0.f && g <= (float)(S[k] - 1))) return false;
-        b[k] = __float2int_rd(g);
-        f[k] = g - (float)b[k];
-        need[k] = f[k] > 0.f;            // then g < S - 1 and b + 1 is inside the volume
-    }
-    const int needmask = (need[0] ? 1 : 0) | (need[1] ? 2 : 0) | (need[2] ? 4 : 0);
-    int ws = 0x7fffffff;
-#pragma unroll
-    for (int d = 0; d < 8; ++d)
-        if ((d & ~needmask) == 0) ws = min(ws, row_ptr(a.weight, a.step, a.Y * (b[2] + (d >> 2)) + b[1] + (d >> 1 & 1))[b[0] + (d & 1)]);
-    if (ws < a.min_weight) return false;
-    float v[8];
-#pragma unroll
-    for (int d = 0; d < 8; ++d) {
-        v[d] = 0.f;
-        if ((d & ~needmask) == 0) v[d] = row_ptr(a.value, a.step, a.Y * (b[2] + (d >> 2)) + b[1] + (d >> 1 & 1))[b[0] + (d & 1)];
-    }
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        const int stride = 1 << k;
-        const float fk = f[k], gk = 1.0f - fk;
-#pragma unroll
-        for (int d = 0; d < 8; d += 2 * stride) v[d] = need[k] ? v[d] * gk + v[d + stride] * fk : v[d];
-    }
-    out = v[0];
-    return true;
+    const TrilinearVolume vol = {a.value, a.weight, nullptr, a.step, a.X, a.Y, a.Z, a.voxel_size, a.min_weight};
+    float unused;
+    return trilinear_sample<false>(vol, p0, p1, p2, out, unused) == TRI_OK;
 }
 
 __global__ void __launch_bounds__(64) k_render_views(const RenderArgs a) {

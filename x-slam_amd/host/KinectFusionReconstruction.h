@@ -433,6 +433,24 @@ public:
     int RenderSecondMap(const xs_host::SecondMap &src, const float *c2v, int stride, int P, const float *intr4, int rows, int cols, const xs_render_opts *opts,
                         const RenderOutputs &out, int on_device);
 
+    // The map asked at points the caller supplies, and at the pixels of a depth frame (kf_sample.cpp; DESIGN.md section 4.29;
+    // xs_tsdf_sample_points and xs_tsdf_sample_depth in include/xslam_amd.h: the contract).  points: n x 3 float32 metres in a frame that T16 (a
+    // real 4 x 4, row-major; null: none, the points' bits as they are) takes to the sampled map's volume frame.  The outputs are the contract's
+    // arrays, each optional (null: not wanted).  on_device bit 0: the points (the depth image) are device memory, bit 1: the outputs are, and
+    // the call leaves them there without copying.  The device is drained, one launch run, and the stream drained again: the outputs are
+    // complete on return.  Nothing of either map or of any cache is modified, and no cache is needed.
+    // SamplePoints asks THIS map, SampleSecondMap another one (axes >= 1; its grad array only where dvalue is wanted).  FrameResiduals asks
+    // this map at the points of a depth frame (u16 millimetres, depth_step bytes per row, 0: packed) seen from camera2volume c2v (4 x 4 with
+    // `stride` floats per entry, as RenderViews takes it; intr4 null: the configuration's, rows, cols 0, 0: its image size): value is the
+    // frame's signed residual against the map in units of the truncation distance, images [rows][cols] and [3][rows][cols].
+    // All return 1, -2 in shard mode (a point's eight corners may straddle two ranks' z-slabs), 0 without a volume, -1 on bad arguments
+    // (whatever the kernels' calls refuse, a T16 entry that is not finite, a second map that is not taken).
+    struct SampleOutputs { unsigned char *status = nullptr; float *value = nullptr; float *dvalue = nullptr; float *gradient = nullptr; unsigned long long *counts = nullptr; };
+    int SamplePoints(const float *points, long long n, const double *T16, int min_weight, const SampleOutputs &out, int on_device);
+    int SampleSecondMap(const xs_host::SecondMap &src, const float *points, long long n, const double *T16, int min_weight, const SampleOutputs &out, int on_device);
+    int FrameResiduals(const unsigned short *depth, size_t depth_step, const float *c2v, int stride, const float *intr4, int rows, int cols, int min_weight,
+                       const SampleOutputs &out, int on_device);
+
     // counters of the last frame (synchronise the stream)
     long long lastUpdatedVoxels();
     long long lastRaycastHits();
@@ -539,6 +557,8 @@ private:
     // the views of one volume through xs_render_views, in chunks; `ws` holds a mask built for (res, the options' min_weight) unless the cull is off
     int RenderVolume(const float *value, const int *weight, size_t step, const int *res, float vs, void *ws, const float *c2v, int stride, int P, const float *intr4,
                      int rows, int cols, const xs_render_opts &opts, const RenderOutputs &out, int on_device);
+    // one xs_tsdf_sample_points launch over a volume described as a SecondMap (this map's included), with the staging of host points and outputs
+    int SampleVolume(const xs_host::SecondMap &vol, const float *points, long long n, const double *T16, int min_weight, const SampleOutputs &out, int on_device);
     DeviceArray2D<ushort> depth_ingest_d_;     // device copy of a host frame (ProcessFrameHost)
     ushort *ingest_pinned_[2] = {nullptr, nullptr};
     hipEvent_t ingest_done_[2] = {nullptr, nullptr};

@@ -8,6 +8,7 @@
 #include "merge_host.hpp"
 #include "newton_host.hpp"
 #include "pack_host.hpp"
+#include "sample_host.hpp"
 #include <cstring>
 #include <exception>
 #include <fstream>
@@ -654,6 +655,44 @@ int xs_kf_render_checkpoint(void *kf, const char *path, int views, const float *
     const int rc = ((KF *)kf)->OpenCheckpointMap(path, c);
     return rc != 1 ? rc : ((KF *)kf)->RenderSecondMap(c.map, c2v, complex_poses ? 2 : 1, views, intr4, rows, cols, opts,
                                                       render_outputs(depth, depth_u16, normal, shade, counts4), on_device);
+}
+static KF::SampleOutputs sample_outputs(unsigned char *status, float *value, float *dvalue, float *gradient, unsigned long long *counts4) {
+    KF::SampleOutputs o;
+    o.status = status; o.value = value; o.dvalue = dvalue; o.gradient = gradient; o.counts = counts4;
+    return o;
+}
+int xs_kf_sample_points(void *kf, long long n, const float *points, const double *T16, int min_weight, unsigned char *status, float *value, float *dvalue,
+                        float *gradient, unsigned long long *counts4, int on_device) {
+    return ((KF *)kf)->SamplePoints(points, n, T16, min_weight, sample_outputs(status, value, dvalue, gradient, counts4), on_device);
+}
+int xs_kf_sample_volume(void *kf, const float *src_value, const int *src_weight, const float *src_grad, size_t src_step, const int *src_res, float src_voxel_size,
+                        float src_tranc_dist, long long n, const float *points, const double *T16, int min_weight, unsigned char *status, float *value,
+                        float *dvalue, float *gradient, unsigned long long *counts4, int on_device) {
+    return ((KF *)kf)->SampleSecondMap(second_map(src_value, src_weight, src_grad, src_step, src_res, src_voxel_size, src_tranc_dist), points, n, T16, min_weight,
+                                       sample_outputs(status, value, dvalue, gradient, counts4), on_device);
+}
+int xs_kf_sample_map(void *kf, void *other_kf, long long n, const float *points, const double *T16, int min_weight, unsigned char *status, float *value,
+                     float *dvalue, float *gradient, unsigned long long *counts4, int on_device) {
+    xs_host::SecondMap m;
+    const int rc = ((KF *)kf)->OtherInstanceMap((KF *)other_kf, dvalue != nullptr, m);
+    return rc != 1 ? rc : ((KF *)kf)->SampleSecondMap(m, points, n, T16, min_weight, sample_outputs(status, value, dvalue, gradient, counts4), on_device);
+}
+int xs_kf_sample_checkpoint(void *kf, const char *path, long long n, const float *points, const double *T16, int min_weight, unsigned char *status, float *value,
+                            float *dvalue, float *gradient, unsigned long long *counts4, int on_device) {
+    if (!path) return -1;
+    KF::CheckpointMap c;
+    const int rc = ((KF *)kf)->OpenCheckpointMap(path, c);
+    return rc != 1 ? rc : ((KF *)kf)->SampleSecondMap(c.map, points, n, T16, min_weight, sample_outputs(status, value, dvalue, gradient, counts4), on_device);
+}
+int xs_kf_frame_residuals(void *kf, const unsigned short *depth, size_t depth_step, const float *c2v, int complex_poses, const float *intr4, int rows, int cols,
+                          int min_weight, unsigned char *status, float *value, float *dvalue, float *gradient, unsigned long long *counts4, int on_device) {
+    return ((KF *)kf)->FrameResiduals(depth, depth_step, c2v, complex_poses ? 2 : 1, intr4, rows, cols, min_weight,
+                                      sample_outputs(status, value, dvalue, gradient, counts4), on_device);
+}
+int xs_host_sample_compose(const double *T_a2v16, const double *T_p2a16, double *T16) {
+    if (!T_a2v16 || !T_p2a16 || !T16) return -1;
+    xs_host::sample_compose(T_a2v16, T_p2a16, T16);
+    return 0;
 }
 int xs_host_align_search_free(int n, const double *centroid_this3, const double *centroid_other3, double box_t, double *T16xN) {
     return xs_host::align_search_free(n, centroid_this3, centroid_other3, box_t, T16xN) ? 0 : -1;

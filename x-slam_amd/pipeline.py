@@ -36,7 +36,17 @@ _DIFF_TAIL = [C.c_int, C.c_float, C.c_float, C.c_int, C.c_ulonglong, C.c_int, C.
 # what the four render calls share behind their source: views, c2v, complex_poses, intr4, rows, cols, opts, five outputs, on_device
 _RENDER_TAIL = [C.c_int, _f32p, C.c_int, _f32p, C.c_int, C.c_int, C.POINTER(capi.RenderOpts), _vp, _vp, _vp, _vp, _vp, C.c_int]
 
+# what the five sample calls share behind their source: min_weight, five outputs, on_device
+_SAMPLE_TAIL = [C.c_int, _vp, _vp, _vp, _vp, _vp, C.c_int]
+_SAMPLE_POINTS = [C.c_longlong, _vp, _f64p]   # n, points, T16
+
 _SIGS = {
+    "xs_kf_sample_points": (C.c_int, [_vp] + _SAMPLE_POINTS + _SAMPLE_TAIL),
+    "xs_kf_sample_volume": (C.c_int, [_vp, _vp, _vp, _vp, _sz, _i32p, C.c_float, C.c_float] + _SAMPLE_POINTS + _SAMPLE_TAIL),
+    "xs_kf_sample_map": (C.c_int, [_vp, _vp] + _SAMPLE_POINTS + _SAMPLE_TAIL),
+    "xs_kf_sample_checkpoint": (C.c_int, [_vp, C.c_char_p] + _SAMPLE_POINTS + _SAMPLE_TAIL),
+    "xs_kf_frame_residuals": (C.c_int, [_vp, _vp, _sz, _f32p, C.c_int, _f32p, C.c_int, C.c_int] + _SAMPLE_TAIL),
+    "xs_host_sample_compose": (C.c_int, [_f64p, _f64p, _f64p]),
     "xs_kf_render_views": (C.c_int, [_vp] + _RENDER_TAIL),
     "xs_kf_render_volume": (C.c_int, [_vp, _vp, _vp, _sz, _i32p, C.c_float, C.c_float] + _RENDER_TAIL),
     "xs_kf_render_map": (C.c_int, [_vp, _vp] + _RENDER_TAIL),
@@ -404,6 +414,27 @@ class RenderedViews(collections.namedtuple("RenderedViews", "depth depth_u16 nor
     a hit), depth_u16 uint16 [P, rows, cols] (millimetres, what process_frame and relocalize take), normal float32 [P, 3, rows, cols] (volume
     frame, pointing into free space, NaN without one), shade uint8 [P, rows, cols] (headlight shading, 0 without a normal) and counts uint32
     [P, 4] = {hit, backface, rejected, none} rays.  An output that was not asked for is None."""
+
+
+class MapSamples(collections.namedtuple("MapSamples", "status value dvalue gradient counts")):
+    """What KinectFusion.sample returns for N points: status uint8 [N] (capi.SAMPLE_OUTSIDE 0, SAMPLE_UNSEEN 1, SAMPLE_OK 2), value float32 [N] (the
+    trilinear TSDF in units of the truncation distance, NaN where the status is not OK), dvalue float32 [N] (the grad volume interpolated the
+    same way), gradient float32 [N, 3] (value per metre, NaN where one of its six samples is refused) and counts uint64 [4] = {outside, unseen, ok,
+    no_depth} (int64 as a torch tensor).  An output that was not asked for is None."""
+
+
+class FrameResiduals(collections.namedtuple("FrameResiduals", "status value dvalue gradient counts")):
+    """What KinectFusion.frame_residuals returns: MapSamples' fields as images, status and the floats [rows, cols], gradient [3, rows, cols]; a pixel
+    without a usable depth has status capi.SAMPLE_NO_DEPTH (3)."""
+
+
+def sample_compose(T_a2v, T_p2a):
+    """T = T_a2v T_p2a (real 4 x 4, float64) for KinectFusion.sample: the points are in a frame P whose pose in frame A is T_p2a, and T_a2v takes A to
+    the volume (CPU)."""
+    a, b, out = _real44(T_a2v), _real44(T_p2a), np.zeros(16, np.float64)
+    if _lib.xs_host_sample_compose(a.ctypes.data_as(_f64p), b.ctypes.data_as(_f64p), out.ctypes.data_as(_f64p)) != 0:
+        raise ValueError("sample_compose: two 4 x 4 matrices are needed")
+    return out.reshape(4, 4)
 
 
 def save_view_pgm(path, shade):
@@ -1130,6 +1161,105 @@ class KinectFusion:
         """render_views of the map in a checkpoint file of a whole volume (save_checkpoint, dense or sparse), validated as merge_checkpoint does."""
         kw = {**dict(intr=None, size=None, t_near=0.2, t_far=5.0, step=None, min_weight=1, outputs=("depth", "normal", "shade"), cull=True, device=False), **kw}
         return self._render_call("xs_kf_render_checkpoint", (path.encode(),), c2vs, **kw)
+
+    _SAMPLE_OUTPUTS = ("status", "value", "dvalue", "gradient", "counts")
+
+    @classmethod
+    def _sample_buffers(cls, name, outputs, shapes, device):
+        """The output buffers of a sample call: (dict of arrays or tensors, dict of their addresses)."""
+        wanted = set(outputs)
+        if not wanted or not wanted <= set(cls._SAMPLE_OUTPUTS):
+            raise ValueError(f"{name}: outputs must name some of status, value, dvalue, gradient, counts")
+        dtypes = dict(status=np.uint8, value=np.float32, dvalue=np.float32, gradient=np.float32, counts=np.uint64)
+        out, ptr = {}, {}
+        for n in wanted:
+            if device:
+                import torch
+                dt = {np.uint8: torch.uint8, np.float32: torch.float32, np.uint64: torch.int64}[dtypes[n]]
+                out[n] = torch.empty(shapes[n], dtype=dt, device="cuda")
+                ptr[n] = out[n].data_ptr()
+            else:
+                out[n] = np.zeros(shapes[n], dtypes[n])
+                ptr[n] = out[n].ctypes.data
+        return out, ptr
+
+    def _sample_call(self, name, source, points, T, min_weight, outputs, device):
+        if hasattr(points, "data_ptr"):   # a torch tensor on the GPU
+            if not points.is_cuda or not points.is_contiguous() or points.dim() != 2 or points.shape[1] != 3 or points.element_size() != 4 or not points.is_floating_point():
+                raise ValueError(f"{name}: a torch points tensor must be contiguous float32 [N, 3] on the GPU")
+            n, pp, on_device, keep = int(points.shape[0]), points.data_ptr(), 1, points
+        else:
+            keep = np.ascontiguousarray(points, dtype=np.float32)
+            if keep.ndim != 2 or keep.shape[1] != 3:
+                raise ValueError(f"{name}: points must be [N, 3]")
+            n, pp, on_device = keep.shape[0], keep.ctypes.data, 0
+        if n < 1:
+            raise ValueError(f"{name}: at least one point is needed")
+        t = None if T is None else _real44(T)
+        out, ptr = self._sample_buffers(name, outputs, dict(status=(n,), value=(n,), dvalue=(n,), gradient=(n, 3), counts=(4,)), device)
+        rc = getattr(_lib, name)(self.h, *source, n, pp, None if t is None else t.ctypes.data_as(_f64p), int(min_weight), ptr.get("status"), ptr.get("value"),
+                                 ptr.get("dvalue"), ptr.get("gradient"), ptr.get("counts"), on_device | (2 if device else 0))
+        self._map_call(name, rc, "more than 2^30 points, T not finite, dvalue of a map without a grad array")
+        return MapSamples(*(out.get(f) for f in MapSamples._fields))
+
+    def sample(self, points, T=None, min_weight=1, outputs=("status", "value", "gradient"), device=False):
+        """The map asked at N points: what is the signed distance here, which way does it grow, has this place been seen.  points [N, 3] in metres,
+        a numpy array or a contiguous float32 torch tensor on the GPU, in a frame that T (real 4 x 4; None: they are in the volume frame already
+        and their bits are used as they are) takes to the volume frame.  Returns a MapSamples of the `outputs` asked for (status, value, dvalue,
+        gradient, counts): numpy arrays, or torch tensors on the GPU with device=True.  value is the trilinear interpolation of the stored TSDF
+        (the render's F, bit for bit), which is normalised by the truncation distance: value * tranc_dist() is the signed distance in metres
+        near the surface, positive in free space, and the field is TRUNCATED: farther than tranc_dist() from the surface it is +-1 and says
+        only which side the point is on, or the point is UNSEEN.  gradient is the central difference over one voxel, in value per metre: it
+        points into free space with a length of about 1 / tranc_dist() near the surface.  dvalue is the same interpolation of the run's
+        derivative volume (the CSFD seed's).  A voxel with a weight below min_weight is unseen.  XsError in shard mode, ValueError on bad
+        arguments."""
+        return self._sample_call("xs_kf_sample_points", (), points, T, min_weight, outputs, device)
+
+    def sample_map(self, other, points, T=None, min_weight=1, outputs=("status", "value", "gradient"), device=False):
+        """sample of the map of `other` (another KinectFusion of this process, which is only read); T takes the points to ITS volume frame."""
+        return self._sample_call("xs_kf_sample_map", (other.h,), points, T, min_weight, outputs, device)
+
+    def sample_checkpoint(self, path, points, T=None, min_weight=1, outputs=("status", "value", "gradient"), device=False):
+        """sample of the map in a checkpoint file of a whole volume (save_checkpoint, dense or sparse), validated as merge_checkpoint does."""
+        return self._sample_call("xs_kf_sample_checkpoint", (path.encode(),), points, T, min_weight, outputs, device)
+
+    def frame_residuals(self, depth, c2v, min_weight=1, outputs=("status", "value"), device=False, intr=None):
+        """A depth frame judged against the map before it is fused: every pixel's point (depth [rows, cols] u16 millimetres, a numpy array or a torch
+        tensor on the GPU; unprojected with intr, None: the configuration's, and placed by the camera2volume c2v [4, 4] or [4, 4, 2]) sampled in
+        the map.  Returns a FrameResiduals of images: value is the pixel's signed residual in units of the truncation distance (0 on the
+        surface the map holds; large where an object moved or the pose is off), status says why a pixel has none."""
+        m = np.ascontiguousarray(c2v, dtype=np.float32)
+        if m.shape not in ((4, 4), (4, 4, 2)):
+            raise ValueError("frame_residuals: c2v must be [4, 4] or [4, 4, 2]")
+        if hasattr(depth, "data_ptr"):
+            if not depth.is_cuda or depth.dim() != 2 or depth.element_size() != 2 or depth.stride(1) != 1:
+                raise ValueError("frame_residuals: a torch depth image must be 16-bit [rows, cols] on the GPU")
+            rows, cols, dp, step, on_device, keep = int(depth.shape[0]), int(depth.shape[1]), depth.data_ptr(), depth.stride(0) * 2, 1, depth
+        else:
+            keep = np.ascontiguousarray(depth, dtype=np.uint16)
+            if keep.ndim != 2:
+                raise ValueError("frame_residuals: depth must be [rows, cols]")
+            rows, cols, dp, step, on_device = keep.shape[0], keep.shape[1], keep.ctypes.data, keep.shape[1] * 2, 0
+        k = None if intr is None else np.ascontiguousarray(intr, dtype=np.float32).reshape(4)
+        name = "xs_kf_frame_residuals"
+        shape = (rows, cols)
+        out, ptr = self._sample_buffers(name, outputs, dict(status=shape, value=shape, dvalue=shape, gradient=(3,) + shape, counts=(4,)), device)
+        rc = _lib.xs_kf_frame_residuals(self.h, dp, step, m.reshape(-1).ctypes.data_as(_f32p), int(m.ndim == 3), None if k is None else k.ctypes.data_as(_f32p), rows, cols,
+                                        int(min_weight), ptr.get("status"), ptr.get("value"), ptr.get("dvalue"), ptr.get("gradient"), ptr.get("counts"),
+                                        on_device | (2 if device else 0))
+        self._map_call(name, rc, "an empty or oversized image, a pose or intrinsics that are not finite")
+        return FrameResiduals(*(out.get(f) for f in FrameResiduals._fields))
+
+    def surface_error(self, points, T=None, min_weight=1):
+        """How far a set of surface points (a ground-truth scan, another sensor's cloud) lies from the surface the map holds: a dict of the counts
+        outside, unseen and ok, and over the OK points mean_abs, rms and max_abs of d = value * tranc_dist() in metres (NaN without an OK point).
+        Float64 host arithmetic on sample's value output.  The field is truncated: a point farther than tranc_dist() from the surface
+        contributes tranc_dist()."""
+        s = self.sample(points, T=T, min_weight=min_weight, outputs=("status", "value", "counts"))
+        d = s.value[s.status == capi.SAMPLE_OK].astype(np.float64) * float(self.tranc_dist())
+        stats = dict(mean_abs=float(np.abs(d).mean()), rms=float(np.sqrt((d * d).mean())), max_abs=float(np.abs(d).max())) if d.size else \
+            dict(mean_abs=float("nan"), rms=float("nan"), max_abs=float("nan"))
+        return dict(outside=int(s.counts[0]), unseen=int(s.counts[1]), ok=int(s.counts[2]), **stats)
 
     def _diff_call(self, name, source, T, min_weight, lo, hi, cell_vox, min_size, masks, capacity):
         t = _real44(np.eye(4) if T is None else T)
