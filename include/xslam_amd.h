@@ -978,6 +978,45 @@ int xs_tsdf_sample_depth(const uint16_t *depth_dev, size_t depth_step, int rows,
                          const xs_sample_opts *opts, unsigned char *status, float *value_out, float *dvalue, float *gradient3,
                          unsigned long long *counts4, void *stream);
 
+/* ---- registering a point cloud to the volume: Gauss-Newton terms over the points (xs_register.hip) ---------------
+ * No counterpart in the reference.  The residual of a point p under a rigid transform is the map's value at the transformed point, its
+ * Jacobian the map's gradient there: the 29 sums of the normal equations for `transforms` (1 .. XS_REGISTER_MAX_TRANSFORMS) transforms over
+ * the same n points (1 .. 2^30) in one launch.  points3xN_dev: xs_tsdf_sample_points' device array.  xform12xN: host array, never null,
+ * transform m's row-major R, then t at + 12 m; it is copied into the launch's arguments and may be reused when the call returns.  The volume
+ * (value, weight, one pitch vol_step in bytes, rows in (z * Y + y) order, the pointers at plane 0) is only read; byte offsets row * vol_step
+ * are computed in 64 bits.  Transform m's 29 doubles land at out29xN_dev + 29 m, in the layout of xs_tsdf_gauss_newton_terms; nothing else
+ * but the workspace is written.
+ *
+ * Transform m, point p; every float operation is one IEEE float32 operation in the order written (the library is built -ffp-contract=off):
+ *   1. P[c] = ((R[c][0] * p[0] + R[c][1] * p[1]) + R[c][2] * p[2]) + t[c]:  xs_tsdf_sample_points' transformed point.
+ *   2. (status, r, g[3]) = the status, value and gradient xs_tsdf_sample_points defines at P with this min_weight and no grad array: the bytes
+ *      that call would write for the point.
+ *   3. The point is DROPPED if its status is not OK;  or the gradient is refused (one of the six samples at +- half a voxel is not OK: the
+ *      three gradient words are the NaN 0x7fffffff);  or fabsf(r) > max_residual.
+ *   4. J[0] = g[0], J[1] = g[1], J[2] = g[2];  J[3] = P[1] * g[2] - P[2] * g[1];  J[4] = P[2] * g[0] - P[0] * g[2];
+ *      J[5] = P[0] * g[1] - P[1] * g[0]  (two products and one subtraction each):  the derivative of F(exp(delta) T p) at delta = 0 for
+ *      delta = (translation, rotation), the order of se3Exp and of xs_host_align_step.
+ *   5. A kept point adds, in double: double(J[j]) * double(J[k]) (j <= k, row-major) to [0, 21), double(J[k]) * double(r) to [21, 27),
+ *      double(r) * double(r) to [27], 1 to [28].  Every product of two float32 factors is exact in double.
+ * No seed and no step h: the sums are the normal equations as they stand (xs_host_align_step takes them unscaled).
+ * Order (xs_tsdf_align_terms' with "band entry" read as "point"): point i belongs to chunk i / 64, lane i % 64; wave w of workgroup (b, m)
+ * takes chunks 4 b + w, + 4 nblocks, ... with nblocks = clamp(ceil(ceil(n / 64) / 4), 1, 4096), and adds its points' terms to 29 double sums
+ * per lane in that order; the lanes, the four waves and the workgroups' records are then added in a fixed order with one arrival ticket per
+ * transform.  The order is a function of n alone: two launches on the same inputs give equal bytes, and transform m's 29 doubles depend on
+ * nothing but m's twelve floats, the points and the volume — not on m, on `transforms` or on the other transforms.  No floating-point
+ * atomics.  A transform that keeps no point yields 29 zeros.
+ * Workspace: xs_tsdf_register_workspace_bytes(transforms) bytes (0 for transforms outside 1 .. XS_REGISTER_MAX_TRANSFORMS): one arrival ticket
+ * per transform in its first 256 bytes, then the records.  Zero the first 256 bytes ONCE after allocation (xs_tsdf_reduce_workspace_init);
+ * every launch leaves them zero.  One launch at a time per workspace.  No synchronisation.
+ * hipErrorInvalidValue, with nothing launched and nothing written: transforms outside 1 .. 32; n outside 1 .. 2^30; a null points,
+ * transforms, value, weight, resolution, workspace or output pointer; xs_tsdf_sample_points' resolution, pitch and voxel-size rules;
+ * min_weight < 1; max_residual not finite or <= 0; a transform entry that is not finite. */
+#define XS_REGISTER_MAX_TRANSFORMS 32
+size_t xs_tsdf_register_workspace_bytes(int transforms);
+int xs_tsdf_register_terms(int transforms, long long n, const float *points3xN_dev, const float *xform12xN, const float *value, const int *weight,
+                           size_t vol_step, const int *res, float voxel_size, int min_weight, float max_residual, void *workspace,
+                           double *out29xN_dev, void *stream);
+
 /* ---- surface mesh (export; marching cubes with complex-step vertex derivatives) -------------------------------------------------------
  * No working counterpart in the reference (its extractMesh, ExtractPointCloud.cu:364-715, is never called).
  * Cube (x, y, z), x < X-1, y < Y-1, z in [z0, z1), is live when all 8 corners have weight >= min_weight and value < 0.99 and its corners

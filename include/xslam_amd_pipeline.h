@@ -520,6 +520,30 @@ int xs_kf_frame_residuals(void *kf, const unsigned short *depth, size_t depth_st
                           int min_weight, unsigned char *status, float *value, float *dvalue, float *gradient, unsigned long long *counts4, int on_device);
 int xs_host_sample_compose(const double *T_a2v16, const double *T_p2a16, double *T16);
 
+/* A point cloud registered to a map (xs_tsdf_register_terms in xslam_amd.h: the contract).  Damped Gauss-Newton on
+ * the residual "the map's value at T p" over the n points (n x 3 floats in metres, 1 <= n <= 2^30; on_device bit 0: device memory): the
+ * transform T (cloud frame to the map's volume frame) that puts the cloud on the map's surface.  T16xN: N >= 1 starting transforms, each a
+ * real 4 x 4, row-major; every start runs `iterations` damped steps ((J^T J + damping diag(J^T J)) delta = -J^T r, T <- exp(delta) T in
+ * float64, each pass's transforms rounded once to float32 for the kernel) and one final pass that only reports the loss, the starts in one
+ * launch per pass.  A point takes part where the map's value and its gradient exist at T p with min_weight and |value| <= max_residual.
+ * T16_out: the start that ended ok (at least six points on every pass, the final loss pass included, and a positive definite system on every
+ * step) with the highest S = count - sum r^2 (ties: the lower index): xs_kf_align_map's rule, iterations = 0 included.
+ * report7 = {the winner's index, its count, its sum r^2, its mean loss, launches run, starts that ended ok, n}.  loss_history (optional,
+ * iterations + 1 doubles): the winner's mean loss per pass.
+ * register_points asks this instance's map; register_map another instance's; register_checkpoint a checkpoint of a whole volume in either
+ * format.  The device is drained before and the stream after.  Nothing of any map or cache is modified; xs_kf_volume_generation stays.
+ * Return codes: xs_kf_align_map's: 1; 0 without a volume or when no start ended ok (T16_out and loss_history untouched, report7[0] = -1);
+ * -1 on bad arguments (n outside 1 .. 2^30, a null pointer, N < 1, iterations < 0, min_weight < 1, damping negative or not finite,
+ * max_residual <= 0 or not finite, a start that is not finite in float32, a second map the merge would refuse); -2 in shard mode.
+ * xs_host_register_step: xs_host_align_step on the kernel's sums as they stand (no scaling); 0, or -1 with T16 untouched.  CPU only. */
+int xs_kf_register_points(void *kf, long long n, const float *points, int on_device, const double *T16xN, int N, int iterations, double damping,
+                          int min_weight, float max_residual, double *T16_out, double *report7, double *loss_history);
+int xs_kf_register_map(void *kf, void *other_kf, long long n, const float *points, int on_device, const double *T16xN, int N, int iterations,
+                       double damping, int min_weight, float max_residual, double *T16_out, double *report7, double *loss_history);
+int xs_kf_register_checkpoint(void *kf, const char *path, long long n, const float *points, int on_device, const double *T16xN, int N, int iterations,
+                              double damping, int min_weight, float max_residual, double *T16_out, double *report7, double *loss_history);
+int xs_host_register_step(const double *s29, double damping, double *T16);
+
 /* ---- The reference's own call shape (x-slam_amd/host/reference_shape.hpp) ---------------------------------------------------------
  * The per-frame sequence of Experiments/test_xkinect_fusion/main.cpp:46-60 + KinectFusionReconstruction.cpp:147-332 over nothing but the
  * reference-signature launchers (bilateralFilter, pyrDown, createVMap / createNMap, estimateCombined per iteration, integrateTsdfVolume,

@@ -205,6 +205,8 @@ _SIGS = {
     "xs_tsdf_align_terms": (C.c_int, [C.c_int, C.POINTER(BandIndex), _vp, _vp, _sz, _i32p, _f32p, C.c_int, C.c_float, _vp, _vp, _vp]),
     "xs_tsdf_score_transforms_workspace_bytes": (_sz, [C.c_int]),
     "xs_tsdf_score_transforms": (C.c_int, [C.c_int, C.POINTER(BandIndex), C.c_int, _vp, _vp, _sz, _i32p, _f32p, C.c_int, C.c_float, _vp, _vp, _vp]),
+    "xs_tsdf_register_workspace_bytes": (_sz, [C.c_int]),
+    "xs_tsdf_register_terms": (C.c_int, [C.c_int, C.c_longlong, _vp, _f32p, _vp, _vp, _sz, _i32p, C.c_float, C.c_int, C.c_float, _vp, _vp, _vp]),
     "xs_mesh_workspace_bytes": (_sz, [_i32p, C.POINTER(MeshOpts)]),
     "xs_extract_mesh": (C.c_int, [_vp, _vp, _vp, _sz, _i32p, C.c_float, C.POINTER(MeshOpts), _vp, _vp, _vp, _vp, _sz, _vp, _sz, _vp,
                                   C.POINTER(_sz), C.POINTER(_sz), _vp]),
@@ -1098,6 +1100,30 @@ def tsdf_align_terms(index, src_value, src_weight, src_step, src_res, maps, min_
     s = _ia(src_res, 3)
     check(_lib.xs_tsdf_align_terms(m.size // 144, C.byref(index), _ptr(src_value), _ptr(src_weight), src_step, s.ctypes.data_as(_i32p), m.ctypes.data_as(_f32p),
                                    int(min_weight), float(max_residual), _ptr(workspace), _ptr(out29xN), _stream(stream)))
+
+
+REGISTER_MAX_TRANSFORMS = 32   # XS_REGISTER_MAX_TRANSFORMS
+
+
+def register_workspace_bytes(transforms):
+    """xs_tsdf_register_workspace_bytes (host only): tickets and records for up to `transforms` transforms; 0 outside 1 .. 32.  Zero its first 256
+    bytes once (tsdf_reduce_workspace_init)."""
+    return int(_lib.xs_tsdf_register_workspace_bytes(int(transforms)))
+
+
+def register_terms(n, points, xforms, value, weight, vol_step, res, voxel_size, min_weight, max_residual, workspace, out29xN, transforms=None, stream=None):
+    """xs_tsdf_register_terms: the 29 Gauss-Newton sums {J^T J upper triangle, J^T r, sum r^2, count} of N transforms xforms [N, 12] float32
+    (row-major R, then t: cloud frame to volume frame) over n points (device float32 [n, 3], metres) against a volume (device tensors or
+    addresses of plane 0) in one launch; transform m's sums land at out29xN[29 m : 29 m + 29] (float64 device tensor).  transforms: N, where it
+    is not to be taken from xforms.  A None among the arrays goes through as a null pointer.  No synchronisation."""
+    m = None if xforms is None else np.ascontiguousarray(xforms, dtype=np.float32).reshape(-1)
+    if transforms is None:
+        assert m is not None and m.size % 12 == 0
+        transforms = m.size // 12
+    r = None if res is None else _ia(res, 3)
+    check(_lib.xs_tsdf_register_terms(int(transforms), int(n), _ptr(points), None if m is None else m.ctypes.data_as(_f32p), _ptr(value), _ptr(weight), vol_step,
+                                      None if r is None else r.ctypes.data_as(_i32p), float(voxel_size), int(min_weight), float(max_residual), _ptr(workspace),
+                                      _ptr(out29xN), _stream(stream)))
 
 
 ALIGN_SCORE_MAX_TRANSFORMS = 4096   # XS_ALIGN_SCORE_MAX_TRANSFORMS

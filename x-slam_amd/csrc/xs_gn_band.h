@@ -2,7 +2,8 @@
 // record fold (registers -> wave -> LDS -> one record per workgroup -> the last workgroup adds the records in index order), the walk that
 // deals the band voxels (gt != 0, |gt| <= 0.95) of a slab out to the lanes, the six-pose CSFD residual of the Gauss-Newton pass, the
 // dual-complex squared residual of the Hessian kernels and the real-valued one of the loss kernels.
-// Included by exactly those two files, and by xs_align.hip for the record fold and the wave's float tree alone.
+// Included by exactly those two files, by xs_align.hip for the record fold and the wave's float tree alone, and by xs_register.hip for the
+// record fold alone.
 #pragma once
 #include <type_traits>
 #include "xs_device.h"

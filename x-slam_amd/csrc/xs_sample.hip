@@ -3,9 +3,9 @@
 //
 // The contract is in include/xslam_amd.h (xs_tsdf_sample_points, xs_tsdf_sample_depth), operation by operation; what the calls refuse is
 // ../host/sample_host.hpp's, shared with the orchestrator and the host selftest.  F(P) is xs_trilinear.h's, shared with xs_render.hip.
-//   sample_at             the per-point device function: the centre sample (with the grad array beside it where dvalue is wanted), then, where a
-//                         gradient is wanted and the centre is OK, the six samples at +- half a voxel.  Seven evaluations of up to eight
-//                         corners each, all gathers; nothing is kept between them.
+//   sample_at             the per-point device function, in xs_sample_at.h (xs_register.hip shares it): the centre sample (with the grad array
+//                         beside it where dvalue is wanted), then, where a gradient is wanted and the centre is OK, the six samples at +- half a
+//                         voxel.  Seven evaluations of up to eight corners each, all gathers; nothing is kept between them.
 //   k_sample_points       lane = point, wave = workgroup = 64 consecutive points: the three coordinates are 12-byte strided loads, the outputs
 //                         coalesced stores.  The transform arrives in the kernel arguments (scalar registers).
 //   k_sample_depth        lane = pixel, wave = workgroup = 64 consecutive pixels of one image row (blockIdx.y).
@@ -14,7 +14,7 @@
 #include <math.h>
 #include <stdio.h>
 #include <string.h>
-#include "xs_trilinear.h"
+#include "xs_sample_at.h"
 #include "../../include/xslam_amd.h"
 #include "../host/sample_host.hpp"
 
@@ -26,32 +26,6 @@ static_assert(TRI_OUTSIDE == SAMPLE_OUTSIDE && TRI_UNSEEN == SAMPLE_UNSEEN && TR
 struct SampleOut {
     unsigned char *status; float *value; float *dvalue; float *gradient; unsigned long long *counts;
 };
-
-struct SampleResult { int status; float value, dvalue, grad[3]; };
-
-// every output of one point P; the NaN 0x7fffffff wherever the contract says so
-template <bool SECOND>
-__device__ __forceinline__ void sample_at(const TrilinearVolume &vol, bool want_gradient, float p0, float p1, float p2, SampleResult &r) {
-    r.value = qnan_f(); r.dvalue = qnan_f(); r.grad[0] = r.grad[1] = r.grad[2] = qnan_f();
-    float v = 0.f, q = 0.f;
-    r.status = trilinear_sample<SECOND>(vol, p0, p1, p2, v, q);
-    if (r.status != TRI_OK) return;
-    r.value = v;
-    if (SECOND) r.dvalue = q;
-    if (!want_gradient) return;
-    const float h = 0.5f * vol.voxel_size;
-    float G[3] = {0.f, 0.f, 0.f};
-    bool ok = true;
-#pragma unroll 1
-    for (int c = 0; c < 3 && ok; ++c) {
-        float Fp = 0.f, Fm = 0.f, unused;
-        ok = trilinear_sample<false>(vol, c == 0 ? p0 + h : p0, c == 1 ? p1 + h : p1, c == 2 ? p2 + h : p2, Fp, unused) == TRI_OK &&
-             trilinear_sample<false>(vol, c == 0 ? p0 - h : p0, c == 1 ? p1 - h : p1, c == 2 ? p2 - h : p2, Fm, unused) == TRI_OK;
-        const float g = Fp - Fm;
-        if (c == 0) G[0] = g; else if (c == 1) G[1] = g; else G[2] = g;
-    }
-    if (ok) { r.grad[0] = G[0] / vol.voxel_size; r.grad[1] = G[1] / vol.voxel_size; r.grad[2] = G[2] / vol.voxel_size; }
-}
 
 __device__ __forceinline__ void sample_dispatch(const TrilinearVolume &vol, bool want_dvalue, bool want_gradient, float p0, float p1, float p2, SampleResult &r) {
     if (want_dvalue) sample_at<true>(vol, want_gradient, p0, p1, p2, r);     // (uniform over the launch)

@@ -451,6 +451,18 @@ public:
     int FrameResiduals(const unsigned short *depth, size_t depth_step, const float *c2v, int stride, const float *intr4, int rows, int cols, int min_weight,
                        const SampleOutputs &out, int on_device);
 
+    // A point cloud registered to a map (kf_register.cpp; xs_tsdf_register_terms in include/xslam_amd.h: the contract;
+    // register_host.hpp: the host's side).  points: n x 3 float32 metres (on_device bit 0: device memory) in a frame that each of the N starts
+    // T16xN (real 4 x 4, row-major) takes to the map's volume frame.  The starts run through gn_batch_loop: per pass one
+    // xs_tsdf_register_terms launch over the starts still active and one fetch of their sums, then register_step on each.  The winner, the
+    // "ended ok" rule, iterations = 0 and the return codes are AlignVolume's; report7 = {its index, its count, its sum r^2, its mean loss,
+    // launches run, starts that ended ok, n}.  The device is drained before and the stream after.  Nothing of any map or cache is modified.
+    // RegisterPoints asks THIS map, RegisterSecondMap another one (axes >= 1, no grad array needed).
+    int RegisterPoints(const float *points, long long n, int on_device, const double *T16xN, int N, int iterations, double damping, int min_weight,
+                       float max_residual, double *T16_out, double report[7], std::vector<double> *loss_history);
+    int RegisterSecondMap(const xs_host::SecondMap &src, const float *points, long long n, int on_device, const double *T16xN, int N, int iterations,
+                          double damping, int min_weight, float max_residual, double *T16_out, double report[7], std::vector<double> *loss_history);
+
     // counters of the last frame (synchronise the stream)
     long long lastUpdatedVoxels();
     long long lastRaycastHits();
@@ -509,6 +521,8 @@ private:
         DeviceArray<double> align_sums;            // XS_ALIGN_MAX_TRANSFORMS x 29
         DeviceArray<unsigned char> ascore_ws;      // xs_tsdf_score_transforms_workspace_bytes(XS_ALIGN_SCORE_MAX_TRANSFORMS)
         DeviceArray<double> ascore_sums;           // XS_ALIGN_SCORE_MAX_TRANSFORMS x 2
+        DeviceArray<unsigned char> register_ws;    // xs_tsdf_register_workspace_bytes(XS_REGISTER_MAX_TRANSFORMS)
+        DeviceArray<double> register_sums;         // XS_REGISTER_MAX_TRANSFORMS x 29
     } reloc_;
     const float *GaussNewtonDenseView();       // the owned planes as the dense array the Gauss-Newton kernels index (packed into gn_dense when pitched)
     void BandIndexPrepare();                   // (re)builds the band index when the volume changed since it was built
@@ -559,6 +573,9 @@ private:
                      int rows, int cols, const xs_render_opts &opts, const RenderOutputs &out, int on_device);
     // one xs_tsdf_sample_points launch over a volume described as a SecondMap (this map's included), with the staging of host points and outputs
     int SampleVolume(const xs_host::SecondMap &vol, const float *points, long long n, const double *T16, int min_weight, const SampleOutputs &out, int on_device);
+    // the registration loop over a volume described as a SecondMap (this map's included), with the staging of host points
+    int RegisterVolume(const xs_host::SecondMap &vol, const float *points, long long n, int on_device, const double *T16xN, int N, int iterations, double damping,
+                       int min_weight, float max_residual, double *T16_out, double report[7], std::vector<double> *loss_history);
     DeviceArray2D<ushort> depth_ingest_d_;     // device copy of a host frame (ProcessFrameHost)
     ushort *ingest_pinned_[2] = {nullptr, nullptr};
     hipEvent_t ingest_done_[2] = {nullptr, nullptr};

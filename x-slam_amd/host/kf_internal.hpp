@@ -1,6 +1,6 @@
 // kf_internal.hpp — what more than one translation unit of the orchestrator needs and no caller of the class does
 // (KinectFusionReconstruction.cpp: lifecycle and frame path; kf_relocalize.cpp; kf_planning.cpp; kf_export.cpp: point cloud, mesh, counters, raw
-// volume; kf_checkpoint.cpp: saving, reading and restoring checkpoints; kf_second_map.cpp: the calls that take a second map; kf_reintegrate.cpp: frames taken out and fused again; kf_render.cpp: views of a map; kf_sample.cpp: the map asked at the caller's points).
+// volume; kf_checkpoint.cpp: saving, reading and restoring checkpoints; kf_second_map.cpp: the calls that take a second map; kf_reintegrate.cpp: frames taken out and fused again; kf_render.cpp: views of a map; kf_sample.cpp: the map asked at the caller's points; kf_register.cpp: a point cloud registered to a map).
 #pragma once
 #include "KinectFusionReconstruction.h"
 #include "pack_host.hpp"

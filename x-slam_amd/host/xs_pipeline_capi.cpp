@@ -8,6 +8,7 @@
 #include "merge_host.hpp"
 #include "newton_host.hpp"
 #include "pack_host.hpp"
+#include "register_host.hpp"
 #include "sample_host.hpp"
 #include <cstring>
 #include <exception>
@@ -694,6 +695,35 @@ int xs_host_sample_compose(const double *T_a2v16, const double *T_p2a16, double 
     xs_host::sample_compose(T_a2v16, T_p2a16, T16);
     return 0;
 }
+static int register_call(KF *k, const xs_host::SecondMap *m, long long n, const float *points, int on_device, const double *T16xN, int N, int iterations,
+                         double damping, int min_weight, float max_residual, double *T16_out, double *report7, double *loss_history) {
+    std::vector<double> history;
+    std::vector<double> *h = loss_history ? &history : nullptr;
+    const int rc = m ? k->RegisterSecondMap(*m, points, n, on_device, T16xN, N, iterations, damping, min_weight, max_residual, T16_out, report7, h)
+                     : k->RegisterPoints(points, n, on_device, T16xN, N, iterations, damping, min_weight, max_residual, T16_out, report7, h);
+    if (loss_history) std::copy(history.begin(), history.end(), loss_history);   // at most iterations + 1 entries
+    return rc;
+}
+int xs_kf_register_points(void *kf, long long n, const float *points, int on_device, const double *T16xN, int N, int iterations, double damping,
+                          int min_weight, float max_residual, double *T16_out, double *report7, double *loss_history) {
+    return register_call((KF *)kf, nullptr, n, points, on_device, T16xN, N, iterations, damping, min_weight, max_residual, T16_out, report7, loss_history);
+}
+int xs_kf_register_map(void *kf, void *other_kf, long long n, const float *points, int on_device, const double *T16xN, int N, int iterations,
+                       double damping, int min_weight, float max_residual, double *T16_out, double *report7, double *loss_history) {
+    xs_host::register_report_clear(report7);
+    xs_host::SecondMap m;
+    const int rc = ((KF *)kf)->OtherInstanceMap((KF *)other_kf, false, m);
+    return rc != 1 ? rc : register_call((KF *)kf, &m, n, points, on_device, T16xN, N, iterations, damping, min_weight, max_residual, T16_out, report7, loss_history);
+}
+int xs_kf_register_checkpoint(void *kf, const char *path, long long n, const float *points, int on_device, const double *T16xN, int N, int iterations,
+                              double damping, int min_weight, float max_residual, double *T16_out, double *report7, double *loss_history) {
+    if (!path) return -1;
+    xs_host::register_report_clear(report7);
+    KF::CheckpointMap c;
+    const int rc = ((KF *)kf)->OpenCheckpointMap(path, c);
+    return rc != 1 ? rc : register_call((KF *)kf, &c.map, n, points, on_device, T16xN, N, iterations, damping, min_weight, max_residual, T16_out, report7, loss_history);
+}
+int xs_host_register_step(const double *s29, double damping, double *T16) { return xs_host::register_step(s29, damping, T16) ? 0 : -1; }
 int xs_host_align_search_free(int n, const double *centroid_this3, const double *centroid_other3, double box_t, double *T16xN) {
     return xs_host::align_search_free(n, centroid_this3, centroid_other3, box_t, T16xN) ? 0 : -1;
 }

@@ -40,7 +40,14 @@ _RENDER_TAIL = [C.c_int, _f32p, C.c_int, _f32p, C.c_int, C.c_int, C.POINTER(capi
 _SAMPLE_TAIL = [C.c_int, _vp, _vp, _vp, _vp, _vp, C.c_int]
 _SAMPLE_POINTS = [C.c_longlong, _vp, _f64p]   # n, points, T16
 
+# what the three register calls share behind their source: n, points, on_device, T16xN, N, iterations, damping, min_weight, max_residual, T16_out, report7, history
+_REGISTER_TAIL = [C.c_longlong, _vp, C.c_int, _f64p, C.c_int, C.c_int, C.c_double, C.c_int, C.c_float, _f64p, _f64p, _f64p]
+
 _SIGS = {
+    "xs_kf_register_points": (C.c_int, [_vp] + _REGISTER_TAIL),
+    "xs_kf_register_map": (C.c_int, [_vp, _vp] + _REGISTER_TAIL),
+    "xs_kf_register_checkpoint": (C.c_int, [_vp, C.c_char_p] + _REGISTER_TAIL),
+    "xs_host_register_step": (C.c_int, [_f64p, C.c_double, _f64p]),
     "xs_kf_sample_points": (C.c_int, [_vp] + _SAMPLE_POINTS + _SAMPLE_TAIL),
     "xs_kf_sample_volume": (C.c_int, [_vp, _vp, _vp, _vp, _sz, _i32p, C.c_float, C.c_float] + _SAMPLE_POINTS + _SAMPLE_TAIL),
     "xs_kf_sample_map": (C.c_int, [_vp, _vp] + _SAMPLE_POINTS + _SAMPLE_TAIL),
@@ -272,6 +279,16 @@ def align_step(s29, damping, T):
     s = np.ascontiguousarray(s29, dtype=np.float64).reshape(29)
     t = _real44(T).copy()
     rc = _lib.xs_host_align_step(s.ctypes.data_as(_f64p), float(damping), t.ctypes.data_as(_f64p))
+    return rc == 0, t
+
+
+def register_step(s29, damping, T):
+    """One damped Gauss-Newton step on the 29 sums of capi.register_terms as they stand (no scaling): (taken, T [4, 4] float64) with
+    T <- exp(delta) T, delta = (translation, rotation); not taken (T unchanged) when count < 6 or A + damping diag(A) is not positive
+    definite (CPU)."""
+    s = np.ascontiguousarray(s29, dtype=np.float64).reshape(29)
+    t = _real44(T).copy()
+    rc = _lib.xs_host_register_step(s.ctypes.data_as(_f64p), float(damping), t.ctypes.data_as(_f64p))
     return rc == 0, t
 
 
@@ -1323,6 +1340,51 @@ class KinectFusion:
         """align_map with the other map read from a checkpoint file of a whole volume (save_checkpoint, dense or sparse: either format is accepted), validated as merge_checkpoint does.
         Intended use: kf.merge_checkpoint(path, kf.align_checkpoint(path, T_guess)[1])."""
         return self._align_call("xs_kf_align_checkpoint", path.encode(), T0, iterations, damping, min_weight, max_residual)
+
+    def _register_call(self, name, source, points, T0, iterations, damping, min_weight, max_residual):
+        if hasattr(points, "data_ptr"):   # a torch tensor on the GPU
+            if not points.is_cuda or not points.is_contiguous() or points.dim() != 2 or points.shape[1] != 3 or points.element_size() != 4 or not points.is_floating_point():
+                raise ValueError(f"{name}: a torch points tensor must be contiguous float32 [N, 3] on the GPU")
+            n, pp, on_device, keep = int(points.shape[0]), points.data_ptr(), 1, points
+        else:
+            keep = np.ascontiguousarray(points, dtype=np.float32)
+            if keep.ndim != 2 or keep.shape[1] != 3:
+                raise ValueError(f"{name}: points must be [N, 3]")
+            n, pp, on_device = keep.shape[0], keep.ctypes.data, 0
+        if n < 1:
+            raise ValueError(f"{name}: at least one point is needed")
+        t = np.asarray(np.eye(4) if T0 is None else T0, dtype=np.float64)
+        t = np.ascontiguousarray(t.reshape(-1, 4, 4))
+        iterations = int(iterations)
+        out, report, hist = np.zeros((4, 4), np.float64), np.zeros(7, np.float64), np.zeros(max(iterations, 0) + 1, np.float64)
+        rc = getattr(_lib, name)(self.h, *source, n, pp, on_device, t.ctypes.data_as(_f64p), t.shape[0], iterations, float(damping), int(min_weight),
+                                 float(max_residual), out.ctypes.data_as(_f64p), report.ctypes.data_as(_f64p), hist.ctypes.data_as(_f64p))
+        self._map_call(name, rc, "more than 2^30 points, T not finite, iterations < 0, min_weight < 1, max_residual or damping out of range", zero_ok=True)
+        rep = {"start": int(report[0]), "count": int(report[1]), "sum_r2": float(report[2]), "loss": float(report[3]), "passes": int(report[4]),
+               "ended_ok": int(report[5]), "points": int(report[6]), "loss_history": hist.copy() if rc == 1 else hist[:0].copy()}
+        return rc == 1, (out if rc == 1 else t[0].copy()), rep
+
+    def register_points(self, points, T0=None, iterations=10, damping=1e-3, min_weight=1, max_residual=0.9):
+        """Registers a point cloud (a lidar sweep, another sensor's points, a ground-truth scan, an exported cloud of an earlier session) to this
+        map: damped Gauss-Newton on "the map's value at T p" over the points, whose Jacobian is the map's gradient there, one launch per pass
+        for all starts.  points [N, 3] in metres, a numpy array or a contiguous float32 torch tensor on the GPU.  T0: a starting guess (real
+        4 x 4: a point of the cloud's frame to the volume frame; None: the identity), or a stack [N, 4, 4] of them, refined together; the
+        best by S = count - sum r^2 among the starts that kept six points on every pass wins (align_map's rule; iterations=0 ranks the starts
+        without stepping).  A point takes part where the map holds a value and a gradient at T p with min_weight and |value| <= max_residual.
+        The default max_residual is 0.9 rather than align_map's 1.0: a sample of exactly +-1 is the truncated field, which has gradient 0 and
+        carries no information about T, so such points only dilute the loss.  Returns (ok, T [4, 4] float64, report dict: start, count,
+        sum_r2, loss, passes, ended_ok, points, loss_history [iterations + 1]); ok False (T = the first start) when no start ended ok.
+        Nothing is modified.  XsError in shard mode, ValueError on bad arguments.
+        Intended use: kf.surface_error(scan, kf.register_points(scan, T_guess)[1])."""
+        return self._register_call("xs_kf_register_points", (), points, T0, iterations, damping, min_weight, max_residual)
+
+    def register_map_points(self, other, points, T0=None, iterations=10, damping=1e-3, min_weight=1, max_residual=0.9):
+        """register_points against the map of `other` (another KinectFusion of this process, which is only read); T takes the points to ITS volume frame."""
+        return self._register_call("xs_kf_register_map", (other.h,), points, T0, iterations, damping, min_weight, max_residual)
+
+    def register_checkpoint_points(self, path, points, T0=None, iterations=10, damping=1e-3, min_weight=1, max_residual=0.9):
+        """register_points against the map in a checkpoint file of a whole volume (save_checkpoint, dense or sparse), validated as merge_checkpoint does."""
+        return self._register_call("xs_kf_register_checkpoint", (path.encode(),), points, T0, iterations, damping, min_weight, max_residual)
 
     _BAD_SEARCH = "T not finite, a count, stride, box, min_weight, max_residual or damping out of range"
 
