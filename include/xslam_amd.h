@@ -1017,6 +1017,70 @@ int xs_tsdf_register_terms(int transforms, long long n, const float *points3xN_d
                            size_t vol_step, const int *res, float voxel_size, int min_weight, float max_residual, void *workspace,
                            double *out29xN_dev, void *stream);
 
+/* ---- fusing a point cloud into the volume: a scatter of integers, then a fold (xs_fuse.hip) ---------------------
+ * No counterpart in the reference.  Every other call that writes the volume takes a depth image or a second volume and gathers; this one
+ * takes points with a sensor origin, walks each point's ray, and SCATTERS: one lane per point, adding to voxels that other lanes add to as
+ * well.  What is added is an integer, so the order of the additions cannot matter: xs_tsdf_fuse_points_accumulate adds, per ray and voxel, a
+ * fixed-point observation and a count to one 64-bit word of an accumulator with one integer atomic whose result is not used, and
+ * xs_tsdf_fuse_points_fold turns the accumulator into one weighted observation per touched voxel, averaged into the volume by the merge's
+ * rule, and leaves the accumulator zero.  No floating-point atomics: two runs, or the same points in any order, give equal bytes, and a
+ * host model adding uint64 words reproduces every word.  Every float operation below is one IEEE float32 operation in the order written (the
+ * library is built -ffp-contract=off).  No synchronisation.
+ *
+ * The accumulator: xs_tsdf_fuse_accumulator_bytes(res) bytes (8 X Y Z; 0 for a null or unusable resolution), dense, the word of voxel
+ * (x, y, z) at index (z Y + y) X + x computed in 64 bits; count in bits 40 .. 63, the sum of q in bits 0 .. 39.  Zero it ONCE after
+ * allocation; the fold leaves every word of its planes zero.  Several accumulates may precede one fold, as long as no more than
+ * XS_FUSE_MAX_POINTS (2^24 - 1) points lie between two folds: q <= 2^16, so neither field can overflow.
+ *
+ * xs_tsdf_fuse_points_accumulate: n points (1 .. XS_FUSE_MAX_POINTS), xs_tsdf_sample_points' device array; xform12 (host, optional): row-major
+ * R, then t; origin3 (host): the sensor origin in the points' frame; opts: never null.  Point p:
+ *   1. With a transform P[c] = ((R[c][0] * p[0] + R[c][1] * p[1]) + R[c][2] * p[2]) + t[c] and O the same formula applied to origin3;
+ *      without one P = p and O = origin3, the bits as they are.
+ *   2. v = P - O;  L = sqrtf((v[0] * v[0] + v[1] * v[1]) + v[2] * v[2]).  The point is DROPPED unless L >= min_range && L <= max_range (a NaN
+ *      fails; L == 0 fails, min_range being positive).  d[c] = v[c] / L.
+ *   3. step = 0.5f * voxel_size;  K = (int)ceilf(tranc_dist / step) (formed on the host in these operations; at most XS_FUSE_MAX_HALF_STEPS);
+ *      k_far = (int)floorf(L / step);  k_lo = carve ? -k_far : -min(K, k_far): the ray never starts behind the sensor.  k = k_lo .. K, ascending.
+ *   4. Q[c] = P[c] + (float(k) * step) * d[c];  g[c] = Q[c] / voxel_size.  The sample is OUTSIDE unless g[c] >= 0 && g[c] < float(res[c]) on
+ *      every axis, tested in float before any conversion;  i[c] = (int)floorf(g[c]).
+ *   5. An inside sample whose voxel i equals the voxel of this ray's previous inside sample is skipped (each index is monotone in k: a ray
+ *      visits a voxel once).
+ *   6. C[c] = (float(i[c]) + 0.5f) * voxel_size;  sd = ((P[0] - C[0]) * d[0] + (P[1] - C[1]) * d[1]) + (P[2] - C[2]) * d[2]: the distance from
+ *      the voxel centre to the point along the ray, positive in front of it;  u = sd / tranc_dist.  The sample is skipped if u < -1.0f;
+ *      then u = fminf(u, 1.0f).
+ *   7. q = (int)rintf((u + 1.0f) * 32768.0f), in 0 .. 65536 (ties to even);  (1ull << 40) | q is added to the voxel's word: a VISIT.
+ * counts4_dev (device, never null) is INCREMENTED by {points used, points dropped, visits, samples outside}: integer atomics, one per
+ * counter and workgroup.  Nothing else is written; the volume is not an argument.
+ * hipErrorInvalidValue, with nothing launched and nothing written: n outside 1 .. XS_FUSE_MAX_POINTS; a null points, origin, resolution,
+ * options, accumulator or counts pointer; opts->struct_bytes not sizeof(xs_fuse_opts); xs_tsdf_merge's axis rule; voxel_size or tranc_dist
+ * not positive and finite; K above XS_FUSE_MAX_HALF_STEPS; an entry of the transform or the origin, min_range or max_range not finite;
+ * min_range <= 0; max_range < min_range; max_range / step > 2^20.
+ *
+ * xs_tsdf_fuse_points_fold: one lane per voxel of planes [z0, z1) of a volume given as xs_tsdf_merge takes its destination (one pitch
+ * `step` in bytes for the three arrays, byte offsets in 64 bits, the pointers at plane 0).  a = the voxel's accumulator word:
+ *   a >> 40 == 0: the voxel keeps its bits, nothing is stored to it or to its word, and it does not count.
+ *   otherwise, in double: m = double(a & ((1ull << 40) - 1)) / double(a >> 40);  o = float(m * 0x1p-15 - 1.0): the mean observation, one
+ *      rounding to float32.  wp = the voxel's weight, ws = obs_weight.  wp == 0: value = o, grad = 0.0f.  Otherwise
+ *      value = (prev * float(wp) + o * float(ws)) / float(wp + ws) and grad = (gprev * float(wp)) / float(wp + ws): the cloud carries no
+ *      derivative, its observation is real.  weight = min(wp + ws, max_weight).  The word is set to 0.  The voxel counts as written.
+ * *written_dev (optional, device) is INCREMENTED by the voxels written.  A row's padding, the planes outside the range and their words are
+ * never touched.  A sweep thus weighs as ONE observation per voxel it touches, like a depth frame, however many of its rays pass through it.
+ * hipErrorInvalidValue, with nothing launched: a null array, resolution or accumulator; xs_tsdf_merge's axis, pitch and plane-range rules;
+ * max_weight outside [1, 1 << 24]; obs_weight outside [1, max_weight]. */
+#define XS_FUSE_MAX_POINTS ((1 << 24) - 1)
+#define XS_FUSE_MAX_HALF_STEPS 256
+typedef struct xs_fuse_opts {
+    unsigned struct_bytes;     /* sizeof(xs_fuse_opts) */
+    float min_range;           /* metres, > 0: a shorter ray is dropped */
+    float max_range;           /* metres, >= min_range: a longer ray is dropped */
+    int carve;                 /* 0: the ray starts at most tranc_dist in front of the point; otherwise at the sensor, writing free space */
+} xs_fuse_opts;
+size_t xs_tsdf_fuse_accumulator_bytes(const int *res);
+int xs_tsdf_fuse_points_accumulate(long long n, const float *points3xN_dev, const float *xform12, const float *origin3, const int *res, float voxel_size,
+                                   float tranc_dist, const xs_fuse_opts *opts, unsigned long long *accumulator, unsigned long long *counts4_dev,
+                                   void *stream);
+int xs_tsdf_fuse_points_fold(float *value, int *weight, float *grad, size_t step, const int *res, int z0, int z1, unsigned long long *accumulator,
+                             int obs_weight, int max_weight, unsigned long long *written_dev, void *stream);
+
 /* ---- surface mesh (export; marching cubes with complex-step vertex derivatives) -------------------------------------------------------
  * No working counterpart in the reference (its extractMesh, ExtractPointCloud.cu:364-715, is never called).
  * Cube (x, y, z), x < X-1, y < Y-1, z in [z0, z1), is live when all 8 corners have weight >= min_weight and value < 0.99 and its corners

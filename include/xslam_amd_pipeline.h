@@ -544,6 +544,24 @@ int xs_kf_register_checkpoint(void *kf, const char *path, long long n, const flo
                               double damping, int min_weight, float max_residual, double *T16_out, double *report7, double *loss_history);
 int xs_host_register_step(const double *s29, double damping, double *T16);
 
+/* A registered point cloud fused into this instance's map (xs_tsdf_fuse_points_accumulate and xs_tsdf_fuse_points_fold
+ * in xslam_amd.h: the contract).  points: n x 3 floats in metres (n >= 1; on_device bit 0: device memory) and origin3, the sensor's position,
+ * in a frame that T16 (real 4 x 4, row-major, as xs_kf_register_points returns it; NULL: the volume frame, the bits as they are) takes to the
+ * volume frame.  Each point's ray is walked in half-voxel steps from at most the truncation distance in front of the point (carve != 0: from
+ * the sensor) to the truncation distance behind it; every voxel entered receives the signed distance to the point along the ray, in units of
+ * the truncation distance and clamped at 1.  A voxel receives ONE observation of weight `weight` (1 .. the configuration's
+ * max_integration_weight) per run of at most 2^24 - 1 points, the mean over the rays that entered it, averaged in as a depth frame's is.  Rays
+ * shorter than min_range (> 0) or longer than max_range are dropped.  The result does not depend on the order of the points.
+ * counts5 (optional) = {points used, points dropped, visits, samples outside the volume, voxels written}.  Afterwards everything derived
+ * from the volume follows as after xs_kf_reintegrate; xs_kf_volume_generation advances; poses and the frame number stay.  The accumulator
+ * (8 bytes per voxel) is allocated on first use and kept; xs_kf_release_fuse_scratch frees it.
+ * Return 1, 0 without a volume, -1 on bad arguments (a null pointer, n < 1, an entry that is not finite, min_range <= 0, max_range <
+ * min_range or above 2^19 voxels, a weight outside its range, a truncation distance above 128 voxels) with the state unchanged, -2 in shard
+ * mode. */
+int xs_kf_fuse_points(void *kf, long long n, const float *points, int on_device, const double *T16, const float *origin3, float min_range, float max_range,
+                      int carve, int weight, unsigned long long *counts5);
+void xs_kf_release_fuse_scratch(void *kf);
+
 /* ---- The reference's own call shape (x-slam_amd/host/reference_shape.hpp) ---------------------------------------------------------
  * The per-frame sequence of Experiments/test_xkinect_fusion/main.cpp:46-60 + KinectFusionReconstruction.cpp:147-332 over nothing but the
  * reference-signature launchers (bilateralFilter, pyrDown, createVMap / createNMap, estimateCombined per iteration, integrateTsdfVolume,

@@ -80,6 +80,11 @@ class SampleOpts(C.Structure):
     _fields_ = [("struct_bytes", C.c_uint), ("min_weight", C.c_int)]
 
 
+class FuseOpts(C.Structure):
+    """xs_fuse_opts (include/xslam_amd.h)."""
+    _fields_ = [("struct_bytes", C.c_uint), ("min_range", C.c_float), ("max_range", C.c_float), ("carve", C.c_int)]
+
+
 _SIGS = {
     "xs_tsdf_sample_points": (C.c_int, [C.c_longlong, _vp, _f32p, _vp, _vp, _vp, _sz, _i32p, C.c_float, C.POINTER(SampleOpts), _vp, _vp, _vp, _vp, _vp, _vp]),
     "xs_tsdf_sample_depth": (C.c_int, [_vp, _sz, C.c_int, C.c_int, _f32p, _f32p, _f32p, _vp, _vp, _vp, _sz, _i32p, C.c_float, C.POINTER(SampleOpts), _vp, _vp, _vp,
@@ -205,6 +210,9 @@ _SIGS = {
     "xs_tsdf_align_terms": (C.c_int, [C.c_int, C.POINTER(BandIndex), _vp, _vp, _sz, _i32p, _f32p, C.c_int, C.c_float, _vp, _vp, _vp]),
     "xs_tsdf_score_transforms_workspace_bytes": (_sz, [C.c_int]),
     "xs_tsdf_score_transforms": (C.c_int, [C.c_int, C.POINTER(BandIndex), C.c_int, _vp, _vp, _sz, _i32p, _f32p, C.c_int, C.c_float, _vp, _vp, _vp]),
+    "xs_tsdf_fuse_accumulator_bytes": (_sz, [_i32p]),
+    "xs_tsdf_fuse_points_accumulate": (C.c_int, [C.c_longlong, _vp, _f32p, _f32p, _i32p, C.c_float, C.c_float, C.POINTER(FuseOpts), _vp, _vp, _vp]),
+    "xs_tsdf_fuse_points_fold": (C.c_int, [_vp, _vp, _vp, _sz, _i32p, C.c_int, C.c_int, _vp, C.c_int, C.c_int, _vp, _vp]),
     "xs_tsdf_register_workspace_bytes": (_sz, [C.c_int]),
     "xs_tsdf_register_terms": (C.c_int, [C.c_int, C.c_longlong, _vp, _f32p, _vp, _vp, _sz, _i32p, C.c_float, C.c_int, C.c_float, _vp, _vp, _vp]),
     "xs_mesh_workspace_bytes": (_sz, [_i32p, C.POINTER(MeshOpts)]),
@@ -1124,6 +1132,46 @@ def register_terms(n, points, xforms, value, weight, vol_step, res, voxel_size, 
     check(_lib.xs_tsdf_register_terms(int(transforms), int(n), _ptr(points), None if m is None else m.ctypes.data_as(_f32p), _ptr(value), _ptr(weight), vol_step,
                                       None if r is None else r.ctypes.data_as(_i32p), float(voxel_size), int(min_weight), float(max_residual), _ptr(workspace),
                                       _ptr(out29xN), _stream(stream)))
+
+
+FUSE_MAX_POINTS, FUSE_MAX_HALF_STEPS = (1 << 24) - 1, 256   # XS_FUSE_MAX_POINTS, XS_FUSE_MAX_HALF_STEPS
+
+
+def fuse_opts(min_range=0.2, max_range=5.0, carve=False):
+    """An xs_fuse_opts."""
+    o = FuseOpts()
+    o.struct_bytes = C.sizeof(FuseOpts)
+    o.min_range, o.max_range, o.carve = float(min_range), float(max_range), int(bool(carve))
+    return o
+
+
+def fuse_accumulator_bytes(res):
+    """xs_tsdf_fuse_accumulator_bytes (host only): 8 bytes per voxel; 0 for a null or unusable resolution."""
+    r = None if res is None else _ia(res, 3)
+    return int(_lib.xs_tsdf_fuse_accumulator_bytes(None if r is None else r.ctypes.data_as(_i32p)))
+
+
+def fuse_points_accumulate(n, points, origin, res, voxel_size, tranc_dist, opts, accumulator, counts, xform12=None, stream=None):
+    """xs_tsdf_fuse_points_accumulate: the rays from `origin` [3] (the points' frame) to n points (device float32 [n, 3], metres; xform12 = row-major R
+    then t takes both to the volume frame, None: as they are) walked in half-voxel steps; every voxel a ray enters has (1 << 40) | q added to its
+    word of `accumulator` (device uint64, fuse_accumulator_bytes(res) bytes, zeroed once) by an integer atomic.  counts (device uint64 [4]) is
+    INCREMENTED by {points used, points dropped, visits, samples outside}.  opts: fuse_opts(...).  A None goes through as a null pointer."""
+    m, mp = _f32_or_null(xform12)
+    o, op = _f32_or_null(origin)
+    r = None if res is None else _ia(res, 3)
+    check(_lib.xs_tsdf_fuse_points_accumulate(int(n), _ptr(points), mp, op, None if r is None else r.ctypes.data_as(_i32p), float(voxel_size), float(tranc_dist),
+                                              C.byref(opts) if opts is not None else None, _ptr(accumulator), _ptr(counts), _stream(stream)))
+
+
+def fuse_points_fold(value, weight, grad, step, res, accumulator, obs_weight=1, max_weight=100, z0=0, z1=None, written=None, stream=None):
+    """xs_tsdf_fuse_points_fold: every voxel of planes [z0, z1) whose accumulator word has a count receives its mean observation with weight
+    obs_weight by the merge's running mean (grad scaled by wp / (wp + ws)), and the word is cleared.  Arrays are device tensors or addresses of
+    plane 0; `written` (uint64 / int64 device word, optional) is incremented by the voxels written.  No synchronisation."""
+    r = None if res is None else _ia(res, 3)
+    if z1 is None:
+        z1 = 0 if r is None else int(r[2])
+    check(_lib.xs_tsdf_fuse_points_fold(_ptr(value), _ptr(weight), _ptr(grad), step, None if r is None else r.ctypes.data_as(_i32p), int(z0), int(z1),
+                                        _ptr(accumulator), int(obs_weight), int(max_weight), _ptr(written), _stream(stream)))
 
 
 ALIGN_SCORE_MAX_TRANSFORMS = 4096   # XS_ALIGN_SCORE_MAX_TRANSFORMS

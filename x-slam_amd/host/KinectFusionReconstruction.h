@@ -463,6 +463,23 @@ public:
     int RegisterSecondMap(const xs_host::SecondMap &src, const float *points, long long n, int on_device, const double *T16xN, int N, int iterations,
                           double damping, int min_weight, float max_residual, double *T16_out, double report[7], std::vector<double> *loss_history);
 
+    // A registered point cloud fused into THIS map (kf_fuse.cpp; xs_tsdf_fuse_points_accumulate and
+    // xs_tsdf_fuse_points_fold in include/xslam_amd.h: the contract; fuse_host.hpp: the host's side).  points: n x 3 float32 metres (on_device
+    // bit 0: device memory) and origin3, the sensor's position, in a frame that T16 (a real 4 x 4, row-major; null: none, the bits as they are)
+    // takes to the volume frame; it is rounded by register_xform12's rule, so RegisterPoints' T16_out is fused at the bits it was scored at.
+    // Rays shorter than min_range or longer than max_range are dropped; with carve the rays write free space from the sensor on; `weight` is
+    // the observation's weight (1 .. max_integration_weight).  The device is drained; the cloud goes through in fuse_host.hpp's runs of at
+    // most 2^24 - 1 points, one accumulate and one fold over the whole volume each (a voxel touched by two runs thus receives two
+    // observations); then everything derived from the volume follows as after ReintegrateFrames: volume_generation, the sign map, the cached
+    // planning and relocalisation maps, the previous frame's model maps.  Poses, frame_id and the trajectory record are untouched.
+    // counts5 (optional) = {points used, points dropped, visits, samples outside, voxels written}.  The accumulator (8 bytes per voxel: 1 GiB at
+    // 512^3) is allocated and zeroed on first use and kept with the instance; ReleaseFuseScratch frees it, and the next call allocates it again.
+    // Returns 1, -2 in shard mode (a ray crosses the ranks' z-slabs), 0 without a volume, -1 on bad arguments (whatever the two calls refuse,
+    // a T16 entry that is not finite, a null pointer, arrays of unequal pitch) with the state unchanged.
+    int FusePoints(const float *points, long long n, int on_device, const double *T16, const float *origin3, float min_range, float max_range, int carve,
+                   int weight, unsigned long long counts5[5]);
+    void ReleaseFuseScratch() { fuse_acc_.release(); }
+
     // counters of the last frame (synchronise the stream)
     long long lastUpdatedVoxels();
     long long lastRaycastHits();
@@ -576,6 +593,7 @@ private:
     // the registration loop over a volume described as a SecondMap (this map's included), with the staging of host points
     int RegisterVolume(const xs_host::SecondMap &vol, const float *points, long long n, int on_device, const double *T16xN, int N, int iterations, double damping,
                        int min_weight, float max_residual, double *T16_out, double report[7], std::vector<double> *loss_history);
+    DeviceArray<unsigned long long> fuse_acc_; // FusePoints' accumulator: one word per voxel, zero between calls
     DeviceArray2D<ushort> depth_ingest_d_;     // device copy of a host frame (ProcessFrameHost)
     ushort *ingest_pinned_[2] = {nullptr, nullptr};
     hipEvent_t ingest_done_[2] = {nullptr, nullptr};

@@ -724,6 +724,11 @@ int xs_kf_register_checkpoint(void *kf, const char *path, long long n, const flo
     return rc != 1 ? rc : register_call((KF *)kf, &c.map, n, points, on_device, T16xN, N, iterations, damping, min_weight, max_residual, T16_out, report7, loss_history);
 }
 int xs_host_register_step(const double *s29, double damping, double *T16) { return xs_host::register_step(s29, damping, T16) ? 0 : -1; }
+int xs_kf_fuse_points(void *kf, long long n, const float *points, int on_device, const double *T16, const float *origin3, float min_range, float max_range,
+                      int carve, int weight, unsigned long long *counts5) {
+    return ((KF *)kf)->FusePoints(points, n, on_device, T16, origin3, min_range, max_range, carve, weight, counts5);
+}
+void xs_kf_release_fuse_scratch(void *kf) { ((KF *)kf)->ReleaseFuseScratch(); }
 int xs_host_align_search_free(int n, const double *centroid_this3, const double *centroid_other3, double box_t, double *T16xN) {
     return xs_host::align_search_free(n, centroid_this3, centroid_other3, box_t, T16xN) ? 0 : -1;
 }

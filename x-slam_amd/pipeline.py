@@ -48,6 +48,8 @@ _SIGS = {
     "xs_kf_register_map": (C.c_int, [_vp, _vp] + _REGISTER_TAIL),
     "xs_kf_register_checkpoint": (C.c_int, [_vp, C.c_char_p] + _REGISTER_TAIL),
     "xs_host_register_step": (C.c_int, [_f64p, C.c_double, _f64p]),
+    "xs_kf_fuse_points": (C.c_int, [_vp, C.c_longlong, _vp, C.c_int, _f64p, _f32p, C.c_float, C.c_float, C.c_int, C.c_int, C.POINTER(C.c_ulonglong)]),
+    "xs_kf_release_fuse_scratch": (None, [_vp]),
     "xs_kf_sample_points": (C.c_int, [_vp] + _SAMPLE_POINTS + _SAMPLE_TAIL),
     "xs_kf_sample_volume": (C.c_int, [_vp, _vp, _vp, _vp, _sz, _i32p, C.c_float, C.c_float] + _SAMPLE_POINTS + _SAMPLE_TAIL),
     "xs_kf_sample_map": (C.c_int, [_vp, _vp] + _SAMPLE_POINTS + _SAMPLE_TAIL),
@@ -1385,6 +1387,54 @@ class KinectFusion:
     def register_checkpoint_points(self, path, points, T0=None, iterations=10, damping=1e-3, min_weight=1, max_residual=0.9):
         """register_points against the map in a checkpoint file of a whole volume (save_checkpoint, dense or sparse), validated as merge_checkpoint does."""
         return self._register_call("xs_kf_register_checkpoint", (path.encode(),), points, T0, iterations, damping, min_weight, max_residual)
+
+    _FUSE_COUNTS = ("used", "dropped", "visits", "outside", "written")
+
+    def fuse_points(self, points, T=None, origin=(0.0, 0.0, 0.0), min_range=0.2, max_range=5.0, carve=False, weight=1):
+        """Fuses a point cloud (a lidar sweep, another sensor's points, a ground-truth scan, an earlier session's cloud) into the map.  points [N, 3]
+        in metres, a numpy array or a contiguous float32 torch tensor on the GPU, and origin, the sensor's position, both in a frame that T (real
+        4 x 4, as register_points returns it; None: the volume frame, the bits as they are) takes to the volume frame.  Each point's ray from the
+        origin is walked in half-voxel steps through the truncation band around the point (carve=True: from the sensor on, which turns the
+        unknown space the ray crosses into free space for the planning calls, at the cost of a walk as long as the ray); a voxel the sweep
+        touches receives one observation of `weight`, the mean over the rays through it of the signed distance to the point ALONG THE RAY,
+        averaged in as a depth frame's is.  Rays shorter than min_range or longer than max_range are dropped.  Integer atomics only: the
+        result does not depend on the order of the points, and two calls on equal maps give equal bytes.  Returns a dict of used and dropped
+        points, visits (voxel additions), outside (ray samples that left the volume) and written voxels.  Everything derived from the map
+        follows; poses and the frame number stay.  XsError in shard mode, ValueError on bad arguments.
+        Intended use: kf.fuse_points(sweep, kf.register_points(sweep, T_guess)[1], origin=sensor_position)."""
+        name = "xs_kf_fuse_points"
+        if hasattr(points, "data_ptr"):   # a torch tensor on the GPU
+            if not points.is_cuda or not points.is_contiguous() or points.dim() != 2 or points.shape[1] != 3 or points.element_size() != 4 or not points.is_floating_point():
+                raise ValueError(f"{name}: a torch points tensor must be contiguous float32 [N, 3] on the GPU")
+            n, pp, on_device, keep = int(points.shape[0]), points.data_ptr(), 1, points
+        else:
+            keep = np.ascontiguousarray(points, dtype=np.float32)
+            if keep.ndim != 2 or keep.shape[1] != 3:
+                raise ValueError(f"{name}: points must be [N, 3]")
+            n, pp, on_device = keep.shape[0], keep.ctypes.data, 0
+        if n < 1:
+            raise ValueError(f"{name}: at least one point is needed")
+        t = None if T is None else _real44(T)
+        o = np.ascontiguousarray(origin, dtype=np.float32).reshape(-1)
+        if o.size != 3:
+            raise ValueError(f"{name}: origin must have three entries")
+        counts = (C.c_ulonglong * 5)()
+        rc = _lib.xs_kf_fuse_points(self.h, n, pp, on_device, None if t is None else t.ctypes.data_as(_f64p), o.ctypes.data_as(_f32p), float(min_range),
+                                    float(max_range), int(bool(carve)), int(weight), counts)
+        self._map_call(name, rc, "T, origin or a range not finite, min_range <= 0, max_range < min_range or too long, weight outside 1 .. max_integration_weight")
+        return {k: int(counts[i]) for i, k in enumerate(self._FUSE_COUNTS)}
+
+    def register_and_fuse(self, points, T0=None, origin=(0.0, 0.0, 0.0), iterations=10, damping=1e-3, min_weight=1, max_residual=0.9, min_range=0.2, max_range=5.0,
+                          carve=False, weight=1):
+        """register_points followed, when it succeeded, by fuse_points at the winning transform: (ok, T, register report, fuse counts or None).
+        Nothing is fused when no start ended ok."""
+        ok, T, rep = self.register_points(points, T0, iterations, damping, min_weight, max_residual)
+        fused = self.fuse_points(points, T, origin, min_range, max_range, carve, weight) if ok else None
+        return ok, T, rep, fused
+
+    def release_fuse_scratch(self):
+        """Frees fuse_points' accumulator (8 bytes per voxel); the next fuse_points allocates it again."""
+        _lib.xs_kf_release_fuse_scratch(self.h)
 
     _BAD_SEARCH = "T not finite, a count, stride, box, min_weight, max_residual or damping out of range"
 
