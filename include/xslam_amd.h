@@ -670,7 +670,7 @@ int xs_tsdf_merge(float *value, int *weight, float *grad, size_t step, const int
                   const int *src_weight, const float *src_grad, size_t src_step, const int *src_res, const float *xform12, int min_weight,
                   int max_weight, unsigned flags, unsigned long long *written_dev, void *workspace, void *stream);
 
-/* ---- taking fused frames out of the volume and fusing frames with a sign (xs_integrate.hip) ---------------------
+/* ---- taking fused frames out of the volume and fusing frames with a sign (xs_reintegrate.hip) ---------------------
  * No counterpart in the reference.  One pass over planes [z0, z1) applies up to XS_REINTEGRATE_MAX_OPS observations to every voxel, each
  * with a sign.  The volume arguments are xs_integrate_scaled's: value / weight / grad at the first stored plane z0 (the whole volume: plane 0,
  * z0 = 0, z1 = res[2]), one pitch `vol_step` (bytes), z over global plane indices; only planes [z0, z1) are touched.  Every op's image is

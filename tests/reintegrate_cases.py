@@ -1,4 +1,4 @@
-"""The cases that hold signed re-integration (xs_tsdf_reintegrate, x-slam_amd/csrc/xs_integrate.hip) to a model written from the per-voxel
+"""The cases that hold signed re-integration (xs_tsdf_reintegrate, x-slam_amd/csrc/xs_reintegrate.hip) to a model written from the per-voxel
 contract in include/xslam_amd.h and not from the kernel: a numpy statement of the rules in float32, operation by operation (the library is
 built with -ffp-contract=off and divides with correct rounding, so the model is exact, not close), and a float64 twin that takes every discrete
 decision (seen, the weights) from the same inputs and redoes the arithmetic in float64.  An op of the model is (sign, seen, t_value, t_grad):

@@ -418,7 +418,7 @@ def test_full_size_properties_512(dev):
 # ---- round 4: depth tiles and the brick classification (free space / nothing to write / exact walk) ----------------------------
 def tiles_numpy(scaled, tw=8, th=8):
     """{lo, hi} per tw x th pixels of a scaled depth image over its VALID pixels, lo negated where the tile holds an invalid one (depth 0),
-    {-inf, 0} where it holds no valid one (csrc/xs_integrate.hip, k_scale_depth)."""
+    {-inf, 0} where it holds no valid one (csrc/xs_scale_depth.hip, k_scale_depth)."""
     h, w = scaled.shape
     ty, tx = -(-h // th), -(-w // tw)
     out = np.zeros((ty, tx, 2), np.float32)

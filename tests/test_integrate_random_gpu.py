@@ -1,5 +1,5 @@
-"""Randomized differential test of the integrate kernel's box classes (FREE / EMPTY / plane by plane, EDGE, SPECKLE: xs_integrate.hip
-classify_box, integrate_edge_column, valid_slot_request) against the per-voxel walk over every listed brick (XS_INTEGRATE_NO_TILES),
+"""Randomized differential test of the integrate kernel's box classes (FREE / EMPTY / plane by plane, EDGE, SPECKLE: xs_integrate_classify.hip
+classify_box, xs_integrate_stream.h integrate_edge_column, valid_slot_request) against the per-voxel walk over every listed brick (XS_INTEGRATE_NO_TILES),
 which the oracle tests pin (tests/test_integrate_gpu.py).  The classes' shortcuts rest on numeric margins — a reciprocal-based
 projection trusted outside `near_margin` of a pixel boundary, an in-image window trusted outside 1/32 px — so hand-picked scenes
 are not enough: here the pose, the sensor, the depth image and its invalid pixels are drawn at random.
@@ -182,7 +182,7 @@ def test_randomized_classes_against_the_walk(dev, oracle):
 
 @pytest.mark.parametrize("case", ["wide_4096x2048", "too_wide_6000x2400", "seed_1e-3"])
 def test_streamed_classes_stop_where_their_margins_are_not_proven(dev, case):
-    """stream_margins (xs_integrate.hip): the nearest-pixel margin is 8 ulp of E = max(cols + |cx|, rows + |cy|) — a 4096 x 2048 sensor (the
+    """stream_margins (xs_integrate_args.h): the nearest-pixel margin is 8 ulp of E = max(cols + |cx|, rows + |cy|) — a 4096 x 2048 sensor (the
     largest the tile room takes) streams its EDGE / SPECKLE planes with 1 / 256 px and stays bit-identical to the walk; with E >= 8192,
     or with imaginary pose parts of 1e-3 (whose products reach the real part of the exact projection), no box is classed EDGE or
     SPECKLE — such boxes walk — and the volume is the walk's all the same."""

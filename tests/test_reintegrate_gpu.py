@@ -1,4 +1,4 @@
-"""GPU: xs_tsdf_reintegrate (x-slam_amd/csrc/xs_integrate.hip) against the float32 model of tests/reintegrate_cases.py.  The observations the
+"""GPU: xs_tsdf_reintegrate (x-slam_amd/csrc/xs_reintegrate.hip) against the float32 model of tests/reintegrate_cases.py.  The observations the
 model applies are what the integrate kernel's exact walk writes into zeroed volumes (capi.integrate_scaled_ex with XS_INTEGRATE_NO_TILES), for
 the nearest-pixel and the bilinear instance and for real and complex poses.  Values, weights and grads are compared with np.array_equal, counts
 exactly; guard planes, padding and voxels no op sees must keep their bits."""
