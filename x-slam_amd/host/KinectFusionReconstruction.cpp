@@ -1085,15 +1085,6 @@ int KinectFusionReconstruction::CalculatePointCloud(MapArr &xyz_g_d, MapArr &nor
 
 void KinectFusionReconstruction::synchronize() { hipSafeCall(hipStreamSynchronize(current_stream())); }
 
-// The sign map from the volume alone (allocation, checkpoint, anything that wrote the value array without the integrate kernels).
-void KinectFusionReconstruction::RebuildSignMap() {
-    ++volume_generation;   // the documented "the volume was written" call: the relocalisation index is rebuilt too
-    if (!sign_map_on() || !sign_map_.ptr() || !tsdf_volume_d_ptr) return;
-    DeviceArray2D<float> value = tsdf_volume_d_ptr->value();
-    check_rc(xs_signmap_rebuild_slab(sign_map_.ptr(), res3(), raycast_sign_map_shift, tsdf_volume_d_ptr->getTsdfTruncDist(), value.ptr(0), value.step(),
-                                     zs0, zs1, current_stream()), "sign map");
-}
-
 // ---- per-stage HIP event timing (on the stream the kernels are launched on) -----------------
 void KinectFusionReconstruction::set_profiling(int level) {
     const bool on = level > 0;

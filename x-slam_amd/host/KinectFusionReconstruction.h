@@ -373,7 +373,7 @@ public:
                           const int *frame_index, unsigned long long counts4[4]);
     // Aligning a second map to the volume before it is merged (xs_tsdf_align_terms in include/xslam_amd.h: the
     // contract).  Axes >= 2.  T16xN: N >= 1 starting transforms.
-    // The device is drained, the band index of THIS map prepared, and gn_batch_loop (gn_host.hpp) run over the starts:
+    // The device is drained, the band index of THIS map prepared, and gn_multistart (gn_host.hpp) run over the starts:
     // a pass is one xs_tsdf_align_terms launch per chunk of the starts still active, a step align_host.hpp's align_step.  T16_out receives
     // the start that ended ok — at least six voxels on every pass, the last one included, and a positive definite system on every step —
     // with the highest S = count - sum r^2 (ties: the lower index; S is relocalize_global's truncated-quadratic score for max_residual <= 1: above
@@ -453,7 +453,7 @@ public:
 
     // A point cloud registered to a map (kf_register.cpp; xs_tsdf_register_terms in include/xslam_amd.h: the contract;
     // register_host.hpp: the host's side).  points: n x 3 float32 metres (on_device bit 0: device memory) in a frame that each of the N starts
-    // T16xN (real 4 x 4, row-major) takes to the map's volume frame.  The starts run through gn_batch_loop: per pass one
+    // T16xN (real 4 x 4, row-major) takes to the map's volume frame.  The starts run through gn_multistart: per pass one
     // xs_tsdf_register_terms launch over the starts still active and one fetch of their sums, then register_step on each.  The winner, the
     // "ended ok" rule, iterations = 0 and the return codes are AlignVolume's; report7 = {its index, its count, its sum r^2, its mean loss,
     // launches run, starts that ended ok, n}.  The device is drained before and the stream after.  Nothing of any map or cache is modified.
@@ -585,9 +585,13 @@ private:
     bool takes_second_map(const xs_host::SecondMap &m, int min_axis, bool need_grad) const;   // second_map_ok against this volume
     void drain_device();   // what every call that takes a second map does before its first launch
     void invalidate_derived_maps() { reloc_.band_key = BandKey{}; plan_.grid_key = GridKey{}; plan_.clear_key = ClearKey{}; plan_.frontier_key = FrontierKey{}; plan_.render_key = GridKey{}; reach_forget(); }
+    int OwnMap(bool with_grad, xs_host::SecondMap &out) const;   // this volume (it must exist) as a SecondMap, grad only with_grad: 1; -1 for unequal pitches
+    // what MergeVolume, FusePoints and ReintegrateFrames do after their write: volume_generation, the sign map, the cached planning and
+    // relocalisation maps, the previous frame's model maps at the current pose, and the stream drained (kf_second_map.cpp, beside RebuildSignMap)
+    void volume_written_off_path();
     // the views of one volume through xs_render_views, in chunks; `ws` holds a mask built for (res, the options' min_weight) unless the cull is off
-    int RenderVolume(const float *value, const int *weight, size_t step, const int *res, float vs, void *ws, const float *c2v, int stride, int P, const float *intr4,
-                     int rows, int cols, const xs_render_opts &opts, const RenderOutputs &out, int on_device);
+    int RenderVolume(const xs_host::SecondMap &vol, void *ws, const float *c2v, int stride, int P, const float *intr4, int rows, int cols, const xs_render_opts &opts,
+                     const RenderOutputs &out, int on_device);
     // one xs_tsdf_sample_points launch over a volume described as a SecondMap (this map's included), with the staging of host points and outputs
     int SampleVolume(const xs_host::SecondMap &vol, const float *points, long long n, const double *T16, int min_weight, const SampleOutputs &out, int on_device);
     // the registration loop over a volume described as a SecondMap (this map's included), with the staging of host points

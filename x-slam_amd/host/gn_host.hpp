@@ -1,6 +1,7 @@
 // gn_host.hpp — the host's side of Gauss-Newton relocalisation (DESIGN.md sections 4.15, 4.16): the six seeded poses of a pass, the scaling of its
-// sums, the damped 6 x 6 step that Gauss-Newton and Newton (newton_host.hpp) share, and the batched loop both run.  Pure host code, no device
-// call and no HIP header: the orchestrator uses it between launches and tests/cxx/gn_selftest.cpp runs it under the sanitizers without a GPU.
+// sums, the damped 6 x 6 step that Gauss-Newton and Newton (newton_host.hpp) share, the batched loop both run, and the multi-start loop over it that
+// the map alignment and the point registration run.  Pure host code, no device call and no HIP header: the orchestrator uses it between launches
+// and tests/cxx/gn_selftest.cpp runs it under the sanitizers without a GPU.
 #pragma once
 #include "host_algebra.hpp"
 #include <algorithm>
@@ -105,6 +106,46 @@ int gn_batch_loop(int F, int iterations, std::vector<double> *loss_history, int 
         active.swap(next);
     }
     return (int)std::count(ok, ok + F, 1);
+}
+
+struct GnMultistart {
+    int win = -1, ended_ok = 0, passes = 0;   // the winning start (-1: none), the starts that could have won, the evaluate calls made
+    double sums[29] = {};                      // the winner's sums of its last pass
+    std::vector<double> history;               // and its loss per pass
+};
+// gn_batch_loop over the N starts of one problem (evaluate and step as it takes them), and the start that wins: the one that ended ok, with at
+// least six voxels in its last pass too (gn_batch_loop lets the loss pass end ok whatever it counts: a start that its last step, or no step at
+// all, left off the map is no result), with the highest S = count - sum r^2 (relocalize_global's score; ties: the lower index).  loss_pass: a
+// last pass that only reports the loss, so the winner is picked where it ended; without it the sums are those the last step was taken from,
+// and iterations = 0 launches nothing and nobody wins.
+template <class Evaluate, class Step>
+GnMultistart gn_multistart(int N, int iterations, int chunk, bool loss_pass, Evaluate &&evaluate, Step &&step) {
+    GnMultistart r;
+    std::vector<std::vector<double>> history((size_t)N);
+    std::vector<double> last((size_t)N * 29, 0.0);
+    std::vector<int> ok((size_t)N, 0);
+    gn_batch_loop(N, iterations, loss_pass ? history.data() : nullptr, ok.data(), chunk, [&](const int *starts, int n, double *sums) {
+        evaluate(starts, n, sums);
+        ++r.passes;
+        for (int i = 0; i < n; ++i) std::copy(sums + 29 * i, sums + 29 * i + 29, &last[(size_t)starts[i] * 29]);
+    }, step);
+    auto S = [&](int n) { return last[(size_t)n * 29 + 28] - last[(size_t)n * 29 + 27]; };
+    for (int n = 0; n < N; ++n) {
+        if (!ok[(size_t)n] || last[(size_t)n * 29 + 28] < 6) continue;
+        ++r.ended_ok;
+        if (r.win < 0 || S(n) > S(r.win)) r.win = n;
+    }
+    if (r.win < 0) return r;
+    std::copy(&last[(size_t)r.win * 29], &last[(size_t)r.win * 29] + 29, r.sums);
+    r.history = history[(size_t)r.win];
+    return r;
+}
+// report[0 .. 5] of a multi-start call: {the winner's index, its count, sum r^2 and mean loss (as the caller cleared them without a winner),
+// evaluate calls, starts that ended ok}
+inline void gn_multistart_report(const GnMultistart &r, double *report) {
+    if (!report) return;
+    report[4] = (double)r.passes; report[5] = (double)r.ended_ok;
+    if (r.win >= 0) { report[0] = (double)r.win; report[1] = r.sums[28]; report[2] = r.sums[27]; report[3] = r.sums[28] > 0 ? r.sums[27] / r.sums[28] : 0.0; }
 }
 
 }  // namespace xs_host

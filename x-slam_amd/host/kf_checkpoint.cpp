@@ -116,6 +116,58 @@ void CheckpointFile::write_to(float *dv, int *dw, float *dg, size_t step, unsign
     restore_rows(dw, step, weight, p.res[0], rows);
 }
 
+// xs_host_checkpoint_info (include/xslam_amd_pipeline.h: the layout of out32): a file's header and what its format's validation says.  No device call.
+int xs_host::checkpoint_info(const char *path, double *out32) {
+    if (!path || !out32) return -1;
+    for (int i = 0; i < 32; ++i) out32[i] = 0.0;
+    std::ifstream f(path, std::ios::binary);
+    if (!f) return -1;
+    f.seekg(0, std::ios::end);
+    const long long file_bytes = (long long)f.tellg();
+    f.seekg(0, std::ios::beg);
+    PackHeader h{};
+    if (file_bytes < (long long)sizeof(CkptPrefix)) return -1;
+    f.read(reinterpret_cast<char *>(&h.p), sizeof(h.p));
+    if (!f) return -1;
+    const bool v3 = pack_magic_is(h.p.magic, "XSTSDF3"), v2 = pack_magic_is(h.p.magic, "XSTSDF2");
+    if (!v2 && !v3) return -1;
+    const CkptPrefix &p = h.p;
+    out32[0] = v3 ? 3.0 : 2.0;
+    for (int i = 0; i < 3; ++i) out32[2 + i] = p.res[i];
+    out32[5] = p.voxel_size; out32[6] = p.tranc_dist; out32[7] = p.frame_id; out32[8] = p.n_poses; out32[9] = p.zs0; out32[10] = p.zs1;
+    out32[11] = p.shard_rank; out32[12] = p.shard_count;
+    out32[27] = (double)file_bytes;
+    PackError e = PACK_OK;
+    if (v2) {
+        uint64_t words = 0;
+        e = pack_validate_dense(p, (uint64_t)file_bytes, &words);
+        out32[26] = (double)words;
+    } else {
+        if (file_bytes < (long long)sizeof(PackHeader)) e = PACK_BAD_LENGTH;
+        else {
+            f.read(reinterpret_cast<char *>(&h) + sizeof(h.p), sizeof(h) - sizeof(h.p));
+            out32[13] = h.brick_edge; out32[14] = h.nbx; out32[15] = h.nby; out32[16] = h.nbz;
+            out32[17] = (double)h.nbricks; out32[26] = (double)h.payload_words;
+            uint64_t head = 0;
+            e = f ? pack_validate_header(h, &head) : PACK_BAD_LENGTH;
+            if (e == PACK_OK) {
+                if ((uint64_t)file_bytes < head) e = PACK_BAD_LENGTH;
+                else {
+                    std::vector<unsigned char> cls((size_t)pack_class_bytes_padded(h.nbricks));
+                    f.seekg((std::streamoff)(sizeof(PackHeader) + (uint64_t)p.n_poses * PACK_POSE_BYTES), std::ios::beg);
+                    f.read(reinterpret_cast<char *>(cls.data()), (std::streamsize)cls.size());
+                    uint64_t hist[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+                    e = f ? pack_validate(h, cls.data(), (uint64_t)file_bytes, hist) : PACK_BAD_LENGTH;
+                    for (int c = 0; c < 8; ++c) out32[18 + c] = (double)hist[c];
+                }
+            }
+        }
+    }
+    out32[1] = e == PACK_OK ? 1.0 : 0.0;
+    out32[28] = (double)e;
+    return 0;
+}
+
 bool KinectFusionReconstruction::saveCheckpointSparse(const std::string &filename, unsigned long long *stats12) {
     if (stats12) std::fill(stats12, stats12 + 12, 0ull);
     if (!tsdf_volume_d_ptr) return false;
@@ -210,6 +262,8 @@ bool KinectFusionReconstruction::loadCheckpoint(const std::string &filename) {
     // validated: commit
     synchronize();
     c.write_to(dv.ptr(0), dw.ptr(0), dg.ptr(0), dv.step(), checkpoint_staging_words);
+    // Not volume_written_off_path(): the poses are restored between the sign map and the model maps, which are rendered at the restored pose;
+    // the derived maps are not invalidated (their keys hold volume_generation, which moves) and sign_map_stale_ stays as it is.
     ++volume_generation;
     RebuildSignMap();    // the volume was written behind the integrate kernels' back
     world2camera_record.swap(c.poses);

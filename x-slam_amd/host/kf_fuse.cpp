@@ -51,14 +51,7 @@ int KinectFusionReconstruction::FusePoints(const float *points, long long n, int
         check_rc(xs_tsdf_fuse_points_fold(value.ptr(0), weights.ptr(0), grad.ptr(0), value.step(), res3(), 0, res3()[2], fuse_acc_.ptr(), weight,
                                           max_integration_weight, counts.ptr() + 4, st), "fuse fold");
     }
-    // what ReintegrateFrames does after its write, all of it
-    ++volume_generation;
-    RebuildSignMap();    // the volume was written behind the integrate kernels' back
-    sign_map_stale_ = false;
-    invalidate_derived_maps();
-    CalculatePointCloud(vmaps_g_prev_d[0], nmaps_g_prev_d[0]);
-    ModelMapPyramid();
-    synchronize();
+    volume_written_off_path();
     if (counts5) hipSafeCall(hipMemcpy(counts5, counts.ptr(), 5 * sizeof(unsigned long long), hipMemcpyDeviceToHost));
     return 1;
 }

@@ -1,6 +1,10 @@
 // kf_internal.hpp — what more than one translation unit of the orchestrator needs and no caller of the class does
 // (KinectFusionReconstruction.cpp: lifecycle and frame path; kf_relocalize.cpp; kf_planning.cpp; kf_export.cpp: point cloud, mesh, counters, raw
-// volume; kf_checkpoint.cpp: saving, reading and restoring checkpoints; kf_second_map.cpp: the calls that take a second map; kf_reintegrate.cpp: frames taken out and fused again; kf_render.cpp: views of a map; kf_sample.cpp: the map asked at the caller's points; kf_register.cpp: a point cloud registered to a map).
+// volume; kf_checkpoint.cpp: saving, reading and restoring checkpoints; kf_second_map.cpp: the calls that take a second map; kf_reintegrate.cpp:
+// frames taken out and fused again; kf_render.cpp: views of a map; kf_sample.cpp: the map asked at the caller's points; kf_register.cpp: a point
+// cloud registered to a map; kf_fuse.cpp: a point cloud fused into the map; and the C ABI over them, xs_host_capi.cpp: the calls that take no
+// instance, xs_pipeline_capi.cpp: lifecycle, frame path, relocalisation, planning, export, statistics, xs_pipeline_maps_capi.cpp: the calls
+// that take a second map or edit or query a map).
 #pragma once
 #include "KinectFusionReconstruction.h"
 #include "pack_host.hpp"
@@ -29,6 +33,47 @@ inline void pack_real_pose(const xs_host::Matrix4cf &pose, float R9[9], float t3
         t3[r] = pose.m[r][3].real();
     }
 }
+
+// A pose as the C ABI passes it (32 floats: 4 x 4 (re, im) pairs, row-major) as a Matrix4cf, an array of them, and the way back.
+inline xs_host::Matrix4cf pose_of(const float *c2v32) {
+    xs_host::Matrix4cf m;
+    std::memcpy(static_cast<void *>(&m), c2v32, 32 * sizeof(float));
+    return m;
+}
+inline std::vector<xs_host::Matrix4cf> poses_of(const float *c2v32xP, int poses) {
+    std::vector<xs_host::Matrix4cf> m((size_t)(poses > 0 ? poses : 0));
+    for (int p = 0; p < poses; ++p) m[(size_t)p] = pose_of(c2v32xP + 32 * (size_t)p);
+    return m;
+}
+inline void pose_to(const xs_host::Matrix4cf &m, float *c2v32) { std::memcpy(c2v32, &m, 32 * sizeof(float)); }
+
+namespace xs_host { int checkpoint_info(const char *path, double *out32); }   // kf_checkpoint.cpp: what xs_host_checkpoint_info returns
+
+// An input array of a launch: the caller's pointer when that is device memory, otherwise a buffer of the call's own the array is copied to on `st`.
+template <class T>
+struct DeviceInput {
+    DeviceArray<T> own;
+    const T *ptr;
+    DeviceInput(const T *src, size_t count, bool on_device, hipStream_t st) : ptr(src) {
+        if (on_device) return;
+        own.create(count);
+        hipSafeCall(hipMemcpyAsync(own.ptr(), src, count * sizeof(T), hipMemcpyHostToDevice, st));
+        ptr = own.ptr();
+    }
+};
+// An optional output array of a launch (null: not wanted) that is written in chunks of at most `chunk` elements: the caller's pointer when that
+// is device memory, otherwise a buffer of the call's own, one chunk long, that fetch() copies to its place in the caller's host array.
+template <class T>
+struct StagedOutput {
+    DeviceArray<T> own;
+    T *out;
+    bool staged;
+    StagedOutput(T *out, size_t chunk, bool on_device) : out(out), staged(out && !on_device) { if (staged) own.create(chunk); }
+    T *at(size_t offset) { return staged ? own.ptr() : out ? out + offset : nullptr; }   // where a launch writes the chunk that begins at `offset`
+    void fetch(size_t offset, size_t count, hipStream_t st) {
+        if (staged) hipSafeCall(hipMemcpyAsync(out + offset, own.ptr(), count * sizeof(T), hipMemcpyDeviceToHost, st));
+    }
+};
 
 // An XSTSDF3 file read whole into host memory and validated in full (pack_validate).
 struct SparseFile {

@@ -82,14 +82,7 @@ int KinectFusionReconstruction::ReintegrateFrames(int n, const DeviceArray2D<ush
             if (frame_index[i] + 1 == (int)world2camera_record.size()) world2camera = world2camera_record.back();
         }
     }
-    // what MergeVolume does after its write, all of it
-    ++volume_generation;
-    RebuildSignMap();    // the volume was written behind the integrate kernels' back
-    sign_map_stale_ = false;
-    invalidate_derived_maps();
-    CalculatePointCloud(vmaps_g_prev_d[0], nmaps_g_prev_d[0]);
-    ModelMapPyramid();
-    synchronize();
+    volume_written_off_path();
     if (counts4) hipSafeCall(hipMemcpy(counts4, count.ptr(), 4 * sizeof(unsigned long long), hipMemcpyDeviceToHost));
     return 1;
 }

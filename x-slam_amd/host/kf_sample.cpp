@@ -10,28 +10,16 @@ namespace {
 using Out = KinectFusionReconstruction::SampleOutputs;
 bool any_output(const Out &o) { return o.status || o.value || o.dvalue || o.gradient || o.counts; }
 
-// The outputs of one launch over `count` points: the caller's own pointers when they are device memory, otherwise device buffers of the call's
-// own that fetch() copies to the caller's host arrays.
+// The outputs of one launch over `count` points, each where the launch writes it (StagedOutput); fetch() brings the staged ones to the caller.
 struct Staged {
-    DeviceArray<unsigned char> status;
-    DeviceArray<float> value, dvalue, gradient;
-    DeviceArray<unsigned long long> counts;
-    Out dev;
-    Staged(const Out &out, size_t count, bool on_device) : dev(out) {
-        if (on_device) return;
-        if (out.status) { status.create(count); dev.status = status.ptr(); }
-        if (out.value) { value.create(count); dev.value = value.ptr(); }
-        if (out.dvalue) { dvalue.create(count); dev.dvalue = dvalue.ptr(); }
-        if (out.gradient) { gradient.create(3 * count); dev.gradient = gradient.ptr(); }
-        if (out.counts) { counts.create(4); dev.counts = counts.ptr(); }
-    }
-    void fetch(const Out &out, size_t count, bool on_device, hipStream_t st) const {
-        if (on_device) return;
-        if (out.status) hipSafeCall(hipMemcpyAsync(out.status, dev.status, count, hipMemcpyDeviceToHost, st));
-        if (out.value) hipSafeCall(hipMemcpyAsync(out.value, dev.value, count * sizeof(float), hipMemcpyDeviceToHost, st));
-        if (out.dvalue) hipSafeCall(hipMemcpyAsync(out.dvalue, dev.dvalue, count * sizeof(float), hipMemcpyDeviceToHost, st));
-        if (out.gradient) hipSafeCall(hipMemcpyAsync(out.gradient, dev.gradient, 3 * count * sizeof(float), hipMemcpyDeviceToHost, st));
-        if (out.counts) hipSafeCall(hipMemcpyAsync(out.counts, dev.counts, 4 * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+    StagedOutput<unsigned char> status;
+    StagedOutput<float> value, dvalue, gradient;
+    StagedOutput<unsigned long long> counts;
+    Staged(const Out &out, size_t count, bool on_device)
+        : status(out.status, count, on_device), value(out.value, count, on_device), dvalue(out.dvalue, count, on_device),
+          gradient(out.gradient, 3 * count, on_device), counts(out.counts, 4, on_device) {}
+    void fetch(size_t count, hipStream_t st) {
+        status.fetch(0, count, st); value.fetch(0, count, st); dvalue.fetch(0, count, st); gradient.fetch(0, 3 * count, st); counts.fetch(0, 4, st);
     }
 };
 xs_sample_opts opts_of(int min_weight) {
@@ -50,18 +38,14 @@ int KinectFusionReconstruction::SampleVolume(const SecondMap &vol, const float *
     const bool points_dev = on_device & 1, out_dev = on_device & 2;
     hipStream_t st = current_stream();
     drain_device();
-    DeviceArray<float> points_d;
-    if (!points_dev) {
-        points_d.create(3 * (size_t)n);
-        hipSafeCall(hipMemcpyAsync(points_d.ptr(), points, 3 * (size_t)n * sizeof(float), hipMemcpyHostToDevice, st));
-    }
-    const Staged staged(out, (size_t)n, out_dev);
+    const DeviceInput<float> points_d(points, 3 * (size_t)n, points_dev, st);
+    Staged staged(out, (size_t)n, out_dev);
     const xs_sample_opts o = opts_of(min_weight);
-    const int rc = xs_tsdf_sample_points(n, points_dev ? points : points_d.ptr(), T16 ? xform : nullptr, vol.value, vol.weight, vol.grad, vol.step, vol.res,
-                                         vol.voxel_size, &o, staged.dev.status, staged.dev.value, staged.dev.dvalue, staged.dev.gradient, staged.dev.counts, st);
+    const int rc = xs_tsdf_sample_points(n, points_d.ptr, T16 ? xform : nullptr, vol.value, vol.weight, vol.grad, vol.step, vol.res, vol.voxel_size, &o,
+                                         staged.status.at(0), staged.value.at(0), staged.dvalue.at(0), staged.gradient.at(0), staged.counts.at(0), st);
     if (rc == (int)hipErrorInvalidValue) return -1;   // the arguments: nothing was launched
     check_rc(rc, "SamplePoints");
-    staged.fetch(out, (size_t)n, out_dev, st);
+    staged.fetch((size_t)n, st);
     hipSafeCall(hipStreamSynchronize(st));
     return 1;
 }
@@ -69,11 +53,8 @@ int KinectFusionReconstruction::SampleVolume(const SecondMap &vol, const float *
 int KinectFusionReconstruction::SamplePoints(const float *points, long long n, const double *T16, int min_weight, const SampleOutputs &out, int on_device) {
     if (shard_count > 1) return -2;   // a point's eight corners may straddle two ranks' z-slabs
     if (!tsdf_volume_d_ptr) return 0;
-    const DeviceArray2D<float> value = tsdf_volume_d_ptr->value(), grad = tsdf_volume_d_ptr->grad();
-    const DeviceArray2D<int> weight = tsdf_volume_d_ptr->weight();
-    if (value.step() != weight.step() || (out.dvalue && value.step() != grad.step())) return -1;
-    const SecondMap self{value.ptr(), weight.ptr(), out.dvalue ? grad.ptr() : nullptr, value.step(), {res3()[0], res3()[1], res3()[2]}, voxel_size,
-                         tsdf_volume_d_ptr->getTsdfTruncDist()};
+    SecondMap self;
+    if (OwnMap(out.dvalue != nullptr, self) != 1) return -1;
     return SampleVolume(self, points, n, T16, min_weight, out, on_device);
 }
 
@@ -95,9 +76,8 @@ int KinectFusionReconstruction::FrameResiduals(const unsigned short *depth, size
     const bool depth_dev = on_device & 1, out_dev = on_device & 2;
     if (depth_step == 0) depth_step = (size_t)cols * 2;
     if (depth_step % 2 != 0 || depth_step < (size_t)cols * 2) return -1;
-    const DeviceArray2D<float> value = tsdf_volume_d_ptr->value(), grad = tsdf_volume_d_ptr->grad();
-    const DeviceArray2D<int> weight = tsdf_volume_d_ptr->weight();
-    if (value.step() != weight.step() || (out.dvalue && value.step() != grad.step())) return -1;
+    SecondMap self;
+    if (OwnMap(out.dvalue != nullptr, self) != 1) return -1;
     float R[9], t[3];
     render_pose(c2v, stride, R, t);
     hipStream_t st = current_stream();
@@ -108,14 +88,14 @@ int KinectFusionReconstruction::FrameResiduals(const unsigned short *depth, size
         hipSafeCall(hipMemcpy2DAsync(depth_d.ptr(), (size_t)cols * 2, depth, depth_step, (size_t)cols * 2, (size_t)rows, hipMemcpyHostToDevice, st));
     }
     const size_t count = (size_t)rows * (size_t)cols;
-    const Staged staged(out, count, out_dev);
+    Staged staged(out, count, out_dev);
     const xs_sample_opts o = opts_of(min_weight);
     const int rc = xs_tsdf_sample_depth(depth_dev ? depth : depth_d.ptr(), depth_dev ? depth_step : (size_t)cols * 2, rows, cols, intr4 ? intr4 : &kinect_intrinsic.fx, R, t,
-                                        value.ptr(), weight.ptr(), out.dvalue ? grad.ptr() : nullptr, value.step(), res3(), voxel_size, &o, staged.dev.status,
-                                        staged.dev.value, staged.dev.dvalue, staged.dev.gradient, staged.dev.counts, st);
+                                        self.value, self.weight, self.grad, self.step, self.res, self.voxel_size, &o, staged.status.at(0), staged.value.at(0),
+                                        staged.dvalue.at(0), staged.gradient.at(0), staged.counts.at(0), st);
     if (rc == (int)hipErrorInvalidValue) return -1;
     check_rc(rc, "FrameResiduals");
-    staged.fetch(out, count, out_dev, st);
+    staged.fetch(count, st);
     hipSafeCall(hipStreamSynchronize(st));
     return 1;
 }

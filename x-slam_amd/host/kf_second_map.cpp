@@ -1,6 +1,7 @@
 // kf_second_map.cpp — what enters the orchestrator as a whole map (merge_host.hpp: SecondMap): the two ways to obtain one, from another instance and
 // from a checkpoint file, and the five operations that take one: merged into this volume, aligned to it beforehand, from a guess or from none, many
-// transforms scored against it, or compared with it voxel by voxel into clusters of change.  None of it runs during tracking.
+// transforms scored against it, or compared with it voxel by voxel into clusters of change; and what follows a write to the volume off the frame path.  Except for RebuildSignMap
+// after a write through xs_kf_volume_ptr, none of it runs during tracking.
 #include "kf_internal.hpp"
 #include "align_host.hpp"
 #include "align_search_host.hpp"
@@ -17,11 +18,14 @@ int KinectFusionReconstruction::OtherInstanceMap(KinectFusionReconstruction *oth
     if (other->shard_count > 1) return -2;
     if (!other->tsdf_volume_d_ptr) return -1;
     other->synchronize();
-    auto v = other->tsdf_volume_d_ptr->value(), g = other->tsdf_volume_d_ptr->grad();
-    auto w = other->tsdf_volume_d_ptr->weight();
+    return other->OwnMap(with_grad, out);
+}
+
+int KinectFusionReconstruction::OwnMap(bool with_grad, SecondMap &out) const {
+    auto v = tsdf_volume_d_ptr->value(), g = tsdf_volume_d_ptr->grad();
+    auto w = tsdf_volume_d_ptr->weight();
     if (v.step() != w.step() || (with_grad && v.step() != g.step())) return -1;
-    out = SecondMap{v.ptr(), w.ptr(), with_grad ? g.ptr() : nullptr, v.step(), {other->res3()[0], other->res3()[1], other->res3()[2]}, other->voxel_size,
-                    other->tsdf_volume_d_ptr->getTsdfTruncDist()};
+    out = SecondMap{v.ptr(), w.ptr(), with_grad ? g.ptr() : nullptr, v.step(), {res3()[0], res3()[1], res3()[2]}, voxel_size, tsdf_volume_d_ptr->getTsdfTruncDist()};
     return 1;
 }
 
@@ -53,6 +57,24 @@ void KinectFusionReconstruction::drain_device() {
     synchronize();
     hipSafeCall(hipDeviceSynchronize());
 }
+// The sign map from the volume alone (allocation, checkpoint, anything that wrote the value array without the integrate kernels).
+void KinectFusionReconstruction::RebuildSignMap() {
+    ++volume_generation;   // the documented "the volume was written" call: the relocalisation index is rebuilt too
+    if (!sign_map_on() || !sign_map_.ptr() || !tsdf_volume_d_ptr) return;
+    DeviceArray2D<float> value = tsdf_volume_d_ptr->value();
+    check_rc(xs_signmap_rebuild_slab(sign_map_.ptr(), res3(), raycast_sign_map_shift, tsdf_volume_d_ptr->getTsdfTruncDist(), value.ptr(0), value.step(),
+                                     zs0, zs1, current_stream()), "sign map");
+}
+// A merge, fused points or reintegrated frames wrote the volume: everything derived from it follows (volume_generation moves here and in RebuildSignMap).
+void KinectFusionReconstruction::volume_written_off_path() {
+    ++volume_generation;
+    RebuildSignMap();
+    sign_map_stale_ = false;
+    invalidate_derived_maps();
+    CalculatePointCloud(vmaps_g_prev_d[0], nmaps_g_prev_d[0]);
+    ModelMapPyramid();
+    synchronize();
+}
 
 // ---- merging a second map ----------------------------------------------------------------------------------
 int KinectFusionReconstruction::MergeVolume(const SecondMap &src, const double *T16, int min_weight, unsigned long long *written) {
@@ -73,13 +95,7 @@ int KinectFusionReconstruction::MergeVolume(const SecondMap &src, const double *
     hipSafeCall(hipMemsetAsync(count.ptr(), 0, sizeof(unsigned long long), current_stream()));
     check_rc(xs_tsdf_merge(value.ptr(0), weight.ptr(0), grad.ptr(0), value.step(), res3(), 0, res3()[2], src.value, src.weight, src.grad, src.step, src.res,
                            xform, min_weight, max_integration_weight, 0u, count.ptr(), ws.ptr(), current_stream()), "merge");
-    ++volume_generation;
-    RebuildSignMap();    // the volume was written behind the integrate kernels' back
-    sign_map_stale_ = false;
-    invalidate_derived_maps();
-    CalculatePointCloud(vmaps_g_prev_d[0], nmaps_g_prev_d[0]);
-    ModelMapPyramid();
-    synchronize();
+    volume_written_off_path();
     if (written) hipSafeCall(hipMemcpy(written, count.ptr(), sizeof(unsigned long long), hipMemcpyDeviceToHost));
     return 1;
 }
@@ -103,12 +119,8 @@ int KinectFusionReconstruction::AlignVolume(const SecondMap &src, const double *
     BandIndexPrepare();
     ensure_reduce_workspace(reloc_.align_ws, xs_tsdf_align_workspace_bytes(XS_ALIGN_MAX_TRANSFORMS), "align workspace");
     if (reloc_.align_sums.size() < (size_t)XS_ALIGN_MAX_TRANSFORMS * 29) reloc_.align_sums.create((size_t)XS_ALIGN_MAX_TRANSFORMS * 29);
-    std::vector<std::vector<double>> history((size_t)N);   // (always kept: the last pass's sums pick the winner)
-    std::vector<double> last((size_t)N * 29, 0.0);
-    std::vector<int> ok((size_t)N, 0);
     std::vector<float> maps((size_t)XS_ALIGN_MAX_TRANSFORMS * 144);
-    int passes = 0;
-    gn_batch_loop(N, iterations, history.data(), ok.data(), XS_ALIGN_MAX_TRANSFORMS,
+    const GnMultistart r = gn_multistart(N, iterations, XS_ALIGN_MAX_TRANSFORMS, true,   // (the loss pass always: its sums pick the winner)
         [&](const int *starts, int n, double *sums) {
             for (int i = 0; i < n; ++i) {
                 float *m = &maps[(size_t)i * 144];
@@ -121,29 +133,14 @@ int KinectFusionReconstruction::AlignVolume(const SecondMap &src, const double *
             check_rc(xs_tsdf_align_terms(n, &reloc_.band, src.value, src.weight, src.step, src.res, maps.data(), min_weight, max_residual, reloc_.align_ws.ptr(),
                                          reloc_.align_sums.ptr(), current_stream()), "AlignTerms");
             fetch_sums(reloc_.align_sums.ptr(), (size_t)n * 29, sums);
-            ++passes;
-            for (int i = 0; i < n; ++i) {
-                gn_scale_sums(sums + 29 * i, sums + 29 * i);
-                std::copy(sums + 29 * i, sums + 29 * i + 29, last.begin() + (size_t)starts[i] * 29);
-            }
+            for (int i = 0; i < n; ++i) gn_scale_sums(sums + 29 * i, sums + 29 * i);
         },
         [&](int n, const double *s, int) { return align_step(s, damping, &T[(size_t)n * 16]); });
-    // the winner: the start that ended ok, with at least six voxels in its last pass too (gn_batch_loop lets the loss pass end ok whatever it
-    // counts: a start that its last step, or no step at all, left off the other map is no result), with the highest S = count - sum r^2
-    // (relocalize_global's score; ties: the lower index)
-    auto S = [&](int n) { return last[(size_t)n * 29 + 28] - last[(size_t)n * 29 + 27]; };
-    int win = -1, ended_ok = 0;
-    for (int n = 0; n < N; ++n) {
-        if (!ok[(size_t)n] || last[(size_t)n * 29 + 28] < 6) continue;
-        ++ended_ok;
-        if (win < 0 || S(n) > S(win)) win = n;
-    }
-    if (report) { report[4] = (double)passes; report[5] = (double)ended_ok; report[6] = (double)reloc_.band.count; }
-    if (win < 0) return 0;
-    const double *s = &last[(size_t)win * 29];
-    for (int i = 0; i < 16; ++i) T16_out[i] = T[(size_t)win * 16 + i];
-    if (report) { report[0] = (double)win; report[1] = s[28]; report[2] = s[27]; report[3] = s[28] > 0 ? s[27] / s[28] : 0.0; }
-    if (loss_history) *loss_history = history[(size_t)win];
+    gn_multistart_report(r, report);
+    if (report) report[6] = (double)reloc_.band.count;
+    if (r.win < 0) return 0;
+    for (int i = 0; i < 16; ++i) T16_out[i] = T[(size_t)r.win * 16 + i];
+    if (loss_history) *loss_history = r.history;
     return 1;
 }
 

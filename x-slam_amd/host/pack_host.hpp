@@ -1,9 +1,8 @@
 // pack_host.hpp — the host's side of the brick-sparse volume checkpoint XSTSDF3 (INTEGRATION.md "Checkpoint formats"):
 // the file header, the words a brick of a given class takes in the payload, the validation of a header with its class bytes against the file's
 // length, the exclusive sum of the words per brick, the partition of the bricks into chunks that fit a staging buffer, and the file rules of the
-// dense XSTSDF2.  No device call and no HIP header: kf_checkpoint.cpp uses it around the kernels of csrc/xs_pack.hip and in its reader,
-// xs_pipeline_capi.cpp for xs_host_checkpoint_info, xs_pack.hip itself for the brick grid, and tests/cxx/pack_selftest.cpp runs all of it under the
-// sanitizers without a GPU.
+// dense XSTSDF2.  No device call and no HIP header: kf_checkpoint.cpp uses it around the kernels of csrc/xs_pack.hip, in its reader and for
+// xs_host_checkpoint_info, xs_pack.hip itself for the brick grid, and tests/cxx/pack_selftest.cpp runs all of it under the sanitizers without a GPU.
 //
 // The file, little endian:  PackHeader (88 bytes) | n_poses x 128 bytes (Matrix4cf, as XSTSDF2) | nbricks class bytes, zero-padded to a multiple of 4 |
 // payload_words 32-bit words.  Brick (bx, by, bz) of 8 x 8 x 8 voxels, bz counted from the first stored plane, has index (bz nby + by) nbx + bx.
