@@ -1017,6 +1017,41 @@ int xs_tsdf_register_terms(int transforms, long long n, const float *points3xN_d
                            size_t vol_step, const int *res, float voxel_size, int min_weight, float max_residual, void *workspace,
                            double *out29xN_dev, void *stream);
 
+/* ---- the loss of many transforms of a point cloud in one pass over the points (xs_register.hip: k_register_score) --
+ * No counterpart in the reference.  {sum r^2, count} of the residual above, without its Jacobian, for `transforms` (1 ..
+ * XS_REGISTER_SCORE_MAX_TRANSFORMS) transforms over every stride-th of the n points in one launch: what xs_tsdf_score_transforms is to a
+ * second map, and what finds the transform xs_tsdf_register_terms starts from when nobody supplies one.  The points, the volume and the
+ * 64-bit row offsets: as for xs_tsdf_register_terms.  xform12xP: host array, never null, transform p's row-major R, then t at + 12 p; the call
+ * copies it into the workspace on the stream (hipMemcpyAsync from pageable memory: it may be reused when the call returns).  Transform p's
+ * two doubles land at out2xP_dev + 2 p: {sum r^2, count}; nothing but the pairs and the workspace is written.
+ *
+ * Scored points: points stride i, i = 0 .. ceil(n / stride) - 1 (stride 1: the whole cloud); scored point i belongs to chunk i / 64, lane
+ * i % 64.  Scored point q, transform p; every float operation is one IEEE float32 operation in the order written:
+ *   1. P[c] = ((R[c][0] * q[0] + R[c][1] * q[1]) + R[c][2] * q[2]) + t[c]:  xs_tsdf_sample_points' transformed point.
+ *   2. (status, r) = the status and value xs_tsdf_sample_points defines at P with this min_weight and no grad array (the same device
+ *      function, F of xs_trilinear.h: g = P / voxel_size - 0.5f, only the corners on axes with a fraction > 0 read and tested).
+ *   3. The point is KEPT iff status == OK && fabsf(r) <= max_residual (a NaN drops).  There is no gradient and no gradient gate: a point
+ *      whose gradient xs_tsdf_register_terms refuses (one of its six outer samples is not OK) counts here, so a transform's count may exceed
+ *      that call's, never fall below it.
+ *   4. A kept point adds the float32 product r * r and counts 1.
+ * Order (xs_tsdf_score_transforms'): wave w of workgroup (b, tile) takes chunks 4 b + w, + 4 nblocks, ... with nblocks =
+ * clamp(ceil(ceil(scored / 64) / 4), 1, 1024); per (chunk, transform) a six-level pairwise float tree across the wave over kept-or-zero
+ * terms, everything after that in double: a lane per transform adds its chunks' tree sums in order, then the four waves in wave order, one
+ * record per workgroup, one arrival ticket per tile of 64 transforms, and the tile's last workgroup adds the records in index order.  The
+ * order is a function of ceil(n / stride) alone: two launches on the same inputs give equal bytes, and transform p's pair does not depend on
+ * `transforms`, on p or on the other transforms.  All terms are >= 0, so |sum - sum of the float32 terms in double| <= 8 * 2^-24 * sum.  No
+ * floating-point atomics.  A transform that keeps no point yields {+0.0, 0}.
+ * Workspace: xs_tsdf_score_points_workspace_bytes(transforms) bytes (0 outside 1 .. XS_REGISTER_SCORE_MAX_TRANSFORMS): one arrival ticket per
+ * tile in its first 256 bytes, the transforms, the records.  Zero the first 256 bytes ONCE after allocation (xs_tsdf_reduce_workspace_init);
+ * every launch leaves each ticket at zero again.  One launch at a time per workspace.  No synchronisation.
+ * hipErrorInvalidValue, with nothing launched and nothing written: xs_tsdf_register_terms' refusals, transforms outside 1 .. 4096,
+ * stride < 1. */
+#define XS_REGISTER_SCORE_MAX_TRANSFORMS 4096
+size_t xs_tsdf_score_points_workspace_bytes(int transforms);
+int xs_tsdf_score_points(int transforms, long long n, int stride, const float *points3xN_dev, const float *xform12xP, const float *value,
+                         const int *weight, size_t vol_step, const int *res, float voxel_size, int min_weight, float max_residual, void *workspace,
+                         double *out2xP_dev, void *stream);
+
 /* ---- fusing a point cloud into the volume: a scatter of integers, then a fold (xs_fuse.hip) ---------------------
  * No counterpart in the reference.  Every other call that writes the volume takes a depth image or a second volume and gathers; this one
  * takes points with a sensor origin, walks each point's ray, and SCATTERS: one lane per point, adding to voxels that other lanes add to as

@@ -544,6 +544,67 @@ int xs_kf_register_checkpoint(void *kf, const char *path, long long n, const flo
                               double damping, int min_weight, float max_residual, double *T16_out, double *report7, double *loss_history);
 int xs_host_register_step(const double *s29, double damping, double *T16);
 
+/* ---- Scoring many transforms of a point cloud, and registration with no starting guess (xs_tsdf_score_points in
+ * xslam_amd.h: the contract) ------------------------------------------------------------------------------------------------------------
+ * score_point_transforms: {sum r^2, count} of "the map's value at T p" over every stride-th of the n points (as xs_kf_register_points takes
+ * them) for each of the P transforms T16xP + 16 p (real 4 x 4, row-major: cloud frame to the map's volume frame, each rounded once to
+ * float32 as xs_kf_register_points rounds its starts), in launches of 4096; out2xP + 2 p.  No gradient gate: a point counts wherever the map
+ * holds a value at T p with min_weight and |value| <= max_residual.  score_point_transforms asks this instance's map, _map another
+ * instance's, _checkpoint a checkpoint of a whole volume in either format.  The device is drained before and the stream after; nothing of
+ * any map or cache is modified.  Return 1; 0 without a volume; -1 on bad arguments (n outside 1 .. 2^30, a null pointer, P < 1, stride < 1,
+ * min_weight < 1, max_residual <= 0 or not finite, a T that is not finite in float32, a second map the merge would refuse); -2 in shard mode.
+ *
+ * register_points_global: xs_kf_register_points without a guess.  The cloud's centroid (xs_host_points_centroid over the scored points) and
+ * the map's band centroid give every candidate rotation its translation; round 0 scores opts->candidates transforms of
+ * xs_host_align_search_free with "this" = the cloud and "other" = the map (or the opts->user_n transforms of opts->user_T16xN, when given)
+ * and keeps the opts->keep best by S = count - sum r^2; each of opts->rounds further rounds scores floor(candidates / keep) transforms of
+ * xs_host_align_search_around about every kept one (pivot: the cloud's centroid; boxes refine_t and refine_r, halved per round; a kept
+ * transform is entry 0 of its own group, so the best S never falls) and keeps the best again: xs_kf_align_map_global's rounds and ranking.
+ * The kept transforms then start xs_kf_register_points' loop over ALL n points, whose winner and "ended ok" rule decide.
+ * report12 = {the winner's rank after the last round, its S before refinement on the strided cloud, its count, sum r^2 and mean loss after
+ * refinement, scoring launches run, registration passes run, starts that ended ok, n, scored points per transform, the distance of the
+ * map's band centroid from the image of the cloud's centroid under the winner, 0}.
+ * The score cannot tell a scene from its image under one of its own symmetries: a symmetric scene has several equally good answers.
+ * opts NULL: the defaults, which xs_kf_register_search_defaults writes (box_t and refine_t: the map's truncation distance; max_residual 0.9,
+ * xs_kf_register_points' usual one: a point in seen free space has r = 1 and adds nothing to S at 0.9 or at 1).  Otherwise every field is
+ * taken as given.  Return codes: xs_kf_register_points', including 0 with T16_out untouched when no start ends ok or the map has no band
+ * voxel; -1 also for a wrong struct_bytes, candidates < 1, keep outside 1 .. 32, rounds < 0, stride < 1, a box that is negative or not
+ * finite, user_n < 0 or user_n > 0 without user_T16xN, and for ceil(n / stride) > 2^24 scored points (raise the stride: the search needs no
+ * more, and the final loop runs over all n regardless); -2 in shard mode.  Nothing of any map or cache is modified;
+ * xs_kf_volume_generation stays.
+ * xs_host_points_centroid: the mean of points stride i, i = 0 .. ceil(n / stride) - 1 (host array, n x 3 floats), each axis added in
+ * double in index order and divided by the scored count; 0, or -1 (nothing written) for n < 1, stride < 1 or a null pointer.  CPU only. */
+typedef struct xs_register_search_opts {
+    unsigned struct_bytes;        /* sizeof(xs_register_search_opts) */
+    int candidates;               /* 2048 */
+    int keep;                     /* 8 (1 .. 32) */
+    int rounds;                   /* 2 */
+    int stride;                   /* 4 */
+    int iterations;               /* 10 */
+    int min_weight;               /* 1 */
+    int user_n;                   /* 0 */
+    double box_t;                 /* metres; the truncation distance */
+    double refine_t;              /* metres; the truncation distance */
+    double refine_r;              /* radians; 0.25 */
+    double damping;               /* 1e-3 */
+    double max_residual;          /* 0.9 */
+    const double *user_T16xN;     /* NULL */
+} xs_register_search_opts;
+void xs_kf_register_search_defaults(void *kf, xs_register_search_opts *opts);
+int xs_kf_score_point_transforms(void *kf, long long n, const float *points, int on_device, int P, const double *T16xP, int stride, int min_weight,
+                                 float max_residual, double *out2xP);
+int xs_kf_score_point_transforms_map(void *kf, void *other_kf, long long n, const float *points, int on_device, int P, const double *T16xP, int stride,
+                                     int min_weight, float max_residual, double *out2xP);
+int xs_kf_score_point_transforms_checkpoint(void *kf, const char *path, long long n, const float *points, int on_device, int P, const double *T16xP,
+                                            int stride, int min_weight, float max_residual, double *out2xP);
+int xs_kf_register_points_global(void *kf, long long n, const float *points, int on_device, const xs_register_search_opts *opts, double *T16_out,
+                                 double *report12);
+int xs_kf_register_points_global_map(void *kf, void *other_kf, long long n, const float *points, int on_device, const xs_register_search_opts *opts,
+                                     double *T16_out, double *report12);
+int xs_kf_register_points_global_checkpoint(void *kf, const char *path, long long n, const float *points, int on_device,
+                                            const xs_register_search_opts *opts, double *T16_out, double *report12);
+int xs_host_points_centroid(const float *points, long long n, int stride, double *out3);
+
 /* A registered point cloud fused into this instance's map (xs_tsdf_fuse_points_accumulate and xs_tsdf_fuse_points_fold
  * in xslam_amd.h: the contract).  points: n x 3 floats in metres (n >= 1; on_device bit 0: device memory) and origin3, the sensor's position,
  * in a frame that T16 (real 4 x 4, row-major, as xs_kf_register_points returns it; NULL: the volume frame, the bits as they are) takes to the

@@ -215,6 +215,8 @@ _SIGS = {
     "xs_tsdf_fuse_points_fold": (C.c_int, [_vp, _vp, _vp, _sz, _i32p, C.c_int, C.c_int, _vp, C.c_int, C.c_int, _vp, _vp]),
     "xs_tsdf_register_workspace_bytes": (_sz, [C.c_int]),
     "xs_tsdf_register_terms": (C.c_int, [C.c_int, C.c_longlong, _vp, _f32p, _vp, _vp, _sz, _i32p, C.c_float, C.c_int, C.c_float, _vp, _vp, _vp]),
+    "xs_tsdf_score_points_workspace_bytes": (_sz, [C.c_int]),
+    "xs_tsdf_score_points": (C.c_int, [C.c_int, C.c_longlong, C.c_int, _vp, _f32p, _vp, _vp, _sz, _i32p, C.c_float, C.c_int, C.c_float, _vp, _vp, _vp]),
     "xs_mesh_workspace_bytes": (_sz, [_i32p, C.POINTER(MeshOpts)]),
     "xs_extract_mesh": (C.c_int, [_vp, _vp, _vp, _sz, _i32p, C.c_float, C.POINTER(MeshOpts), _vp, _vp, _vp, _vp, _sz, _vp, _sz, _vp,
                                   C.POINTER(_sz), C.POINTER(_sz), _vp]),
@@ -1132,6 +1134,30 @@ def register_terms(n, points, xforms, value, weight, vol_step, res, voxel_size, 
     check(_lib.xs_tsdf_register_terms(int(transforms), int(n), _ptr(points), None if m is None else m.ctypes.data_as(_f32p), _ptr(value), _ptr(weight), vol_step,
                                       None if r is None else r.ctypes.data_as(_i32p), float(voxel_size), int(min_weight), float(max_residual), _ptr(workspace),
                                       _ptr(out29xN), _stream(stream)))
+
+
+REGISTER_SCORE_MAX_TRANSFORMS = 4096   # XS_REGISTER_SCORE_MAX_TRANSFORMS
+
+
+def tsdf_score_points_workspace_bytes(transforms):
+    """xs_tsdf_score_points_workspace_bytes (host only): tickets, transforms and records for up to `transforms` transforms; 0 outside 1 .. 4096.
+    Zero its first 256 bytes once (tsdf_reduce_workspace_init)."""
+    return int(_lib.xs_tsdf_score_points_workspace_bytes(int(transforms)))
+
+
+def tsdf_score_points(n, points, xforms, value, weight, vol_step, res, voxel_size, min_weight, max_residual, workspace, out2xP, stride=1, transforms=None, stream=None):
+    """xs_tsdf_score_points: {sum r^2, count} of P transforms xforms [P, 12] float32 (row-major R, then t: cloud frame to volume frame) over every
+    stride-th of n points (device float32 [n, 3], metres) against a volume (device tensors or addresses of plane 0) in one launch; transform
+    p's pair lands at out2xP[2 p : 2 p + 2] (float64 device tensor).  transforms: P, where it is not to be taken from xforms.  A None among the
+    arrays goes through as a null pointer.  No synchronisation."""
+    m = None if xforms is None else np.ascontiguousarray(xforms, dtype=np.float32).reshape(-1)
+    if transforms is None:
+        assert m is not None and m.size % 12 == 0
+        transforms = m.size // 12
+    r = None if res is None else _ia(res, 3)
+    check(_lib.xs_tsdf_score_points(int(transforms), int(n), int(stride), _ptr(points), None if m is None else m.ctypes.data_as(_f32p), _ptr(value), _ptr(weight),
+                                    vol_step, None if r is None else r.ctypes.data_as(_i32p), float(voxel_size), int(min_weight), float(max_residual),
+                                    _ptr(workspace), _ptr(out2xP), _stream(stream)))
 
 
 FUSE_MAX_POINTS, FUSE_MAX_HALF_STEPS = (1 << 24) - 1, 256   # XS_FUSE_MAX_POINTS, XS_FUSE_MAX_HALF_STEPS

@@ -21,6 +21,7 @@
 #include <string.h>
 #include "xs_gn_band.h"
 #include "xs_complex.h"
+#include "xs_score_fold.h"
 #include "../../include/xslam_amd.h"
 
 static_assert(XS_ALIGN_MAX_TRANSFORMS == 32, "the header's bound");
@@ -183,8 +184,8 @@ extern "C" int xs_tsdf_align_terms(int transforms, const xs_band_index *index, c
 // p.  A wave none of whose lanes lies inside the source, or none of whose lanes passes the weight gate, goes on to the next transform without
 // the loads: what it leaves out is the addition of +0.0 to a sum that is never -0.0, and of 0 to a count.  Then per workgroup: the four waves
 // in wave order, one record of 64 doubles + 64 counts, an arrival ticket per tile, and the tile's last workgroup adds the records in index
-// order.  Every step's order is a function of the index's count and the stride alone.
-enum { ASCORE_TILE = 64, ASCORE_XFORMS_OFFSET = 256, ASCORE_MAX_BLOCKS = 1024, ASCORE_RECORD_BYTES = ASCORE_TILE * (sizeof(double) + sizeof(unsigned)) };
+// order (score_tile_fold_and_finish of xs_score_fold.h, shared with k_register_score).  Every step's order is a function of the index's count and the stride alone.
+enum { ASCORE_TILE = SCORE_TILE, ASCORE_XFORMS_OFFSET = 256, ASCORE_MAX_BLOCKS = SCORE_MAX_BLOCKS, ASCORE_RECORD_BYTES = SCORE_RECORD_BYTES };   // (xs_score_fold.h)
 static_assert(XS_ALIGN_SCORE_MAX_TRANSFORMS / ASCORE_TILE * sizeof(unsigned) == ASCORE_XFORMS_OFFSET, "one ticket per tile in the first 256 bytes");
 struct AlignXform { float m[12]; };
 static size_t ascore_records_offset() { return ASCORE_XFORMS_OFFSET + (size_t)XS_ALIGN_SCORE_MAX_TRANSFORMS * sizeof(AlignXform); }
@@ -206,10 +207,7 @@ struct AlignScoreArgs {
 };
 
 __global__ void __launch_bounds__(256) k_align_score(const AlignScoreArgs g) {
-    __shared__ double s_sum[4][ASCORE_TILE];
-    __shared__ unsigned s_cnt[4][ASCORE_TILE];
-    __shared__ unsigned s_last;
-    const int lane = threadIdx.x, wave = __builtin_amdgcn_readfirstlane(threadIdx.y), tid = wave * 64 + lane;
+    const int lane = threadIdx.x, wave = __builtin_amdgcn_readfirstlane(threadIdx.y);
     const unsigned nblocks = gridDim.x, bid = blockIdx.x, tile = blockIdx.y;
     const int p0 = (int)tile * ASCORE_TILE, np = min(ASCORE_TILE, g.transforms - p0);   // (the last tile may be partial: its other lanes keep zeros)
     const AlignXform *__restrict__ xforms = g.xforms + p0;
@@ -276,56 +274,7 @@ __global__ void __launch_bounds__(256) k_align_score(const AlignScoreArgs g) {
             if (lane == j) { acc += (double)s; cnt += n; }
         }
     }
-    // the four waves in wave order, then one record per workgroup: transform lane's sum and count, stored by the lanes of wave 0
-    s_sum[wave][lane] = acc;
-    s_cnt[wave][lane] = cnt;
-    __syncthreads();
-    char *tile_records = g.records + (size_t)tile * nblocks * ASCORE_RECORD_BYTES;
-    if (tid < ASCORE_TILE) {
-        const double s = ((s_sum[0][tid] + s_sum[1][tid]) + s_sum[2][tid]) + s_sum[3][tid];
-        const unsigned n = ((s_cnt[0][tid] + s_cnt[1][tid]) + s_cnt[2][tid]) + s_cnt[3][tid];
-        char *rec = tile_records + (size_t)bid * ASCORE_RECORD_BYTES;
-        __hip_atomic_store(reinterpret_cast<double *>(rec) + tid, s, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __hip_atomic_store(reinterpret_cast<unsigned *>(rec + ASCORE_TILE * sizeof(double)) + tid, n, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-    // the hand-off of block_fold_and_finish_of (xs_gn_band.h): write-through record stores by wave 0, acknowledged, then its first lane's ticket
-    if (wave == 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    if (tid == 0) {
-        const unsigned tk = __hip_atomic_fetch_add(g.tickets + tile, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        s_last = tk == nblocks - 1 ? 1u : 0u;
-        if (s_last) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    }
-    __syncthreads();
-    if (!s_last) return;
-    // the tile's last workgroup: thread (q, l) adds transform l's records q, q + 4, ... in that order, eight loads in flight; the four row
-    // groups are then added in group order
-    {
-        const int l = tid % ASCORE_TILE, q = tid / ASCORE_TILE;
-        double s = 0.0;
-        unsigned long long n = 0;
-        auto rsum = [&](unsigned b) { return reinterpret_cast<const double *>(tile_records + (size_t)b * ASCORE_RECORD_BYTES)[l]; };
-        auto rcnt = [&](unsigned b) { return reinterpret_cast<const unsigned *>(tile_records + (size_t)b * ASCORE_RECORD_BYTES + ASCORE_TILE * sizeof(double))[l]; };
-        unsigned b = q;
-        for (; b + 4 * 7 < nblocks; b += 4 * 8) {
-            double v[8]; unsigned m[8];
-#pragma unroll
-            for (int k = 0; k < 8; ++k) { v[k] = rsum(b + 4 * k); m[k] = rcnt(b + 4 * k); }
-#pragma unroll
-            for (int k = 0; k < 8; ++k) { s += v[k]; n += m[k]; }
-        }
-        for (; b < nblocks; b += 4) { s += rsum(b); n += rcnt(b); }
-        __shared__ unsigned long long s_n[4][ASCORE_TILE];
-        s_sum[q][l] = s;   // (wave 0 read its workgroup's own sums before the ticket's barrier)
-        s_n[q][l] = n;
-        __syncthreads();
-        if (tid < np) {
-            g.out[2 * (size_t)(p0 + tid)] = ((s_sum[0][tid] + s_sum[1][tid]) + s_sum[2][tid]) + s_sum[3][tid];
-            g.out[2 * (size_t)(p0 + tid) + 1] = (double)(((s_n[0][tid] + s_n[1][tid]) + s_n[2][tid]) + s_n[3][tid]);
-        }
-        // the ticket goes back to zero for the next launch on this workspace (xs_tsdf_reduce_workspace_init zeroes it once)
-        if (tid == 0) __hip_atomic_store(g.tickets + tile, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
+    score_tile_fold_and_finish(acc, cnt, g.records, g.tickets, g.out, p0, np);   // xs_score_fold.h: the waves, the record, the ticket, the last workgroup's fold
 }
 
 extern "C" size_t xs_tsdf_score_transforms_workspace_bytes(int transforms) {

@@ -19,6 +19,7 @@
 #include <vector>
 
 struct xs_align_search_opts;   // include/xslam_amd_pipeline.h
+struct xs_register_search_opts;
 
 class KinectFusionReconstruction {
 public:
@@ -462,6 +463,21 @@ public:
                        float max_residual, double *T16_out, double report[7], std::vector<double> *loss_history);
     int RegisterSecondMap(const xs_host::SecondMap &src, const float *points, long long n, int on_device, const double *T16xN, int N, int iterations,
                           double damping, int min_weight, float max_residual, double *T16_out, double report[7], std::vector<double> *loss_history);
+    // Many transforms of a cloud scored against a map, and registration with no starting guess (kf_register.cpp; DESIGN.md section 4.32;
+    // xs_tsdf_score_points in include/xslam_amd.h: the contract; register_search_host.hpp: the host's side).  src: the map (null: THIS map,
+    // through OwnMap, so that all sources take one path).  ScorePointTransforms: every T16xP + 16 p rounded by register_xform12, launches of
+    // XS_REGISTER_SCORE_MAX_TRANSFORMS over every stride-th point, {sum r^2, count} per transform.  RegisterPointsGlobal: AlignVolumeGlobal's
+    // rounds and ranking with the cloud as "this" (its centroid: points_centroid over the scored points, for a device cloud over a strided
+    // copy of them) and the map as "other" (second_map_centroid, for this instance's map too: no cache is touched), then RegisterVolume's
+    // loop over all n points from the kept transforms.  opts null: RegisterSearchDefaults.  report12 as AlignVolumeGlobal's with [8] = n,
+    // [9] = scored points per transform, [10] = the distance of the map's band centroid from the image of the cloud's under the winner.
+    // Both: 1; 0 without a volume (the search also when nothing ended ok or the map has no band voxel, T16_out untouched); -1 on bad
+    // arguments (the search also for more than 2^24 scored points: raise the stride); -2 in shard mode.  Nothing is modified.
+    int ScorePointTransforms(const xs_host::SecondMap *src, const float *points, long long n, int on_device, const double *T16xP, int P, int stride,
+                             int min_weight, float max_residual, double *out2xP);
+    void RegisterSearchDefaults(struct xs_register_search_opts *opts) const;
+    int RegisterPointsGlobal(const xs_host::SecondMap *src, const float *points, long long n, int on_device, const struct xs_register_search_opts *opts,
+                             double *T16_out, double report[12]);
 
     // A registered point cloud fused into THIS map (kf_fuse.cpp; xs_tsdf_fuse_points_accumulate and
     // xs_tsdf_fuse_points_fold in include/xslam_amd.h: the contract; fuse_host.hpp: the host's side).  points: n x 3 float32 metres (on_device
@@ -540,6 +556,8 @@ private:
         DeviceArray<double> ascore_sums;           // XS_ALIGN_SCORE_MAX_TRANSFORMS x 2
         DeviceArray<unsigned char> register_ws;    // xs_tsdf_register_workspace_bytes(XS_REGISTER_MAX_TRANSFORMS)
         DeviceArray<double> register_sums;         // XS_REGISTER_MAX_TRANSFORMS x 29
+        DeviceArray<unsigned char> rscore_ws;      // xs_tsdf_score_points_workspace_bytes(XS_REGISTER_SCORE_MAX_TRANSFORMS)
+        DeviceArray<double> rscore_sums;           // XS_REGISTER_SCORE_MAX_TRANSFORMS x 2
     } reloc_;
     const float *GaussNewtonDenseView();       // the owned planes as the dense array the Gauss-Newton kernels index (packed into gn_dense when pitched)
     void BandIndexPrepare();                   // (re)builds the band index when the volume changed since it was built
@@ -597,6 +615,11 @@ private:
     // the registration loop over a volume described as a SecondMap (this map's included), with the staging of host points
     int RegisterVolume(const xs_host::SecondMap &vol, const float *points, long long n, int on_device, const double *T16xN, int N, int iterations, double damping,
                        int min_weight, float max_residual, double *T16_out, double report[7], std::vector<double> *loss_history);
+    // the map a point-cloud call asks: src, or this volume when src is null; -2 in shard mode, 0 without a volume, -1 for a map that is refused
+    int register_map_of(const xs_host::SecondMap *src, xs_host::SecondMap &out) const;
+    // P transforms (float xform12 each) scored over every stride-th of n device points, in launches of XS_REGISTER_SCORE_MAX_TRANSFORMS
+    int ScorePointsVolume(const xs_host::SecondMap &vol, const float *points_dev, long long n, const float *xform12xP, int P, int stride, int min_weight,
+                          float max_residual, double *out2xP, int *launches);
     DeviceArray<unsigned long long> fuse_acc_; // FusePoints' accumulator: one word per voxel, zero between calls
     DeviceArray2D<ushort> depth_ingest_d_;     // device copy of a host frame (ProcessFrameHost)
     ushort *ingest_pinned_[2] = {nullptr, nullptr};

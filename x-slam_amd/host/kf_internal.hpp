@@ -48,6 +48,9 @@ inline std::vector<xs_host::Matrix4cf> poses_of(const float *c2v32xP, int poses)
 inline void pose_to(const xs_host::Matrix4cf &m, float *c2v32) { std::memcpy(c2v32, &m, 32 * sizeof(float)); }
 
 namespace xs_host { int checkpoint_info(const char *path, double *out32); }   // kf_checkpoint.cpp: what xs_host_checkpoint_info returns
+// kf_second_map.cpp: the centroid of a map's band from a band build into temporary buffers (no cache of any instance is touched): 1; 0 for an
+// empty band; -1 for a resolution the band build does not take.  AlignVolumeGlobal asks it for the other map, RegisterPointsGlobal for the map.
+int second_map_centroid(const xs_host::SecondMap &src, double centroid3[3]);
 
 // An input array of a launch: the caller's pointer when that is device memory, otherwise a buffer of the call's own the array is copied to on `st`.
 template <class T>

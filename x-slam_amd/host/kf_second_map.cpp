@@ -188,8 +188,9 @@ bool search_opts_ok(const xs_align_search_opts &o) {
     if (o.user_n < 0 || (o.user_n > 0 && !o.user_T16xN)) return false;
     return true;
 }
-// The centroid of the other map's band from one band build over it (count, then fill) into temporary buffers: the map's owner keeps its caches.
-// 1; 0 for an empty band; -1 for a resolution the band build does not take.
+}  // namespace
+// The centroid of a map's band from one band build over it (count, then fill) into temporary buffers: the map's owner keeps its caches.
+// 1; 0 for an empty band; -1 for a resolution the band build does not take.  (Declared in kf_internal.hpp: RegisterPointsGlobal uses it too.)
 int second_map_centroid(const SecondMap &src, double c_other[3]) {
     hipStream_t st = current_stream();
     const int X = src.res[0];
@@ -221,7 +222,6 @@ int second_map_centroid(const SecondMap &src, double c_other[3]) {
     if (idx.count > 0) hipSafeCall(hipMemcpy(keys.data(), idx.keys, (size_t)idx.count * sizeof(unsigned long long), hipMemcpyDeviceToHost));
     return band_centroid(keys.data(), idx.count, (double)src.voxel_size, c_other) ? 1 : 0;
 }
-}  // namespace
 
 int KinectFusionReconstruction::AlignVolumeGlobal(const SecondMap &src, const xs_align_search_opts *opts, double *T16_out, double report[12]) {
     align_report_clear(report, 12);

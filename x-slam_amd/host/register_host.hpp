@@ -12,18 +12,24 @@ constexpr int REGISTER_MAX_TRANSFORMS = 32;
 
 // why a call is refused (0: it is not); the order is the order of the checks
 enum RegisterRefusal : int { REGISTER_ACCEPTED = 0, REGISTER_TRANSFORMS, REGISTER_COUNT, REGISTER_NULL, REGISTER_RES, REGISTER_PITCH, REGISTER_VOXEL,
-                             REGISTER_MIN_WEIGHT, REGISTER_MAX_RESIDUAL, REGISTER_NOT_FINITE };
+                             REGISTER_MIN_WEIGHT, REGISTER_MAX_RESIDUAL, REGISTER_NOT_FINITE, REGISTER_STRIDE };
 inline const char *register_refusal_str(int r) {
     static const char *const s[] = {"ok", "transforms outside 1 .. XS_REGISTER_MAX_TRANSFORMS", "n outside 1 .. 2^30", "null pointer", "bad resolution", "bad pitch",
                                     "voxel_size is not positive and finite", "min_weight below 1", "max_residual is not finite and positive",
                                     "a transform entry is not finite"};
     return r >= 0 && r <= REGISTER_NOT_FINITE ? s[r] : "?";
 }
+// the same for xs_tsdf_score_points, which has its own bound on the transforms and refuses a stride as well (REGISTER_STRIDE: that call alone)
+inline const char *register_score_refusal_str(int r) {
+    return r == REGISTER_TRANSFORMS ? "transforms outside 1 .. XS_REGISTER_SCORE_MAX_TRANSFORMS" : r == REGISTER_STRIDE ? "stride below 1" : register_refusal_str(r);
+}
 
-// Everything xs_tsdf_register_terms refuses.  xform12xN: host array, transform m's twelve floats at + 12 m.
+// Everything xs_tsdf_register_terms refuses.  xform12xN: host array, transform m's twelve floats at + 12 m.  max_transforms: the call's bound
+// (xs_tsdf_score_points validates with the same table and its own).
 inline int register_validate(int transforms, long long n, const void *points, const float *xform12xN, bool have_volume, size_t vol_step, const int *res,
-                             float voxel_size, int min_weight, float max_residual, const void *workspace, const void *out) {
-    if (transforms < 1 || transforms > REGISTER_MAX_TRANSFORMS) return REGISTER_TRANSFORMS;
+                             float voxel_size, int min_weight, float max_residual, const void *workspace, const void *out,
+                             int max_transforms = REGISTER_MAX_TRANSFORMS) {
+    if (transforms < 1 || transforms > max_transforms) return REGISTER_TRANSFORMS;
     if (n < 1 || n > SAMPLE_MAX_POINTS) return REGISTER_COUNT;
     if (!points || !xform12xN || !have_volume || !res || !workspace || !out) return REGISTER_NULL;
     if (!render_res_ok(res)) return REGISTER_RES;
@@ -35,6 +41,19 @@ inline int register_validate(int transforms, long long n, const void *points, co
         if (!std::isfinite(xform12xN[i])) return REGISTER_NOT_FINITE;
     return REGISTER_ACCEPTED;
 }
+
+// Everything xs_tsdf_score_points refuses: the table above with its own bound on the transforms, and a stride below 1.
+constexpr int REGISTER_SCORE_MAX_TRANSFORMS = 4096;
+constexpr long long REGISTER_SEARCH_MAX_SCORED = 1ll << 24;   // the search's bound on ceil(n / stride): "raise the stride"
+inline int register_score_validate(int transforms, long long n, int stride, const void *points, const float *xform12xP, bool have_volume, size_t vol_step,
+                                   const int *res, float voxel_size, int min_weight, float max_residual, const void *workspace, const void *out) {
+    if (transforms < 1 || transforms > REGISTER_SCORE_MAX_TRANSFORMS) return REGISTER_TRANSFORMS;
+    if (stride < 1) return REGISTER_STRIDE;
+    return register_validate(transforms, n, points, xform12xP, have_volume, vol_step, res, voxel_size, min_weight, max_residual, workspace, out,
+                             REGISTER_SCORE_MAX_TRANSFORMS);
+}
+// the scored points of xs_tsdf_score_points: points 0, stride, 2 stride, ...
+inline long long register_scored_points(long long n, int stride) { return (n + stride - 1) / stride; }
 
 // xform12 of xs_tsdf_register_terms from T16 (a real 4 x 4, row-major, taking a point of the cloud's frame to the volume frame): sample_xform12's
 // rule, one rounding to float32 per entry; false, nothing written, for an entry that is not finite in double or after the rounding.

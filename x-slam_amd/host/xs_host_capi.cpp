@@ -9,6 +9,7 @@
 #include "merge_host.hpp"
 #include "newton_host.hpp"
 #include "register_host.hpp"
+#include "register_search_host.hpp"
 #include "sample_host.hpp"
 #include <exception>
 
@@ -137,6 +138,7 @@ int xs_host_align_search_rank(const double *out2xP, int P, int keep, int *idx_ou
 int xs_host_band_centroid(const unsigned long long *keys, long long count, double voxel_size, double *out3) {
     return xs_host::band_centroid(keys, count, voxel_size, out3) ? 0 : -1;
 }
+int xs_host_points_centroid(const float *points, long long n, int stride, double *out3) { return xs_host::points_centroid(points, n, stride, out3) ? 0 : -1; }
 int xs_host_merge_affine(const double *T16, double dst_voxel_size, double src_voxel_size, float *out12) {
     return xs_host::merge_affine(T16, dst_voxel_size, src_voxel_size, out12) ? 0 : -1;
 }

@@ -1,6 +1,7 @@
 // xs_pipeline_maps_capi.cpp — the C ABI's calls that take a second map or edit or query a map (include/xslam_amd_pipeline.h): merge, align, score,
 // diff, render, sample and register with the map from the caller's pointers (*_volume), from another instance (*_map) or from a file
-// (*_checkpoint), and reintegrate, fuse and frame_residuals on this instance's own map.  None of it runs during tracking.
+// (*_checkpoint), a cloud's transforms scored and a cloud registered with no guess against this instance's map, another's or a file's, and
+// reintegrate, fuse and frame_residuals on this instance's own map.  None of it runs during tracking.
 #include "../../include/xslam_amd_pipeline.h"
 #include "kf_internal.hpp"
 #include "align_host.hpp"
@@ -189,6 +190,39 @@ int xs_kf_register_checkpoint(void *kf, const char *path, long long n, const flo
             return ((KF *)kf)->RegisterSecondMap(m, points, n, on_device, T16xN, N, iterations, damping, min_weight, max_residual, T16_out, report7, h);
         });
     });
+}
+// ---- score a cloud's transforms, register with no guess (the map: this instance's through a null source, another instance's, a file's) ----
+int xs_kf_score_point_transforms(void *kf, long long n, const float *points, int on_device, int P, const double *T16xP, int stride, int min_weight,
+                                 float max_residual, double *out2xP) {
+    return ((KF *)kf)->ScorePointTransforms(nullptr, points, n, on_device, T16xP, P, stride, min_weight, max_residual, out2xP);
+}
+int xs_kf_score_point_transforms_map(void *kf, void *other_kf, long long n, const float *points, int on_device, int P, const double *T16xP, int stride,
+                                     int min_weight, float max_residual, double *out2xP) {
+    return with_other_map(kf, other_kf, false, [&](const SecondMap &m) {
+        return ((KF *)kf)->ScorePointTransforms(&m, points, n, on_device, T16xP, P, stride, min_weight, max_residual, out2xP);
+    });
+}
+int xs_kf_score_point_transforms_checkpoint(void *kf, const char *path, long long n, const float *points, int on_device, int P, const double *T16xP,
+                                            int stride, int min_weight, float max_residual, double *out2xP) {
+    return with_checkpoint_map(kf, path, [&](const SecondMap &m) {
+        return ((KF *)kf)->ScorePointTransforms(&m, points, n, on_device, T16xP, P, stride, min_weight, max_residual, out2xP);
+    });
+}
+void xs_kf_register_search_defaults(void *kf, xs_register_search_opts *opts) { ((KF *)kf)->RegisterSearchDefaults(opts); }
+int xs_kf_register_points_global(void *kf, long long n, const float *points, int on_device, const xs_register_search_opts *opts, double *T16_out,
+                                 double *report12) {
+    return ((KF *)kf)->RegisterPointsGlobal(nullptr, points, n, on_device, opts, T16_out, report12);
+}
+int xs_kf_register_points_global_map(void *kf, void *other_kf, long long n, const float *points, int on_device, const xs_register_search_opts *opts,
+                                     double *T16_out, double *report12) {
+    xs_host::align_report_clear(report12, 12);   // (before the source is looked at)
+    return with_other_map(kf, other_kf, false, [&](const SecondMap &m) { return ((KF *)kf)->RegisterPointsGlobal(&m, points, n, on_device, opts, T16_out, report12); });
+}
+int xs_kf_register_points_global_checkpoint(void *kf, const char *path, long long n, const float *points, int on_device,
+                                            const xs_register_search_opts *opts, double *T16_out, double *report12) {
+    if (!path) return -1;   // (before the report is cleared)
+    xs_host::align_report_clear(report12, 12);
+    return with_checkpoint_map(kf, path, [&](const SecondMap &m) { return ((KF *)kf)->RegisterPointsGlobal(&m, points, n, on_device, opts, T16_out, report12); });
 }
 // ---- the edits of this instance's own map ----
 int xs_kf_reintegrate(void *kf, int n, const uint16_t *const *depth_dev, size_t step_bytes, const float *c2v_old32xN, const float *c2v_new32xN,

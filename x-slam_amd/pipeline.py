@@ -43,7 +43,25 @@ _SAMPLE_POINTS = [C.c_longlong, _vp, _f64p]   # n, points, T16
 # what the three register calls share behind their source: n, points, on_device, T16xN, N, iterations, damping, min_weight, max_residual, T16_out, report7, history
 _REGISTER_TAIL = [C.c_longlong, _vp, C.c_int, _f64p, C.c_int, C.c_int, C.c_double, C.c_int, C.c_float, _f64p, _f64p, _f64p]
 
+class RegisterSearchOpts(C.Structure):
+    """xs_register_search_opts (include/xslam_amd_pipeline.h): xs_align_search_opts' fields"""
+    _fields_ = AlignSearchOpts._fields_
+
+
+# what the three point-score calls share behind their source: n, points, on_device, P, T16xP, stride, min_weight, max_residual, out2xP
+_POINT_SCORE_TAIL = [C.c_longlong, _vp, C.c_int, C.c_int, _f64p, C.c_int, C.c_int, C.c_float, _f64p]
+# and the three global registrations: n, points, on_device, opts, T16_out, report12
+_REGISTER_GLOBAL_TAIL = [C.c_longlong, _vp, C.c_int, C.POINTER(RegisterSearchOpts), _f64p, _f64p]
+
 _SIGS = {
+    "xs_kf_register_search_defaults": (None, [_vp, C.POINTER(RegisterSearchOpts)]),
+    "xs_kf_score_point_transforms": (C.c_int, [_vp] + _POINT_SCORE_TAIL),
+    "xs_kf_score_point_transforms_map": (C.c_int, [_vp, _vp] + _POINT_SCORE_TAIL),
+    "xs_kf_score_point_transforms_checkpoint": (C.c_int, [_vp, C.c_char_p] + _POINT_SCORE_TAIL),
+    "xs_kf_register_points_global": (C.c_int, [_vp] + _REGISTER_GLOBAL_TAIL),
+    "xs_kf_register_points_global_map": (C.c_int, [_vp, _vp] + _REGISTER_GLOBAL_TAIL),
+    "xs_kf_register_points_global_checkpoint": (C.c_int, [_vp, C.c_char_p] + _REGISTER_GLOBAL_TAIL),
+    "xs_host_points_centroid": (C.c_int, [_f32p, C.c_longlong, C.c_int, _f64p]),
     "xs_kf_register_points": (C.c_int, [_vp] + _REGISTER_TAIL),
     "xs_kf_register_map": (C.c_int, [_vp, _vp] + _REGISTER_TAIL),
     "xs_kf_register_checkpoint": (C.c_int, [_vp, C.c_char_p] + _REGISTER_TAIL),
@@ -332,6 +350,17 @@ def band_centroid(keys, voxel_size):
     out = np.zeros(3, np.float64)
     if _lib.xs_host_band_centroid(k.ctypes.data_as(C.POINTER(C.c_uint64)), k.size, float(voxel_size), out.ctypes.data_as(_f64p)) != 0:
         raise ValueError("band_centroid: no key")
+    return out
+
+
+def points_centroid(points, stride=1):
+    """The centroid [3] float64 of every stride-th point of a host cloud [N, 3] float32: each axis added in double in index order, divided by
+    the count (xs_host_points_centroid, CPU): the cloud centroid register_points_global matches to the map's.  ValueError for no point or
+    stride < 1."""
+    p = np.ascontiguousarray(points, dtype=np.float32).reshape(-1, 3)
+    out = np.zeros(3, np.float64)
+    if _lib.xs_host_points_centroid(p.ctypes.data_as(_f32p), p.shape[0], int(stride), out.ctypes.data_as(_f64p)) != 0:
+        raise ValueError("points_centroid: no point, or stride < 1")
     return out
 
 
@@ -1343,7 +1372,9 @@ class KinectFusion:
         Intended use: kf.merge_checkpoint(path, kf.align_checkpoint(path, T_guess)[1])."""
         return self._align_call("xs_kf_align_checkpoint", path.encode(), T0, iterations, damping, min_weight, max_residual)
 
-    def _register_call(self, name, source, points, T0, iterations, damping, min_weight, max_residual):
+    @staticmethod
+    def _points_arg(name, points):
+        """(n, address, on_device, the array to keep alive) of a cloud: a numpy array [N, 3] or a contiguous float32 torch tensor on the GPU."""
         if hasattr(points, "data_ptr"):   # a torch tensor on the GPU
             if not points.is_cuda or not points.is_contiguous() or points.dim() != 2 or points.shape[1] != 3 or points.element_size() != 4 or not points.is_floating_point():
                 raise ValueError(f"{name}: a torch points tensor must be contiguous float32 [N, 3] on the GPU")
@@ -1355,6 +1386,10 @@ class KinectFusion:
             n, pp, on_device = keep.shape[0], keep.ctypes.data, 0
         if n < 1:
             raise ValueError(f"{name}: at least one point is needed")
+        return n, pp, on_device, keep
+
+    def _register_call(self, name, source, points, T0, iterations, damping, min_weight, max_residual):
+        n, pp, on_device, keep = self._points_arg(name, points)
         t = np.asarray(np.eye(4) if T0 is None else T0, dtype=np.float64)
         t = np.ascontiguousarray(t.reshape(-1, 4, 4))
         iterations = int(iterations)
@@ -1403,17 +1438,7 @@ class KinectFusion:
         follows; poses and the frame number stay.  XsError in shard mode, ValueError on bad arguments.
         Intended use: kf.fuse_points(sweep, kf.register_points(sweep, T_guess)[1], origin=sensor_position)."""
         name = "xs_kf_fuse_points"
-        if hasattr(points, "data_ptr"):   # a torch tensor on the GPU
-            if not points.is_cuda or not points.is_contiguous() or points.dim() != 2 or points.shape[1] != 3 or points.element_size() != 4 or not points.is_floating_point():
-                raise ValueError(f"{name}: a torch points tensor must be contiguous float32 [N, 3] on the GPU")
-            n, pp, on_device, keep = int(points.shape[0]), points.data_ptr(), 1, points
-        else:
-            keep = np.ascontiguousarray(points, dtype=np.float32)
-            if keep.ndim != 2 or keep.shape[1] != 3:
-                raise ValueError(f"{name}: points must be [N, 3]")
-            n, pp, on_device = keep.shape[0], keep.ctypes.data, 0
-        if n < 1:
-            raise ValueError(f"{name}: at least one point is needed")
+        n, pp, on_device, keep = self._points_arg(name, points)
         t = None if T is None else _real44(T)
         o = np.ascontiguousarray(origin, dtype=np.float32).reshape(-1)
         if o.size != 3:
@@ -1424,10 +1449,90 @@ class KinectFusion:
         self._map_call(name, rc, "T, origin or a range not finite, min_range <= 0, max_range < min_range or too long, weight outside 1 .. max_integration_weight")
         return {k: int(counts[i]) for i, k in enumerate(self._FUSE_COUNTS)}
 
+    def _score_points_call(self, name, source, points, Ts, stride, min_weight, max_residual):
+        n, pp, on_device, keep = self._points_arg(name, points)
+        t = np.ascontiguousarray(np.asarray(Ts, dtype=np.float64).reshape(-1, 4, 4))
+        out = np.zeros((t.shape[0], 2), np.float64)
+        rc = getattr(_lib, name)(self.h, *source, n, pp, on_device, t.shape[0], t.ctypes.data_as(_f64p), int(stride), int(min_weight), float(max_residual),
+                                 out.ctypes.data_as(_f64p))
+        self._map_call(name, rc, "more than 2^30 points, " + self._BAD_SEARCH)
+        return out
+
+    def score_point_transforms(self, points, Ts, stride=1, min_weight=1, max_residual=0.9):
+        """{sum r^2, count} [P, 2] float64 of "this map's value at T p" over every stride-th point of a cloud (as register_points takes it), for
+        each T of Ts [P, 4, 4] (cloud frame to volume frame), in one launch per 4096 transforms: register_points' residual without its
+        gradient, so a point counts wherever the map holds a value with min_weight and |value| <= max_residual.  S = count - sum r^2 ranks the
+        transforms.  Nothing is modified.  XsError in shard mode, ValueError on bad arguments."""
+        return self._score_points_call("xs_kf_score_point_transforms", (), points, Ts, stride, min_weight, max_residual)
+
+    def score_map_point_transforms(self, other, points, Ts, stride=1, min_weight=1, max_residual=0.9):
+        """score_point_transforms against the map of `other` (another KinectFusion of this process, which is only read)."""
+        return self._score_points_call("xs_kf_score_point_transforms_map", (other.h,), points, Ts, stride, min_weight, max_residual)
+
+    def score_checkpoint_point_transforms(self, path, points, Ts, stride=1, min_weight=1, max_residual=0.9):
+        """score_point_transforms against the map in a checkpoint file of a whole volume (either format), validated as merge_checkpoint does."""
+        return self._score_points_call("xs_kf_score_point_transforms_checkpoint", (path.encode(),), points, Ts, stride, min_weight, max_residual)
+
+    def _register_global_call(self, name, source, points, candidates, keep, rounds, stride, box_t, refine_t, refine_r, iterations, damping, min_weight, max_residual, Ts):
+        n, pp, on_device, alive = self._points_arg(name, points)
+        o = RegisterSearchOpts()
+        _lib.xs_kf_register_search_defaults(self.h, C.byref(o))
+        o.candidates, o.keep, o.rounds, o.stride, o.iterations, o.min_weight = int(candidates), int(keep), int(rounds), int(stride), int(iterations), int(min_weight)
+        if box_t is not None:
+            o.box_t = float(box_t)
+        if refine_t is not None:
+            o.refine_t = float(refine_t)
+        o.refine_r, o.damping, o.max_residual = float(refine_r), float(damping), float(max_residual)
+        user = None
+        if Ts is not None:
+            user = np.ascontiguousarray(np.asarray(Ts, dtype=np.float64).reshape(-1, 4, 4))
+            o.user_n, o.user_T16xN = user.shape[0], user.ctypes.data_as(_f64p)
+        out, report = np.eye(4, dtype=np.float64), np.zeros(12, np.float64)
+        rc = getattr(_lib, name)(self.h, *source, n, pp, on_device, C.byref(o), out.ctypes.data_as(_f64p), report.ctypes.data_as(_f64p))
+        self._map_call(name, rc, "more than 2^30 points or more than 2^24 scored ones (raise the stride), " + self._BAD_SEARCH, zero_ok=True)
+        rep = {"rank": int(report[0]), "S_before": float(report[1]), "count": int(report[2]), "sum_r2": float(report[3]), "loss": float(report[4]),
+               "score_launches": int(report[5]), "passes": int(report[6]), "ended_ok": int(report[7]), "points": int(report[8]),
+               "scored_points": int(report[9]), "centroid_distance": float(report[10])}
+        return rc == 1, out, rep
+
+    def register_points_global(self, points, candidates=2048, keep=8, rounds=2, stride=4, box_t=None, refine_t=None, refine_r=0.25, iterations=10, damping=1e-3,
+                               min_weight=1, max_residual=0.9, Ts=None):
+        """register_points with no starting guess: a lidar sweep taken somewhere in the mapped room, yesterday's exported cloud in another frame,
+        a ground-truth scan.  `candidates` transforms that cover all rotations (transform_candidates_free; translations take the centroid of
+        the scored points onto the map's band centroid, jittered by box_t metres) are scored over every stride-th point
+        (score_point_transforms), the `keep` best by S = count - sum r^2 are refined over `rounds` rounds of candidates about each
+        (transform_candidates_around about the cloud's centroid: boxes refine_t metres and refine_r radians, halved per round), and the kept
+        transforms start register_points' loop over ALL the points.  box_t, refine_t None: the map's truncation distance.  Ts [N, 4, 4]:
+        candidates of the caller's that replace the free ones.  Returns (ok, T [4, 4] float64, report dict: rank, S_before, count, sum_r2,
+        loss, score_launches, passes, ended_ok, points, scored_points, centroid_distance); ok False (T = the identity) when no start ended ok
+        or the map has no band voxel.  The score cannot tell a scene from its image under one of its own symmetries: a symmetric scene has
+        several equally good answers and any of them may be returned.  A cloud that covers only part of the map has its centroid elsewhere:
+        widen box_t.  Nothing is modified.  XsError in shard mode, ValueError on bad arguments.
+        Intended use: kf.fuse_points(sweep, kf.register_points_global(sweep)[1], origin=sensor_position)."""
+        return self._register_global_call("xs_kf_register_points_global", (), points, candidates, keep, rounds, stride, box_t, refine_t, refine_r, iterations, damping,
+                                          min_weight, max_residual, Ts)
+
+    def register_map_points_global(self, other, points, candidates=2048, keep=8, rounds=2, stride=4, box_t=None, refine_t=None, refine_r=0.25, iterations=10,
+                                   damping=1e-3, min_weight=1, max_residual=0.9, Ts=None):
+        """register_points_global against the map of `other` (another KinectFusion of this process, which is only read); T takes the points to ITS volume frame."""
+        return self._register_global_call("xs_kf_register_points_global_map", (other.h,), points, candidates, keep, rounds, stride, box_t, refine_t, refine_r,
+                                          iterations, damping, min_weight, max_residual, Ts)
+
+    def register_checkpoint_points_global(self, path, points, candidates=2048, keep=8, rounds=2, stride=4, box_t=None, refine_t=None, refine_r=0.25, iterations=10,
+                                          damping=1e-3, min_weight=1, max_residual=0.9, Ts=None):
+        """register_points_global against the map in a checkpoint file of a whole volume (save_checkpoint, dense or sparse), validated as merge_checkpoint does."""
+        return self._register_global_call("xs_kf_register_points_global_checkpoint", (path.encode(),), points, candidates, keep, rounds, stride, box_t, refine_t,
+                                          refine_r, iterations, damping, min_weight, max_residual, Ts)
+
     def register_and_fuse(self, points, T0=None, origin=(0.0, 0.0, 0.0), iterations=10, damping=1e-3, min_weight=1, max_residual=0.9, min_range=0.2, max_range=5.0,
-                          carve=False, weight=1):
+                          carve=False, weight=1, global_search=False):
         """register_points followed, when it succeeded, by fuse_points at the winning transform: (ok, T, register report, fuse counts or None).
-        Nothing is fused when no start ended ok."""
+        Nothing is fused when no start ended ok.  global_search=True: the registration is register_points_global at its defaults (with these
+        iterations, damping, min_weight and max_residual) and T0 is not used; the report is that call's."""
+        if global_search:
+            ok, T, rep = self.register_points_global(points, iterations=iterations, damping=damping, min_weight=min_weight, max_residual=max_residual)
+            fused = self.fuse_points(points, T, origin, min_range, max_range, carve, weight) if ok else None
+            return ok, T, rep, fused
         ok, T, rep = self.register_points(points, T0, iterations, damping, min_weight, max_residual)
         fused = self.fuse_points(points, T, origin, min_range, max_range, carve, weight) if ok else None
         return ok, T, rep, fused
