@@ -1,4 +1,5 @@
-"""Float64 model of how the ICP reduction's last workgroup adds the per-workgroup records (x-slam_amd/csrc/xs_icp.hip): the order
+"""Float64 model of how the ICP reduction's last workgroup adds the per-workgroup records (x-slam_amd/csrc/xs_icp.hip: the gather in k_icp;
+xs_icp_fold.h: sum_row_groups): the order
 of every addition, so that the 55 sums of a launch can be held against it bit for bit.
 
 Row group g of G adds records g, g + G, g + 2G, ... in that order, starting from +0.0; the G group sums are then added in group
@@ -11,8 +12,8 @@ SUMS = 55
 
 
 def row_groups(cols, rows, y0=0, y1=None):
-    """G of the instance a launch over the pixel rows [y0, y1) of a cols x rows image runs (icp_blocks / icp_dispatch of xs_icp.hip,
-    default settings)."""
+    """G of the instance a launch over the pixel rows [y0, y1) of a cols x rows image runs (icp_blocks of xs_icp_launch.h,
+    icp_dispatch of xs_icp.hip, default settings)."""
     tiles = -(-cols // 64) * ((rows if y1 is None else y1) - y0)
     if 8 * 512 < tiles <= 10 * 512:
         return 36                       # 256 sixteen-wave workgroups of 18 or 19 tiles

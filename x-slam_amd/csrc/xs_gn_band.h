@@ -124,7 +124,7 @@ __device__ __forceinline__ void block_fold_and_finish_of(double (&v)[NV], double
             for (int gg = 1; gg < G; ++gg) t += s_red[gg][tid];
             out[tid] = t;
             // the host's copy: system-scope stores into pinned memory by lanes of wave 0 (NV <= 64), then — once they are acknowledged — the
-            // sequence word by its first lane: a host that sees the word sees the sums (the protocol of the ICP records, xs_icp.hip)
+            // sequence word by its first lane: a host that sees the word sees the sums (the protocol of the ICP records: publish_host_record of xs_icp.hip, xs_icp_sum_records of xs_icp_host.hip)
             if (publish) __hip_atomic_store(&publish[tid], t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
         }
         // the ticket goes back to zero for the next launch on this workspace (xs_tsdf_reduce_workspace_init zeroes it once): no fill per launch

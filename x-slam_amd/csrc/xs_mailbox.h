@@ -1,5 +1,5 @@
 // xs_mailbox.h — the pose mailbox shared by k_icp<POSE_POSTED> (xs_icp.hip) and the posted Gauss-Newton pass (xs_residual.hip).
-// mailbox_post (host, below: xs_icp_post_pose, xs_gn_post_poses) writes it, a kernel that was enqueued before its pose existed polls it.  128 bytes = four 32-byte
+// mailbox_post (host, below: xs_icp_post_pose of xs_icp_host.hip, xs_gn_post_poses) writes it, a kernel that was enqueued before its pose existed polls it.  128 bytes = four 32-byte
 // SECTORS of eight words, EVERY sector starting with the sequence number:
 //     sector 0 = {seq, cmd, f[0..5]}   sector 1 = {seq, f[6..12]}   sector 2 = {seq, 0, f[13..18]}   sector 3 = {seq, f[19..23], 0, 0}
 // with f = the 18 floats of a complex 3x3 followed by the 6 of a complex 3-vector; cmd 0 = run, 1 = abandon the launch.  A 32-byte sector is the
